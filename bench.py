@@ -23,18 +23,23 @@ over 8 GPUs).
 Rank 0 prints ONE JSON line under 6 KB (compact_line: the driver keeps the last 8 KB of stdout) with the contract fields plus
   roofline        the kernel with the largest measured time against the roof that binds it.  pitch / analyze -> FP64
                   vector peak with the flops the kernel EXECUTES (`frac`), `issue_frac` = the share of SIMD time the vector
-                  ALU is issuing; everything else -> HBM, algorithmic bytes.  `traffic` = measured HBM bytes per launch;
-                  for the headline kernel `traffic`, `issue_frac` and `valu_insts_per_frame` are MEASURED IN THE RUN (three
-                  short `rocprofv3 --pmc` child passes, live_traffic()), elsewhere they come from the committed PMC passes
-                  (profiles/pmc_traffic.json): `traffic_source` says which
+                  ALU is issuing; everything else -> HBM, algorithmic bytes.  `traffic` = measured HBM bytes per launch, from
+                  the committed PMC passes (profiles/pmc_traffic.json) unless --full measures them: `traffic_source` says which
   roofline_hbm    the pitch kernel against the HBM roof, as north_star asks (tiny by construction)
+These come from the HIP events of the timed steps themselves.  A plain run does nothing else: it sets up, warms up, times
+the steps, writes --dump-outputs if asked and prints the line.  With --full, rank 0 then adds
+  live traffic    for the headline kernel `traffic`, `issue_frac` and `valu_insts_per_frame` MEASURED IN THE RUN (three
+                  short `rocprofv3 --pmc` child passes, live_traffic())
   cpu_baseline    the CPU oracle (C restatement of the reference path) timed natively (oracle/vbx_cpu_bench.c) on
                   1 core and on all the cores the process may use, at the GPU leg's frame geometry
   sub_benchmarks  (default run, N = 1) {name: frames/s}: BASELINE configs 2, 3 (kmax 1 / 8 / the whole candidate Vec), 4, fourteen
                   other frame shapes, the pipeline on real 44.1 kHz speech, config 5 whole on one GPU -- a few steps each
                   outside the headline's timed region
+  cross_rank_check  (N > 1) the rows around every shard cut against one GPU's, bit for bit
 and writes the FULL record (every sub-benchmark's kernels and rooflines, per-shape tables, the parity note, the model strings) to
---detail (default gpurun_out/bench_detail.json).
+--detail (default with --full: bench_out/bench_detail.json).
+--dump-outputs DIR writes what the last timed step computed (the pipeline: the per-frame records and statuses) as DIR/<name>.npy,
+float64, a fixed seeded sample of rows beyond 64 MB: the inputs are generated from fixed offsets, so two builds compare row for row.
 Other workloads (--workload config2|config3|config4|frontend) time a single BASELINE config; --frame-len / --hop move the
 pipeline and config3 to another frame shape (2048 / 1024 is the reference example's), under its own metric name.
 """
@@ -93,15 +98,20 @@ def parse():
     ap.add_argument("--workload", default="pipeline", choices=["pipeline", "config2", "config3", "config4", "frontend"])
     ap.add_argument("--kmax", type=int, default=1, help="pitch candidates kept per frame (1 = PitchExtractor output; "
                     "64 = the head of the reference's sorted list, which disables the exact top-k pruning)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the CPU baseline, the sub-benchmarks of the default run, "
+                    "the headline kernel's HBM traffic measured in child passes, the cross-rank check, the extra legs of --host-fed and "
+                    "--signal speech, and the detail file.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed as "
+                    "DIR/<name>.npy (float64; a fixed seeded sample of rows when the arrays exceed 64 MB together)")
     ap.add_argument("--cpu-seconds", type=float, default=16.0, help="wall budget of the CPU baseline leg (both legs together)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-sub", action="store_true", help="skip the sub_benchmarks of the default run (configs 2, 3, 4)")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not measure the headline kernel's HBM traffic in this run (two short "
                     "rocprofv3 --pmc child passes, FETCH_SIZE and WRITE_SIZE, ~10 s each): roofline.traffic then comes from the committed "
                     "profiles/pmc_traffic.json")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"), help="where the FULL record goes (per-shape "
-                    "tables, per-kernel times of every sub-benchmark, the parity note, the model strings); stdout carries only the "
-                    "compact line (< 6 KB: the driver keeps the last 8 KB of stdout)")
+    ap.add_argument("--detail", default=None, help="where the FULL record goes (per-shape tables, per-kernel times of every sub-benchmark, "
+                    "the parity note, the model strings; default with --full: bench_out/bench_detail.json, otherwise none); stdout "
+                    "carries only the compact line (< 6 KB: the driver keeps the last 8 KB of stdout)")
     ap.add_argument("--signal", default="synthetic", choices=["synthetic", "speech"], help="speech: the pipeline on a recording of REAL "
                     "speech (tests/golden/sample-two_vowels.wav, 44.1 kHz, tiled with per-tile gains and a -70 dB dither) at the "
                     "shapes a 44.1 kHz caller uses (1103 / 441 = 25 ms / 10 ms; 1024 / 512 = tests/lib.rs:56-57), order 13 "
@@ -115,7 +125,10 @@ def parse():
                     "restarts from the initial estimates at every utterance start).  0 (default): the WHOLE recording is one "
                     "utterance, what the reference's user loop over a file is (tests/lib.rs:75-79) -- at N > 1 the even frame split "
                     "cuts it and the track is carried across the rank boundaries (vbx_comm_stitch_tracks_f64)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.full and args.detail is None:
+        args.detail = os.path.join(ROOT, "bench_out", "bench_detail.json")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -496,6 +509,8 @@ def bench_frontend(args, torch, dev, vb, pkg):
         vb.L.vbx_rms_f64(vb.ctx, audio.data_ptr(), F, N48, H48, win.ptr, rms.data_ptr())
         vb.preemphasis(audio, 0.1, frame_len=N48, stride=H48, n_frames=Fp, out=pe)
     dt, prof, _ = timed(vb, torch, step, args.warmup, args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"rms": rms, "preemphasis": pe})
     k = {name: ms / max(c, 1) for name, (ms, c) in prof.items()}
     ach = n * 10 / (k["pcm16"] * 1e-3) / 1e9
     traffic, tsrc = measured_traffic("pcm16", n)
@@ -568,18 +583,8 @@ def bench_host_fed(args, torch, dev, vb, pkg):
                                     out=rec[c * C:(c + 1) * C], record_ld=REC, status=st3)
             freed[b].record(main)
     dt, prof, work = timed(vb, torch, step, args.warmup, args.steps)
-    # the same chunks already resident (no copy in the loop): what the link costs
-    def step_resident(i):
-        for c in range(n_chunks):
-            vb.analyze_frames_pcm16(bufs[c % 2], params, seg_start=seg, frame_len=N, stride=H, n_frames=C,
-                                    out=rec[c * C:(c + 1) * C], record_ld=REC, status=st3)
-    dt_res, _, _ = timed(vb, torch, step_resident, 1, args.steps)
-    # the copies alone
-    t0 = time.perf_counter()
-    for c in range(n_chunks):
-        bufs[c % 2].copy_(host[c * C * H:c * C * H + ns_chunk], non_blocking=True)
-    torch.cuda.synchronize()
-    dt_copy = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"records": rec, "status": st3.t()})   # status: the last chunk's
     kms = {k: round(ms / max(c, 1), 3) for k, (ms, c) in prof.items()}
     out = {"metric": "frames/sec (host-fed: 16-bit PCM in pinned host memory -> PCIe -> pitch+LPC+formants+MFCC), 48 kHz 25 ms/10 ms hop",
            "value": F * args.steps / dt, "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -588,11 +593,25 @@ def bench_host_fed(args, torch, dev, vb, pkg):
            "config": {"workload": f"host-fed pipeline, {F} frames ({F * H / SR / 3600:.2f} h) as int16 PCM in pinned host memory, "
                                   f"chunks of {C} frames, two device buffers, copy stream beside the kernels",
                       "frames_per_gpu": F, "frame_len": N, "hop": H, "chunk_frames": C, "pcm_bytes_per_frame": 2 * H},
-           "pcie": {"bytes_per_step": int(2 * ns_chunk * n_chunks), "copy_alone_GBps": 2 * ns_chunk * n_chunks / dt_copy / 1e9,
-                    "link_peak_GBps": 63.0, "inclusive_GBps": 2 * ns_chunk * n_chunks * args.steps / dt / 1e9},
-           "same_chunks_resident_frames_per_s": F * args.steps / dt_res,
-           "pcie_inclusive_over_resident": dt_res / dt,
+           "pcie": {"bytes_per_step": int(2 * ns_chunk * n_chunks), "link_peak_GBps": 63.0,
+                    "inclusive_GBps": 2 * ns_chunk * n_chunks * args.steps / dt / 1e9},
            "kernels_ms_per_chunk": kms}
+    if args.full:
+        # the same chunks already resident (no copy in the loop): what the link costs
+        def step_resident(i):
+            for c in range(n_chunks):
+                vb.analyze_frames_pcm16(bufs[c % 2], params, seg_start=seg, frame_len=N, stride=H, n_frames=C,
+                                        out=rec[c * C:(c + 1) * C], record_ld=REC, status=st3)
+        dt_res, _, _ = timed(vb, torch, step_resident, 1, args.steps)
+        # the copies alone
+        t0 = time.perf_counter()
+        for c in range(n_chunks):
+            bufs[c % 2].copy_(host[c * C * H:c * C * H + ns_chunk], non_blocking=True)
+        torch.cuda.synchronize()
+        dt_copy = time.perf_counter() - t0
+        out["pcie"]["copy_alone_GBps"] = 2 * ns_chunk * n_chunks / dt_copy / 1e9
+        out["same_chunks_resident_frames_per_s"] = F * args.steps / dt_res
+        out["pcie_inclusive_over_resident"] = dt_res / dt
     emit(out, args.detail)
     vb.close()
     return 0
@@ -679,12 +698,14 @@ SPEECH_WAV = os.path.join(ROOT, "tests", "golden", "sample-two_vowels.wav")
 SPEECH_SHAPES = ((1103, 441), (1024, 512))
 
 
-def bench_speech(vb, torch, dev, pkg, hours=1.0, steps=2, warmup=1, shapes=SPEECH_SHAPES, order=13):
+def bench_speech(vb, torch, dev, pkg, hours=1.0, steps=2, warmup=1, shapes=SPEECH_SHAPES, order=13, signals=("speech", "synthetic"),
+                 dump=None):
     """The full pipeline on REAL speech: what the reference's callers feed it (tests/lib.rs:60-83,
     examples/formant_extraction/src/main.rs:36-47 read WAV files).  Per shape: frames/s on the speech recording and on the
     synthetic signal with the same parameters, and the share of frames the one-pass Burg's guard / the conjugate-pair root
     finder's check hand to the reference's own recursions (`burg_direct`, `roots_direct`): the fast paths' coverage is a
-    property of the material, so it is measured on material."""
+    property of the material, so it is measured on material.  `dump`, if given, receives the speech leg's outputs at the first
+    shape right after its timed steps."""
     import wave
     from importlib import import_module
     with wave.open(SPEECH_WAV, "rb") as w:
@@ -693,8 +714,10 @@ def bench_speech(vb, torch, dev, pkg, hours=1.0, steps=2, warmup=1, shapes=SPEEC
     ns = int(hours * 3600 * sr)
     syn = import_module(pkg.__name__ + ".synth")
     speech = syn.speech_recording(torch, dev, pcm, ns)
-    synth = torch.empty(ns, dtype=torch.float64, device=dev)
-    vb.synth_speech(ns, sample_offset=0, sample_rate=sr, out=synth)
+    synth = None
+    if "synthetic" in signals:
+        synth = torch.empty(ns, dtype=torch.float64, device=dev)
+        vb.synth_speech(ns, sample_offset=0, sample_rate=sr, out=synth)
     est0 = np.array([[f, 1.0] for f in pkg.MALE_FORMANT_ESTIMATES])
     params = pkg.AnalysisParams.make(sr, pitch=(0.2, 75.0, 600.0), lpc_order=P, formant_order=order, est_init=est0,
                                      mfcc=(13, 100.0, 8000.0))
@@ -706,9 +729,14 @@ def bench_speech(vb, torch, dev, pkg, hours=1.0, steps=2, warmup=1, shapes=SPEEC
         st3 = torch.empty((3, F), dtype=torch.int32, device=dev)
         row = {"frame_len": n, "hop": hop, "frames": F}
         for name, audio in (("speech", speech), ("synthetic", synth)):
+            if name not in signals:
+                continue
+
             def step(i, audio=audio, n=n, hop=hop, F=F, rec=rec, st3=st3):
                 vb.analyze_frames(audio, params, frame_len=n, stride=hop, n_frames=F, out=rec, record_ld=REC, status=st3)
             dt, prof, work = timed(vb, torch, step, warmup, steps)
+            if dump is not None and name == "speech" and not rows:
+                dump({"records": rec, "status": st3.t()})
             kms = {k: round(ms / max(c, 1), 3) for k, (ms, c) in prof.items()}
             frames_w, cand_w, evals_w, terms_w = work
             row[name] = {"value": F * steps / dt, "ms_per_step": dt / steps * 1e3,
@@ -720,7 +748,8 @@ def bench_speech(vb, torch, dev, pkg, hours=1.0, steps=2, warmup=1, shapes=SPEEC
                          "lpc_exact": vb.last_lpc_exact_count() / F,
                          "frames_with_nonzero_status": int((st3 != 0).any(dim=0).sum().item()),
                          "dominant_kernel": dominant_kernel(prof), "kernels_ms": kms}
-        row["speech_over_synthetic"] = row["speech"]["value"] / row["synthetic"]["value"]
+        if "synthetic" in row:
+            row["speech_over_synthetic"] = row["speech"]["value"] / row["synthetic"]["value"]
         rows.append(row)
         del rec, st3
     del speech, synth
@@ -886,7 +915,7 @@ def _sub_value(s):
     if "value" in s:
         return s["value"]
     if s.get("name") == "speech_44k":
-        return {f"{r['frame_len']}/{r['hop']}": {"speech": r["speech"]["value"], "synthetic": r["synthetic"]["value"],
+        return {f"{r['frame_len']}/{r['hop']}": {"speech": r["speech"]["value"], "synthetic": r.get("synthetic", {}).get("value"),
                                                  "burg_direct": r["speech"]["burg_direct"]} for r in s.get("shapes", [])}
     if "shapes" in s:
         return {f"{r['frame_len']}/{r['hop']}": r["value"] for r in s["shapes"]}
@@ -956,6 +985,32 @@ def emit(out, detail_path):
         except OSError as e:
             sys.stderr.write(f"bench.py: could not write {detail_path}: {e}\n")
     print(compact_line(out, written), flush=True)
+
+
+DUMP_LIMIT = 60 << 20      # bytes of array data --dump-outputs writes at most (64 MB with room for the .npy headers)
+
+
+def _dump_rows(n, share, seed):
+    return np.sort(np.random.default_rng(seed).choice(n, int(n * share), replace=False))
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Writes {name: array (torch tensor or ndarray), frames along axis 0} as out_dir/<name>.npy in float64.  When the arrays hold
+    more than DUMP_LIMIT bytes together, each keeps the same share of its rows: a sorted sample drawn by a generator seeded with
+    `seed` from the row count alone, so two runs with the same arguments write the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(int(np.prod(a.shape)) * 8 for a in arrays.values())
+    share = min(1.0, DUMP_LIMIT / max(total, 1))
+    for name, a in arrays.items():
+        n = int(a.shape[0])
+        if not isinstance(a, np.ndarray):
+            import torch
+            if share < 1.0:
+                a = a.index_select(0, torch.as_tensor(_dump_rows(n, share, seed), device=a.device))
+            a = a.cpu().numpy()
+        elif share < 1.0:
+            a = a[_dump_rows(n, share, seed)]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def guarded(name, fn, torch=None):
@@ -1095,7 +1150,10 @@ def run_rank(args):
     if args.signal == "speech":
         if wl != "pipeline" or world != 1:
             raise SystemExit("bench.py --signal speech: the pipeline on one GPU only")
-        r = bench_speech(vb, torch, dev, pkg, hours=min(args.hours, 2.0) if args.hours != 12.5 else 1.0, steps=args.steps, warmup=args.warmup)
+        dump = (lambda arrays: dump_outputs(args.dump_outputs, arrays)) if args.dump_outputs else None
+        legs = {} if args.full else {"shapes": SPEECH_SHAPES[:1], "signals": ("speech",)}      # the headline's leg alone
+        r = bench_speech(vb, torch, dev, pkg, hours=min(args.hours, 2.0) if args.hours != 12.5 else 1.0, steps=args.steps, warmup=args.warmup,
+                         dump=dump, **legs)
         head = r["shapes"][0]
         emit({"metric": "frames/sec (pipeline on real 44.1 kHz speech, 1103-sample frames / 441-sample hop, order 13)",
               "value": head["speech"]["value"], "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -1210,6 +1268,21 @@ def run_rank(args):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
+    if rank == 0 and args.dump_outputs:
+        vb.sync()
+        if comm is not None:
+            comm.sync()
+        if wl == "pipeline":
+            b_last = (args.warmup + args.steps - 1) % len(rec)
+            outs = {"records": gathered[b_last] if world > 1 else rec[b_last], "status": st3.t()}
+        elif wl == "config2":
+            outs = {"autocorr": o_r, "lpc": o_a}
+        elif wl == "config3":
+            outs = {"pitch_candidates": o_cand, "candidate_count": o_cnt, "pitch_status": o_pst}
+        else:
+            outs = {"formants": o_form, "formant_status": o_fst}
+        dump_outputs(args.dump_outputs, outs)
+
     if rank == 0:
         total = F * world * args.steps
         default_shape = wl not in ("pipeline", "config3") or (frame_len, stride) == (N48, H48)
@@ -1237,7 +1310,7 @@ def run_rank(args):
             out["roofline_hbm"] = hbm
         # the headline kernel's HBM traffic measured in THIS run (two short rocprofv3 --pmc child passes); on any failure the committed
         # evidence file's figure stays, and traffic_source says which it is
-        if (wl == "pipeline" and default_shape and world == 1 and not args.no_live_traffic and roof.get("kernel") in LIVE_KERNELS
+        if (args.full and wl == "pipeline" and default_shape and world == 1 and not args.no_live_traffic and roof.get("kernel") in LIVE_KERNELS
                 and not os.environ.get("ROCP_TOOL_LIBRARIES") and "rocprof" not in os.environ.get("LD_PRELOAD", "")):      # (not under a profiler already)
             lt = guarded("live_traffic", lambda: live_traffic(roof["kernel"]))
             if isinstance(lt, tuple):
@@ -1255,15 +1328,16 @@ def run_rank(args):
                 out["live_traffic_error"] = lt.get("error")
         # what "parity" means for this line: GPU == oracle is tested; oracle == reference is pinned
         # by the reference's own known-answer tests where it has any, and is NOT where it has none
-        out["parity"] = PARITY_NOTE
+        if args.full:
+            out["parity"] = PARITY_NOTE
         if wl == "config4":
             # three kernels in sequence -- Burg, the root finder, the chunked tracker scan (four launches + a sweep, timed as
             # one) -- so besides the dominant kernel's line: the whole config against both roofs (4264 B and
             # ~135 kflop per frame)
             out["whole_config"] = config4_whole(F, dt / args.steps, kernels, args.steps)
-        # N > 1 (or VBX_BENCH_SELFCHECK=1 at N = 1, a rehearsal of the same code against an interior "cut"): are the gathered rows
+        # --full, N > 1 (or VBX_BENCH_SELFCHECK=1 at N = 1, a rehearsal of the same code against an interior "cut"): are the gathered rows
         # around every shard cut what ONE GPU computes for the same stretch of the recording?
-        if wl == "pipeline" and args.utterance_frames <= 0 and (world > 1 or os.environ.get("VBX_BENCH_SELFCHECK")):
+        if args.full and wl == "pipeline" and args.utterance_frames <= 0 and (world > 1 or os.environ.get("VBX_BENCH_SELFCHECK")):
             vb.sync()
             if comm is not None:
                 comm.sync()
@@ -1276,9 +1350,9 @@ def run_rank(args):
                 out["valid"] = False
                 out["invalid_because"] = "cross_rank_check: the gathered rows around a shard cut are not the single-GPU rows"
                 rc_final = 3
-        if not args.no_cpu:          # rank 0, outside the timed region, at every N
+        if args.full and not args.no_cpu:          # rank 0, outside the timed region, at every N
             out["cpu_baseline"] = guarded("cpu_baseline", lambda: cpu_baseline(wl, args.cpu_seconds, frame_len, stride))
-        if wl == "pipeline" and default_shape and world == 1 and not args.no_sub:
+        if args.full and wl == "pipeline" and default_shape and world == 1 and not args.no_sub:
             del rec, gathered                                                 # the records' HBM back before the dense batches
             out["sub_benchmarks"] = guarded("sub_benchmarks", lambda: sub_benchmarks(vb, torch, dev, pkg, audio, F), torch)
             if isinstance(out["sub_benchmarks"], dict):                       # the guard's error record

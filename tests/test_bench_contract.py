@@ -45,7 +45,8 @@ def test_traffic_file_has_every_kernel_the_bench_can_ask_for():
 
 def test_bench_help_lists_the_workloads_and_shape_options():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, check=True).stdout
-    for word in ("--gpus", "--steps", "--warmup", "--frame-len", "--hop", "--no-sub", "pipeline", "config2", "config3", "config4", "frontend"):
+    for word in ("--gpus", "--steps", "--warmup", "--frame-len", "--hop", "--no-sub", "--full", "--dump-outputs", "pipeline", "config2",
+                 "config3", "config4", "frontend"):
         assert word in out, word
 
 
@@ -144,3 +145,28 @@ def test_live_counter_csv_parsing(tmp_path):
     (d / "2_counter_collection.csv").write_text(head + row(9, k, "FETCH_SIZE", 1.0))
     with pytest.raises(RuntimeError):
         b.counter_values(str(tmp_path / "FETCH_SIZE"), b.LIVE_KERNELS["analyze"], ["FETCH_SIZE"])
+
+
+def test_dumped_outputs_are_float64_and_a_fixed_sample_beyond_the_limit(tmp_path):
+    """--dump-outputs: arrays under the limit are written whole; above it every array keeps the same seeded rows (arrays with
+    as many rows keep the same ones), the files stay under 64 MB together, and a second dump writes the same bytes."""
+    import numpy as np
+    import torch
+    b = _bench()
+    small = {"a": np.arange(12, dtype=np.int32).reshape(4, 3), "b": torch.arange(4, dtype=torch.float64)}
+    b.dump_outputs(str(tmp_path / "small"), small)
+    a = np.load(tmp_path / "small" / "a.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, small["a"]) and np.array_equal(np.load(tmp_path / "small" / "b.npy"), np.arange(4.0))
+    n = 400_000
+    rec = np.arange(n, dtype=np.float64)[:, None] * np.ones(24)                      # 77 MB: above the limit
+    big = {"records": rec, "status": torch.arange(3 * n, dtype=torch.int32).reshape(3, n).t()}
+    for run in ("x", "y"):
+        b.dump_outputs(str(tmp_path / run), big)
+    files = [tmp_path / "x" / f for f in ("records.npy", "status.npy")]
+    assert sum(os.path.getsize(f) for f in files) <= 64 << 20
+    r, s = np.load(files[0]), np.load(files[1])
+    assert 0 < r.shape[0] < n and r.shape[1] == 24 and s.shape == (r.shape[0], 3) and s.dtype == np.float64
+    rows = r[:, 0].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s[:, 0], rows) and np.array_equal(s[:, 2], rows + 2 * n)
+    for f in ("records.npy", "status.npy"):
+        assert (tmp_path / "x" / f).read_bytes() == (tmp_path / "y" / f).read_bytes()

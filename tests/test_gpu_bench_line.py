@@ -1,5 +1,5 @@
 """The line bench.py prints, end to end on the GPU (a short run): exactly one JSON line on stdout with the contract's fields,
-`roofline` with measured traffic, `cpu_baseline` with both legs."""
+`roofline` with measured traffic, `cpu_baseline` with both legs (--full); a plain run's line and the outputs it dumps."""
 import json
 import os
 import subprocess
@@ -33,7 +33,7 @@ def _bench(*args, env=None, detail=False, tmp=None):
 
 
 def test_default_workload_line():
-    d, full = _bench("--hours", "0.25", "--steps", "2", "--warmup", "1", "--cpu-seconds", "4", detail=True)
+    d, full = _bench("--full", "--hours", "0.25", "--steps", "2", "--warmup", "1", "--cpu-seconds", "4", detail=True)
     assert d["value"] == pytest.approx(full["value"], rel=1e-5) and d["roofline"]["frac"] == pytest.approx(full["roofline"]["frac"], rel=1e-5)
     assert set(d["sub_benchmarks"]) == {s["name"] for s in full["sub_benchmarks"]}
     assert all(not (isinstance(v, dict) and "error" in v) for v in d["sub_benchmarks"].values()), d["sub_benchmarks"]
@@ -85,6 +85,27 @@ def test_default_workload_line():
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and c["one_core"]["cores"] == 1 and c["sample"]
 
 
+def test_plain_run_times_the_headline_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full the line carries the headline and the roofline of its own timed steps, nothing measured elsewhere; the
+    outputs of the last timed step (one record and the three statuses per frame) are the same, bit for bit, in two runs."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        d = _bench("--hours", "0.25", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / run))
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f64" and d["unit"] == "frames/s"
+        assert d["value"] == pytest.approx(d["config"]["frames_per_gpu"] / (d["ms_per_step"] * 1e-3), rel=1e-4)
+        for k in ("cpu_baseline", "sub_benchmarks", "cross_rank_check", "parity", "live_traffic_error"):
+            assert k not in d, k
+        assert d["roofline"]["kernel"] == "analyze" and d["roofline"]["traffic_source"].startswith("committed")
+        dumps.append({n: np.load(tmp_path / run / f"{n}.npy") for n in ("records", "status")})
+    F = d["config"]["frames_per_gpu"]
+    rec, st = dumps[0]["records"], dumps[0]["status"]
+    assert rec.dtype == st.dtype == np.float64 and rec.shape == (F, d["config"]["record_bytes"] // 8) and st.shape == (F, 3)
+    assert np.all(st == 0)
+    for n in ("records", "status"):
+        assert dumps[0][n].tobytes() == dumps[1][n].tobytes(), n
+
+
 def test_config_workloads_pick_the_measured_dominant_kernel():
     d, full = _bench("--workload", "config4", "--frames", "200000", "--steps", "3", "--warmup", "1", "--no-cpu", detail=True)
     assert d["metric"].startswith("frames/sec (config4") and d["roofline"]["kernel"] in d["kernels_ms"]
@@ -97,7 +118,7 @@ def test_config_workloads_pick_the_measured_dominant_kernel():
 def test_speech_mode_line():
     """bench.py --signal speech: the pipeline on the tiled 44.1 kHz fixture under its own metric name, with the fast paths'
     fallback shares and the refinement's work counters beside the synthetic signal at the same shapes."""
-    d, full = _bench("--signal", "speech", "--hours", "0.1", "--steps", "1", "--warmup", "1", "--no-cpu", detail=True)
+    d, full = _bench("--full", "--signal", "speech", "--hours", "0.1", "--steps", "1", "--warmup", "1", "--no-cpu", detail=True)
     assert "real 44.1 kHz speech" in d["metric"] and d["data"].startswith("real speech") and d["value"] > 1e6
     assert d["speech"]["1103/441"]["speech"] == pytest.approx(d["value"], rel=1e-5)
     rows = full["speech"]["shapes"]
@@ -111,11 +132,11 @@ def test_cross_rank_check_rehearsal_on_one_gpu():
     """At N > 1 rank 0 re-analyses the frames around every shard cut on its own GPU and compares them, bit for bit, with the rows
     the ranks produced and the gather delivered (`cross_rank_check` in the bench line).  VBX_BENCH_SELFCHECK=1 runs the same code
     at N = 1 against an interior "cut": the check itself is exercised on every one-GPU box."""
-    d = _bench("--hours", "0.5", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-sub", env={"VBX_BENCH_SELFCHECK": "1"})
+    d = _bench("--full", "--hours", "0.5", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-sub", env={"VBX_BENCH_SELFCHECK": "1"})
     c = d["cross_rank_check"]
     assert "error" not in c, c
     assert c["rows_compared"] >= 7000 and c["rows_different"] == 0 and c["verdict"] == "bit-identical", c
-    assert "cross_rank_check" not in _bench("--hours", "0.25", "--steps", "1", "--warmup", "1", "--no-cpu", "--no-sub")
+    assert "cross_rank_check" not in _bench("--full", "--hours", "0.25", "--steps", "1", "--warmup", "1", "--no-cpu", "--no-sub")
 
 
 def test_two_ranks_without_a_second_gpu_fail_loudly_and_never_fall_back():
