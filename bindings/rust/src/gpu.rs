@@ -89,6 +89,36 @@ impl FrameStatus {
     }
 }
 
+/// Which LPC rows a context computes from frames (`VBX_LPC_POLICY_*`, include/voxbox_hip.h).
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub enum LpcPolicy {
+    /// the default: a conditioning probe, and the exact row where the f64 recursion is ill-conditioned
+    Exact,
+    /// no probe, no redo (what `VBX_LPC_EXACT=0` gives)
+    Plain,
+    /// the crate's own f64 arithmetic, bit for bit: the sequential lag fold and the plain recursion
+    Reference,
+}
+
+impl LpcPolicy {
+    pub fn code(self) -> i32 {
+        match self {
+            LpcPolicy::Exact => ffi::VBX_LPC_POLICY_EXACT,
+            LpcPolicy::Plain => ffi::VBX_LPC_POLICY_PLAIN,
+            LpcPolicy::Reference => ffi::VBX_LPC_POLICY_REFERENCE,
+        }
+    }
+
+    pub fn from_code(code: i32) -> Option<LpcPolicy> {
+        match code {
+            ffi::VBX_LPC_POLICY_EXACT => Some(LpcPolicy::Exact),
+            ffi::VBX_LPC_POLICY_PLAIN => Some(LpcPolicy::Plain),
+            ffi::VBX_LPC_POLICY_REFERENCE => Some(LpcPolicy::Reference),
+            _ => None,
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // context and device memory
 // ---------------------------------------------------------------------------------------------------------------
@@ -138,6 +168,17 @@ impl Gpu {
     /// Waits for everything queued on the context's stream.
     pub fn sync(&self) -> GpuResult<()> {
         self.check(unsafe { ffi::vbx_sync(self.raw) })
+    }
+
+    /// Sets which LPC rows this context computes from frames (initially `Plain` under `VBX_LPC_EXACT=0`, else `Exact`).
+    pub fn set_lpc_policy(&self, policy: LpcPolicy) -> GpuResult<()> {
+        self.check(unsafe { ffi::vbx_ctx_set_lpc_policy(self.raw, policy.code()) })
+    }
+
+    pub fn lpc_policy(&self) -> GpuResult<LpcPolicy> {
+        let mut code: i32 = 0;
+        self.check(unsafe { ffi::vbx_ctx_get_lpc_policy(self.raw, &mut code) })?;
+        LpcPolicy::from_code(code).ok_or_else(|| GpuError { code: ffi::VBX_E_INVALID, message: format!("unknown LPC policy {}", code) })
     }
 
     /// Uninitialised device memory for `len` elements.

@@ -27,4 +27,4 @@ pub mod ffi;
 pub mod gpu;
 
 pub use gpu::{find_formants, gather_plan, shard_range, shard_samples, AnalysisParams, Comm, DeviceBuf, FormantExtractor, FrameBatch, FrameStatus,
-              Frames, Gpu, GpuError, GpuEstimates, GpuFrame, PcmBatch, PolyBatch, Records, ResonanceRows, RootRow, RootRows};
+              Frames, Gpu, GpuError, GpuEstimates, GpuFrame, LpcPolicy, PcmBatch, PolyBatch, Records, ResonanceRows, RootRow, RootRows};

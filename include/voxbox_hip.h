@@ -212,7 +212,8 @@ int vbx_pitch_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_l
 /* ------------------------------------------------------------------ spectrum.rs: LPC */
 
 /* LPC::lpc(n_coeffs) on autocorrelation rows (Levinson-Durbin, src/spectrum.rs:63-92).
- * r: [F, r_stride] with r_stride >= n_coeffs+1; out: [F, n_coeffs+1] = [1, a1..ap]. */
+ * r: [F, r_stride] with r_stride >= n_coeffs+1; out: [F, n_coeffs+1] = [1, a1..ap].  The recursion runs in the source's order;
+ * only under VBX_LPC_POLICY_REFERENCE (below) is it the crate's operation for operation (otherwise multiply-adds may be fused). */
 int vbx_lpc_f64(vbx_ctx *ctx, const double *r, size_t n_frames, size_t r_stride,
                 size_t n_coeffs, double *out);
 /* LPC::lpc_mut(n_coeffs, ac, kc, tmp) (src/spectrum.rs:62-84): as vbx_lpc_f64, and out_kc: [F, n_coeffs]
@@ -227,10 +228,28 @@ int vbx_lpc_mut_f64(vbx_ctx *ctx, const double *r, size_t n_frames, size_t r_str
  * recursion repeated on lag sums moved by +-16 eps of r[0] -- and a row such a perturbation moves by more than 1e-6 in the parity
  * metric is recomputed from the frame's samples with the lag sums and the recursion in double-double: the exact row of the f64
  * frame, rounded once, where the reference's own f64 row (src/periodic.rs:284 + src/spectrum.rs:63-84) is 1e-6 .. 3e-4 from it
- * (frame_len <= 4096, n_coeffs <= 31; VBX_LPC_EXACT=0 turns it off). */
+ * (frame_len <= 4096, n_coeffs <= 31; VBX_LPC_EXACT=0 turns it off).  That is the default policy; a caller that
+ * must return the crate's own rows bit for bit sets VBX_LPC_POLICY_REFERENCE (below): then neither probe nor redo runs. */
 int vbx_autocorr_lpc_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len,
                          size_t stride, const double *window, size_t n_coeffs, int normalize,
                          double *out_r, double *out_lpc);
+
+/* Which LPC rows a context computes from frames (ABI 5, added): a per-context setting, read by vbx_autocorrelate_f64,
+ * vbx_autocorr_lpc_f64, vbx_lpc_f64 / vbx_lpc_mut_f64 and the LPC column of vbx_analyze_frames_f64 / _pcm16.
+ *  VBX_LPC_POLICY_EXACT     (default) the probe above + the double-double redo of the rows it lists: within 1e-6 of the EXACT row
+ *  VBX_LPC_POLICY_PLAIN     no probe, no redo: the rows of rounds 1-5 (what VBX_LPC_EXACT=0 gives) -- neither exact nor the crate's
+ *  VBX_LPC_POLICY_REFERENCE the crate's own f64 arithmetic, BIT FOR BIT: every lag sum the sequential fold of src/periodic.rs:276-289
+ *                           (seeded with x[0], each product rounded before the add), [normalize as src/waves.rs:60-76,] the recursion
+ *                           of src/spectrum.rs:63-84, no contraction -- at every frame length and order these entry points accept.
+ *                           The other columns of an analyze record are unchanged.  Costs the lag sums' FFT / matrix-core forms
+ *                           (DESIGN.md section 1 has the measured rates).
+ * The initial value comes from the environment: VBX_LPC_EXACT=0 gives PLAIN, anything else EXACT; set overrides it.
+ * set: VBX_E_INVALID for an unknown value. */
+#define VBX_LPC_POLICY_EXACT 0
+#define VBX_LPC_POLICY_PLAIN 1
+#define VBX_LPC_POLICY_REFERENCE 2
+int vbx_ctx_set_lpc_policy(vbx_ctx *ctx, int policy);
+int vbx_ctx_get_lpc_policy(const vbx_ctx *ctx, int *h_policy);
 
 /* LPC::lpc_praat(n_coeffs) per frame (Burg, src/spectrum.rs:94-146).  out: [F, n_coeffs]
  * (no leading 1, sign-flipped as the reference); status[F]: VBX_FRAME_ERR_LPC when denum <= 0.

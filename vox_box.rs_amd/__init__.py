@@ -20,5 +20,6 @@ from .voxbox import (  # noqa: F401
     ShardPlan, shard_plan, shard_local_segments, mfcc_bins,
     GATHER_NONE, GATHER_RECV, GATHER_SEND, GATHER_COPY,
     MAX_PITCH_CANDIDATES, pitch_max_candidates,
+    LPC_POLICY_EXACT, LPC_POLICY_PLAIN, LPC_POLICY_REFERENCE,
 )
 from . import shard  # noqa: F401

@@ -63,7 +63,9 @@ struct vbx_ctx {
     int last_mfcc_interp = 0;                             // the last vbx_mfcc_f64 call took the interpolated form (tests)
     int last_spectral_split = 0;                          // the last fused / pitch call ran as two kernels (tests)
     int mfcc_defer = 1;                                   // VBX_MFCC_DEFER=0: log10 + DCT of the fused call's MFCC rows inside the frame's wavefront (rounds 2-5; A/B)
-    int lpc_exact = 1;                                    // VBX_LPC_EXACT=0: no conditioning probe, no double-double redo of flagged LPC rows (rounds 1-5; tests, A/B)
+    int lpc_policy = VBX_LPC_POLICY_EXACT;                // VBX_LPC_POLICY_*; VBX_LPC_EXACT=0 initialises PLAIN (no conditioning probe, no double-double redo:
+                                                          //   the rows of rounds 1-5), vbx_ctx_set_lpc_policy overrides
+    bool lpc_list_armed = false;                          // the last call that writes LPC rows from frames armed the probe's list (vbx_internal_last_lpc_exact_count)
     int pow2_split = -1;                                  // VBX_POW2_SPLIT=0: the 4096-point plan as ONE kernel (transforms and refinement fused, as before round 5; tests, A/B)
     int mfcc_interp = -1;                                 // VBX_MFCC_INTERP=0: never (the chirp-z kernel beside the fused one, as before round 5; tests, A/B)
     std::map<std::pair<size_t, double>, std::pair<int32_t *, double *>> resample_tabs;   // (n, ratio) -> (index, fraction)
@@ -421,6 +423,7 @@ int get_slopes_dev(vbx_ctx *ctx, size_t n, size_t k, double lo, double hi, doubl
 int check_frames(vbx_ctx *ctx, const char *fn, const void *x, size_t n_frames, size_t frame_len, size_t stride,
                  size_t max_len = VBX_MAX_FRAME_LEN) {
     if (!ctx) return fail(nullptr, VBX_E_INVALID, std::string(fn) + ": null context");
+    ctx->lpc_list_armed = false;   // every frame-batch call: only one that arms the LPC probe's list (below) sets it again
     if (n_frames == 0) return 1;   // empty batch: nothing to do
     if (!x) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": null frame pointer");
     if (frame_len < 1 || frame_len > max_len)
@@ -489,6 +492,20 @@ int vbx_internal_device(vbx_ctx *ctx) { return ctx ? ctx->device : 0; }
 
 int vbx_abi_version(void) { return VBX_ABI_VERSION; }
 
+int vbx_ctx_set_lpc_policy(vbx_ctx *ctx, int policy) {
+    VBX_REQUIRE(ctx, ctx != nullptr, "null context");
+    VBX_REQUIRE(ctx, policy == VBX_LPC_POLICY_EXACT || policy == VBX_LPC_POLICY_PLAIN || policy == VBX_LPC_POLICY_REFERENCE,
+                "vbx_ctx_set_lpc_policy: unknown policy");
+    ctx->lpc_policy = policy;
+    return VBX_SUCCESS;
+}
+
+int vbx_ctx_get_lpc_policy(const vbx_ctx *ctx, int *h_policy) {
+    if (!ctx || !h_policy) return fail(const_cast<vbx_ctx *>(ctx), VBX_E_INVALID, "vbx_ctx_get_lpc_policy: null argument");
+    *h_policy = ctx->lpc_policy;
+    return VBX_SUCCESS;
+}
+
 int vbx_ctx_create(vbx_ctx **out, int device, void *hip_stream) {
     if (!out) return fail(nullptr, VBX_E_INVALID, "vbx_ctx_create: null out");
     *out = nullptr;
@@ -511,7 +528,7 @@ int vbx_ctx_create(vbx_ctx **out, int device, void *hip_stream) {
     { const char *e = std::getenv("VBX_MFCC_MFMA"); ctx->mfcc_force_mfma = e && e[0] == '1'; }
     { const char *e = std::getenv("VBX_MFCC_CZT"); ctx->mfcc_czt = e ? (e[0] == '1' ? 1 : 0) : -1; }
     { const char *e = std::getenv("VBX_MFCC_DEFER"); ctx->mfcc_defer = (e && e[0] == '0') ? 0 : 1; }
-    { const char *e = std::getenv("VBX_LPC_EXACT"); ctx->lpc_exact = (e && e[0] == '0') ? 0 : 1; }
+    { const char *e = std::getenv("VBX_LPC_EXACT"); ctx->lpc_policy = (e && e[0] == '0') ? VBX_LPC_POLICY_PLAIN : VBX_LPC_POLICY_EXACT; }
     { const char *e = std::getenv("VBX_POW2_SPLIT"); ctx->pow2_split = e ? (e[0] == '0' ? 0 : 1) : -1; }
     { const char *e = std::getenv("VBX_MFCC_INTERP"); ctx->mfcc_interp = e ? (e[0] == '0' ? 0 : 1) : -1; }
     { const char *e = std::getenv("VBX_MFCC_CZT_SPLIT"); ctx->mfcc_czt_split = e != nullptr && e[0] == '1'; }
@@ -757,6 +774,13 @@ int vbx_autocorrelate_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t
     VBX_REQUIRE(ctx, out != nullptr, "null output");
     VBX_REQUIRE(ctx, n_lags >= 1 && n_lags <= frame_len, "n_lags must be in [1, frame_len] (the reference panics beyond)");
     VBX_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->lpc_policy == VBX_LPC_POLICY_REFERENCE) {
+        // every lag the crate's sequential fold (k_lpc_ref.hip) instead of the FFT / matrix-core / register forms
+        VBX_REQUIRE(ctx, frame_len <= 0x7fffffffull, "frame_len too large");
+        { Prof p(ctx, "autocorr_ref"); launch_lpc_ref(ctx->stream, x, false, (long)n_frames, (int)frame_len, (long)stride, window, (int)n_lags, 0, 0,
+                                                      out, (long)n_lags, nullptr, 0); }
+        return check_launch(ctx, __func__);
+    }
     rc = run_autocorrelate(ctx, ctx->stream, x, n_frames, frame_len, stride, window, n_lags, out);
     if (rc != VBX_SUCCESS) return rc;
     return check_launch(ctx, __func__);
@@ -814,12 +838,13 @@ static int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, c
     // LPC rows: levinson_rows_kernel_t (k_lpc.hip) lists the frames whose Levinson row a few eps of lag-sum rounding can move by more
     // than 1e-6; lpc_exact_list_kernel redoes those in double-double.  VBX_LPC_EXACT=0: no probe, the rows of rounds 1-5 (A/B, tests).
     L.lpc_list = nullptr; L.lpc_count = nullptr;
-    if (L.out_lpc != nullptr && ctx->lpc_exact) {
+    if (L.out_lpc != nullptr && ctx->lpc_policy == VBX_LPC_POLICY_EXACT) {
         void *lw = nullptr;
         rc = ws_get(ctx, vbx_ctx::WS_LPC_LIST, ((size_t)L.F + 4) * sizeof(int32_t), &lw);
         if (rc != VBX_SUCCESS) return rc;
         L.lpc_count = (int32_t *)lw; L.lpc_list = (int32_t *)lw + 4;
         VBX_HIP(ctx, hipMemsetAsync(L.lpc_count, 0, sizeof(int32_t), st));
+        ctx->lpc_list_armed = true;
     }
     // the 4096-point plan runs as two kernels with the lag curves in a scratch buffer between them (vbx_spectral.hpp, SP_ANALYZE_SPLIT):
     // batches of up to 131,072 frames (~10 KB each)
@@ -865,6 +890,14 @@ static int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, c
             Prof p(ctx, "lpc_exact_list", st);
             const int cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
             launch_lpc_exact_list(st, L.lpc_list, L.lpc_count, cus, L.x, L.n, L.stride, L.window, L.pcm, SPECTRAL_LPC_ORDER, L.out_lpc, L.lpc_ld);
+        }
+        if (ctx->lpc_policy == VBX_LPC_POLICY_REFERENCE) {
+            // the crate's rows (k_lpc_ref.hip) over the column, after the kernels above on the same stream: the fused kernel and the
+            // Levinson pass run as under every policy (their instantiations, and so every other column, unchanged), only the LPC
+            // row is replaced
+            Prof p(ctx, "lpc_ref", st);
+            launch_lpc_ref(st, L.x, L.pcm != 0, L.F, L.n, L.stride, L.window, SPECTRAL_LPC_ORDER + 1, SPECTRAL_LPC_ORDER, 0, nullptr, 0,
+                           L.out_lpc, L.lpc_ld);
         }
     }
     return check_launch(ctx, "launch_spectral");
@@ -955,6 +988,13 @@ int vbx_lpc_mut_f64(vbx_ctx *ctx, const double *r, size_t n_frames, size_t r_str
     VBX_REQUIRE(ctx, n_coeffs >= 1 && n_coeffs <= VBX_MAX_LPC_ORDER && r_stride >= n_coeffs + 1, "bad order / stride");
     VBX_REQUIRE(ctx, n_frames <= 0x7fffffffull, "too many rows");
     VBX_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->lpc_policy == VBX_LPC_POLICY_REFERENCE) {
+        // the recursion with contraction off, operation for operation src/spectrum.rs:63-84 (the default kernel lets the compiler fuse
+        // its multiply-adds)
+        Prof p(ctx, "levinson_ref_rows");
+        launch_levinson_ref_rows(ctx->stream, r, (long)n_frames, (long)r_stride, (int)n_coeffs, out_ac, (long)n_coeffs + 1, out_kc);
+        return check_launch(ctx, __func__);
+    }
     { Prof p(ctx, "levinson_rows"); launch_levinson_rows(ctx->stream, r, (long)n_frames, (long)r_stride, (int)n_coeffs, out_ac, (long)n_coeffs + 1, out_kc); }
     return check_launch(ctx, __func__);
 }
@@ -971,15 +1011,24 @@ static int run_autocorr_lpc(vbx_ctx *ctx, hipStream_t st, const double *x, size_
     VBX_REQUIRE(ctx, lpc_ld >= n_coeffs + 1, "LPC rows must hold n_coeffs + 1 entries");
     const int n_lags = (int)n_coeffs + 1;
     int rc;
+    if (ctx->lpc_policy == VBX_LPC_POLICY_REFERENCE) {
+        // the crate's own arithmetic (k_lpc_ref.hip): fold, [normalize,] recursion, bit for bit; no probe, no redo
+        VBX_REQUIRE(ctx, frame_len <= 0x7fffffffull, "frame_len too large");
+        { Prof p(ctx, "lpc_ref", st);
+          launch_lpc_ref(st, x, false, (long)n_frames, (int)frame_len, (long)stride, window, n_lags, (int)n_coeffs, normalize, out_r, n_lags,
+                         out_lpc, (long)lpc_ld); }
+        return check_launch(ctx, "vbx_autocorr_lpc_f64");
+    }
     // LPC rows: a conditioning probe lists the frames whose row a few eps of lag-sum rounding can move by more than 1e-6; those are
     // redone from the frame in double-double (k_lpc_exact.hip).  VBX_LPC_EXACT=0: the rows of rounds 1-5.
     int32_t *lpc_list = nullptr, *lpc_count = nullptr;
-    if (out_lpc != nullptr && ctx->lpc_exact && lpc_exact_supported((int)frame_len, (int)n_coeffs)) {
+    if (out_lpc != nullptr && ctx->lpc_policy == VBX_LPC_POLICY_EXACT && lpc_exact_supported((int)frame_len, (int)n_coeffs)) {
         void *lw = nullptr;
         rc = ws_get(ctx, vbx_ctx::WS_LPC_LIST, (n_frames + 4) * sizeof(int32_t), &lw);
         if (rc != VBX_SUCCESS) return rc;
         lpc_count = (int32_t *)lw; lpc_list = (int32_t *)lw + 4;
         VBX_HIP(ctx, hipMemsetAsync(lpc_count, 0, sizeof(int32_t), st));
+        ctx->lpc_list_armed = true;
     }
     auto redo = [&]() {
         if (lpc_list == nullptr) return;
@@ -2135,11 +2184,12 @@ int vbx_internal_last_unsure_count(vbx_ctx *ctx, int32_t *h_count) {
 }
 
 // internal (tests, bench): how many frames of the last fused analyze call the Levinson probe handed to the double-double
-// recursion (k_lpc_exact.hip); -1 if the call had no LPC rows or the probe is off
+// recursion (k_lpc_exact.hip); -1 if the last frame-batch call (every entry point that takes frames: check_frames clears the
+// flag) armed no probe list -- no LPC rows, an unsupported shape, or a policy other than VBX_LPC_POLICY_EXACT
 int vbx_internal_last_lpc_exact_count(vbx_ctx *ctx, int32_t *h_count) {
     VBX_REQUIRE(ctx, ctx && h_count, "null argument");
     *h_count = -1;
-    if (!ctx->ws[vbx_ctx::WS_LPC_LIST] || !ctx->lpc_exact) return VBX_SUCCESS;
+    if (!ctx->ws[vbx_ctx::WS_LPC_LIST] || !ctx->lpc_list_armed) return VBX_SUCCESS;
     VBX_HIP(ctx, hipSetDevice(ctx->device));
     VBX_HIP(ctx, hipDeviceSynchronize());
     VBX_HIP(ctx, hipMemcpy(h_count, ctx->ws[vbx_ctx::WS_LPC_LIST], sizeof(int32_t), hipMemcpyDeviceToHost));

@@ -236,6 +236,13 @@ bool lpc_exact_supported(int n, int p);                               // frames 
 void launch_lpc_exact_list(hipStream_t s, const int32_t *frame_list, const int32_t *list_count, int cus, const double *x, int n,
                            long stride, const double *window, bool pcm, int p, double *out_lpc, long lpc_ld);
 
+// k_lpc_ref.hip (VBX_LPC_POLICY_REFERENCE): the crate's own f64 arithmetic, bit for bit -- lag sums as the sequential fold of
+// src/periodic.rs:276-289, [normalize,] the recursion of src/spectrum.rs:63-84, no contraction.  p == 0: lag sums only
+// (n_lags <= n, out_r: [F, r_ld]); p >= 1: n_lags = p + 1, out_r (optional) and out_lpc [F, lpc_ld].  pcm: x is 16-bit PCM.
+void launch_lpc_ref(hipStream_t s, const void *x, bool pcm, long F, int n, long stride, const double *window, int n_lags, int p,
+                    int normalize, double *out_r, long r_ld, double *out_lpc, long lpc_ld);
+void launch_levinson_ref_rows(hipStream_t s, const double *r, long rows, long r_stride, int p, double *out, long out_ld, double *out_kc);
+
 // the f32 instantiation (Sample = f32): the same kernels with float frames and float outputs
 void launch_autocorr_fewlags_f32(hipStream_t s, const float *x, long F, int n, long stride, const float *window,
                                  int n_lags, int normalize, float *out_r, float *out_lpc, long lpc_ld = 0);

@@ -47,6 +47,9 @@ constexpr size_t MAX_RESONANCES = VBX_MAX_RESONANCES;                       // l
 inline const double *male_formant_estimates() { return VBX_MALE_FORMANT_ESTIMATES; }     // lib.rs:27
 inline const double *female_formant_estimates() { return VBX_FEMALE_FORMANT_ESTIMATES; } // lib.rs:28
 
+// which LPC rows a context computes from frames (vbx_ctx_set_lpc_policy): Reference = the crate's own f64 rows, bit for bit
+enum class LpcPolicy : int { Exact = VBX_LPC_POLICY_EXACT, Plain = VBX_LPC_POLICY_PLAIN, Reference = VBX_LPC_POLICY_REFERENCE };
+
 class Context {
 public:
     explicit Context(int device = 0, void *hip_stream = nullptr) {
@@ -59,6 +62,12 @@ public:
     vbx_ctx *get() const { return ctx_; }
     void check(int rc) const { if (rc != VBX_SUCCESS) throw Error(rc, vbx_last_error(ctx_)); }
     void sync() const { check(vbx_sync(ctx_)); }
+    void set_lpc_policy(LpcPolicy p) const { check(vbx_ctx_set_lpc_policy(ctx_, static_cast<int>(p))); }
+    LpcPolicy lpc_policy() const {
+        int p = 0;
+        check(vbx_ctx_get_lpc_policy(ctx_, &p));
+        return static_cast<LpcPolicy>(p);
+    }
 private:
     vbx_ctx *ctx_ = nullptr;
 };

@@ -23,6 +23,8 @@ MALE_FORMANT_ESTIMATES = (320.0, 1440.0, 2760.0, 3200.0)      # src/lib.rs:27
 FEMALE_FORMANT_ESTIMATES = (480.0, 1760.0, 3200.0, 3520.0)    # src/lib.rs:28
 MAX_RESONANCES = 32
 MAX_PITCH_CANDIDATES = 1026           # VBX_MAX_PITCH_CANDIDATES
+# VBX_LPC_POLICY_*: which LPC rows a context computes from frames (include/voxbox_hip.h, VoxBox.lpc_policy)
+LPC_POLICY_EXACT, LPC_POLICY_PLAIN, LPC_POLICY_REFERENCE = 0, 1, 2
 
 
 def pitch_max_candidates(frame_len):
@@ -116,6 +118,8 @@ def load_library():
         "vbx_abi_version": (C.c_int, []),
         "vbx_ctx_create": (C.c_int, [C.POINTER(vp), i32, vp]),
         "vbx_ctx_destroy": (None, [vp]),
+        "vbx_ctx_set_lpc_policy": (C.c_int, [vp, i32]),
+        "vbx_ctx_get_lpc_policy": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "vbx_sync": (C.c_int, [vp]),
         "vbx_last_error": (C.c_char_p, [vp]),
         "vbx_device_info": (C.c_int, [vp, C.c_char_p, sz, C.POINTER(C.c_int)]),
@@ -415,7 +419,7 @@ def _ptr(a):
 class VoxBox:
     """One libvoxbox_hip context = one GPU + one HIP stream."""
 
-    def __init__(self, device=0, stream=None):
+    def __init__(self, device=0, stream=None, lpc_policy=None):
         self.L = load_library()
         self._allocs = set()
         ctx = C.c_void_p()
@@ -425,6 +429,20 @@ class VoxBox:
             raise VoxBoxError(f"vbx_ctx_create failed ({rc}): {msg.decode() if msg else ''}")
         self.ctx = ctx
         self._tables = {}
+        if lpc_policy is not None:
+            self.lpc_policy = lpc_policy
+
+    @property
+    def lpc_policy(self):
+        """LPC_POLICY_EXACT (default: the exact row where the f64 recursion is ill-conditioned), LPC_POLICY_PLAIN, or
+        LPC_POLICY_REFERENCE (the crate's own f64 rows, bit for bit).  Initialised from VBX_LPC_EXACT (0: PLAIN)."""
+        v = C.c_int(0)
+        self._check(self.L.vbx_ctx_get_lpc_policy(self.ctx, C.byref(v)))
+        return int(v.value)
+
+    @lpc_policy.setter
+    def lpc_policy(self, policy):
+        self._check(self.L.vbx_ctx_set_lpc_policy(self.ctx, int(policy)))
 
     # -- plumbing ---------------------------------------------------------------------
     def _check(self, rc):
@@ -1018,7 +1036,7 @@ class VoxBox:
 
     def last_lpc_exact_count(self):
         """Frames of the last fused analyze call whose Levinson row the conditioning probe handed to the double-double recursion
-        (k_lpc_exact.hip); -1 if the call wrote no LPC rows or VBX_LPC_EXACT=0."""
+        (k_lpc_exact.hip); -1 if the call wrote no LPC rows or armed no probe (a policy other than LPC_POLICY_EXACT)."""
         n = C.c_int32(0)
         self._check(self.L.vbx_internal_last_lpc_exact_count(self.ctx, C.byref(n)))
         return int(n.value)
