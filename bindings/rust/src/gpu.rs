@@ -119,6 +119,59 @@ impl LpcPolicy {
     }
 }
 
+/// The path cost of [`FrameBatch::pitch_path`] (`vbx_pitch_path_params`).  `Default` is Praat's "To Pitch (ac)" set at a
+/// 10 ms hop.  `PitchExtractor::new(candidates, voiced_unvoiced_cost, voicing_threshold)` (src/periodic.rs:328) stores the
+/// two fields of the same names and never reads them; [`PitchPathParams::from_extractor`] is that constructor here.  The
+/// crate's iterator (`candidates[t][0]`, src/periodic.rs:337-353) stays what `pitch_all`'s column 0 is.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct PitchPathParams {
+    pub voicing_threshold: f64,
+    pub silence_threshold: f64,
+    pub octave_cost: f64,
+    pub octave_jump_cost: f64,
+    pub voiced_unvoiced_cost: f64,
+    pub ceiling_hz: f64,
+    /// hop / sample_rate, seconds
+    pub time_step: f64,
+    /// 0: the library's choice; >= the frame count: one sequential scan per segment (same result)
+    pub chunk_frames: usize,
+}
+
+impl Default for PitchPathParams {
+    fn default() -> Self {
+        PitchPathParams {
+            voicing_threshold: 0.45,
+            silence_threshold: 0.03,
+            octave_cost: 0.01,
+            octave_jump_cost: 0.35,
+            voiced_unvoiced_cost: 0.14,
+            ceiling_hz: 600.0,
+            time_step: 0.01,
+            chunk_frames: 0,
+        }
+    }
+}
+
+impl PitchPathParams {
+    /// `PitchExtractor::new(_, voiced_unvoiced_cost, voicing_threshold)`'s two arguments, Praat's values for the rest.
+    pub fn from_extractor(voiced_unvoiced_cost: f64, voicing_threshold: f64) -> Self {
+        PitchPathParams { voiced_unvoiced_cost, voicing_threshold, ..Default::default() }
+    }
+
+    fn raw(&self) -> ffi::VbxPitchPathParams {
+        ffi::VbxPitchPathParams {
+            voicing_threshold: self.voicing_threshold,
+            silence_threshold: self.silence_threshold,
+            octave_cost: self.octave_cost,
+            octave_jump_cost: self.octave_jump_cost,
+            voiced_unvoiced_cost: self.voiced_unvoiced_cost,
+            ceiling_hz: self.ceiling_hz,
+            time_step: self.time_step,
+            chunk_frames: self.chunk_frames,
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // context and device memory
 // ---------------------------------------------------------------------------------------------------------------
@@ -497,6 +550,53 @@ impl<'g> FrameBatch<'g> {
             )
         })?;
         Ok((out.to_vec()?, status.to_vec()?))
+    }
+
+    /// max |x| of every frame's samples (no window; NaN samples ignored): the `local_peak` of [`FrameBatch::pitch_path`].
+    pub fn frame_peak(&self) -> GpuResult<Vec<f64>> {
+        let out = self.gpu.alloc::<f64>(self.n_frames)?;
+        self.frame_peak_into(&out)?;
+        out.to_vec()
+    }
+
+    fn frame_peak_into(&self, out: &DeviceBuf<'g, f64>) -> GpuResult<()> {
+        self.gpu.check(unsafe {
+            ffi::vbx_frame_peak_f64(self.gpu.raw, self.samples.as_ptr(), self.n_frames, self.frame_len, self.stride, out.as_mut_ptr())
+        })
+    }
+
+    /// The third pass `Pitched::pitch` describes (src/periodic.rs:394-395) and `PitchExtractor` (src/periodic.rs:320-354) does not
+    /// run: `pitch(sample_rate, threshold, _, _, min, max)`'s first `kmax` candidates of every frame, the frames' peaks, and one
+    /// path per segment through them (`seg_start`: ascending utterance starts, empty = one utterance) that maximises candidate
+    /// strength minus octave-jump and voicing-change costs (Boersma 1993; the definition is in include/voxbox_hip.h).  Returns
+    /// the chosen `Pitch` of every frame (`frequency` 0 and the unvoiced score where the path is unvoiced) and its list position
+    /// (-1: the unvoiced state the path appends).  `PitchExtractor::new(_, voiced_unvoiced_cost, voicing_threshold)` is
+    /// `PitchPathParams::from_extractor(voiced_unvoiced_cost, voicing_threshold)`.  Everything stays on the device in between.
+    pub fn pitch_path(&self, sample_rate: f64, threshold: f64, min: f64, max: f64, kmax: usize, seg_start: &[i64],
+                      params: &PitchPathParams) -> GpuResult<(Vec<Pitch<f64>>, Vec<i32>)> {
+        let f = self.n_frames;
+        let cand = self.gpu.alloc::<ffi::VbxPitch>(f * kmax)?;
+        let count = self.gpu.alloc::<i32>(f)?;
+        let status = self.gpu.alloc::<i32>(f)?;
+        let peak = self.gpu.alloc::<f64>(f)?;
+        let path = self.gpu.alloc::<ffi::VbxPitch>(f)?;
+        let index = self.gpu.alloc::<i32>(f)?;
+        self.gpu.check(unsafe {
+            ffi::vbx_pitch_f64(
+                self.gpu.raw, self.samples.as_ptr(), f, self.frame_len, self.stride, self.win_ptr(), sample_rate, threshold, min, max, kmax,
+                cand.as_mut_ptr(), count.as_mut_ptr(), status.as_mut_ptr(),
+            )
+        })?;
+        self.frame_peak_into(&peak)?;
+        let raw = params.raw();
+        let seg = if seg_start.is_empty() { ptr::null() } else { seg_start.as_ptr() };
+        self.gpu.check(unsafe {
+            ffi::vbx_pitch_path_f64(
+                self.gpu.raw, cand.as_ptr(), count.as_ptr(), status.as_ptr(), f, kmax, peak.as_ptr(), seg, seg_start.len(), &raw,
+                path.as_mut_ptr(), index.as_mut_ptr(),
+            )
+        })?;
+        Ok((path.to_vec()?.iter().map(|p| Pitch::new(p.frequency, p.strength)).collect(), index.to_vec()?))
     }
 
     /// `RMS::rms` of every frame (src/waves.rs:10-23).

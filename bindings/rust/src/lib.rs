@@ -12,6 +12,8 @@
 //! * **fused** (`FrameBatch::analyze` / `PcmBatch::analyze`): pitch + LPC + find_formants + MFCC of every frame as one
 //!   record per frame from one call (`vbx_analyze_frames_f64` / `_pcm16`), the buffer [`gpu::Comm::gather_records`] sends
 //!   to rank 0 when the recording is sharded over the GPUs of a node ([`gpu::shard_range`], [`gpu::shard_samples`]);
+//! * **pitch path** (`FrameBatch::pitch_path`): the third pass of `Pitched::pitch` that `PitchExtractor` leaves out --
+//!   one pitch per frame from the candidate lists, Boersma's path cost, exact and in parallel on the device;
 //! * **tracker** (`ResonanceRows::estimate_formants_all`, `ResonanceRows::formant_extractor`): `EstimateFormants` /
 //!   `FormantExtractor` (src/spectrum.rs:216-369) over resonance rows on the device;
 //! * **drop-in** (`FrameBatch::frames()` yields [`gpu::GpuFrame`] views that implement the crate's traits):
@@ -27,4 +29,4 @@ pub mod ffi;
 pub mod gpu;
 
 pub use gpu::{find_formants, gather_plan, shard_range, shard_samples, AnalysisParams, Comm, DeviceBuf, FormantExtractor, FrameBatch, FrameStatus,
-              Frames, Gpu, GpuError, GpuEstimates, GpuFrame, LpcPolicy, PcmBatch, PolyBatch, Records, ResonanceRows, RootRow, RootRows};
+              Frames, Gpu, GpuError, GpuEstimates, GpuFrame, LpcPolicy, PcmBatch, PitchPathParams, PolyBatch, Records, ResonanceRows, RootRow, RootRows};

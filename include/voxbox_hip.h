@@ -209,6 +209,50 @@ int vbx_pitch_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_l
                   const double *window, double sample_rate, double threshold, double fmin, double fmax,
                   size_t kmax, vbx_pitch *out_cand, int32_t *out_count, int32_t *status);
 
+/* The pitch PATH (added in ABI 5): the "third pass" of src/periodic.rs:394-395 -- "a path through these candidates that maximizes
+ * both the smoothness of the pitch contour and the strength of the pitches" -- which PitchExtractor::new(candidates,
+ * voiced_unvoiced_cost, voicing_threshold) (src/periodic.rs:320-354) takes the parameters of but never runs (its iterator
+ * returns candidates[t][0]).  Boersma's (1993) path cost over the lists vbx_pitch_f64 writes, one path per segment.
+ * Definition (the contract; IEEE binary64, round to nearest, in exactly this order, no fused multiply-add):
+ *   host constants  corr = 0.01 / time_step, cvu = voiced_unvoiced_cost * corr, cj = octave_jump_cost * corr,
+ *                   Lc = log2(ceiling_hz), q = silence_threshold / (1 + voicing_threshold)
+ *   states of t     the first m_t = min(count[t], kmax) entries of the frame's row, in list order; if none of them has
+ *                   frequency 0, one unvoiced state is appended (reported as index -1).  A frame whose status is not
+ *                   VBX_FRAME_OK has only that unvoiced state.  A state is voiced iff its frequency is > 0.
+ *   lambda_t(s)     voiced (f, a): a - octave_cost * (Lc - log2 f);  unvoiced: u_t = voicing_threshold + max(0, 2 - rho_t / q),
+ *                   rho_t = local_peak[t] / P (P = the largest local_peak of the frame's segment; rho = 0 when P == 0) -- the use
+ *                   the crate's unused local_peak / global_peak arguments of Pitched::pitch (src/periodic.rs:356-358) point at;
+ *                   u_t = voicing_threshold when local_peak is NULL or silence_threshold == 0
+ *   c(p -> s)       both unvoiced 0; exactly one voiced cvu; both voiced cj * |log2 f_p - log2 f_s|
+ *   recursion       e_0 = lambda_0, D_0 = e_0 - max e_0; for t >= 1: a(s) = max_p (D_{t-1}(p) - c(p -> s)), psi_t(s) = the first
+ *                   p in state order attaining it, e_t(s) = a(s) + lambda_t(s), D_t(s) = e_t(s) - max_s' e_t(s')
+ *   path            ends in the first state with D_{T-1} = 0, traced back through psi.
+ * out_path[t] = the chosen list entry for a voiced state, {0.0, u_t} for an unvoiced one; out_index[t] (optional) = the chosen
+ * state's list position, -1 for the appended unvoiced state.  cand / count / status are what vbx_pitch_f64 writes with the same
+ * kmax (1 <= kmax <= 63: at most 64 states); status may be NULL (every frame OK); h_seg_start / n_segments follow
+ * vbx_analyze_frames_f64 (NULL = one utterance).  The scan runs in speculative chunks with exact repair: the result is the
+ * sequential scan's, bit for bit, for any chunk_frames (DESIGN.md "Pitch path").  Asynchronous on the context's stream.
+ * VBX_E_INVALID: kmax 0 or > 63, a negative or non-finite parameter, time_step <= 0, ceiling_hz <= 0, silence_threshold > 0
+ * with a NULL local_peak, a bad segment list.
+ * PitchExtractor::new's arguments map onto voiced_unvoiced_cost and voicing_threshold; the rest default to Praat's "To Pitch (ac)"
+ * values: silence 0.03, voicing 0.45, octave 0.01, octave-jump 0.35, voiced/unvoiced 0.14, ceiling 600 Hz. */
+typedef struct {
+    double voicing_threshold, silence_threshold, octave_cost, octave_jump_cost, voiced_unvoiced_cost;
+    double ceiling_hz, time_step;   /* time_step = hop / sample_rate, seconds */
+    size_t chunk_frames;            /* 0: the library's choice; >= n_frames: one sequential scan per segment */
+} vbx_pitch_path_params;
+/* max |x| per frame of the batch (no window), NaN samples ignored (an all-NaN frame gives NaN): the local_peak of the path.
+ * out_peak: [F]. */
+int vbx_frame_peak_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
+                       double *out_peak);
+int vbx_pitch_path_f64(vbx_ctx *ctx, const vbx_pitch *cand, const int32_t *count, const int32_t *status,
+                       size_t n_frames, size_t kmax, const double *local_peak,
+                       const int64_t *h_seg_start, size_t n_segments, const vbx_pitch_path_params *h_params,
+                       vbx_pitch *out_path, int32_t *out_index);
+/* chunks the repair rounds and the final sweep of the last vbx_pitch_path_f64 call redid (synchronises the stream); -1 if the
+ * context's last frame-batch or path call was not a path call */
+int vbx_internal_last_path_chunks_redone(vbx_ctx *ctx, int64_t *h_out);
+
 /* ------------------------------------------------------------------ spectrum.rs: LPC */
 
 /* LPC::lpc(n_coeffs) on autocorrelation rows (Levinson-Durbin, src/spectrum.rs:63-92).

@@ -1,0 +1,416 @@
+// k_pitch_path.hip -- the pitch path over the candidate lists of vbx_pitch_f64 (Boersma 1993 path cost; the "third pass"
+// src/periodic.rs:394-395 describes and PitchExtractor, src/periodic.rs:320-354, takes the parameters of but never runs).
+//
+// The definition (include/voxbox_hip.h, DESIGN.md "Pitch path") is a Viterbi recursion over at most kmax + 1 <= 64 states per
+// frame, normalised so that the leader of every frame is exactly 0.  All arithmetic is IEEE binary64 in the order written
+// there, with no fused multiply-add.
+//
+// Parallel form (the same scheme as the formant tracker's chunked scan, k_tracker.hip):
+//   peak    pp_chunk_peak_kernel / pp_seg_peak_kernel   P = max local_peak per segment (only when u_t uses it)
+//   A       pp_spec_kernel    one lane GROUP of G = pow2 >= states lanes per chunk of C frames (64 / G groups per wavefront):
+//                             warm up over the W frames before the chunk from a fresh start, scan the chunk, store psi [F][G]
+//                             (uint8), the entry state D and the exit state D.  Lane s owns state s; the predecessor loop reads
+//                             {D(p), log2 f_p} of the previous frame from LDS (one broadcast ds_read_b128 per p).
+//   B       pp_check_kernel / pp_repair_kernel (rounds)  a chunk whose entry D is not bit for bit its predecessor's exit D is
+//                             redone from that exit, in parallel.
+//   S       pp_mask_kernel + pp_sweep_kernel   one group per segment walks the chunks in order and redoes what is still
+//                             inconsistent: this pass alone makes psi the sequential scan's; the rounds leave it little to do.
+//   back    pp_map_kernel     per chunk, every lane walks psi back through the NEXT chunk of the segment (staged in LDS):
+//                             the map  state at this chunk's last frame <- state at the next chunk's last frame.
+//           pp_compose_kernel a log-depth suffix composition of those maps (the last chunk of a segment holds the constant
+//                             map to the segment's leader) gives every chunk's true end state.
+//           pp_write_kernel   per chunk, the group walks back from that state and writes out_path / out_index.
+#include "vbx_kernels.hpp"
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#pragma clang fp contract(off)   // the definition's arithmetic, operation for operation: no multiply-add may be fused
+
+namespace vbx {
+
+// ---- frame peak: max |x| per frame, NaN samples ignored (one wavefront per frame, coalesced) --------------------------------
+__global__ __launch_bounds__(256) void frame_peak_kernel(const double *__restrict__ x, long F, long n, long stride,
+                                                         double *__restrict__ out) {
+    const long f = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (f >= F) return;                                        // wavefront-uniform
+    const double *row = x + f * stride;
+    double m = __builtin_nan("");                              // fmax(NaN, v) = v: an all-NaN frame stays NaN (np.nanmax)
+    for (long i = lane; i < n; i += 64) m = fmax(m, fabs(row[i]));
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = fmax(m, __shfl_xor(m, d, 64));
+    if (lane == 0) out[f] = m;
+}
+
+void launch_frame_peak(hipStream_t s, const double *x, long F, long n, long stride, double *out) {
+    hipLaunchKernelGGL(frame_peak_kernel, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, s, x, F, n, stride, out);
+}
+
+// ---- per-segment peak of local_peak: per chunk, then per segment over its chunks (exact: a max is order-free) -------------
+__global__ __launch_bounds__(64) void pp_chunk_peak_kernel(const double *__restrict__ lp, const pp_chunk_t *__restrict__ ch, long nch,
+                                                           double *__restrict__ cpk) {
+    const long c = blockIdx.x;
+    if (c >= nch) return;
+    const pp_chunk_t k = ch[c];
+    double m = __builtin_nan("");
+    for (long t = k.f0 + threadIdx.x; t < k.f1; t += 64) m = fmax(m, lp[t]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = fmax(m, __shfl_xor(m, d, 64));
+    if (threadIdx.x == 0) cpk[c] = m;
+}
+
+__global__ __launch_bounds__(64) void pp_seg_peak_kernel(const double *__restrict__ cpk, const int64_t *__restrict__ seg_chunk0, long nseg,
+                                                         double *__restrict__ spk) {
+    const long sg = blockIdx.x;
+    if (sg >= nseg) return;
+    double m = __builtin_nan("");
+    for (long c = seg_chunk0[sg] + threadIdx.x; c < seg_chunk0[sg + 1]; c += 64) m = fmax(m, cpk[c]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = fmax(m, __shfl_xor(m, d, 64));
+    if (threadIdx.x == 0) spk[sg] = m;
+}
+
+// ---- one frame of the recursion ---------------------------------------------------------------------------------------------
+struct pp_raw_t { int cnt, st; pitch_t e; double lp; };
+struct pp_frame_t { double lam, lf; int n; bool voiced, active; unsigned long long vmask; };
+
+template <int G> __device__ __forceinline__ unsigned long long pp_gmask() { return (G == 64) ? ~0ull : ((1ull << G) - 1ull); }
+
+// the frame's raw inputs as lane s sees them: independent loads, requested one frame ahead of their use
+__device__ __forceinline__ void pp_fetch(const pp_par_t &P, long t, int s, pp_raw_t &r) {
+    r.st = (P.status != nullptr) ? P.status[t] : 0;
+    r.cnt = P.count[t];
+    r.e = (s < P.kmax) ? P.cand[t * (long)P.kmax + s] : pitch_t{0.0, 0.0};
+    r.lp = (P.use_u) ? P.lpk[t] : 0.0;
+}
+
+// u_t = voicing_threshold + max(0, 2 - rho / q), rho = local_peak / P (0 when P == 0)
+__device__ __forceinline__ double pp_unvoiced(const pp_par_t &P, double lp, int seg) {
+    if (!P.use_u) return P.vt;
+    const double pk = P.spk[seg];
+    const double rho = (pk == 0.0) ? 0.0 : lp / pk;
+    const double v = 2.0 - rho / P.q;
+    return P.vt + ((v > 0.0) ? v : 0.0);
+}
+
+// states, voicedness, log2 f and lambda of lane s (group-uniform control flow: the ballots see the whole group)
+template <int G>
+__device__ __forceinline__ void pp_decode(const pp_par_t &P, const pp_raw_t &r, int seg, int s, int gbase, pp_frame_t &fr) {
+    int m = (r.st == 0) ? r.cnt : 0;                           // a frame whose status is not OK has only the unvoiced state
+    m = (m < 0) ? 0 : ((m > P.kmax) ? P.kmax : m);
+    const bool listed = s < m;
+    const unsigned long long zb = __ballot(listed && r.e.frequency == 0.0);
+    const unsigned long long vb = __ballot(listed && r.e.frequency > 0.0);
+    const bool has_zero = ((zb >> gbase) & pp_gmask<G>()) != 0ull;
+    fr.n = m + (has_zero ? 0 : 1);                             // the appended unvoiced state sits at index m
+    fr.vmask = (vb >> gbase) & pp_gmask<G>();
+    fr.active = s < fr.n;
+    fr.voiced = listed && r.e.frequency > 0.0;
+    if (fr.voiced) {
+        fr.lf = log2(r.e.frequency);
+        fr.lam = r.e.strength - P.oc * (P.Lc - fr.lf);
+    } else {
+        fr.lf = 0.0;
+        fr.lam = pp_unvoiced(P, r.lp, seg);
+    }
+}
+
+// D_t of lane s from D_{t-1} (prev[p] = {D(p), log2 f_p}, pn states, voiced mask pv); arg = psi_t(s)
+template <int G>
+__device__ __forceinline__ double pp_step(const pp_par_t &P, const pp_frame_t &fr, bool first, const double2 *prev, int pn,
+                                          unsigned long long pv, int &arg) {
+    double e;
+    arg = 0;
+    if (first) {
+        e = fr.lam;
+    } else {
+        double best = 0.0;
+        for (int p = 0; p < pn; p++) {
+            const double2 q = prev[p];                         // broadcast within the group
+            const bool vp = ((pv >> p) & 1ull) != 0ull;
+            double c;
+            if (fr.voiced && vp) c = P.cj * fabs(q.y - fr.lf);
+            else c = (fr.voiced != vp) ? P.cvu : 0.0;
+            const double v = q.x - c;
+            if (p == 0 || v > best) { best = v; arg = p; }     // strict >: ties go to the lower index
+        }
+        e = best + fr.lam;
+    }
+    if (!fr.active) { e = -INFINITY; arg = 0; }
+    double m = e;
+#pragma unroll
+    for (int d = 1; d < G; d <<= 1) { const double o = __shfl_xor(m, d, G); m = (o > m) ? o : m; }
+    m = __shfl(m, 0, G);                                       // one value for the whole group
+    return fr.active ? e - m : -INFINITY;
+}
+
+// the first state with D == 0 (the leader)
+template <int G>
+__device__ __forceinline__ int pp_leader(double D, bool active, int gbase) {
+    const unsigned long long z = (__ballot(active && D == 0.0) >> gbase) & pp_gmask<G>();
+    return (z == 0ull) ? 0 : __builtin_ctzll(z);
+}
+
+// chunk c redone from the entry state D_in (its previous frame exists: c is not the first chunk of its segment)
+template <int G>
+__device__ void pp_run(const pp_par_t &P, long c, double D, int s, int gbase, double2 (*lds)[64]) {
+    const pp_chunk_t k = P.ch[c];
+    pp_raw_t r, nx;
+    pp_frame_t fr;
+    pp_fetch(P, k.f0 - 1, s, r);
+    pp_decode<G>(P, r, k.seg, s, gbase, fr);
+    int buf = 0;
+    lds[buf][gbase + s] = make_double2(D, fr.lf);
+    int pn = fr.n;
+    unsigned long long pv = fr.vmask;
+    pp_fetch(P, k.f0, s, r);
+    for (long t = k.f0; t < k.f1; t++) {
+        if (t + 1 < k.f1) pp_fetch(P, t + 1, s, nx);
+        pp_decode<G>(P, r, k.seg, s, gbase, fr);
+        int arg;
+        D = pp_step<G>(P, fr, false, &lds[buf][gbase], pn, pv, arg);
+        P.psi[t * G + s] = (uint8_t)arg;
+        buf ^= 1;
+        lds[buf][gbase + s] = make_double2(D, fr.lf);
+        pn = fr.n; pv = fr.vmask;
+        r = nx;
+    }
+    P.exitd[c * G + s] = D;
+    const int lead = pp_leader<G>(D, fr.active, gbase);
+    if (k.last && s == 0) P.lead[k.seg] = lead;
+    if (s == 0) atomicAdd(P.redone, 1ull);
+}
+
+// ---- A: speculative chunks ---------------------------------------------------------------------------------------------------
+template <int G>
+__global__ __launch_bounds__(64) void pp_spec_kernel(const pp_par_t P, long W) {
+    __shared__ double2 lds[2][64];
+    const int s = threadIdx.x & (G - 1), gbase = threadIdx.x & ~(G - 1);
+    const long c = (long)blockIdx.x * (64 / G) + (threadIdx.x / G);
+    if (c >= P.nch) return;                                    // group-uniform
+    const pp_chunk_t k = P.ch[c];
+    const long w = (k.f0 - W > k.s0) ? k.f0 - W : k.s0;        // warm up from a fresh start W frames early
+    const bool exact = (w == k.s0);                            // ... which is the true start when the segment begins there
+    double D = -INFINITY;
+    int pn = 0, buf = 0;
+    unsigned long long pv = 0ull;
+    pp_raw_t r, nx;
+    pp_frame_t fr;
+    fr.active = false;
+    pp_fetch(P, w, s, r);
+    for (long t = w; t < k.f1; t++) {
+        if (t + 1 < k.f1) pp_fetch(P, t + 1, s, nx);
+        if (t == k.f0) { P.entry[c * G + s] = D; if (s == 0) P.exact[c] = exact ? 1 : 0; }
+        pp_decode<G>(P, r, k.seg, s, gbase, fr);
+        int arg;
+        D = pp_step<G>(P, fr, t == w, &lds[buf][gbase], pn, pv, arg);
+        if (t >= k.f0) P.psi[t * G + s] = (uint8_t)arg;
+        buf ^= 1;
+        lds[buf][gbase + s] = make_double2(D, fr.lf);
+        pn = fr.n; pv = fr.vmask;
+        r = nx;
+    }
+    P.exitd[c * G + s] = D;
+    const int lead = pp_leader<G>(D, fr.active, gbase);
+    if (k.last && s == 0) P.lead[k.seg] = lead;
+}
+
+// ---- B: check / repair rounds ------------------------------------------------------------------------------------------------
+template <int G>
+__global__ __launch_bounds__(64) void pp_check_kernel(const pp_par_t P) {
+    const int s = threadIdx.x & (G - 1), gbase = threadIdx.x & ~(G - 1);
+    const long c = (long)blockIdx.x * (64 / G) + (threadIdx.x / G);
+    if (c >= P.nch) return;
+    int redo = 0;
+    if (!P.exact[c]) {                                         // not exact: not the first chunk of its segment
+        const double want = P.exitd[(c - 1) * G + s];
+        const bool diff = __double_as_longlong(want) != __double_as_longlong(P.entry[c * G + s]);
+        if (((__ballot(diff) >> gbase) & pp_gmask<G>()) != 0ull) { redo = 1; P.want[c * G + s] = want; }
+    }
+    if (s == 0) P.redo[c] = redo;
+}
+
+template <int G>
+__global__ __launch_bounds__(64) void pp_repair_kernel(const pp_par_t P) {
+    __shared__ double2 lds[2][64];
+    const int s = threadIdx.x & (G - 1), gbase = threadIdx.x & ~(G - 1);
+    const long c = (long)blockIdx.x * (64 / G) + (threadIdx.x / G);
+    if (c >= P.nch || !P.redo[c]) return;                      // group-uniform
+    const double D = P.want[c * G + s];
+    P.entry[c * G + s] = D;                                    // what the chunk's psi now follows from
+    pp_run<G>(P, c, D, s, gbase, lds);
+}
+
+// the check's flags, 64 chunks to a word (the sweep skips 64 clean chunks per read)
+__global__ __launch_bounds__(64) void pp_mask_kernel(const pp_par_t P) {
+    const long c = (long)blockIdx.x * 64 + threadIdx.x;
+    const unsigned long long m = __ballot(c < P.nch && P.redo[c] != 0);
+    if (threadIdx.x == 0) P.mask[blockIdx.x] = m;
+}
+
+// ---- S: the guarantee.  One group (block of G lanes) per segment, chunk boundaries in order ---------------------------------
+template <int G>
+__global__ __launch_bounds__(64) void pp_sweep_kernel(const pp_par_t P, const int64_t *__restrict__ seg_chunk0) {
+    __shared__ double2 lds[2][64];
+    const int s = threadIdx.x;                                 // blockDim.x == G: gbase 0
+    const long sg = blockIdx.x;
+    const long k0 = seg_chunk0[sg], k1 = seg_chunk0[sg + 1];
+    long c = k0 + 1;
+    bool forced = false;                                       // the previous chunk was redone: its successor's flag is stale
+    while (c < k1) {
+        if (!forced) {                                         // next flagged chunk at or after c
+            long wi = c >> 6;
+            unsigned long long word = P.mask[wi] & (~0ull << (c & 63));
+            while (word == 0ull) {
+                wi++;
+                if (wi * 64 >= k1) break;
+                word = P.mask[wi];
+            }
+            if (word == 0ull) break;
+            c = wi * 64 + __builtin_ctzll(word);
+            if (c >= k1) break;
+        }
+        bool redo = false;
+        if (!P.exact[c]) {
+            const bool diff = __double_as_longlong(P.exitd[(c - 1) * G + s]) != __double_as_longlong(P.entry[c * G + s]);
+            redo = ((__ballot(diff) >> 0) & pp_gmask<G>()) != 0ull;
+        }
+        if (redo) {
+            const double D = P.exitd[(c - 1) * G + s];
+            P.entry[c * G + s] = D;
+            pp_run<G>(P, c, D, s, 0, lds);
+        }
+        forced = redo;
+        c++;
+    }
+}
+
+// ---- backtrack -----------------------------------------------------------------------------------------------------------------
+constexpr int PP_TILE = 256;                                   // frames of psi per LDS tile: 256 G bytes per group, 16 KB per wavefront
+
+// the group's lanes copy psi rows [t0, t1) into its tile (rows are G bytes: whole 32-bit words, G >= 4)
+template <int G>
+__device__ __forceinline__ void pp_stage(const pp_par_t &P, long t0, long t1, int s, uint32_t *tile) {
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(P.psi + t0 * G);
+    const int nw = (int)(t1 - t0) * (G / 4);
+    for (int i = s; i < nw; i += G) tile[i] = src[i];
+    __builtin_amdgcn_wave_barrier();
+}
+
+// map[c][s] = the state at chunk c's last frame when the state at chunk c + 1's last frame is s; a segment's last chunk holds
+// the constant map to the segment's leader
+template <int G>
+__global__ __launch_bounds__(64) void pp_map_kernel(const pp_par_t P, uint8_t *__restrict__ map) {
+    __shared__ uint32_t tiles[64 * PP_TILE / 4];
+    const int s = threadIdx.x & (G - 1), gbase = threadIdx.x & ~(G - 1);
+    const long c = (long)blockIdx.x * (64 / G) + (threadIdx.x / G);
+    if (c >= P.nch) return;
+    const pp_chunk_t k = P.ch[c];
+    if (k.last) { map[c * G + s] = (uint8_t)P.lead[k.seg]; return; }
+    const pp_chunk_t n = P.ch[c + 1];
+    uint32_t *tile = tiles + gbase * (PP_TILE / 4);
+    const uint8_t *tb = reinterpret_cast<const uint8_t *>(tile);
+    int cur = s;
+    for (long t1 = n.f1; t1 > n.f0;) {
+        const long t0 = (t1 - PP_TILE > n.f0) ? t1 - PP_TILE : n.f0;
+        pp_stage<G>(P, t0, t1, s, tile);
+        for (long t = t1 - 1; t >= t0; t--) cur = tb[(t - t0) * G + cur];
+        __builtin_amdgcn_wave_barrier();
+        t1 = t0;
+    }
+    map[c * G + s] = (uint8_t)cur;
+}
+
+// out[c] = in[c] o in[c + d]: after passes d = 1, 2, 4, .. >= the longest segment's chunk count every map is constant
+template <int G>
+__global__ __launch_bounds__(256) void pp_compose_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, long nch, long d) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nch * G) return;
+    const long c = i / G;
+    out[i] = (c + d < nch) ? in[c * G + in[(c + d) * G + (i % G)]] : in[i];
+}
+
+// the true state at every frame of chunk c, walked back from its last frame's, and the outputs
+template <int G>
+__global__ __launch_bounds__(64) void pp_write_kernel(const pp_par_t P, const uint8_t *__restrict__ map, pitch_t *__restrict__ out_path,
+                                                      int32_t *__restrict__ out_index) {
+    __shared__ uint32_t tiles[64 * PP_TILE / 4];
+    __shared__ uint8_t paths[64 / G][PP_TILE];
+    const int s = threadIdx.x & (G - 1), gbase = threadIdx.x & ~(G - 1);
+    const long c = (long)blockIdx.x * (64 / G) + (threadIdx.x / G);
+    if (c >= P.nch) return;
+    const pp_chunk_t k = P.ch[c];
+    uint32_t *tile = tiles + gbase * (PP_TILE / 4);
+    const uint8_t *tb = reinterpret_cast<const uint8_t *>(tile);
+    uint8_t *path = paths[threadIdx.x / G];
+    int cur = map[c * G];                                      // constant map: the true state at frame k.f1 - 1
+    for (long t1 = k.f1; t1 > k.f0;) {
+        const long t0 = (t1 - PP_TILE > k.f0) ? t1 - PP_TILE : k.f0;
+        pp_stage<G>(P, t0, t1, s, tile);
+        for (long t = t1 - 1; t >= t0; t--) {                  // every lane of the group walks the same states
+            if (s == 0) path[t - t0] = (uint8_t)cur;
+            cur = tb[(t - t0) * G + cur];
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (long t = t0 + s; t < t1; t += G) {
+            const int st = path[t - t0];
+            const int status = (P.status != nullptr) ? P.status[t] : 0;
+            int m = (status == 0) ? P.count[t] : 0;
+            m = (m < 0) ? 0 : ((m > P.kmax) ? P.kmax : m);
+            pitch_t o{0.0, 0.0};
+            bool voiced = false;
+            if (st < m) { o = P.cand[t * (long)P.kmax + st]; voiced = o.frequency > 0.0; }
+            if (!voiced) { o.frequency = 0.0; o.strength = pp_unvoiced(P, P.use_u ? P.lpk[t] : 0.0, k.seg); }
+            out_path[t] = o;
+            if (out_index != nullptr) out_index[t] = (st < m) ? st : -1;
+        }
+        __builtin_amdgcn_wave_barrier();
+        t1 = t0;
+    }
+}
+
+// ---- launches ---------------------------------------------------------------------------------------------------------------
+void launch_pitch_path_peak(hipStream_t s, const pp_par_t &P, const int64_t *seg_chunk0, long nseg, double *cpk) {
+    hipLaunchKernelGGL(pp_chunk_peak_kernel, dim3((unsigned)P.nch), dim3(64), 0, s, P.lpk, P.ch, P.nch, cpk);
+    hipLaunchKernelGGL(pp_seg_peak_kernel, dim3((unsigned)nseg), dim3(64), 0, s, cpk, seg_chunk0, nseg, const_cast<double *>(P.spk));
+}
+
+#define VBX_PP_DISPATCH(G_, CALL)                    \
+    switch (G_) {                                    \
+        case 4: { constexpr int G = 4; CALL; } break;   \
+        case 8: { constexpr int G = 8; CALL; } break;   \
+        case 16: { constexpr int G = 16; CALL; } break; \
+        case 32: { constexpr int G = 32; CALL; } break; \
+        default: { constexpr int G = 64; CALL; } break; \
+    }
+
+static dim3 pp_group_grid(long nch, int G) { return dim3((unsigned)((nch + (64 / G) - 1) / (64 / G))); }
+
+void launch_pitch_path_spec(hipStream_t s, const pp_par_t &P, int G_, long W) {
+    VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_spec_kernel<G>, pp_group_grid(P.nch, G), dim3(64), 0, s, P, W));
+}
+void launch_pitch_path_check(hipStream_t s, const pp_par_t &P, int G_) {
+    VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_check_kernel<G>, pp_group_grid(P.nch, G), dim3(64), 0, s, P));
+}
+void launch_pitch_path_repair(hipStream_t s, const pp_par_t &P, int G_) {
+    VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_repair_kernel<G>, pp_group_grid(P.nch, G), dim3(64), 0, s, P));
+}
+void launch_pitch_path_mask(hipStream_t s, const pp_par_t &P) {
+    hipLaunchKernelGGL(pp_mask_kernel, dim3((unsigned)((P.nch + 63) / 64)), dim3(64), 0, s, P);
+}
+void launch_pitch_path_sweep(hipStream_t s, const pp_par_t &P, int G_, const int64_t *seg_chunk0, long nseg) {
+    VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_sweep_kernel<G>, dim3((unsigned)nseg), dim3(G), 0, s, P, seg_chunk0));
+}
+void launch_pitch_path_map(hipStream_t s, const pp_par_t &P, int G_, uint8_t *map) {
+    VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_map_kernel<G>, pp_group_grid(P.nch, G), dim3(64), 0, s, P, map));
+}
+void launch_pitch_path_compose(hipStream_t s, long nch, int G_, const uint8_t *in, uint8_t *out, long d) {
+    VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_compose_kernel<G>, dim3((unsigned)((nch * G + 255) / 256)), dim3(256), 0, s, in, out, nch, d));
+}
+void launch_pitch_path_write(hipStream_t s, const pp_par_t &P, int G_, const uint8_t *map, pitch_t *out_path, int32_t *out_index) {
+    VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_write_kernel<G>, pp_group_grid(P.nch, G), dim3(64), 0, s, P, map, out_path, out_index));
+}
+#undef VBX_PP_DISPATCH
+
+}  // namespace vbx

@@ -40,7 +40,7 @@ struct vbx_ctx {
     std::string arch;
     int cu_count = 0;
     // workspaces (grown on demand, never shrunk)
-    enum { WS_COEFFS, WS_RES, WS_COUNT, WS_STATUS, WS_MISC, WS_SEG, WS_EST, WS_UNSURE, WS_F32_IN, WS_F32_OUT, WS_TRK, WS_BURG_LIST, WS_ROOTS_LIST, WS_LONG, WS_LONG2, WS_CZT, WS_CURVE, WS_LPC_LIST, WS_N };
+    enum { WS_COEFFS, WS_RES, WS_COUNT, WS_STATUS, WS_MISC, WS_SEG, WS_EST, WS_UNSURE, WS_F32_IN, WS_F32_OUT, WS_TRK, WS_BURG_LIST, WS_ROOTS_LIST, WS_LONG, WS_LONG2, WS_CZT, WS_CURVE, WS_LPC_LIST, WS_PATH, WS_PATH_TAB, WS_N };
     void *ws[WS_N] = {nullptr};
     const int32_t *burg_list_count = nullptr;             // device counter of the last one-pass Burg call (tests)
     const int32_t *roots_list_count = nullptr;            // the same for the resonance kernel of find_formants
@@ -92,14 +92,17 @@ struct vbx_ctx {
     hipEvent_t ev_slice[8] = {nullptr}, ev_trk = nullptr;
     // pinned staging of the small host arrays (segment starts, initial estimates): the caller's arrays may be
     // freed on return, and an upload whose content has not changed since the last call is skipped
-    void *stage[2] = {nullptr, nullptr};
-    size_t stage_cap[2] = {0, 0};
-    std::vector<char> staged[2];                          // content now on the device
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};          // completion of the last staged copy
+    void *stage[3] = {nullptr, nullptr, nullptr};         // 0: segment starts, 1: initial estimates, 2: the pitch path's chunk table
+    size_t stage_cap[3] = {0, 0, 0};
+    std::vector<char> staged[3];                          // content now on the device
+    hipEvent_t stage_ev[3] = {nullptr, nullptr, nullptr}; // completion of the last staged copy
     // what the tracker of the last find_formants / analyze_frames call ran on (vbx_track_stitch_f64 continues that track)
     struct { const res_t *res = nullptr; const int32_t *cnt = nullptr, *st = nullptr; long F = 0; int n_est = 0;
              res_t *out = nullptr; long out_ld = 0; } last_track;
     double *stitch_state = nullptr;                       // 2 * VBX_FORMANT_SLOTS doubles: the state a stitch received (vbx_comm.hip)
+    // the last vbx_pitch_path_f64 call (vbx_internal_last_path_chunks_redone): its device counter, cleared by every frame-batch call
+    const unsigned long long *path_redone = nullptr;
+    bool path_last = false;
 };
 
 namespace {
@@ -424,6 +427,7 @@ int check_frames(vbx_ctx *ctx, const char *fn, const void *x, size_t n_frames, s
                  size_t max_len = VBX_MAX_FRAME_LEN) {
     if (!ctx) return fail(nullptr, VBX_E_INVALID, std::string(fn) + ": null context");
     ctx->lpc_list_armed = false;   // every frame-batch call: only one that arms the LPC probe's list (below) sets it again
+    ctx->path_last = false;        // (and vbx_internal_last_path_chunks_redone answers -1 until the next path call)
     if (n_frames == 0) return 1;   // empty batch: nothing to do
     if (!x) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": null frame pointer");
     if (frame_len < 1 || frame_len > max_len)
@@ -581,7 +585,7 @@ void vbx_ctx_destroy(vbx_ctx *ctx) {
     for (auto &e : ctx->ev_slice) if (e) hipEventDestroy(e);
     if (ctx->ev_trk) hipEventDestroy(ctx->ev_trk);
     if (ctx->trk) { hipStreamSynchronize(ctx->trk); hipStreamDestroy(ctx->trk); }
-    for (int i = 0; i < 2; i++) { if (ctx->stage[i]) hipHostFree(ctx->stage[i]); if (ctx->stage_ev[i]) hipEventDestroy(ctx->stage_ev[i]); }
+    for (int i = 0; i < 3; i++) { if (ctx->stage[i]) hipHostFree(ctx->stage[i]); if (ctx->stage_ev[i]) hipEventDestroy(ctx->stage_ev[i]); }
     if (ctx->t0) hipEventDestroy(ctx->t0);
     if (ctx->t1) hipEventDestroy(ctx->t1);
     if (ctx->owns_stream) hipStreamDestroy(ctx->stream);
@@ -2157,6 +2161,155 @@ int vbx_pitch_f32(vbx_ctx *ctx, const float *x, size_t n_frames, size_t frame_le
                              (double)threshold, (double)fmin, (double)fmax, (int)kmax, (pitch_t *)wo, 2 * (long)kmax, out_count, status); }
     { Prof p(ctx, "narrow"); launch_narrow(ctx->stream, (const double *)wo, (long)(n_frames * kmax * 2), (float *)out_cand); }
     return check_launch(ctx, __func__);
+}
+
+// ---- periodic.rs: the pitch path (k_pitch_path.hip) -----------------------------------------
+
+int vbx_frame_peak_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride, double *out_peak) {
+    int rc = check_frames(ctx, __func__, x, n_frames, frame_len, stride, VBX_MAX_LONG_FRAME_LEN);
+    if (rc == 1) return VBX_SUCCESS;
+    if (rc != VBX_SUCCESS) return rc;
+    VBX_REQUIRE(ctx, out_peak != nullptr, "null out_peak");
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    { Prof p(ctx, "frame_peak"); launch_frame_peak(ctx->stream, x, (long)n_frames, (long)frame_len, (long)stride, out_peak); }
+    return check_launch(ctx, __func__);
+}
+
+// Chunk length C and warm-up W of the speculative scan.  The warm-up is where forgetting has to happen: a chunk whose entry state
+// after W frames from a fresh start is not bit for bit the true one is redone (DESIGN.md "Pitch path" has the measured counts).
+#ifndef VBX_PP_CHUNK
+#define VBX_PP_CHUNK 256
+#endif
+#ifndef VBX_PP_WARM
+#define VBX_PP_WARM 64
+#endif
+#ifndef VBX_PP_ROUNDS
+#define VBX_PP_ROUNDS 3
+#endif
+#ifndef VBX_PP_ROUNDS_LONG
+#define VBX_PP_ROUNDS_LONG 8
+#endif
+
+int vbx_pitch_path_f64(vbx_ctx *ctx, const vbx_pitch *cand, const int32_t *count, const int32_t *status,
+                       size_t n_frames, size_t kmax, const double *local_peak,
+                       const int64_t *h_seg_start, size_t n_segments, const vbx_pitch_path_params *h_params,
+                       vbx_pitch *out_path, int32_t *out_index) {
+    VBX_REQUIRE(ctx, ctx != nullptr, "null context");
+    ctx->path_last = false;
+    ctx->lpc_list_armed = false;
+    VBX_REQUIRE(ctx, h_params != nullptr, "null params");
+    const vbx_pitch_path_params pr = *h_params;
+    VBX_REQUIRE(ctx, kmax >= 1 && kmax <= 63, "kmax must be in [1, 63] (at most 64 states per frame)");
+    for (double v : {pr.voicing_threshold, pr.silence_threshold, pr.octave_cost, pr.octave_jump_cost, pr.voiced_unvoiced_cost,
+                     pr.ceiling_hz, pr.time_step})
+        VBX_REQUIRE(ctx, std::isfinite(v) && v >= 0.0, "every parameter must be finite and >= 0");
+    VBX_REQUIRE(ctx, pr.time_step > 0.0 && pr.ceiling_hz > 0.0, "time_step and ceiling_hz must be > 0");
+    VBX_REQUIRE(ctx, !(pr.silence_threshold > 0.0 && local_peak == nullptr), "silence_threshold > 0 needs local_peak");
+    VBX_REQUIRE(ctx, n_frames <= 0x7fffffffull, "too many frames for one launch");
+    const bool segmented = h_seg_start != nullptr && n_segments > 0;
+    if (segmented) {                                           // the rules of vbx_analyze_frames_f64
+        VBX_REQUIRE(ctx, h_seg_start[0] == 0, "seg_start[0] must be 0");
+        for (size_t i = 1; i < n_segments; i++)
+            VBX_REQUIRE(ctx, h_seg_start[i] >= h_seg_start[i - 1] && (size_t)h_seg_start[i] <= n_frames, "seg_start must ascend within [0, n_frames]");
+    }
+    if (n_frames == 0) { ctx->path_redone = nullptr; ctx->path_last = true; return VBX_SUCCESS; }
+    VBX_REQUIRE(ctx, cand != nullptr && count != nullptr && out_path != nullptr, "null argument");
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    const long F = (long)n_frames, W = VBX_PP_WARM;
+    const size_t nseg = segmented ? n_segments : 1;
+    int G = 4;
+    while (G < (int)kmax + 1) G <<= 1;
+    const long C = (pr.chunk_frames == 0) ? VBX_PP_CHUNK : (long)std::min<size_t>(pr.chunk_frames, n_frames);
+    // the chunk table: every segment cut into chunks of C frames (a chunk never spans two segments), then seg_chunk0[nseg + 1]
+    std::vector<pp_chunk_t> chunks;
+    chunks.reserve((size_t)(F / C + (long)nseg));
+    std::vector<int64_t> seg_chunk0(nseg + 1);
+    long max_per_seg = 1, n_guessed = 0;
+    for (size_t sg = 0; sg < nseg; sg++) {
+        const long s0 = segmented ? (long)h_seg_start[sg] : 0, s1 = (segmented && sg + 1 < nseg) ? (long)h_seg_start[sg + 1] : F;
+        seg_chunk0[sg] = (int64_t)chunks.size();
+        for (long f0 = s0; f0 < s1; f0 += C) {
+            const long f1 = (f0 + C < s1) ? f0 + C : s1;
+            chunks.push_back(pp_chunk_t{f0, f1, s0, (long)sg, f1 == s1 ? 1 : 0, 0});
+            if (f0 - W > s0) n_guessed++;                      // entered from a warm-up guess, not from the segment's start
+        }
+        max_per_seg = std::max<long>(max_per_seg, (long)chunks.size() - (long)seg_chunk0[sg]);
+    }
+    seg_chunk0[nseg] = (int64_t)chunks.size();
+    const long nch = (long)chunks.size();
+    std::vector<char> tab((size_t)nch * sizeof(pp_chunk_t) + (nseg + 1) * sizeof(int64_t));
+    std::memcpy(tab.data(), chunks.data(), (size_t)nch * sizeof(pp_chunk_t));
+    std::memcpy(tab.data() + (size_t)nch * sizeof(pp_chunk_t), seg_chunk0.data(), (nseg + 1) * sizeof(int64_t));
+    void *dtab = nullptr;
+    int rc = stage_upload(ctx, 2, vbx_ctx::WS_PATH_TAB, tab.data(), tab.size(), ctx->stream, &dtab);
+    if (rc != VBX_SUCCESS) return rc;
+    const int64_t *d_seg_chunk0 = reinterpret_cast<const int64_t *>(static_cast<char *>(dtab) + (size_t)nch * sizeof(pp_chunk_t));
+    // workspace: psi [F][G] uint8, per chunk entry / exit / wanted D, flags, maps; per segment leader and peak
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_psi = al((size_t)F * G), b_d = al((size_t)nch * G * sizeof(double)), b_i = al((size_t)nch * sizeof(int32_t)),
+                 b_mask = al(((size_t)(nch + 63) / 64 + 1) * sizeof(unsigned long long)), b_lead = al(nseg * sizeof(int32_t)),
+                 b_cpk = al((size_t)nch * sizeof(double)), b_spk = al(nseg * sizeof(double)), b_map = al((size_t)nch * G), b_cnt = 256;
+    void *w = nullptr;
+    rc = ws_get(ctx, vbx_ctx::WS_PATH, b_psi + 3 * b_d + 2 * b_i + b_mask + b_lead + b_cpk + b_spk + 2 * b_map + b_cnt, &w);
+    if (rc != VBX_SUCCESS) return rc;
+    char *p = static_cast<char *>(w);
+    pp_par_t P{};
+    P.psi = reinterpret_cast<uint8_t *>(p); p += b_psi;
+    P.entry = reinterpret_cast<double *>(p); p += b_d;
+    P.exitd = reinterpret_cast<double *>(p); p += b_d;
+    P.want = reinterpret_cast<double *>(p); p += b_d;
+    P.exact = reinterpret_cast<int32_t *>(p); p += b_i;
+    P.redo = reinterpret_cast<int32_t *>(p); p += b_i;
+    P.mask = reinterpret_cast<unsigned long long *>(p); p += b_mask;
+    P.lead = reinterpret_cast<int32_t *>(p); p += b_lead;
+    double *cpk = reinterpret_cast<double *>(p); p += b_cpk;
+    P.spk = reinterpret_cast<double *>(p); p += b_spk;
+    uint8_t *map_a = reinterpret_cast<uint8_t *>(p); p += b_map;
+    uint8_t *map_b = reinterpret_cast<uint8_t *>(p); p += b_map;
+    P.redone = reinterpret_cast<unsigned long long *>(p);
+    P.cand = reinterpret_cast<const pitch_t *>(cand); P.count = count; P.status = status; P.lpk = local_peak;
+    P.F = F; P.kmax = (int)kmax; P.use_u = (local_peak != nullptr && pr.silence_threshold != 0.0) ? 1 : 0;
+    const double corr = 0.01 / pr.time_step;                   // the host constants of the definition, in its order
+    P.vt = pr.voicing_threshold; P.oc = pr.octave_cost;
+    P.cvu = pr.voiced_unvoiced_cost * corr; P.cj = pr.octave_jump_cost * corr;
+    P.Lc = std::log2(pr.ceiling_hz); P.q = pr.silence_threshold / (1.0 + pr.voicing_threshold);
+    P.ch = reinterpret_cast<const pp_chunk_t *>(dtab); P.nch = nch;
+    hipStream_t st = ctx->stream;
+    VBX_HIP(ctx, hipMemsetAsync(P.redone, 0, sizeof(unsigned long long), st));
+    if (P.use_u) { Prof pf(ctx, "pitch_path_peak"); launch_pitch_path_peak(st, P, d_seg_chunk0, (long)nseg, cpk); }
+    { Prof pf(ctx, "pitch_path_spec"); launch_pitch_path_spec(st, P, G, W); }
+    if (n_guessed > 0) {
+        const int rounds = (F / (long)nseg > 8192) ? VBX_PP_ROUNDS_LONG : VBX_PP_ROUNDS;
+        for (int r = 0; r < rounds; r++) {
+            { Prof pf(ctx, "pitch_path_check"); launch_pitch_path_check(st, P, G); }
+            { Prof pf(ctx, "pitch_path_repair"); launch_pitch_path_repair(st, P, G); }
+        }
+        { Prof pf(ctx, "pitch_path_check"); launch_pitch_path_check(st, P, G); launch_pitch_path_mask(st, P); }
+        { Prof pf(ctx, "pitch_path_sweep"); launch_pitch_path_sweep(st, P, G, d_seg_chunk0, (long)nseg); }
+    }
+    { Prof pf(ctx, "pitch_path_backtrack"); launch_pitch_path_map(st, P, G, map_a); }
+    for (long d = 1; d < max_per_seg; d <<= 1) {
+        { Prof pf(ctx, "pitch_path_compose"); launch_pitch_path_compose(st, nch, G, map_a, map_b, d); }
+        std::swap(map_a, map_b);
+    }
+    { Prof pf(ctx, "pitch_path_write"); launch_pitch_path_write(st, P, G, map_a, reinterpret_cast<pitch_t *>(out_path), out_index); }
+    ctx->path_redone = P.redone;
+    ctx->path_last = true;
+    return check_launch(ctx, __func__);
+}
+
+int vbx_internal_last_path_chunks_redone(vbx_ctx *ctx, int64_t *h_out) {
+    VBX_REQUIRE(ctx, ctx && h_out, "null argument");
+    *h_out = -1;
+    if (!ctx->path_last) return VBX_SUCCESS;
+    *h_out = 0;
+    if (!ctx->path_redone) return VBX_SUCCESS;
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    VBX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned long long v = 0;
+    VBX_HIP(ctx, hipMemcpy(&v, ctx->path_redone, sizeof(v), hipMemcpyDeviceToHost));
+    *h_out = (int64_t)v;
+    return VBX_SUCCESS;
 }
 
 // ---- bench utility ------------------------------------------------------------------------

@@ -331,4 +331,29 @@ void launch_synth(hipStream_t s, double *out, size_t n_samples, uint64_t sample_
 // k_selftest.hip
 void launch_selftest(hipStream_t s, double *out /* 64*8 */);
 
+// k_pitch_path.hip: max |x| per frame, and the pitch path over vbx_pitch_f64's candidate lists (speculative chunks + exact repair)
+void launch_frame_peak(hipStream_t s, const double *x, long F, long n, long stride, double *out);
+struct pp_chunk_t { long f0, f1, s0, seg; int32_t last, pad; };   // frames [f0, f1) of segment seg (which starts at s0); host-built
+struct pp_par_t {
+    const pitch_t *cand; const int32_t *count; const int32_t *status; const double *lpk; const double *spk;
+    long F; int kmax; int use_u;                                  // use_u: u_t reads local_peak / P (else u_t = voicing_threshold)
+    double vt, oc, cj, cvu, Lc, q;                                // the host constants of the definition
+    const pp_chunk_t *ch; long nch;
+    uint8_t *psi;                                                 // [F][G]
+    double *entry, *exitd, *want;                                 // [nch][G]
+    int32_t *exact, *redo;                                        // [nch]
+    unsigned long long *mask;                                     // [ceil(nch / 64)]
+    int32_t *lead;                                                // [n_segments]: the leader of each segment's last frame
+    unsigned long long *redone;                                   // chunks redone by the repair rounds and the sweep
+};
+void launch_pitch_path_peak(hipStream_t s, const pp_par_t &P, const int64_t *seg_chunk0, long nseg, double *cpk);
+void launch_pitch_path_spec(hipStream_t s, const pp_par_t &P, int G, long W);
+void launch_pitch_path_check(hipStream_t s, const pp_par_t &P, int G);
+void launch_pitch_path_repair(hipStream_t s, const pp_par_t &P, int G);
+void launch_pitch_path_mask(hipStream_t s, const pp_par_t &P);
+void launch_pitch_path_sweep(hipStream_t s, const pp_par_t &P, int G, const int64_t *seg_chunk0, long nseg);
+void launch_pitch_path_map(hipStream_t s, const pp_par_t &P, int G, uint8_t *map);
+void launch_pitch_path_compose(hipStream_t s, long nch, int G, const uint8_t *in, uint8_t *out, long d);
+void launch_pitch_path_write(hipStream_t s, const pp_par_t &P, int G, const uint8_t *map, pitch_t *out_path, int32_t *out_index);
+
 }  // namespace vbx

@@ -13,6 +13,7 @@
 //   poly.find_roots_mut(work)         polynomial.rs:92 Polynomial::find_roots_mut(ctx, polys, F, len, status)
 //   roots.to_resonance(sr)            spectrum.rs:204  ToResonance::to_resonance(ctx, roots, F, n, sr, ..)
 //   est.estimate_formants(res)        spectrum.rs:232  EstimateFormants::estimate_formants(ctx, ..) (= FormantExtractor)
+//   PitchExtractor's third pass       periodic.rs:320  PitchExtractor::pitch_path(ctx, cand, count, status, F, kmax, peak, ..)
 //   frame.mfcc(k, (lo, hi), sr)       spectrum.rs:410  MFCC::mfcc(ctx, frames, k, lo, hi, sr, ..)
 //   vox_box::find_formants(..)        lib.rs:40        find_formants(ctx, frames, sr, p, segments, est, ..)
 //
@@ -232,6 +233,45 @@ struct EstimateFormants {   // spectrum.rs:216-219, iterated as FormantExtractor
                                   Resonance *out /* [F, n_est] */) {
         c.check(vbx_estimate_formants_f64(c.get(), res, n_frames, n_res, seg.h_seg_start, seg.n, starting_estimates.data(),
                                           starting_estimates.size(), frame_status, out));
+    }
+};
+
+// The pitch path: the third pass PitchExtractor (periodic.rs:320-354,394-395) takes the parameters of but never runs.
+// pitch_path_params(): Praat's "To Pitch (ac)" values; PitchExtractor::new(candidates, voiced_unvoiced_cost, voicing_threshold)
+// sets the two fields of the same names (its iterator, candidates[t][0], is Pitched::pitch's column 0).
+using PitchPathParams = vbx_pitch_path_params;
+inline PitchPathParams pitch_path_params(double time_step = 0.01, double voiced_unvoiced_cost = 0.14, double voicing_threshold = 0.45) {
+    PitchPathParams p{};
+    p.voicing_threshold = voicing_threshold; p.silence_threshold = 0.03; p.octave_cost = 0.01; p.octave_jump_cost = 0.35;
+    p.voiced_unvoiced_cost = voiced_unvoiced_cost; p.ceiling_hz = 600.0; p.time_step = time_step; p.chunk_frames = 0;
+    return p;
+}
+
+struct PitchExtractor {
+    // max |x| per frame (no window, NaN samples ignored): the path's local_peak
+    static void frame_peak(Context &c, const Frames &f, double *out_peak /* [F] */) {
+        c.check(vbx_frame_peak_f64(c.get(), f.x, f.n_frames, f.frame_len, f.stride, out_peak));
+    }
+    // the path over Pitched::pitch's lists (same kmax); status / local_peak / out_index may be null
+    static void pitch_path(Context &c, const Pitch *candidates, const int32_t *count, const int32_t *status, size_t n_frames,
+                           size_t kmax, const double *local_peak, Segments seg, const PitchPathParams &p, Pitch *out_path,
+                           int32_t *out_index) {
+        c.check(vbx_pitch_path_f64(c.get(), candidates, count, status, n_frames, kmax, local_peak, seg.h_seg_start, seg.n, &p,
+                                   out_path, out_index));
+    }
+    // pitch -> frame peak -> path in one call (f.window: the Hanning table pitch expects); status: device [F] (the pitch status)
+    // or null
+    static void pitch_track(Context &c, const Frames &f, double sample_rate, double threshold, double min, double max,
+                            size_t kmax, Segments seg, const PitchPathParams &p, Pitch *out_path, int32_t *out_index,
+                            int32_t *status = nullptr) {
+        DeviceVec<Pitch> cand(c, f.n_frames * kmax);
+        DeviceVec<int32_t> count(c, f.n_frames), st(c, status ? 1 : f.n_frames);
+        DeviceVec<double> peak(c, f.n_frames);
+        int32_t *pst = status ? status : st.data();
+        Pitched::pitch(c, f, sample_rate, threshold, min, max, kmax, cand.data(), count.data(), pst);
+        frame_peak(c, f, peak.data());
+        pitch_path(c, cand.data(), count.data(), pst, f.n_frames, kmax, peak.data(), seg, p, out_path, out_index);
+        c.sync();   // the scratch above is freed on return
     }
 };
 

@@ -92,6 +92,24 @@ class AnalysisParams(C.Structure):
         return cols
 
 
+class PitchPathParams(C.Structure):
+    """vbx_pitch_path_params (include/voxbox_hip.h): the path cost of vbx_pitch_path_f64.  make() defaults to Praat's
+    "To Pitch (ac)" values; PitchExtractor::new(candidates, voiced_unvoiced_cost, voicing_threshold) (src/periodic.rs:328)
+    sets the two fields of the same names."""
+    _fields_ = [("voicing_threshold", C.c_double), ("silence_threshold", C.c_double), ("octave_cost", C.c_double),
+                ("octave_jump_cost", C.c_double), ("voiced_unvoiced_cost", C.c_double), ("ceiling_hz", C.c_double),
+                ("time_step", C.c_double), ("chunk_frames", C.c_size_t)]
+
+    @classmethod
+    def make(cls, time_step=0.01, voicing_threshold=0.45, silence_threshold=0.03, octave_cost=0.01, octave_jump_cost=0.35,
+             voiced_unvoiced_cost=0.14, ceiling_hz=600.0, chunk_frames=0):
+        return cls(voicing_threshold, silence_threshold, octave_cost, octave_jump_cost, voiced_unvoiced_cost, ceiling_hz,
+                   time_step, chunk_frames)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "chunk_frames"}
+
+
 _lib = None
 
 
@@ -148,6 +166,9 @@ def load_library():
         "vbx_improve_extremum_f64": (C.c_int, [vp, vp, sz, C.c_long, sz, vp, sz, sz, vp, vp]),
         "vbx_improve_extremum_ex_f64": (C.c_int, [vp, vp, sz, C.c_long, sz, vp, sz, i32, sz, i32, vp, vp]),
         "vbx_pitch_f64": (C.c_int, [vp, vp, sz, sz, sz, vp, dbl, dbl, dbl, dbl, sz, vp, vp, vp]),
+        "vbx_frame_peak_f64": (C.c_int, [vp, vp, sz, sz, sz, vp]),
+        "vbx_pitch_path_f64": (C.c_int, [vp, vp, vp, vp, sz, sz, vp, vp, sz, C.POINTER(PitchPathParams), vp, vp]),
+        "vbx_internal_last_path_chunks_redone": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "vbx_lpc_f64": (C.c_int, [vp, vp, sz, sz, sz, vp]),
         "vbx_lpc_mut_f64": (C.c_int, [vp, vp, sz, sz, sz, vp, vp]),
         "vbx_window_table_f32": (C.c_int, [i32, sz, vp]),
@@ -630,6 +651,81 @@ class VoxBox:
             if d is not None:
                 d.free()
         return r
+
+    # -- the pitch path: PitchExtractor's third pass (src/periodic.rs:320-354,394-395) -------------
+    def frame_peak(self, x, frame_len=None, stride=None, n_frames=None, out=None):
+        """max |x| per frame (NaN samples ignored): the local_peak of pitch_path."""
+        ptr, F, N, S, tmp = self._frames(x, frame_len, stride, n_frames)
+        o = out if out is not None else self.empty(F)
+        self._check(self.L.vbx_frame_peak_f64(self.ctx, ptr, F, N, S, _ptr(o)))
+        return self._finish(o, out, tmp)
+
+    def pitch_path(self, cand, count, status=None, local_peak=None, seg_start=None, params=None, n_frames=None, kmax=None,
+                   out=None, index=True):
+        """vbx_pitch_path_f64 over the lists pitch() returns: (path [F, 2], index [F]) as numpy, or writes into
+        `out` = (path, index) device buffers and returns None.  cand / count / status / local_peak: host arrays (uploaded) or
+        device buffers (then n_frames and kmax are needed unless they carry a shape).  params: PitchPathParams (default:
+        PitchPathParams.make(), Praat's values at a 10 ms hop)."""
+        params = params if params is not None else PitchPathParams.make()
+        tmps = []
+
+        def dev(a, dtype):
+            if a is None or not isinstance(a, np.ndarray):
+                return a
+            d = self.to_device(np.ascontiguousarray(a, dtype=dtype))
+            tmps.append(d)
+            return d
+        if isinstance(cand, np.ndarray):
+            n_frames, kmax = cand.shape[0], cand.shape[1]
+        elif isinstance(cand, DeviceArray) and len(cand.shape) == 3:
+            n_frames, kmax = cand.shape[0], cand.shape[1]
+        assert n_frames is not None and kmax is not None
+        dc, dn, ds, dl = dev(cand, np.float64), dev(count, np.int32), dev(status, np.int32), dev(local_peak, np.float64)
+        seg = None if seg_start is None else np.ascontiguousarray(seg_start, dtype=np.int64)
+        if out is None:
+            path, idx = self.empty((n_frames, 2)), (self.empty(n_frames, np.int32) if index else None)
+        else:
+            path, idx = out
+        rc = self.L.vbx_pitch_path_f64(self.ctx, _ptr(dc), _ptr(dn), _ptr(ds), int(n_frames), int(kmax), _ptr(dl),
+                                       None if seg is None else seg.ctypes.data, 0 if seg is None else seg.size,
+                                       C.byref(params), _ptr(path), _ptr(idx))
+        try:
+            self._check(rc)
+            if out is not None:
+                return None
+            return path.numpy(), (idx.numpy() if idx is not None else None)
+        finally:
+            for d in tmps + ([path, idx] if out is None else []):
+                if d is not None:
+                    d.free()
+
+    def pitch_track(self, x, sample_rate, fmin, fmax, kmax=15, threshold=0.2, frame_len=None, stride=None, n_frames=None,
+                    window=None, seg_start=None, params=None):
+        """pitch() -> frame_peak() -> pitch_path() on the device in one call: the contour a PitchExtractor that ran its third
+        pass would yield.  window: the Hanning table of frame_len by default; params.time_step defaults to stride / sample_rate.
+        Returns (path [F, 2], index [F], status [F])."""
+        ptr, F, N, S, tmp = self._frames(x, frame_len, stride, n_frames)
+        if params is None:
+            params = PitchPathParams.make(time_step=S / sample_rate)
+        win = window if window is not None else self.window(WINDOW_HANNING, N)
+        cand, cnt, st, pk = self.empty((F, kmax, 2)), self.empty(F, np.int32), self.empty(F, np.int32), self.empty(F)
+        path, idx = self.empty((F, 2)), self.empty(F, np.int32)
+        try:
+            self.pitch(ptr, sample_rate, threshold, fmin, fmax, kmax=kmax, frame_len=N, stride=S, n_frames=F, window=win,
+                       out=(cand, cnt, st))
+            self.frame_peak(ptr, frame_len=N, stride=S, n_frames=F, out=pk)
+            self.pitch_path(cand, cnt, st, pk, seg_start=seg_start, params=params, n_frames=F, kmax=kmax, out=(path, idx))
+            return path.numpy(), idx.numpy(), st.numpy()
+        finally:
+            for d in (cand, cnt, st, pk, path, idx, tmp):
+                if d is not None:
+                    d.free()
+
+    def last_path_chunks_redone(self):
+        """Chunks the repair rounds and the sweep of the last pitch_path call redid; -1 if the last call was not one."""
+        n = C.c_int64(0)
+        self._check(self.L.vbx_internal_last_path_chunks_redone(self.ctx, C.byref(n)))
+        return int(n.value)
 
     # -- spectrum.rs: LPC -------------------------------------------------------------
     def lpc(self, r, n_coeffs):
