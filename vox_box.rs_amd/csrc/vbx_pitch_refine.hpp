@@ -611,13 +611,49 @@ __device__ __forceinline__ double taper_upper(double theta) {
     return fma(0.5, fma(p, t, 1.0), 0.5) * (1.0 + 1.0e-15);
 }
 
-// sum of |y_i| over i in [i0, i1], rounded outward to blocks of PB (p16[j] = sum_{i < PB j} |y_i|, j <= nblk)
-__device__ __forceinline__ double abs_range_bound(const double *p16, int nblk, int i0, int i1) {
+// sum of |y_i| over i in [i0, i1], rounded outward to blocks of PB (p16[j] = sum_{i < PB j} |y_i|, j <= nblk), as two prefix-sum
+// indices that are valid to read whatever the range, so that the caller can request the reads of several ranges together: the
+// sum is p16[j1] - p16[j0], and +0.0 = p16[0] - p16[0] for an empty range.
+__device__ __forceinline__ void abs_range_idx(int nblk, int i0, int i1, int &j0, int &j1) {
     i0 = (i0 < 0) ? 0 : i0;
     const int last = PB * nblk - 1;
     i1 = (i1 > last) ? last : i1;
-    if (i1 < i0) return 0.0;
-    return p16[i1 / PB + 1] - p16[i0 / PB];
+    const bool empty = i1 < i0;
+    j0 = empty ? 0 : (int)((unsigned)i0 / PB);
+    j1 = empty ? 0 : (int)((unsigned)i1 / PB) + 1;
+}
+// the tail of the first-evaluation bound over the ranges [lo, min(2 lo, D + 1)), lo = lo0, lo0 * STEP, ... <= D: each range's
+// sum of |y| on either side times c(n) at its start, accumulated in range order.  TB ranges at a time have their four
+// prefix sums in flight together.
+template <int STEP, int TB>
+__device__ __forceinline__ double first_eval_tail(const double *p16, int nblk, int offset, int nl, int nr, int D, int lo0,
+                                                  double phil, double phir, double hl, double hr) {
+    double tail = 0.0;
+    for (int lo = lo0; lo <= D;) {
+        double sl[TB], sr[TB];
+#pragma unroll
+        for (int q = 0, l = lo; q < TB; q++, l *= STEP) {
+            const int hi = (2 * l < D + 1) ? 2 * l : D + 1;                           // terms [l, hi)
+            int a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+            if (l <= D) {
+                abs_range_idx(nblk, offset + nr - (hi - 1), offset + nr - l, a0, a1);
+                abs_range_idx(nblk, offset + nl + l, offset + nl + hi - 1, b0, b1);
+            }
+            sl[q] = p16[a1] - p16[a0];
+            sr[q] = p16[b1] - p16[b0];
+        }
+#pragma unroll
+        for (int q = 0; q < TB; q++) {
+            if (lo > D) break;
+            const double pl = phil + (double)lo, pr = phir + (double)lo;
+            const double cl = rcp_nr1(pl) * taper_upper(hl * pl);                     // c(n) decreases in n: its value at the range's start
+            const double cr = rcp_nr1(pr) * taper_upper(hr * pr);
+            tail = fma(cl, sl[q], tail);
+            tail = fma(cr, sr[q], tail);
+            lo *= STEP;
+        }
+    }
+    return tail;
 }
 
 // Upper bound of f(v0), the FIRST value brent_maximize (src/periodic.rs:103-188) takes on the bracket
@@ -679,15 +715,7 @@ __device__ __forceinline__ double first_eval_bound(const double *ys, const doubl
         }
     }
     head *= s0;
-    double tail = 0.0;
-    for (int lo = nh; lo <= D; lo *= 2) {
-        const int hi = (2 * lo < D + 1) ? 2 * lo : D + 1;                            // terms [lo, hi)
-        const double pl = phil + (double)lo, pr = phir + (double)lo;
-        const double cl = rcp_nr1(pl) * taper_upper(hl * pl);                        // c(n) decreases in n: its value at the range's start
-        const double cr = rcp_nr1(pr) * taper_upper(hr * pr);
-        tail = fma(cl, abs_range_bound(p16, nblk, offset + nr - (hi - 1), offset + nr - lo), tail);
-        tail = fma(cr, abs_range_bound(p16, nblk, offset + nl + lo, offset + nl + hi - 1), tail);
-    }
+    double tail = first_eval_tail<2, 4>(p16, nblk, offset, nl, nr, D, nh, phil, phir, hl, hr);
     tail *= s0;
     const double ub = head + tail * (1.0 + 1.0e-9) + (1.0e-9 + 1.0e-11 * p16[nblk]);   // rounding of either sum is far below this
     return (ub != ub) ? INF : ub;
@@ -731,24 +759,27 @@ __device__ __forceinline__ double first_eval_bound_quad(const double *ys, const 
         const double s0 = sin_poly(M_PI * fmin(phil, phir)) * 0.31830988618379067154;   // |sin(pi ph)| / pi >= 0
         const double hl = M_PI * rcp_nr1(phil + (double)D), hr = M_PI * rcp_nr1(phir + (double)D);
         const int nh = (BOUND_HEAD < D + 1) ? BOUND_HEAD : D + 1;
-        for (int m = sub; m < nh; m += 4) {
+        double yl[BOUND_HEAD / 4], yr[BOUND_HEAD / 4];          // the lane's samples first, all in flight together
+#pragma unroll
+        for (int j = 0; j < BOUND_HEAD / 4; j++) {
+            const int m = sub + 4 * j;
+            const bool in = m < nh;
+            yl[j] = y_at_padded(ys, nvalid, in ? offset + nr - m : 0);
+            yr[j] = y_at_padded(ys, nvalid, in ? offset + nl + m : 0);
+        }
+#pragma unroll
+        for (int j = 0; j < BOUND_HEAD / 4; j++) {
+            const int m = sub + 4 * j;
+            if (m >= nh) break;
             const double pl = phil + (double)m, pr = phir + (double)m;
-            const double tl = y_at(ys, nvalid, offset + nr - m) * rcp_nr1(pl) * fma(0.5, cos_0_pi(hl * pl), 0.5);
-            const double tr = y_at(ys, nvalid, offset + nl + m) * rcp_nr1(pr) * fma(0.5, cos_0_pi(hr * pr), 0.5);
+            const double tl = yl[j] * rcp_nr1(pl) * fma(0.5, cos_0_pi(hl * pl), 0.5);
+            const double tr = yr[j] * rcp_nr1(pr) * fma(0.5, cos_0_pi(hr * pr), 0.5);
             const double t = tl + tr;
             head += (m & 1) ? -t : t;
         }
         head *= s0;
-        int r = 0;
-        for (int lo = nh; lo <= D; lo *= 2, r++) {
-            if ((r & 3) != sub) continue;
-            const int hi = (2 * lo < D + 1) ? 2 * lo : D + 1;                            // terms [lo, hi)
-            const double pl = phil + (double)lo, pr = phir + (double)lo;
-            const double cl = rcp_nr1(pl) * taper_upper(hl * pl);
-            const double cr = rcp_nr1(pr) * taper_upper(hr * pr);
-            tail = fma(cl, abs_range_bound(p16, nblk, offset + nr - (hi - 1), offset + nr - lo), tail);
-            tail = fma(cr, abs_range_bound(p16, nblk, offset + nl + lo, offset + nl + hi - 1), tail);
-        }
+        // ranges r = sub, sub + 4, ...: lo = nh * 2^r
+        tail = first_eval_tail<16, 2>(p16, nblk, offset, nl, nr, D, nh << sub, phil, phir, hl, hr);
         tail *= s0;
     }
     head = group_sum<4>(head);
