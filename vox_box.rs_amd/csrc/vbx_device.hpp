@@ -35,6 +35,16 @@ __device__ __forceinline__ double dpp_f64(double v) {
     return __hiloint2double(hi, lo);
 }
 
+// The same move into the rows of ROW_MASK and the banks (lane & 3 groups of four inside a row) of BANK_MASK only: every
+// other lane, and a lane without a source, keeps `old`.
+template <int CTRL, int ROW_MASK, int BANK_MASK>
+__device__ __forceinline__ double dpp_f64_into(double old, double v) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(__double2loint(old), lo, CTRL, ROW_MASK, BANK_MASK, false);
+    hi = __builtin_amdgcn_update_dpp(__double2hiint(old), hi, CTRL, ROW_MASK, BANK_MASK, false);
+    return __hiloint2double(hi, lo);
+}
+
 constexpr int DPP_ROW_BCAST15 = 0x142, DPP_ROW_BCAST31 = 0x143;   // lane 15 of each row -> the next row; lane 31 -> rows 2, 3
 
 constexpr int DPP_ROW_ROR1 = 0x121, DPP_ROW_ROR2 = 0x122, DPP_ROW_ROR4 = 0x124, DPP_ROW_ROR8 = 0x128;
@@ -118,6 +128,8 @@ __device__ __forceinline__ long xcd_item(long b, long n) {
     return tile * T + (j & 7) * XCD_RUN + (j >> 3);
 }
 
+constexpr int DPP_QUAD_IDENTITY = 0xE4;     // quad_perm [0,1,2,3]: a plain move (under a row / bank mask: into some lanes only)
+constexpr int DPP_ROW_SHR4 = 0x114;         // lane i <- lane i-4 inside each 16 lanes
 constexpr int DPP_QUAD_XOR1 = 0xB1;         // quad_perm [1,0,3,2]
 constexpr int DPP_QUAD_REV = 0x1B;          // quad_perm [3,2,1,0]
 constexpr int DPP_ROW_HALF_MIRROR = 0x141;  // i <-> 7-i inside each 8 lanes

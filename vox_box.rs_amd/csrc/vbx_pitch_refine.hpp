@@ -25,7 +25,8 @@ __device__ __forceinline__ double fma_sc(double p, double x, const double c) {
 }
 
 // sin(x), cos(x) for |x| <= pi/2 (a little beyond is fine): Taylor to x^21 / x^22 (< 2e-18 truncation)
-__device__ __forceinline__ double sin_poly(double x) {
+// sin(x) = x * sin_poly_q(x): the polynomial factor alone, for callers that fold the last product into a following operation
+__device__ __forceinline__ double sin_poly_q(double x) {
     const double x2 = x * x;
     double p = -1.9572941063391261231e-20;           // -1/21!
     p = fma_sc(p, x2, 8.2206352466243297170e-18);    //  1/19!
@@ -37,8 +38,9 @@ __device__ __forceinline__ double sin_poly(double x) {
     p = fma_sc(p, x2, 1.9841269841269841270e-04);    //  1/7!
     p = fma_sc(p, x2, -8.3333333333333333333e-03);   // -1/5!
     p = fma_sc(p, x2, 1.6666666666666666667e-01);    //  1/3!
-    return x * fma(-x2, p, 1.0);
+    return fma(-x2, p, 1.0);
 }
+__device__ __forceinline__ double sin_poly(double x) { return x * sin_poly_q(x); }
 __device__ __forceinline__ double cos_poly(double x) {
     const double x2 = x * x;
     double p = 8.8967913924505732867e-22;            //  1/22!
@@ -188,32 +190,6 @@ __device__ __forceinline__ double sinc_terms_fast(const double *y, int ibase_l, 
     sinc_stream_t s;
     sinc_stream_init<NSTEP>(s, y, side, n0, ibase_l, ibase_r, phil, phir, max_depth);
     const int step = side ? NSTEP : -NSTEP;
-    int j = 0;
-    for (; j + 4 <= nterms; j += 4) sinc_stream_block4<NSTEP>(s, step);
-    if (j < nterms) sinc_stream_tail<NSTEP>(s, step, nterms - j);
-    return sinc_stream_result(s, n0, s0 * (0.5 * 0.31830988618379067154));
-}
-
-// sinc_terms_fast<64> with what depends on the abscissa's unit cell alone handed in (improve_extremum_sinc_wave keeps it
-// across the evaluations of a Brent run): yp0 = the lane's first sample, nterms its term count, dmd = (double)max_depth.
-// Every floating-point operation is sinc_terms_fast<64>'s, in its order.
-__device__ __forceinline__ double sinc_terms_fast_cell(const double *yp0, int side, int n0, int nterms, double dmd,
-                                                       double phil, double phir) {
-    constexpr int NSTEP = 32;
-    constexpr double S = (double)NSTEP;
-    const int step = side ? NSTEP : -NSTEP;
-    const double s0 = sin_poly(M_PI * fmin(phil, phir));      // sin(pi*phil) == sin(pi*phir)
-    sinc_stream_t s;
-    const double ph = side ? phir : phil;
-    const double h2 = M_PI * rcp_nr2(ph + dmd);               // theta = h2 * (ph + n)  in [0, pi]
-    s.pn = ph + (double)n0;
-    const double theta0 = h2 * s.pn, delta = h2 * S;
-    s.C = cos_0_pi(theta0);
-    s.d = cos_0_pi(theta0 + delta) - s.C;
-    const double sh = sin_poly(0.5 * delta);
-    s.kappa = 4.0 * sh * sh;
-    s.yp = yp0;
-    s.acc0 = 0.0; s.acc1 = 0.0;
     int j = 0;
     for (; j + 4 <= nterms; j += 4) sinc_stream_block4<NSTEP>(s, step);
     if (j < nterms) sinc_stream_tail<NSTEP>(s, step, nterms - j);
@@ -434,6 +410,9 @@ __device__ __forceinline__ void improve_extremum_sinc(const double *y, int nvali
 // taken path.  Same operations on the same values in the same order as improve_extremum_sinc<64>: bit-identical results
 // (tests/test_gpu_parity.py::test_improve_extremum_points compares the two forms).  Returns false when the bracket is not
 // trusted or an early-out applies (the caller then takes the general form).
+// The Brent state (v, w, x, fv, fw, fx) lives in SCALAR registers: each abscissa is read from lane 0 once (the values of an
+// evaluation arrive in scalar registers anyway, group_sum<64> ends in a lane read), so the rotations v = w; w = x; x = t
+// are scalar moves, which cost no vector issue, and the vector unit only sees the iteration's arithmetic.
 __device__ __forceinline__ bool improve_extremum_sinc_wave(const double *y, int nvalid, int ylen, int offset, int nx,
                                                            double ixmid, int depth, double &xmid, double &ymid,
                                                            unsigned &terms, unsigned &evals, double bar, bool &pruned) {
@@ -443,10 +422,10 @@ __device__ __forceinline__ bool improve_extremum_sinc_wave(const double *y, int 
     const double eps = 2.220446049250313e-16;
     const double tol = 1e-10;
     if (__any(ixmid == 0. || ixmid >= (double)nx || !(ixmid - 1. < ixmid + 1.))) return false;   // :193-194, :113
-    double a = ixmid - 1., b = ixmid + 1.;
+    double a = readfirstlane_f64(ixmid - 1.), b = readfirstlane_f64(ixmid + 1.);
     if (!__any(sinc_bracket_trusted(a, b, nvalid, ylen, offset, nx, depth))) return false;
-    // one evaluation of the interpolant at a trusted abscissa (sinc_interp<64>'s trusted arm, decisions as scalar branches).
-    // Round 5, same operations on the same values with fewer instructions around them:
+    // one evaluation of the interpolant at a trusted abscissa (sinc_interp<64>'s trusted arm, decisions as scalar branches),
+    // the same operations on the same values with fewer instructions around them:
     //  * the two exact-integer tests of :41-42 read phil / phir: x - (double)nl IS phil (x - floor(x) is exact), and
     //    (double)nr - x is 1 - phil exactly wherever it could be below 1e-10 (phil >= 0.5: Sterbenz);
     //  * everything that depends on the unit CELL of x alone -- the clamped depth, each lane's term count and first sample's
@@ -455,12 +434,15 @@ __device__ __forceinline__ bool improve_extremum_sinc_wave(const double *y, int 
     //    instead of once per evaluation.
     const int lane = lane_id();
     const int side = lane & 1, n0 = lane >> 1;
-    // two cells are kept: the iteration closes in on an integer lag -- a jump of the mirrored interpolant (Q6) -- from BOTH
-    // sides, so its abscissae alternate between the two cells next to it
-    struct cell_t { int nl, nterms; unsigned tinc; double dmd; const double *yp0; };
-    cell_t ca{-0x7fffffff, 0, 0u, 0.0, y}, cb{-0x7fffffff, 0, 0u, 0.0, y};
-    bool a_is_older = true;
-    auto fill = [&](cell_t &c, int nl) {
+    const int sign_bit = (n0 & 1) << 31;         // the lane's terms carry (-1)^n0 (sinc_stream_result)
+    // Two cells are kept: the iteration closes in on an integer lag -- a jump of the mirrored interpolant (Q6) -- from BOTH
+    // sides, so its abscissae alternate between the two cells next to it.  `cur` is the cell of the last evaluation, `oth`
+    // the one before (the older one: a third cell replaces it).  What is the same in all lanes (the cell's lag, the number of
+    // whole blocks every lane runs, the terms counter's increment) is held in scalar registers: the cell tests are scalar
+    // compares and the block loop below runs on a scalar counter.
+    struct cell_t { int nl, nblk; unsigned tinc; double dmd; int nterms; const double *yp0; };
+    cell_t cur{-0x7fffffff, 0, 0u, 0.0, 0, y}, oth{-0x7fffffff, 0, 0u, 0.0, 0, y};
+    auto fill = [&](cell_t &c, int nl) {         // nl: scalar
         c.nl = nl;
         const int nr = nl + 1;
         int md = depth;
@@ -469,37 +451,70 @@ __device__ __forceinline__ bool improve_extremum_sinc_wave(const double *y, int 
         c.tinc = 2u * (unsigned)(md + 1);
         c.dmd = (double)md;
         c.nterms = (n0 <= md) ? (md - n0) / 32 + 1 : 0;
+        c.nblk = ((31 <= md) ? (md - 31) / 32 + 1 : 0) >> 2;       // lane 63's (n0 = 31: the fewest terms) whole blocks of four
         c.yp0 = y + (side ? (offset + nl + n0) : (offset + nr - n0));
     };
+    // One evaluation: ONE body whatever the cell (a hit, the other cell, a new one), so that set-up, block loop, tail and
+    // wave sum exist once.  Every floating-point operation is sinc_terms_fast<64>'s on the same values in the same order,
+    // the fused ones written out (this function is compiled with contraction off); what differs is where they run:
+    //  * sin(pi ph) takes ONE value per evaluation and sin(delta / 2) one per side, so the two share a pass of the
+    //    polynomial: lanes 60..63 evaluate sin(pi ph) -- every lane reads k = sin(pi ph) / (2 pi) from lane 63 -- and take
+    //    their sin(delta / 2) from lanes 56..59 (four lanes on: the same side, the same value);
+    //  * a lane's block count is nblk or nblk + 1: nblk blocks run unmasked on a scalar counter (no per-lane compare, no
+    //    per-lane counter), then at most one more under the lanes' mask, then the tail.
+    unsigned nterms_s = 0u, nevals_s = 1u;       // the work counters of this run, in scalar registers; handed over at the end
     auto eval = [&](double x) -> double {
         const double fl = floor(x);
-        const int nl = (int)fl;
+        int nlv = (int)fl;
+        asm("" : "+v"(nlv));                                      // convert once, in the vector unit, then read the lane
+        const int nl = __builtin_amdgcn_readfirstlane(nlv);
         const double phil = x - fl, phir = 1.0 - phil;
-        if (__any(phil < 1.0e-10)) return y[offset + nl];                                        // :41
-        if (__any(phir < 1.0e-10)) return y[offset + nl + 1];                                    // :42
-        if (__any(nl == ca.nl)) {
-            a_is_older = false;
-            terms += ca.tinc;
-            return group_sum<64>(sinc_terms_fast_cell(ca.yp0, side, n0, ca.nterms, ca.dmd, phil, phir));
+        if (__any(phil < 1.0e-10)) return readfirstlane_f64(y[offset + nl]);                     // :41
+        if (__any(phir < 1.0e-10)) return readfirstlane_f64(y[offset + nl + 1]);                 // :42
+        if (nl != cur.nl) {
+            if (nl != oth.nl) fill(oth, nl);
+            const cell_t t = cur; cur = oth; oth = t;
         }
-        if (__any(nl != cb.nl)) {
-            if (a_is_older) { fill(ca, nl); a_is_older = false; terms += ca.tinc;
-                              return group_sum<64>(sinc_terms_fast_cell(ca.yp0, side, n0, ca.nterms, ca.dmd, phil, phir)); }
-            fill(cb, nl);
-        }
-        a_is_older = true;
-        terms += cb.tinc;
-        return group_sum<64>(sinc_terms_fast_cell(cb.yp0, side, n0, cb.nterms, cb.dmd, phil, phir));
+        nterms_s += cur.tinc;
+        constexpr int NSTEP = 32;
+        constexpr double S = (double)NSTEP;
+        const int step = side ? NSTEP : -NSTEP;
+        sinc_stream_t s;
+        const double ph = side ? phir : phil;
+        const double h2 = M_PI * rcp_nr2(ph + cur.dmd);           // theta = h2 * (ph + n)  in [0, pi]
+        s.pn = ph + (double)n0;
+        const double delta = h2 * S;
+        // cos(theta0) = -sin(theta0 - pi/2) and cos(theta0 + delta) - cos(theta0), theta0 = h2 * pn
+        const double xc = fma(s.pn, h2, -1.57079632679489661923);
+        s.C = -(xc * sin_poly_q(xc));
+        const double xd = fma(s.pn, h2, delta) - 1.57079632679489661923;
+        s.d = fma(xd, -sin_poly_q(xd), -s.C);
+        // one pass for sin(delta / 2) (lanes 0..59) and sin(pi * min(phil, phir)) (lanes 60..63)
+        double pmin;
+        asm("v_min_f64 %0, %1, %2" : "=v"(pmin) : "v"(phil), "v"(phir));     // neither is NaN or zero here: fmin's value
+        const double xs = dpp_f64_into<DPP_QUAD_IDENTITY, 0x8, 0x8>(0.5 * delta, M_PI * pmin);
+        const double sn = xs * sin_poly_q(xs);
+        const double k = readlane_f64(sn * (0.5 * 0.31830988618379067154), 63);
+        const double sh = dpp_f64_into<DPP_ROW_SHR4, 0x8, 0x8>(sn, sn);                          // lanes 60..63 <- 56..59
+        s.kappa = 4.0 * sh * sh;
+        s.yp = cur.yp0;
+        s.acc0 = 0.0; s.acc1 = 0.0;
+        for (int j = 0; j < cur.nblk; j++) sinc_stream_block4<NSTEP>(s, step);
+        const int rest = cur.nterms - 4 * cur.nblk;               // 0..4 (a lane with n0 below another's has at most one term more)
+        if (rest >= 4) sinc_stream_block4<NSTEP>(s, step);
+        if (rest & 3) sinc_stream_tail<NSTEP>(s, step, rest & 3);
+        const double acc = s.acc0 + s.acc1;
+        const double signed_acc = __hiloint2double(__double2hiint(acc) ^ sign_bit, __double2loint(acc));
+        return group_sum<64>(signed_acc * k);
     };
-    double v = a + golden * (b - a);
+    double v = readfirstlane_f64(a + golden * (b - a));
     double fv = eval(v);
-    evals += 1u;
     double x = v, w = v, fx = fv, fw = fv;
     // a >= -offset: every abscissa of the bracket has its left neighbour at index >= 0, so none of the evaluations a
     // pruned candidate skips could have been an out-of-bounds panic of the reference
     const bool prunable = __any(a >= (double)(-offset));
     pruned = false;
-    if (prunable && __any(((fv <= 1.) ? fv : 1.) < bar)) { pruned = true; return true; }          // f(v0) already caps the strength
+    if (prunable && __any(((fv <= 1.) ? fv : 1.) < bar)) { pruned = true; terms += nterms_s; evals += nevals_s; return true; }          // f(v0) already caps the strength
     for (int it = 1; it <= 60; it++) {
         const double range = b - a;
         const double middle_range = (a + b) * 0.5;
@@ -512,21 +527,23 @@ __device__ __forceinline__ bool improve_extremum_sinc_wave(const double *y, int 
             double p = (x - v) * q - (x - w) * t;
             q = 2. * q - t;
             if (__any(q > 0.)) p = -p; else q = -q;
-            if (__any(fabs(p) < fabs(new_step * q) && p > q * (a - x + 2. * tol_act) && p < q * (b - x - 2. * tol_act))) {
+            // (all three tests evaluated, then one branch: no mask is built and tested in between)
+            if (__any((int)(fabs(p) < fabs(new_step * q)) & (int)(p > q * (a - x + 2. * tol_act)) & (int)(p < q * (b - x - 2. * tol_act)))) {
                 asm volatile("" ::: "memory");   // a real branch: the IEEE division runs when the step is taken (a quarter of
                 new_step = p / q;                // the iterations), not speculated on every one and then selected
             }
         }
         if (__any(fabs(new_step) < tol_act)) new_step = __any(new_step > 0.) ? tol_act : -tol_act;
-        const double t = x + new_step;
+        const double t = readfirstlane_f64(x + new_step);
         const double ft = eval(t);
-        evals += 1u;
+        nevals_s += 1u;
+        // (the empty statements keep these as branches: one register move on the side taken instead of selects on both)
         if (__any(ft <= fx)) {
-            if (__any(t < x)) b = x; else a = x;
+            if (__any(t < x)) { asm volatile(""); b = x; } else { asm volatile(""); a = x; }
             v = w; w = x; x = t;
             fv = fw; fw = fx; fx = ft;
         } else {
-            if (__any(t < x)) a = t; else b = t;
+            if (__any(t < x)) { asm volatile(""); a = t; } else { asm volatile(""); b = t; }
             if (__any(ft <= fw || fabs(w - x) < eps)) {
                 v = w; w = t;
                 fv = fw; fw = ft;
@@ -537,9 +554,10 @@ __device__ __forceinline__ bool improve_extremum_sinc_wave(const double *y, int 
         }
         // brent_maximize only ever replaces fx by a smaller value (:162): the final strength is <= the current fx
         // (<= 1 here, so the reflection of :446 does not apply).  Strictly below the bar it cannot be returned.
-        if (prunable && __any(fx < bar)) { pruned = true; return true; }
+        if (prunable && __any(fx < bar)) { pruned = true; break; }
     }
-    xmid = x; ymid = fx;
+    terms += nterms_s; evals += nevals_s;
+    if (!pruned) { xmid = x; ymid = fx; }
     return true;
 }
 
