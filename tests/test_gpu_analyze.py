@@ -4,6 +4,7 @@ tolerances as their own parity tests) and against the CPU oracle."""
 import numpy as np
 import pytest
 
+from analyze_reference import oracle_records
 from conftest import rel_close
 
 pytestmark = pytest.mark.gpu
@@ -19,26 +20,11 @@ def audio_d(vb):
 
 
 def _oracle_records(oracle, pkg, audio, F, seg, N=N, H=H):
-    w = oracle.window("hanning", N)
+    """The default record (48 kHz, pitch 0.2 / 75 / 600, order 12, 13 MFCCs of 100-8000 Hz) of frames 0..F-1: a thin call
+    into the reference for arbitrary parameters, tests/analyze_reference.py."""
     est0 = np.array([[f, 1.0] for f in pkg.MALE_FORMANT_ESTIMATES])
-    rec = np.zeros((F, 36))
-    st = np.zeros((3, F), dtype=np.int32)
-    est = est0.copy()
-    for t in range(F):
-        fr = audio[t * H:t * H + N]
-        xw = fr * w
-        s, c, _ = oracle.pitch(xw, SR, 0.2, 75.0, 600.0, cap=1)
-        st[0, t] = s
-        rec[t, 0:2] = c[0]
-        if t in seg:
-            est = est0.copy()
-        s, est, _, _ = oracle.find_formants(fr, SR, P, est)
-        st[1, t] = s
-        rec[t, 2:10] = est.reshape(-1)
-        s, m = oracle.mfcc(xw, 13, 100.0, 8000.0, SR)
-        st[2, t] = s
-        rec[t, 10:23] = m
-        rec[t, 23:36] = oracle.lpc(oracle.autocorrelate(xw, P + 1), P)
+    rec, st, _, _ = oracle_records(oracle, audio, N, H, range(F), SR, (0.2, 75.0, 600.0), P, P, est0, (13, 100.0, 8000.0), seg)
+    assert rec.shape == (F, 36)
     return rec, st
 
 

@@ -9,6 +9,7 @@ import wave
 import numpy as np
 import pytest
 
+from analyze_reference import classify_top, tie_gap
 from conftest import rel_close
 
 pytestmark = pytest.mark.gpu
@@ -543,18 +544,15 @@ def _check_pitch(vb, oracle, frames_windowed, sr, thr, fmin, fmax, kmax, stats=N
         if es != 0:
             assert np.all(cand[f] == 0.0)
             continue
-        top_ok = abs(cand[f, 0, 0] - ec[0, 0]) <= 1e-4 * abs(ec[0, 0]) and abs(cand[f, 0, 1] - ec[0, 1]) <= 1e-4
-        if not top_ok:
-            gap = abs(ec[0, 1] - ec[1, 1]) if en > 1 else np.inf
-            is_runner_up = en > 1 and abs(cand[f, 0, 0] - ec[1, 0]) <= 1e-4 * abs(ec[1, 0]) and abs(cand[f, 0, 1] - ec[1, 1]) <= 1e-3
-            if gap < 1e-3 and is_runner_up:
-                n_top_swap += 1
-                worst_gap = max(worst_gap, gap)
-                if (cand[f, 0, 0] == 0.0) != (ec[0, 0] == 0.0):
-                    n_vuv_flip += 1
-                    n_vuv_outside += int(gap > 1e-4)
-            else:
-                n_top_bad += 1
+        verdict = classify_top(cand[f, 0], ec, en)            # the rule itself: tests/analyze_reference.py
+        if verdict in ("swap", "vuv_outside"):
+            n_top_swap += 1
+            worst_gap = max(worst_gap, tie_gap(ec, en))
+            if (cand[f, 0, 0] == 0.0) != (ec[0, 0] == 0.0):
+                n_vuv_flip += 1
+                n_vuv_outside += int(verdict == "vuv_outside")
+        elif verdict == "bad":
+            n_top_bad += 1
         if kmax >= en:
             # full list: compare as sets ordered by frequency (strength order may permute within tolerance)
             g = cand[f, :k][np.argsort(cand[f, :k, 0], kind="stable")]
