@@ -204,7 +204,10 @@ int vbx_improve_extremum_ex_f64(vbx_ctx *ctx, const double *y, size_t ylen, long
  * Which shapes are fast (one MI355X, kmax = 1, frames/s; the table in DESIGN.md section 4 is kept current): 512..1024 samples
  * 44-56 M, 1025..1200 39-42 M, 1201..2048 29 M, 2049..4096 16-17 M (that range runs its refinement in kernels of its
  * own, with the lag curves in a context-owned scratch buffer between them: <= 2.3 GB, 4.4 GB at an odd length),
- * below 512 samples the direct lag sums on the matrix cores 50-70 M.  kmax 2 / 8 / 64 / whole Vec at 1200: 13.5 / 6.5 / 3.25 / 2.7 M. */
+ * below 512 samples the direct lag sums on the matrix cores 50-70 M.  kmax 2 / 8 / 64 / whole Vec at 1200: 13.5 / 6.5 / 3.25 / 2.7 M.
+ * Alignment: x, window and out_cand need 8 bytes (what C gives an array of double / vbx_pitch), out_count and status 4; 16-byte
+ * aligned frames and windows take the kernels' 16-byte loads, anything else their element-wise ones, with the same results bit for
+ * bit (tests/test_gpu_layouts.py).  That holds for every frame-batch entry point of this header unless its comment says otherwise. */
 int vbx_pitch_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
                   const double *window, double sample_rate, double threshold, double fmin, double fmax,
                   size_t kmax, vbx_pitch *out_cand, int32_t *out_count, int32_t *status);
@@ -356,7 +359,8 @@ int vbx_to_resonance_c64(vbx_ctx *ctx, const vbx_complex *roots, size_t n_rows, 
  * h_seg_start[n_segments] (HOST array) are the ascending frame indices at which the caller's
  * state is reset to est_init (h_seg_start[0] must be 0; NULL/0 = one segment).  res: [F, n_res]
  * resonance rows exactly as the reference passes them (zero padded); frame_status (optional):
- * frames with status != 0 leave the state untouched.  out: [F, n_est] estimates after each frame. */
+ * frames with status != 0 leave the state untouched.  out: [F, n_est] estimates after each frame.
+ * Alignment: res and out need 8 bytes (an array of vbx_resonance), frame_status 4. */
 int vbx_estimate_formants_f64(vbx_ctx *ctx, const vbx_resonance *res, size_t n_frames, size_t n_res,
                               const int64_t *h_seg_start, size_t n_segments,
                               const vbx_resonance *h_est_init, size_t n_est,
@@ -374,7 +378,8 @@ int vbx_estimate_formants_f64(vbx_ctx *ctx, const vbx_resonance *res, size_t n_f
  * iteration to convergence too (20 steps per root) and sorts the result by frequency, so the rows agree to ~1e-10 relative
  * (gate 1e-4; counts and statuses equal).  A frame that fails the check is redone by the reference's own iteration, as
  * every frame of the other orders is.  Environment: VBX_ROOTS_DIRECT=1 (read per call) replays the reference's
- * iteration for every frame; VBX_BURG_DIRECT=1 see vbx_lpc_burg_f64. */
+ * iteration for every frame; VBX_BURG_DIRECT=1 see vbx_lpc_burg_f64.
+ * Alignment: out_formants and out_res need 8 bytes (arrays of vbx_resonance), out_res_count and status 4. */
 int vbx_find_formants_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len,
                           size_t stride, double sample_rate, size_t n_coeffs,
                           const int64_t *h_seg_start, size_t n_segments,
@@ -505,7 +510,9 @@ int vbx_pitch_f32_wide(vbx_ctx *ctx, const float *x, size_t n_frames, size_t fra
  * fall back to vbx_mfcc_f64's kernel beside the fused one; VBX_MFCC_INTERP=0 in the environment forces that everywhere.)
  * Output: one record of vbx_record_doubles(params) doubles per frame,
  *   [ pitch.frequency, pitch.strength | formants[n_est] {frequency, bandwidth} | mfcc[mfcc_coeffs] | lpc[lpc_order + 1] ]
- * at out_records + f * record_ld (record_ld even, >= the record size; 16-byte aligned base): the fixed-size
+ * at out_records + f * record_ld (record_ld even, >= the record size; out_records 16-byte ALIGNED -- the one pointer of this
+ * header that needs more than its type's alignment: a base at 8 mod 16 is rejected with VBX_E_INVALID, "records must be 16-byte
+ * aligned", before anything is written; x and status3 need 8 / 4 bytes, pcm 2): the fixed-size
  * per-frame record that the multi-GPU gather below moves.  status3 (optional): [3, F] = pitch / formant / mfcc
  * status rows.  Asynchronous on the context's stream (a second, context-owned stream is used inside and joined). */
 typedef struct {
@@ -576,7 +583,8 @@ int vbx_shard_local_segments(const vbx_shard_plan_t *h_plan, const int64_t *h_se
 /* Step 2 on one device: `formants` are the rows the LAST vbx_find_formants_f64 (out_formants, formants_ld = 2 n_est) or
  * vbx_analyze_frames_* call (out_records + 2, formants_ld = record_ld) on this context wrote, n_frames of them (call it right
  * after that call: it reads the resonance rows the context still holds); d_state_in (device, n_est entries) is the true state
- * before frame `first`; rows [first, stop) are corrected where needed.  *d_changed (device, optional) = rows rewritten. */
+ * before frame `first`; rows [first, stop) are corrected where needed.  *d_changed (device, optional) = rows rewritten.
+ * Alignment: formants as the call that wrote them took it (8 bytes for out_formants; the records' 16), d_state_in 8, d_changed 4. */
 int vbx_track_stitch_f64(vbx_ctx *ctx, vbx_resonance *formants, size_t n_frames, size_t formants_ld, size_t first, size_t stop,
                          const vbx_resonance *d_state_in, int32_t *d_changed);
 

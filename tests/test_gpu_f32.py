@@ -12,6 +12,8 @@ MFCC exists only in the wide form (rustfft's f32 arithmetic is not in the tree).
 import numpy as np
 import pytest
 
+import parity_asserts as pa
+
 pytestmark = pytest.mark.gpu
 SR = 48000.0
 ULP = float(np.finfo(np.float32).eps)
@@ -45,9 +47,8 @@ def test_autocorrelate_f32_equals_the_f32_fold(vb, oracle, audio, n, lags):
     x = _frames32(audio, n, 211 if n <= 1200 else 1, 12 if n <= 1200 else 3, oracle.window("hanning", n))
     x[1] = np.random.default_rng(n).uniform(-1, 1, n).astype(np.float32)         # rectangular frame: x[0] != 0 (Q1)
     got = vb.autocorrelate_f32(x, lags)
-    assert got.dtype == np.float32
+    pa.autocorrelate_f32_rows(oracle, x, lags, got)
     r32 = np.stack([oracle.autocorrelate_f32(f, lags) for f in x])
-    assert np.array_equal(got, r32)
     # the wide form: the f64 kernels on the widened frame, one rounding -- closer to the exact sums than the f32 folds are
     wide = vb.autocorrelate_f32(x, lags, wide=True)
     assert np.array_equal(wide, vb.autocorrelate(x.astype(np.float64), lags).astype(np.float32))
@@ -70,12 +71,9 @@ def test_normalize_and_lpc_f32(vb, oracle, audio):
     x = _frames32(audio, n, 333, 10, oracle.window("hanning", n))
     r = vb.autocorrelate_f32(x, p + 1)
     rn = vb.normalize_f32(r)
-    assert np.array_equal(rn, np.stack([oracle.normalize_f32(row) for row in r]))
+    pa.normalize_f32_rows(oracle, r, rn)
     ac, kc = vb.lpc_mut_f32(rn, p)
-    assert ac.dtype == np.float32 and np.all(ac[:, 0] == 1.0)
-    for f in range(rn.shape[0]):
-        ea, ek = oracle.lpc_f32(rn[f], p)
-        assert np.array_equal(ac[f], ea) and np.array_equal(kc[f], ek), f
+    pa.lpc_f32_rows(oracle, rn, p, ac, kc)
     # fused autocorrelate -> normalize -> lpc, each step the f32 statement
     r2, a2 = vb.autocorr_lpc_f32(x, p, normalize=True)
     assert np.array_equal(r2, rn) and np.array_equal(a2, ac)
@@ -99,12 +97,7 @@ def test_lpc_praat_f32_equals_the_f32_recursion(vb, oracle, audio, n, p):
     x = _frames32(audio, n, 401 if n > 512 else 97, F, oracle.window("hanning", n))
     x[F - 1] = 0.0                                                                # all-zero frame -> Err(LPC)
     co, st = vb.lpc_praat_f32(x, p)
-    assert co.dtype == np.float32
-    for f in range(F):
-        es, ec = oracle.lpc_burg_f32(x[f], p)
-        assert st[f] == es, f
-        if es == 0:
-            assert np.array_equal(co[f], ec), (f, co[f], ec)
+    pa.burg_f32_rows(oracle, x, p, co, st)
     assert st[F - 1] == 1 and np.all(co[F - 1] == 0.0)
     cow, stw = vb.lpc_praat_f32(x, p, wide=True)
     co64, st64 = vb.lpc_praat(x.astype(np.float64), p)
@@ -137,18 +130,7 @@ def test_pitch_f32_follows_the_f32_lag_curve(vb, oracle, audio, n, hop):
     F = min(60, (audio.size - n) // hop + 1)
     x = _frames32(audio, n, hop, F, oracle.window("hanning", n))
     cand, cnt, st = vb.pitch_f32(x, SR, 0.2, 75.0, 600.0, kmax=4)
-    assert cand.dtype == np.float32
-    n_same_bits = n_cmp = 0
-    for f in range(F):
-        es, ec, en = oracle.pitch_f32(x[f], SR, 0.2, 75.0, 600.0)
-        assert st[f] == es and cnt[f] == (en if es == 0 else 0), (f, st[f], es, cnt[f], en)
-        if es != 0:
-            continue
-        tie = en > 1 and abs(ec[0, 1] - ec[1, 1]) < 1e-3
-        if not tie:
-            assert abs(cand[f, 0, 0] - ec[0, 0]) <= 1e-4 * abs(ec[0, 0]) + 1e-12 and abs(cand[f, 0, 1] - ec[0, 1]) <= 1e-4, (f, cand[f, 0], ec[0])
-            n_cmp += 1
-            n_same_bits += int(np.float32(ec[0, 0]) == cand[f, 0, 0] and np.float32(ec[0, 1]) == cand[f, 0, 1])
+    n_cmp, n_same_bits, _ = pa.pitch_f32_rows(oracle, x, SR, 0.2, 75.0, 600.0, cand, cnt, st)
     print("\npitch_f32 n=%d: %d top candidates compared, %d with identical f32 bits" % (n, n_cmp, n_same_bits))
     assert n_cmp >= F // 2
     # the wide form: the f64 path on the widened frames, rounded once

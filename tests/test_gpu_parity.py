@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from analyze_reference import classify_top, tie_gap
+import parity_asserts as pa
 from conftest import rel_close
 
 pytestmark = pytest.mark.gpu
@@ -81,9 +82,7 @@ def test_autocorrelate(vb, oracle, n, lags):
     rng = np.random.default_rng(n * 1000 + lags)
     x = rng.uniform(-1, 1, (9, n))          # rectangular frames: x[0] != 0 exercises the Q1 seed
     got = vb.autocorrelate(x, lags)
-    for f in range(x.shape[0]):
-        exp = oracle.autocorrelate(x[f], lags)
-        assert np.all(rel_close(got[f], exp)), (f, np.max(np.abs(got[f] - exp)))
+    pa.autocorrelate_rows(oracle, x, lags, got)
 
 
 @pytest.mark.parametrize("n,lags", [(1200, 1200), (1024, 100), (2048, 2047), (777, 300), (4096, 4096)])
@@ -161,13 +160,7 @@ def test_autocorr_lpc(vb, oracle, n, p, norm):
     x = np.stack([np.sin(2 * np.pi * (0.01 + 0.002 * k) * t) * 0.5 + 0.2 * rng.standard_normal(n) for k in range(8)])
     x *= oracle.window("hanning", n)
     r, a = vb.autocorr_lpc(x, p, normalize=norm)
-    for f in range(8):
-        er = oracle.autocorrelate(x[f], p + 1)
-        if norm:
-            er = oracle.normalize(er)
-        ea = oracle.lpc(er, p)
-        assert np.all(rel_close(r[f], er)), (f, "r")
-        assert np.all(rel_close(a[f], ea)), (f, "lpc", np.max(np.abs(a[f] - ea)))
+    pa.autocorr_lpc_rows(oracle, x, p, norm, r, a)
 
 
 # ---- Burg -------------------------------------------------------------------------------------
@@ -190,13 +183,7 @@ def test_lpc_praat(vb, oracle, n, p):
                   + 0.05 * rng.standard_normal(n) for k in range(6)])
     x[5] = 0.0                                        # all-zero frame -> Err(LPC) (src/spectrum.rs:123-125)
     co, st = vb.lpc_praat(x, p)
-    for f in range(6):
-        es, ec = oracle.lpc_burg(x[f], p)
-        assert st[f] == es, f
-        if es == 0:
-            assert np.all(rel_close(co[f], ec)), (f, np.max(np.abs(co[f] - ec)))
-        else:
-            assert np.all(co[f] == 0.0)
+    pa.burg_rows(oracle, x, p, co, st)
 
 
 # ---- polynomial ---------------------------------------------------------------------------------
@@ -271,18 +258,7 @@ def test_find_roots_f32_random(vb, oracle):
     P = rng.uniform(-1.0, 1.0, (64, 9)).astype(np.float32)
     P[:, -1] = 1.0
     r, st = vb.find_roots_f32(P.astype(np.complex64))
-    for f in range(P.shape[0]):
-        es, er = oracle.find_roots_f32(P[f].astype(np.complex64))
-        assert st[f] == es
-        if es != 0:
-            continue
-        g = np.sort_complex(r[f, :er.size].astype(np.complex128))
-        e = np.sort_complex(er.astype(np.complex128))
-        # residual check (conditioning-independent): every GPU root is a root of the polynomial to f32 accuracy
-        pv = np.polyval(P[f, ::-1].astype(np.float64), r[f, :er.size].astype(np.complex128))
-        scale = np.polyval(np.abs(P[f, ::-1]).astype(np.float64), np.abs(r[f, :er.size]).astype(np.float64))
-        assert np.all(np.abs(pv) <= 2e-4 * scale), (f, np.abs(pv) / scale)
-        assert g.size == e.size
+    pa.find_roots_f32_rows(oracle, P, r, st)
 
 
 def test_find_roots_random(vb, oracle):

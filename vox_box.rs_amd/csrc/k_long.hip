@@ -430,13 +430,13 @@ __global__ __launch_bounds__(256) void pitch_long_sort_kernel(long n_frames, lon
     else if (total_cand > 1 && ((fl & 8) || threshold != threshold)) code = 3;   // partial_cmp().unwrap() on NaN (Q10)
     const int total = (code == 0) ? total_cand : 0;
     double *orow = out_cand + f * cand_ld;
-    for (int i = t; i < kmax; i += 256) *reinterpret_cast<double2 *>(orow + 2 * i) = double2{0.0, 0.0};
+    for (int i = t; i < kmax; i += 256) store_pair8(orow + 2 * i, double2{0.0, 0.0});
     __syncthreads();
     for (int i = t; i < total; i += 256) {
         const double2 me = row[i];
         int rank = 0;
         for (int j = 0; j < total; j++) { const double sj = row[j].y; rank += (sj > me.y || (sj == me.y && j < i)) ? 1 : 0; }
-        if (rank < kmax) *reinterpret_cast<double2 *>(orow + 2 * rank) = me;
+        if (rank < kmax) store_pair8(orow + 2 * rank, me);
     }
     if (t == 0) {
         if (out_count != nullptr) out_count[f] = total;

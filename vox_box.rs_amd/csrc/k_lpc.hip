@@ -305,7 +305,7 @@ __global__ void levinson_rows_kernel(const T *__restrict__ r, long n_rows, long 
 // the num_coeffs mel filter sums the fused kernel left there) -- in the fused call's record the two rows are neighbours, one pass
 // over the record's cache lines instead of two.
 template <int P, bool PROBE>
-__global__ __launch_bounds__(64) void levinson_rows_kernel_t(const double *__restrict__ r, long n_rows, long r_stride, double *__restrict__ out,
+__global__ __launch_bounds__(64) void levinson_rows_kernel_t(const double *r, long n_rows, long r_stride, double *out /* may be r: no __restrict__ on the two */,
                                                              long out_ld, int32_t *__restrict__ lpc_list, int32_t *__restrict__ lpc_count,
                                                              double *__restrict__ mfcc_rows, long mfcc_ld, int num_coeffs,
                                                              const double *__restrict__ dct_table) {

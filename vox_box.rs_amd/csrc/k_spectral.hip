@@ -806,6 +806,15 @@ bool mfcc_interp_fill(int plan, int n, int b_lo, int nb, void *h_table, mfcc_int
     return d->lds_bytes <= cap;
 }
 
+// The whole-Vec candidate list of the 1200-point plan lives in the frame's own output row (launch_analyze below) ...
+// (the parked list is read and written as double2: only where the rows are 16-byte aligned -- cand_ld is even, so the base
+// decides; a caller's vbx_pitch array at 8 mod 16 keeps the list in LDS, the same candidates in the same order)
+bool spectral_list_parked(const spectral_launch_t &L) {
+    const bool rows16 = (((uintptr_t)L.out_cand) & 15) == 0 && (L.cand_ld & 1) == 0;
+    return L.plan == SPECTRAL_PLAN_1200 && pitch_full_list_bytes(L.n, L.kmax) != 0 && L.kmax >= pitch_full_list_entries(L.n) &&
+           L.out_r == nullptr && !L.mfcc_only && rows16;
+}
+
 int launch_analyze(hipStream_t s, const spectral_launch_t &L) {
     spectral_args_t a;
     a.frames = L.x; a.n_frames = L.F; a.stride = L.stride; a.window = L.window; a.lag_window = L.lag_window;
@@ -830,7 +839,7 @@ int launch_analyze(hipStream_t s, const spectral_launch_t &L) {
     // kmax = VBX_PITCH_MAX_CANDIDATES(frame_len) (the whole Vec of every frame fits its output row): the refined candidates
     // are parked in the row itself instead of an extra LDS region, which keeps the frame state at 13.5 KB = twelve
     // wavefronts per CU (the form compiled for three wavefronts per SIMD, below)
-    if (extra && L.kmax >= pitch_full_list_entries(L.n) && L.out_r == nullptr && !L.mfcc_only) { a.pp.full_off = -1; extra = 0; }
+    if (spectral_list_parked(L)) { a.pp.full_off = -1; extra = 0; }
     const size_t lds = base + extra;
     const bool lpc = L.out_lpc != nullptr, mf = L.out_mfcc != nullptr;
     if (L.mfcc_only) {                                       // n == SP_N, or a padded frame with interpolated bins

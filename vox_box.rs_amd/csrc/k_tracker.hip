@@ -308,7 +308,7 @@ __global__ __launch_bounds__(64) void tracker_kernel(const res_t *__restrict__ r
 #pragma unroll
     for (int e = 0; e < NE; e++) {
         if (t0 == 0) { ef[e] = est_init[e].frequency; eb[e] = est_init[e].bandwidth; }
-        else { const double2 p = *reinterpret_cast<const double2 *>(out + (f0 - 1) * out_ld + 2 * e); ef[e] = p.x; eb[e] = p.y; }
+        else { const double2 p = load_pair8(out + (f0 - 1) * out_ld + 2 * e); ef[e] = p.x; eb[e] = p.y; }
     }
     // The scan is a chain of dependent steps; frame f+1's status, count and leading row entries are requested
     // before frame f is processed so that their latency is off the chain.
@@ -331,7 +331,7 @@ __global__ __launch_bounds__(64) void tracker_kernel(const res_t *__restrict__ r
         if (f + 1 < f1) fetch(f + 1, nxt, nxt_cnt, nxt_ok);
         if (cur_ok) estimate_formants_any<NE>(ef, eb, cur, res + f * (long)n_res, n_res, cur_cnt, res_count != nullptr, general != 0);
 #pragma unroll
-        for (int e = 0; e < NE; e++) { double2 o; o.x = ef[e]; o.y = eb[e]; *reinterpret_cast<double2 *>(out + f * out_ld + 2 * e) = o; }
+        for (int e = 0; e < NE; e++) store_pair8(out + f * out_ld + 2 * e, double2{ef[e], eb[e]});
 #pragma unroll
         for (int i = 0; i < TRK_PF; i++) cur[i] = nxt[i];
         cur_cnt = nxt_cnt; cur_ok = nxt_ok;
@@ -401,19 +401,19 @@ __device__ __forceinline__ void trk_load_row(const trk_in_t &in, long f, double 
 #pragma unroll
     for (int e = 0; e < NS; e++) { ef[e] = 0.0; eb[e] = 0.0; }
 #pragma unroll
-    for (int e = 0; e < NE; e++) { const double2 p = *reinterpret_cast<const double2 *>(in.out + f * in.out_ld + 2 * e); ef[e] = p.x; eb[e] = p.y; }
+    for (int e = 0; e < NE; e++) { const double2 p = load_pair8(in.out + f * in.out_ld + 2 * e); ef[e] = p.x; eb[e] = p.y; }
 }
 template <int NE>
 __device__ __forceinline__ void trk_store_row(const trk_in_t &in, long f, const double (&ef)[NS], const double (&eb)[NS]) {
 #pragma unroll
-    for (int e = 0; e < NE; e++) { double2 o; o.x = ef[e]; o.y = eb[e]; *reinterpret_cast<double2 *>(in.out + f * in.out_ld + 2 * e) = o; }
+    for (int e = 0; e < NE; e++) store_pair8(in.out + f * in.out_ld + 2 * e, double2{ef[e], eb[e]});
 }
 template <int NE>
 __device__ __forceinline__ bool trk_row_is(const trk_in_t &in, long f, const double (&ef)[NS], const double (&eb)[NS]) {
     bool same = true;
 #pragma unroll
     for (int e = 0; e < NE; e++) {
-        const double2 p = *reinterpret_cast<const double2 *>(in.out + f * in.out_ld + 2 * e);
+        const double2 p = load_pair8(in.out + f * in.out_ld + 2 * e);
         same = same && same_bits(p.x, ef[e]) && same_bits(p.y, eb[e]);
     }
     return same;

@@ -62,6 +62,8 @@ struct vbx_ctx {
     std::map<std::tuple<int, int, int, int>, std::pair<void *, mfcc_interp_t>> interp_cache;   // (plan, n, b_lo, nb) -> tables of the interpolated MFCC bins (first == nullptr: no such form)
     int last_mfcc_interp = 0;                             // the last vbx_mfcc_f64 call took the interpolated form (tests)
     int last_spectral_split = 0;                          // the last fused / pitch call ran as two kernels (tests)
+    int last_mfcc_form = 0;                               // which kernel the last vbx_mfcc_f64 call launched: VBX_MFCC_FORM_* below (tests)
+    int last_pitch_form = 0;                              // the same for vbx_pitch_f64: 100 * kernel family + candidate list form (tests)
     int mfcc_defer = 1;                                   // VBX_MFCC_DEFER=0: log10 + DCT of the fused call's MFCC rows inside the frame's wavefront (rounds 2-5; A/B)
     int lpc_policy = VBX_LPC_POLICY_EXACT;                // VBX_LPC_POLICY_*; VBX_LPC_EXACT=0 initialises PLAIN (no conditioning probe, no double-double redo:
                                                           //   the rows of rounds 1-5), vbx_ctx_set_lpc_policy overrides
@@ -913,7 +915,7 @@ static int run_pitch(vbx_ctx *ctx, hipStream_t st, const double *x, size_t n_fra
     VBX_REQUIRE(ctx, out_cand != nullptr, "null output");
     const size_t kcap = frame_len > VBX_MAX_FRAME_LEN ? VBX_PITCH_MAX_CANDIDATES(frame_len) : (size_t)VBX_MAX_PITCH_CANDIDATES;
     VBX_REQUIRE(ctx, kmax >= 1 && kmax <= kcap, "kmax must be in [1, VBX_MAX_PITCH_CANDIDATES] (long frames: [1, frame_len / 4 + 2])");
-    VBX_REQUIRE(ctx, cand_ld >= 2 * kmax && cand_ld % 2 == 0, "candidate rows must be 16-byte aligned and hold kmax entries");
+    VBX_REQUIRE(ctx, cand_ld >= 2 * kmax && cand_ld % 2 == 0, "candidate rows must hold kmax entries and their leading dimension must be even");
     VBX_REQUIRE(ctx, frame_len >= 4, "frame_len must be >= 4");
     const double *lagw = nullptr;
     int rc = get_window_dev(ctx, VBX_WINDOW_HANNING_LAG, frame_len, &lagw);
@@ -934,6 +936,7 @@ static int run_pitch(vbx_ctx *ctx, hipStream_t st, const double *x, size_t n_fra
             rc = run_autocorrelate(ctx, st, x + f0 * stride, m, frame_len, stride, window, frame_len, r);      // :402
             if (rc != VBX_SUCCESS) return rc;
             { Prof p(ctx, "normalize_rows", st); launch_normalize_rows(st, r, (long)m, (int)frame_len); }       // :404
+            ctx->last_pitch_form = 100;
             { Prof p(ctx, "pitch_long", st);
               launch_pitch_long(st, (long)m, (long)frame_len, lagw, sample_rate, threshold, fmin, fmax, (int)kmax,
                                 (double *)out_cand + f0 * cand_ld, (long)cand_ld, out_count ? out_count + f0 : nullptr,
@@ -961,9 +964,11 @@ static int run_pitch(vbx_ctx *ctx, hipStream_t st, const double *x, size_t n_fra
         L.whole_curve = ctx->pitch_whole_curve;
         L.out_cand = (pitch_t *)out_cand; L.cand_ld = (long)cand_ld; L.out_count = out_count; L.pitch_status = status;
         L.work = ctx->prof ? ctx->pitch_work : nullptr;
+        ctx->last_pitch_form = 100 * (3 + L.plan) + (pitch_full_list_bytes(L.n, L.kmax) == 0 ? 0 : spectral_list_parked(L) ? 2 : 1);
         return launch_spectral(ctx, st, L, "pitch");
     }
     {
+        ctx->last_pitch_form = 200 + (pitch_full_list_bytes((int)frame_len, (int)kmax) == 0 ? 0 : 1);
         Prof p(ctx, "pitch", st);
         launch_pitch(st, x, (long)n_frames, (int)frame_len, (long)stride, window, lagw, sample_rate, threshold,
                      fmin, fmax, (int)kmax, (pitch_t *)out_cand, (long)cand_ld, out_count, status,
@@ -1450,6 +1455,13 @@ double *vbx_internal_stitch_state(vbx_ctx *ctx) {
 int vbx_internal_last_track_n_est(vbx_ctx *ctx) { return ctx ? ctx->last_track.n_est : 0; }
 int vbx_internal_last_spectral_split(vbx_ctx *ctx) { return ctx ? ctx->last_spectral_split : 0; }
 int vbx_internal_last_mfcc_interp(vbx_ctx *ctx) { return ctx ? ctx->last_mfcc_interp : 0; }
+// Every MFCC kernel is profiled as "mfcc" and every pitch kernel as "pitch": these say which one the context's last call took.
+// MFCC: 1 the fused kernels' forward transform, 2 the same with interpolated bins, 3 chirp-z, 4 matrix-core two-stage DFT,
+// 5 vector two-stage DFT, 6 Goertzel, 7 the long-frame kernel, 8 every frame panics (rows filled).
+// Pitch: 100 * family (1 long frames, 2 the direct lag sums below 512 samples / VBX_PITCH_MFMA, 3 + spectral plan: the FFT kernels)
+// + the candidate list (0 lane-resident, 1 LDS-resident, 2 parked in the output row).
+int vbx_internal_last_mfcc_form(vbx_ctx *ctx) { return ctx ? ctx->last_mfcc_form : 0; }
+int vbx_internal_last_pitch_form(vbx_ctx *ctx) { return ctx ? ctx->last_pitch_form : 0; }
 // every host-side condition of a stitch / hand-off on these rows, for callers that must know BEFORE they enqueue anything
 // a peer waits for (vbx_comm.hip: an early return between ncclRecv and ncclSend would leave the next rank blocked)
 int vbx_internal_track_check(vbx_ctx *ctx, const vbx_resonance *formants, size_t n_frames, size_t formants_ld) {
@@ -1491,9 +1503,11 @@ static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_fra
     VBX_REQUIRE(ctx, out_ld >= num_coeffs, "output rows must hold num_coeffs entries");
     std::vector<int32_t> hb; bool bad = false; const int32_t *d_bins = nullptr;
     ctx->last_mfcc_interp = 0;
+    ctx->last_mfcc_form = 0;
     int rc = get_bins_dev(ctx, frame_len, num_coeffs, lo_hz, hi_hz, sample_rate, &d_bins, hb, bad);
     if (rc != VBX_SUCCESS) return rc;
     if (bad) {   // the reference panics on every frame (bins do not depend on the data)
+        ctx->last_mfcc_form = 8;
         { Prof p(ctx, "fill_rows", stm); launch_fill_rows(stm, out, (long)n_frames, (int)num_coeffs, (long)out_ld, 0.0, status, VBX_FRAME_ERR_PANIC); }
         return check_launch(ctx, "vbx_mfcc_f64");
     }
@@ -1507,6 +1521,7 @@ static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_fra
         rc = get_goertzel_dev(ctx, frame_len, hb.front(), nb, &tw); if (rc != VBX_SUCCESS) return rc;
         void *w = nullptr;
         rc = ws_get(ctx, vbx_ctx::WS_CZT, mfcc_long_scratch_bytes((long)n_frames, nb), &w); if (rc != VBX_SUCCESS) return rc;
+        ctx->last_mfcc_form = 7;
         { Prof p(ctx, "mfcc_long", stm);
           launch_mfcc_long(stm, x, (long)n_frames, (long)frame_len, (long)stride, window, tw, d_bins, slopes, dct, (int)num_coeffs, nb, out,
                            (long)out_ld, status, (double *)w); }
@@ -1528,6 +1543,7 @@ static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_fra
             L.x = x; L.F = (long)n_frames; L.stride = (long)stride; L.window = window; L.tab = tab;
             L.out_mfcc = out; L.mfcc_ld = (long)out_ld; L.mfcc_status = status;
             L.bins = d_bins; L.slopes = slopes; L.dct = dct; L.num_coeffs = (int)num_coeffs; L.nb = nb;
+            ctx->last_mfcc_form = 1;
             { Prof p(ctx, "mfcc", stm); launch_analyze(stm, L); }
             return check_launch(ctx, "vbx_mfcc_f64");
         }
@@ -1558,6 +1574,7 @@ static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_fra
             spectral_launch_t L{};
             L.plan = plan; L.n = (int)frame_len; L.mfcc_only = true; L.interp = true; L.ip = ip;
             ctx->last_mfcc_interp = 1;
+            ctx->last_mfcc_form = 2;
             L.x = x; L.F = (long)n_frames; L.stride = (long)stride; L.window = window; L.tab = tab;
             L.out_mfcc = out; L.mfcc_ld = (long)out_ld; L.mfcc_status = status;
             L.bins = d_bins; L.slopes = slopes; L.dct = dct; L.num_coeffs = (int)num_coeffs; L.nb = nb;
@@ -1599,6 +1616,7 @@ static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_fra
             rc = get_czt_dev(ctx, frame_len, top, spectral_plan_nc(cplan), czt_n1, &chirp, &bhat); if (rc != VBX_SUCCESS) return rc;
             void *cw = nullptr;
             rc = ws_get(ctx, vbx_ctx::WS_CZT, (czt_n1 ? 4 : 2) * (size_t)spectral_plan_nc(cplan) * sizeof(double), &cw); if (rc != VBX_SUCCESS) return rc;
+            ctx->last_mfcc_form = 3;
             { Prof p(ctx, "mfcc", stm);
               launch_mfcc_czt(stm, cplan, x, (long)n_frames, (int)frame_len, czt_n1, (long)stride, window, tab, chirp, bhat, d_bins, slopes, dct,
                               (int)num_coeffs, nb, out, (long)out_ld, status, (double *)cw); }
@@ -1608,12 +1626,14 @@ static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_fra
     if (mp.ok) {
         const double *ctab = nullptr, *twd = nullptr, *twm = nullptr, *wm = nullptr;
         rc = get_mfcc_mfma_dev(ctx, frame_len, mp, &ctab, &twd, &twm, &wm); if (rc != VBX_SUCCESS) return rc;
+        ctx->last_mfcc_form = 4;
         Prof p(ctx, "mfcc", stm);
         launch_mfcc_mfma(stm, x, (long)n_frames, (int)frame_len, (long)stride, window, mp, ctab, twd, twm, wm, d_bins,
                          slopes, dct, (int)num_coeffs, out, (long)out_ld, status, nb, ctx->cu_count);
     } else if (pl.ok) {
         const double *ctab = nullptr, *twid = nullptr;
         rc = get_dft2_dev(ctx, frame_len, pl, &ctab, &twid); if (rc != VBX_SUCCESS) return rc;
+        ctx->last_mfcc_form = 5;
         Prof p(ctx, "mfcc", stm);
         launch_mfcc_dft2(stm, x, (long)n_frames, (int)frame_len, (long)stride, window, pl, ctab, twid, d_bins,
                          slopes, dct, (int)num_coeffs, out, (long)out_ld, status, nb, ctx->cu_count);
@@ -1621,6 +1641,7 @@ static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_fra
         VBX_REQUIRE(ctx, mfcc_fits((int)frame_len, nb), "frame / bin range does not fit the LDS");
         const double *tw = nullptr;
         rc = get_goertzel_dev(ctx, frame_len, hb.front(), nb, &tw); if (rc != VBX_SUCCESS) return rc;
+        ctx->last_mfcc_form = 6;
         Prof p(ctx, "mfcc", stm);
         launch_mfcc(stm, x, (long)n_frames, (int)frame_len, (long)stride, window, tw, d_bins, slopes, dct, (int)num_coeffs, out, (long)out_ld, status, nb);
     }

@@ -9,6 +9,16 @@
 
 namespace vbx {
 
+// ---- a {double, double} entry of a CALLER's array (vbx_pitch, vbx_resonance) -----------
+// C aligns such an array to 8 bytes and the ABI asks no more, so these accesses promise the compiler 8 bytes, where a
+// cast to double2 would promise 16.  Still one 16-byte global access: global memory takes it at any 8-byte address.
+struct pair8_t { double x, y; };
+__device__ __forceinline__ double2 load_pair8(const double *p) {
+    const pair8_t v = *reinterpret_cast<const pair8_t *>(p);
+    return double2{v.x, v.y};
+}
+__device__ __forceinline__ void store_pair8(double *p, double2 v) { *reinterpret_cast<pair8_t *>(p) = pair8_t{v.x, v.y}; }
+
 // ---- lane broadcast / shuffles on f64 (two 32-bit halves) ---------------------------
 
 __device__ __forceinline__ double readlane_f64(double v, int lane) {

@@ -227,6 +227,7 @@ struct spectral_launch_t {
 };
 size_t spectral_split_row_bytes(int n, double sample_rate, double fmin);   // bytes per frame of that scratch, 0: the shape has no split form
 bool spectral_supported(int n, int lpc_order, int mfcc_nb, int mfcc_b_lo, int num_coeffs);
+bool spectral_list_parked(const spectral_launch_t &L);              // the whole-Vec list goes to the output row, not to LDS
 int launch_analyze(hipStream_t s, const spectral_launch_t &L);       // 1: the call ran as two kernels (SP_ANALYZE_SPLIT), 0: one
 // k_lpc_exact.hip: LPC::lpc(p) of the listed frames from double-double lag sums and a double-double recursion (the exact
 // answer rounded once), over a list only the device knows the length of

@@ -1279,15 +1279,15 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
                 const double sj = full[j].y;                 // same address in every lane: one broadcast read
                 rank += (sj > me.y || (sj == me.y && j < i)) ? 1 : 0;
             }
-            if (i < total && rank < kmax) *reinterpret_cast<double2 *>(row + 2 * rank) = me;
+            if (i < total && rank < kmax) store_pair8(row + 2 * rank, me);
         }
-        for (int i = total + lane; i < kmax; i += 64) *reinterpret_cast<double2 *>(row + 2 * i) = double2{0.0, 0.0};
+        for (int i = total + lane; i < kmax; i += 64) store_pair8(row + 2 * i, double2{0.0, 0.0});
     } else if (lane < kmax) {
         const bool valid = (code == 0) && lane < kept;
         double2 o;
         o.x = valid ? lf : 0.0;                     // Pitch { frequency, strength }
         o.y = valid ? ls : 0.0;
-        *reinterpret_cast<double2 *>(out_cand + f * cand_ld + 2 * lane) = o;   // row f of a [F, cand_ld] array of doubles
+        store_pair8(out_cand + f * cand_ld + 2 * lane, o);   // row f of a [F, cand_ld] array of doubles
     }
     if (lane == 0) {
         if (out_count != nullptr) out_count[f] = (code == 0) ? total_cand : 0;
