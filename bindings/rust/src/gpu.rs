@@ -1169,6 +1169,31 @@ impl<'g> FrameBatch<'g> {
         })?;
         Ok(Records { data, status3, n_frames: self.n_frames, record_ld: ld })
     }
+
+    /// [`FrameBatch::analyze`] with the third pass run (`vbx_analyze_frames_tracked_f64`): columns 0-1 of every record hold the
+    /// pitch path over the call's own `kmax`-entry candidate lists (see [`FrameBatch::pitch_path`]) instead of
+    /// `candidates[0]`, one path per utterance of `seg_start`; every other column is `analyze`'s, bit for bit.  A `path`
+    /// whose `time_step` is 0 takes the view's hop, `stride / sample_rate`.  Also returns the path's list positions
+    /// (-1: the unvoiced state the path appends).
+    pub fn analyze_tracked(&self, params: &AnalysisParams, kmax: usize, path: &PitchPathParams, seg_start: &[i64])
+                           -> GpuResult<(Records<'g>, DeviceBuf<'g, i32>)> {
+        assert!(self.window.is_none(), "analyze_tracked applies the windows itself: pass a rectangular view (windower_rectangle)");
+        let gpu = self.gpu;
+        let p = params.to_ffi();
+        let track = ffi::VbxPitchTrackParams { kmax, path: path.raw() };
+        let rec = unsafe { ffi::vbx_record_doubles(&p) };
+        let ld = rec + (rec & 1);
+        let data = gpu.alloc::<f64>(self.n_frames * ld)?;
+        let status3 = gpu.alloc::<i32>(3 * self.n_frames)?;
+        let index = gpu.alloc::<i32>(self.n_frames)?;
+        let outputs = ffi::VbxPitchTrackOutputs { cand: ptr::null_mut(), count: ptr::null_mut(), peak: ptr::null_mut(), index: index.as_mut_ptr() };
+        let (seg_ptr, n_seg) = if seg_start.is_empty() { (ptr::null(), 0) } else { (seg_start.as_ptr(), seg_start.len()) };
+        gpu.check(unsafe {
+            ffi::vbx_analyze_frames_tracked_f64(gpu.raw, self.samples.as_ptr(), self.n_frames, self.frame_len, self.stride, &p, &track,
+                                                seg_ptr, n_seg, data.as_mut_ptr(), ld, status3.as_mut_ptr(), &outputs)
+        })?;
+        Ok((Records { data, status3, n_frames: self.n_frames, record_ld: ld }, index))
+    }
 }
 
 /// 16-bit PCM samples on the device with a `Windower` view over them: what a WAV reader hands the reference's callers
@@ -1215,6 +1240,27 @@ impl<'g> PcmBatch<'g> {
                                           data.as_mut_ptr(), ld, status3.as_mut_ptr())
         })?;
         Ok(Records { data, status3, n_frames: self.n_frames, record_ld: ld })
+    }
+
+    /// [`FrameBatch::analyze_tracked`] reading the PCM directly (`vbx_analyze_frames_tracked_pcm16`): bit-identical to
+    /// `self.widen()?.analyze_tracked(..)`, and no f64 copy of the recording is needed for the frames' peaks either.
+    pub fn analyze_tracked(&self, params: &AnalysisParams, kmax: usize, path: &PitchPathParams, seg_start: &[i64])
+                           -> GpuResult<(Records<'g>, DeviceBuf<'g, i32>)> {
+        let gpu = self.gpu;
+        let p = params.to_ffi();
+        let track = ffi::VbxPitchTrackParams { kmax, path: path.raw() };
+        let rec = unsafe { ffi::vbx_record_doubles(&p) };
+        let ld = rec + (rec & 1);
+        let data = gpu.alloc::<f64>(self.n_frames * ld)?;
+        let status3 = gpu.alloc::<i32>(3 * self.n_frames)?;
+        let index = gpu.alloc::<i32>(self.n_frames)?;
+        let outputs = ffi::VbxPitchTrackOutputs { cand: ptr::null_mut(), count: ptr::null_mut(), peak: ptr::null_mut(), index: index.as_mut_ptr() };
+        let (seg_ptr, n_seg) = if seg_start.is_empty() { (ptr::null(), 0) } else { (seg_start.as_ptr(), seg_start.len()) };
+        gpu.check(unsafe {
+            ffi::vbx_analyze_frames_tracked_pcm16(gpu.raw, self.samples.as_ptr(), self.n_frames, self.frame_len, self.stride, &p, &track,
+                                                  seg_ptr, n_seg, data.as_mut_ptr(), ld, status3.as_mut_ptr(), &outputs)
+        })?;
+        Ok((Records { data, status3, n_frames: self.n_frames, record_ld: ld }, index))
     }
 }
 

@@ -541,6 +541,51 @@ int vbx_analyze_frames_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_frames, 
                              const vbx_analysis_params *h_params, const int64_t *h_seg_start, size_t n_segments,
                              double *out_records, size_t record_ld, int32_t *status3);
 
+/* The frame loop with the TRACKED pitch contour (added in ABI 5): vbx_analyze_frames_f64 / _pcm16 whose columns 0-1 hold
+ * out_path[t] of vbx_pitch_path_f64 -- the chosen list entry for a voiced state, {0.0, u_t} for an unvoiced one -- instead of
+ * candidates[0], from ONE call: the fused kernel runs at the caller's kmax and writes the frames' candidate lists (what
+ * vbx_pitch_f64 writes at that kmax, to the fused kernels' ~1e-7), max |x| per frame (what vbx_frame_peak_f64 writes; on PCM an
+ * integer max over the 16-bit samples, widened once: the same bits) is taken beside it on the context's second stream, and the
+ * path runs behind both, once per segment of h_seg_start, writing straight into the records.  Every other column, all three
+ * status rows, the record layout, the alignment rule for out_records and the state the call leaves (vbx_track_stitch_f64, the
+ * LPC probe's count) are those of the plain call, bit for bit; vbx_internal_last_path_chunks_redone reports the path's count.
+ * The samples are read once by the spectral pass and once by the peak kernel; no f64 copy of a PCM recording is needed by the
+ * caller (shapes without a PCM kernel are widened into the context-owned copy, as in the plain call).
+ * h_track->kmax: the list length the path runs over, 1..63 (vbx_pitch_f64 takes at least 1026 at every frame_len, so 1..63 is the
+ * whole rule; frame_len itself must be one vbx_pitch_f64 takes: >= 4 samples);
+ * h_track->path: as vbx_pitch_path_f64, except that time_step == 0 means stride / sample_rate.
+ * h_outputs (optional device arrays; the struct pointer or any member may be NULL): the lists, counts, peaks and path indices,
+ * so that vbx_pitch_path_f64 can be run again with other costs (1-2 ms per 4.5 M frames) without recomputing the lists.  Where a member
+ * is NULL the library keeps that array in a context-owned workspace: at most F * (16 kmax + 16) bytes (lists, peaks, counts; the pitch
+ * status row when status3 is NULL), plus the path's own workspace (F * G bytes of back-pointers, G = the power of two >= kmax + 1,
+ * and a few hundred bytes per 256-frame chunk).  With silence_threshold == 0 and peak NULL no peak kernel runs.
+ * VBX_E_INVALID, before anything is written and with the context left usable: a NULL h_track, kmax 0 or > 63, any path parameter
+ * vbx_pitch_path_f64 rejects (other than time_step == 0), anything vbx_analyze_frames_f64 rejects.  n_frames == 0 succeeds.
+ * Sharded runs (below): the path is NOT carried across a shard cut -- each rank's contour is the path of the frames it analysed.
+ * Measured (one MI355X, 4.5 M frames of 1200 / 480 at 48 kHz, all parts on): 9.5 M frames/s at kmax 4, 5.0 M at kmax 15 (f64 and PCM
+ * alike), against 7.9 M / 4.5 M for vbx_analyze_frames_f64 + vbx_pitch_f64(kmax) + vbx_frame_peak_f64 + vbx_pitch_path_f64: the
+ * call saves the kmax = 1 pitch pass, ~90-100 ms of those frames; the list at kmax is what remains. */
+typedef struct {
+    size_t kmax;                   /* list length the path runs over: 1..63 (below vbx_pitch_f64's own cap at every frame_len) */
+    vbx_pitch_path_params path;    /* as vbx_pitch_path_f64; time_step == 0 here means stride / sample_rate */
+} vbx_pitch_track_params;
+typedef struct {                   /* optional device outputs; the struct pointer or any member may be NULL */
+    vbx_pitch *cand;               /* [F, kmax]  the lists the path ran over (what vbx_pitch_f64 writes at this kmax) */
+    int32_t   *count;              /* [F] */
+    double    *peak;               /* [F]  local_peak (what vbx_frame_peak_f64 writes) */
+    int32_t   *index;              /* [F]  out_index of vbx_pitch_path_f64 */
+} vbx_pitch_track_outputs;
+int vbx_analyze_frames_tracked_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
+                                   const vbx_analysis_params *h_params, const vbx_pitch_track_params *h_track,
+                                   const int64_t *h_seg_start, size_t n_segments,
+                                   double *out_records, size_t record_ld, int32_t *status3,
+                                   const vbx_pitch_track_outputs *h_outputs);
+int vbx_analyze_frames_tracked_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
+                                     const vbx_analysis_params *h_params, const vbx_pitch_track_params *h_track,
+                                     const int64_t *h_seg_start, size_t n_segments,
+                                     double *out_records, size_t record_ld, int32_t *status3,
+                                     const vbx_pitch_track_outputs *h_outputs);
+
 /* ------------------------------------------------------------------ multi-GPU: frame-range sharding */
 
 /* The reference has no distribution of any kind; frames are independent (the tracker per utterance), so a long
@@ -571,7 +616,9 @@ int vbx_shard_samples(size_t lo, size_t hi, size_t frame_len, size_t hop, size_t
  * shard's end); continues_prev: the utterance starts more than `warm` frames before lo (the state must come from rank - 1);
  * continues_next: the same for the next rank's first frame.
  * vbx_shard_local_segments: the utterance starts of frames [lo - warm, hi), re-based to the shard (first entry 0): the
- * h_seg_start of the rank's vbx_analyze_frames_f64 / vbx_find_formants_f64 call.  *n_out = entries needed (h_out may be NULL). */
+ * h_seg_start of the rank's vbx_analyze_frames_f64 / vbx_find_formants_f64 call.  *n_out = entries needed (h_out may be NULL).
+ * Only the formant track is carried across a cut.  The pitch path of vbx_analyze_frames_tracked_* is not: each rank's contour is the
+ * path of the frames it analysed (its warm-up frames included), not a piece of the whole recording's path. */
 #define VBX_SHARD_WARM_FRAMES 64
 typedef struct {
     size_t lo, hi, warm, stop;

@@ -1,5 +1,6 @@
 // k_front.hip -- the steps either side of the hot path:
 //   PCM ingestion   i16 -> f64 / 32767  (hound reader as used at tests/lib.rs:17-19)
+//   PCM frame peak  max |s| / 32767 per frame: the pitch path's local_peak on 16-bit PCM (vbx_analyze_frames_tracked_pcm16)
 //   RMS::rms        src/waves.rs:10-23
 //   Filter::preemphasis  src/waves.rs:82-96: backwards recurrence y[i] = x[i] + c*y[i+1], c = 2*pi*factor
 // All three are HBM-bound byte/stream work: coalesced loads, one pass.
@@ -22,6 +23,40 @@ __global__ void pcm16_kernel(const int16_t *__restrict__ pcm, size_t n, double d
         reinterpret_cast<double2 *>(out)[v] = make_double2(div_exact_small(lo, denom, r), div_exact_small(hi, denom, r));
     }
     for (size_t i = n2 * 2 + t0; i < n; i += step) out[i] = div_exact_small((double)pcm[i], denom, r);
+}
+
+// frame peak on 16-bit PCM: max |s| per frame as an integer (|s| in 32 bits: |-32768| does not fit 16), widened once.  x -> x / 32767
+// (correctly rounded) is odd and monotone, so this is frame_peak_kernel's result on the widened samples, bit for bit.  One wavefront
+// per frame; the row's 16-byte aligned middle by 16-byte loads (8 samples), its head and tail sample by sample.
+__global__ __launch_bounds__(256) void frame_peak_pcm16_kernel(const int16_t *__restrict__ pcm, long F, long n, long stride,
+                                                               double *__restrict__ out) {
+    const long f = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (f >= F) return;                                        // wavefront-uniform
+    const int16_t *row = pcm + f * stride;
+    long head = (long)(((16 - (reinterpret_cast<uintptr_t>(row) & 15)) & 15) / 2);
+    if (head > n) head = n;
+    const long nv = (n - head) / 8;
+    int m = 0;
+    if (lane < head) m = abs((int)row[lane]);                  // head < 8
+    const int4 *v = reinterpret_cast<const int4 *>(row + head);
+    for (long i = lane; i < nv; i += 64) {
+        const int4 w = v[i];
+        const int ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            m = max(m, abs((int)(short)(ws[k] & 0xffff)));
+            m = max(m, abs(ws[k] >> 16));
+        }
+    }
+    for (long i = head + nv * 8 + lane; i < n; i += 64) m = max(m, abs((int)row[i]));
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = max(m, __shfl_xor(m, d, 64));
+    if (lane == 0) out[f] = pcm16_value(m);
+}
+
+void launch_frame_peak_pcm16(hipStream_t s, const int16_t *pcm, long F, long n, long stride, double *out) {
+    hipLaunchKernelGGL(frame_peak_pcm16_kernel, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, s, pcm, F, n, stride, out);
 }
 
 // rms: one wavefront per frame

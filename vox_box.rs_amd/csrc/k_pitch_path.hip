@@ -332,9 +332,10 @@ __global__ __launch_bounds__(256) void pp_compose_kernel(const uint8_t *__restri
 }
 
 // the true state at every frame of chunk c, walked back from its last frame's, and the outputs
+// (out_path row t starts ld doubles after row t - 1: 2 for dense rows, record_ld for columns 0-1 of a frame record)
 template <int G>
 __global__ __launch_bounds__(64) void pp_write_kernel(const pp_par_t P, const uint8_t *__restrict__ map, pitch_t *__restrict__ out_path,
-                                                      int32_t *__restrict__ out_index) {
+                                                      long ld, int32_t *__restrict__ out_index) {
     __shared__ uint32_t tiles[64 * PP_TILE / 4];
     __shared__ uint8_t paths[64 / G][PP_TILE];
     const int s = threadIdx.x & (G - 1), gbase = threadIdx.x & ~(G - 1);
@@ -362,7 +363,7 @@ __global__ __launch_bounds__(64) void pp_write_kernel(const pp_par_t P, const ui
             bool voiced = false;
             if (st < m) { o = P.cand[t * (long)P.kmax + st]; voiced = o.frequency > 0.0; }
             if (!voiced) { o.frequency = 0.0; o.strength = pp_unvoiced(P, P.use_u ? P.lpk[t] : 0.0, k.seg); }
-            out_path[t] = o;
+            *reinterpret_cast<pitch_t *>(reinterpret_cast<double *>(out_path) + t * ld) = o;
             if (out_index != nullptr) out_index[t] = (st < m) ? st : -1;
         }
         __builtin_amdgcn_wave_barrier();
@@ -408,8 +409,8 @@ void launch_pitch_path_map(hipStream_t s, const pp_par_t &P, int G_, uint8_t *ma
 void launch_pitch_path_compose(hipStream_t s, long nch, int G_, const uint8_t *in, uint8_t *out, long d) {
     VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_compose_kernel<G>, dim3((unsigned)((nch * G + 255) / 256)), dim3(256), 0, s, in, out, nch, d));
 }
-void launch_pitch_path_write(hipStream_t s, const pp_par_t &P, int G_, const uint8_t *map, pitch_t *out_path, int32_t *out_index) {
-    VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_write_kernel<G>, pp_group_grid(P.nch, G), dim3(64), 0, s, P, map, out_path, out_index));
+void launch_pitch_path_write(hipStream_t s, const pp_par_t &P, int G_, const uint8_t *map, pitch_t *out_path, long ld, int32_t *out_index) {
+    VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_write_kernel<G>, pp_group_grid(P.nch, G), dim3(64), 0, s, P, map, out_path, ld, out_index));
 }
 #undef VBX_PP_DISPATCH
 

@@ -40,7 +40,7 @@ struct vbx_ctx {
     std::string arch;
     int cu_count = 0;
     // workspaces (grown on demand, never shrunk)
-    enum { WS_COEFFS, WS_RES, WS_COUNT, WS_STATUS, WS_MISC, WS_SEG, WS_EST, WS_UNSURE, WS_F32_IN, WS_F32_OUT, WS_TRK, WS_BURG_LIST, WS_ROOTS_LIST, WS_LONG, WS_LONG2, WS_CZT, WS_CURVE, WS_LPC_LIST, WS_PATH, WS_PATH_TAB, WS_N };
+    enum { WS_COEFFS, WS_RES, WS_COUNT, WS_STATUS, WS_MISC, WS_SEG, WS_EST, WS_UNSURE, WS_F32_IN, WS_F32_OUT, WS_TRK, WS_BURG_LIST, WS_ROOTS_LIST, WS_LONG, WS_LONG2, WS_CZT, WS_CURVE, WS_LPC_LIST, WS_PATH, WS_PATH_TAB, WS_TRACK, WS_N };
     void *ws[WS_N] = {nullptr};
     const int32_t *burg_list_count = nullptr;             // device counter of the last one-pass Burg call (tests)
     const int32_t *roots_list_count = nullptr;            // the same for the resonance kernel of find_formants
@@ -90,6 +90,7 @@ struct vbx_ctx {
     // second stream of vbx_analyze_frames_f64 (the formant chain runs beside the pitch kernel) + fork/join events
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_peak = nullptr;                         // vbx_analyze_frames_tracked_*: the side stream's frame peaks exist (the path waits for it)
     hipStream_t trk = nullptr;                            // the tracker's time slices (run_find_formants)
     hipEvent_t ev_slice[8] = {nullptr}, ev_trk = nullptr;
     // pinned staging of the small host arrays (segment starts, initial estimates): the caller's arrays may be
@@ -584,6 +585,7 @@ void vbx_ctx_destroy(vbx_ctx *ctx) {
     if (ctx->side) { hipStreamSynchronize(ctx->side); hipStreamDestroy(ctx->side); }
     if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
+    if (ctx->ev_peak) hipEventDestroy(ctx->ev_peak);
     for (auto &e : ctx->ev_slice) if (e) hipEventDestroy(e);
     if (ctx->ev_trk) hipEventDestroy(ctx->ev_trk);
     if (ctx->trk) { hipStreamSynchronize(ctx->trk); hipStreamDestroy(ctx->trk); }
@@ -909,21 +911,29 @@ static int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, c
     return check_launch(ctx, "launch_spectral");
 }
 
+// What run_pitch rejects about (frame_len, kmax), as a message, or nullptr: also asked by the tracked frame loop before its first
+// launch.  (kmax <= 63 there, below every cap of this function: only the frame_len rules can bind.)
+static const char *pitch_shape_error(size_t frame_len, size_t kmax) {
+    const size_t kcap = frame_len > VBX_MAX_FRAME_LEN ? VBX_PITCH_MAX_CANDIDATES(frame_len) : (size_t)VBX_MAX_PITCH_CANDIDATES;
+    if (!(kmax >= 1 && kmax <= kcap)) return "kmax must be in [1, VBX_MAX_PITCH_CANDIDATES] (long frames: [1, frame_len / 4 + 2])";
+    if (frame_len < 4) return "frame_len must be >= 4";
+    if (frame_len > VBX_MAX_FRAME_LEN) return frame_len <= 0x3fffffff ? nullptr : "frame_len too large for the lag curve's 32-bit indices";
+    if (pitch_lds_bytes((int)frame_len) + pitch_full_list_bytes((int)frame_len, (int)kmax) + 16 > 160 * 1024) return "frame does not fit the LDS";
+    return nullptr;
+}
+
 static int run_pitch(vbx_ctx *ctx, hipStream_t st, const double *x, size_t n_frames, size_t frame_len, size_t stride,
                      const double *window, double sample_rate, double threshold, double fmin, double fmax,
                      size_t kmax, vbx_pitch *out_cand, size_t cand_ld, int32_t *out_count, int32_t *status) {
     VBX_REQUIRE(ctx, out_cand != nullptr, "null output");
-    const size_t kcap = frame_len > VBX_MAX_FRAME_LEN ? VBX_PITCH_MAX_CANDIDATES(frame_len) : (size_t)VBX_MAX_PITCH_CANDIDATES;
-    VBX_REQUIRE(ctx, kmax >= 1 && kmax <= kcap, "kmax must be in [1, VBX_MAX_PITCH_CANDIDATES] (long frames: [1, frame_len / 4 + 2])");
+    if (const char *e = pitch_shape_error(frame_len, kmax)) return fail(ctx, VBX_E_INVALID, std::string(__func__) + ": " + e);
     VBX_REQUIRE(ctx, cand_ld >= 2 * kmax && cand_ld % 2 == 0, "candidate rows must hold kmax entries and their leading dimension must be even");
-    VBX_REQUIRE(ctx, frame_len >= 4, "frame_len must be >= 4");
     const double *lagw = nullptr;
     int rc = get_window_dev(ctx, VBX_WINDOW_HANNING_LAG, frame_len, &lagw);
     if (rc != VBX_SUCCESS) return rc;
     if (frame_len > VBX_MAX_FRAME_LEN) {
         // a frame whose lag curve no LDS holds (k_long.hip): every lag by the chunked matrix-core tiles, the curve as an array in
         // HBM, peak scan -> improve_extremum per candidate -> rank sort; batches of frames so that the scratch stays <= 2 GiB
-        VBX_REQUIRE(ctx, frame_len <= 0x3fffffff, "frame_len too large for the lag curve's 32-bit indices");
         size_t per = (size_t(1) << 31) / pitch_long_scratch_bytes(1, (long)frame_len);
         if (per < 1) per = 1;
         if (per > n_frames) per = n_frames;
@@ -944,8 +954,6 @@ static int run_pitch(vbx_ctx *ctx, hipStream_t st, const double *x, size_t n_fra
         }
         return check_launch(ctx, "vbx_pitch_f64");
     }
-    VBX_REQUIRE(ctx, pitch_lds_bytes((int)frame_len) + pitch_full_list_bytes((int)frame_len, (int)kmax) + 16 <= 160 * 1024,
-                "frame does not fit the LDS");
     if (ctx->prof && !ctx->pitch_work) {
         const size_t wb = PITCH_WORK_WORDS * sizeof(unsigned long long);
         VBX_HIP(ctx, hipMalloc((void **)&ctx->pitch_work, wb));
@@ -1012,11 +1020,15 @@ int vbx_lpc_f64(vbx_ctx *ctx, const double *r, size_t n_frames, size_t r_stride,
     return vbx_lpc_mut_f64(ctx, r, n_frames, r_stride, n_coeffs, out, nullptr);
 }
 
+static bool lpc_order_ok(size_t frame_len, size_t n_coeffs) {      // run_autocorr_lpc's rule (and the tracked frame loop's pre-check)
+    return n_coeffs >= 1 && n_coeffs <= VBX_MAX_LPC_ORDER && n_coeffs + 1 <= frame_len;
+}
+
 static int run_autocorr_lpc(vbx_ctx *ctx, hipStream_t st, const double *x, size_t n_frames, size_t frame_len,
                             size_t stride, const double *window, size_t n_coeffs, int normalize,
                             double *out_r, double *out_lpc, size_t lpc_ld) {
     VBX_REQUIRE(ctx, out_r || out_lpc, "both outputs null");
-    VBX_REQUIRE(ctx, n_coeffs >= 1 && n_coeffs <= VBX_MAX_LPC_ORDER && n_coeffs + 1 <= frame_len, "bad order");
+    VBX_REQUIRE(ctx, lpc_order_ok(frame_len, n_coeffs), "bad order");
     VBX_REQUIRE(ctx, lpc_ld >= n_coeffs + 1, "LPC rows must hold n_coeffs + 1 entries");
     const int n_lags = (int)n_coeffs + 1;
     int rc;
@@ -1764,22 +1776,43 @@ static int ensure_side_stream(vbx_ctx *ctx) {
     VBX_HIP(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
     VBX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
     VBX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+    VBX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_peak, hipEventDisableTiming));
     return VBX_SUCCESS;
 }
+
+// the pitch path (defined with vbx_pitch_path_f64, further down): the argument checks and the launches that entry point shares
+// with the tracked frame loop
+static int check_pitch_path(vbx_ctx *ctx, const char *fn, const vbx_pitch_path_params &pr, size_t n_frames, size_t kmax, bool have_peak,
+                            const int64_t *h_seg_start, size_t n_segments);
+static int run_pitch_path(vbx_ctx *ctx, hipStream_t st, const vbx_pitch *cand, const int32_t *count, const int32_t *status,
+                          size_t n_frames, size_t kmax, const double *local_peak, const int64_t *h_seg_start, size_t n_segments,
+                          const vbx_pitch_path_params &pr, vbx_pitch *out_path, size_t path_ld, int32_t *out_index, const char *fn);
+
+// vbx_analyze_frames_tracked_*: columns 0-1 of the records are the pitch path over the call's own kmax-entry lists
+struct track_req_t { size_t kmax; vbx_pitch_path_params path; vbx_pitch_track_outputs out; };
 
 // x: the frames as f64 samples, or -- pcm16 non-null -- as 16-bit PCM (the kernels that have a PCM form read it directly:
 // 1200-sample frames through the fused spectral kernel, Burg at every length; every other shape is widened into a
 // context-owned f64 copy of the view first and takes the f64 path)
 static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, const int16_t *pcm16, size_t n_frames, size_t frame_len,
                                size_t stride, const vbx_analysis_params *h_p, const int64_t *h_seg_start, size_t n_segments,
-                               double *out_records, size_t record_ld, int32_t *status3) {
+                               double *out_records, size_t record_ld, int32_t *status3, const track_req_t *tk = nullptr) {
     int rc = check_frames(ctx, fn, pcm16 ? (const void *)pcm16 : (const void *)x, n_frames, frame_len, stride, VBX_MAX_LONG_FRAME_LEN);
+    if (rc == 1 && tk) { ctx->path_redone = nullptr; ctx->path_last = true; }      // an empty batch: an empty path
     if (rc != VBX_SUCCESS) return rc < 0 ? rc : VBX_SUCCESS;
     VBX_REQUIRE(ctx, h_p && out_records, "null argument");
     const size_t rec = vbx_record_doubles(h_p);
     VBX_REQUIRE(ctx, record_ld >= rec && record_ld % 2 == 0, "record_ld must be even and >= vbx_record_doubles(params)");
     VBX_REQUIRE(ctx, ((uintptr_t)out_records & 15) == 0, "records must be 16-byte aligned");
     VBX_REQUIRE(ctx, !h_p->formant_order || (h_p->n_est >= 1 && h_p->n_est <= VBX_FORMANT_SLOTS), "n_est must be in [1, 6]");
+    if (tk) {
+        // The tracked form writes its peaks before the parts below look at their own arguments: what they would reject is asked first,
+        // through the predicates those parts use themselves.  (The unfused MFCC kernels choose their form from the geometry: the tracked
+        // form queues them FIRST on the side stream, below, so that their rejection also precedes every write.)
+        if (const char *e = pitch_shape_error(frame_len, tk->kmax)) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": " + e);
+        VBX_REQUIRE(ctx, !h_p->formant_order || burg_order_ok(frame_len, h_p->formant_order), "frame_len must be >= 2, order in [1, 62]");
+        VBX_REQUIRE(ctx, !h_p->lpc_order || lpc_order_ok(frame_len, h_p->lpc_order), "bad order");
+    }
     VBX_HIP(ctx, hipSetDevice(ctx->device));
     rc = ensure_side_stream(ctx);
     if (rc != VBX_SUCCESS) return rc;
@@ -1817,6 +1850,7 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
     }
     // 16-bit PCM frames: the fused kernel of full 1200-sample frames, the pitch fallback and Burg read them directly;
     // anything that would send another kernel over the samples takes one widening pass into a context-owned f64 copy
+    const int16_t *const pcm_in = pcm16;                                   // (the peak kernel reads the caller's PCM whichever form the rest takes)
     const bool pcm_native = pcm16 != nullptr && fused && frame_len == (size_t)SPECTRAL_N &&
                             (!h_p->lpc_order || fused_lpc) && (!h_p->mfcc_coeffs || fused_mfcc);
     if (pcm16 != nullptr && !pcm_native) {
@@ -1836,12 +1870,43 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
                  c_lpc = c_mfcc + h_p->mfcc_coeffs;
     int32_t *st_pitch = nullptr, *st_form = nullptr, *st_mfcc = nullptr;
     if (status3) { st_pitch = status3; st_form = status3 + n_frames; st_mfcc = status3 + 2 * n_frames; }
+    // the tracked form: the lists, counts and peaks the path reads -- the caller's arrays, or context-owned ones
+    vbx_pitch *tk_cand = nullptr; int32_t *tk_count = nullptr; double *tk_peak = nullptr;
+    if (tk) {
+        tk_cand = tk->out.cand; tk_count = tk->out.count;
+        const bool need_peak = tk->path.silence_threshold != 0.0 || tk->out.peak != nullptr;
+        tk_peak = need_peak ? tk->out.peak : nullptr;
+        const size_t b_cand = tk_cand ? 0 : n_frames * tk->kmax * sizeof(vbx_pitch), b_peak = (need_peak && !tk_peak) ? n_frames * sizeof(double) : 0,
+                     b_count = tk_count ? 0 : n_frames * sizeof(int32_t), b_st = st_pitch ? 0 : n_frames * sizeof(int32_t);
+        if (b_cand + b_peak + b_count + b_st) {
+            void *w = nullptr;
+            rc = ws_get(ctx, vbx_ctx::WS_TRACK, b_cand + b_peak + b_count + b_st, &w);
+            if (rc != VBX_SUCCESS) return rc;
+            char *q = static_cast<char *>(w);
+            if (b_cand) { tk_cand = reinterpret_cast<vbx_pitch *>(q); q += b_cand; }
+            if (b_peak) { tk_peak = reinterpret_cast<double *>(q); q += b_peak; }
+            if (b_count) { tk_count = reinterpret_cast<int32_t *>(q); q += b_count; }
+            if (b_st) st_pitch = reinterpret_cast<int32_t *>(q);              // (the path must see the frames the pitch kernel gave up on)
+        }
+    }
     // fork: the formant chain (Burg -> roots -> the latency-bound tracker scan) and the MFCC run on the side stream,
     // beside the FP64-bound pitch kernel
     VBX_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
     // (frames longer than VBX_MAX_FRAME_LEN: everything in order on the context's stream -- the long-frame kernels share one scratch)
     hipStream_t side = frame_len > VBX_MAX_FRAME_LEN ? ctx->stream : ctx->side;
     VBX_HIP(ctx, hipStreamWaitEvent(side, ctx->ev_fork, 0));
+    const bool mfcc_beside = h_p->mfcc_coeffs && !fused_mfcc;              // MFCC from its own kernel on the side stream
+    if (tk && mfcc_beside) {                                               // (tracked: first, see above; its columns are nobody else's)
+        rc = run_mfcc(ctx, side, x, n_frames, frame_len, stride, hann, h_p->mfcc_coeffs, h_p->mfcc_lo_hz, h_p->mfcc_hi_hz,
+                      h_p->sample_rate, out_records + c_mfcc, record_ld, st_mfcc);
+        if (rc != VBX_SUCCESS) return rc;
+    }
+    if (tk_peak) {
+        // max |x| per frame, first on the side stream: HBM-bound, beside the FP64-bound kernel; the path waits for ev_peak
+        if (pcm_in) { Prof p(ctx, "frame_peak_pcm16", side); launch_frame_peak_pcm16(side, pcm_in, (long)n_frames, (long)frame_len, (long)stride, tk_peak); }
+        else { Prof p(ctx, "frame_peak", side); launch_frame_peak(side, x, (long)n_frames, (long)frame_len, (long)stride, tk_peak); }
+        VBX_HIP(ctx, hipEventRecord(ctx->ev_peak, side));
+    }
     if (h_p->formant_order) {
         vbx_resonance est[VBX_FORMANT_SLOTS];
         for (size_t e = 0; e < h_p->n_est; e++) est[e] = h_p->est_init[e];
@@ -1859,7 +1924,7 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
                               out_records + c_lpc, record_ld);
         if (rc != VBX_SUCCESS) return rc;
     }
-    if (fused && h_p->mfcc_coeffs && !fused_mfcc) {
+    if (fused && mfcc_beside && !tk) {
         rc = run_mfcc(ctx, side, x, n_frames, frame_len, stride, hann, h_p->mfcc_coeffs, h_p->mfcc_lo_hz, h_p->mfcc_hi_hz,
                       h_p->sample_rate, out_records + c_mfcc, record_ld, st_mfcc);
         if (rc != VBX_SUCCESS) return rc;
@@ -1870,7 +1935,7 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
                                   out_records + c_lpc, record_ld);
             if (rc != VBX_SUCCESS) return rc;
         }
-        if (h_p->mfcc_coeffs) {
+        if (mfcc_beside && !tk) {
             rc = run_mfcc(ctx, side, x, n_frames, frame_len, stride, hann, h_p->mfcc_coeffs, h_p->mfcc_lo_hz, h_p->mfcc_hi_hz,
                           h_p->sample_rate, out_records + c_mfcc, record_ld, st_mfcc);
             if (rc != VBX_SUCCESS) return rc;
@@ -1901,6 +1966,7 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
         L.pcm = pcm_native;
         L.whole_curve = ctx->pitch_whole_curve;
         L.out_cand = (pitch_t *)out_records; L.cand_ld = (long)record_ld; L.out_count = nullptr; L.pitch_status = st_pitch;
+        if (tk) { L.kmax = (int)tk->kmax; L.out_cand = (pitch_t *)tk_cand; L.cand_ld = 2 * (long)tk->kmax; L.out_count = tk_count; }
         L.work = ctx->prof ? ctx->pitch_work : nullptr;
         if (fused_lpc) { L.out_lpc = out_records + c_lpc; L.lpc_ld = (long)record_ld; }
         if (fused_mfcc) {
@@ -1909,11 +1975,21 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
             L.interp = interp_mfcc; L.ip = ip;
         }
         rc = launch_spectral(ctx, ctx->stream, L, "analyze");
+    } else if (tk) {
+        rc = run_pitch(ctx, ctx->stream, x, n_frames, frame_len, stride, hann, h_p->sample_rate, h_p->pitch_threshold,
+                       h_p->pitch_fmin, h_p->pitch_fmax, tk->kmax, tk_cand, 2 * tk->kmax, tk_count, st_pitch);
     } else {
         rc = run_pitch(ctx, ctx->stream, x, n_frames, frame_len, stride, hann, h_p->sample_rate, h_p->pitch_threshold,
                        h_p->pitch_fmin, h_p->pitch_fmax, 1, (vbx_pitch *)out_records, record_ld, nullptr, st_pitch);
     }
     if (rc != VBX_SUCCESS) return rc;
+    if (tk) {
+        // the path over those lists, on the context's stream behind the kernel that wrote them: its rows are columns 0-1 of the records
+        if (tk_peak) VBX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_peak, 0));
+        rc = run_pitch_path(ctx, ctx->stream, tk_cand, tk_count, st_pitch, n_frames, tk->kmax, tk_peak, h_seg_start, n_segments, tk->path,
+                            (vbx_pitch *)out_records, record_ld, tk->out.index, fn);
+        if (rc != VBX_SUCCESS) return rc;
+    }
     VBX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));       // join: the records are complete on ctx's stream
     return VBX_SUCCESS;
 }
@@ -1931,6 +2007,40 @@ int vbx_analyze_frames_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_frames, 
     if (n_frames != 0 && ctx && !pcm) return fail(ctx, VBX_E_INVALID, "vbx_analyze_frames_pcm16: null frame pointer");
     return analyze_frames_impl(ctx, __func__, nullptr, pcm, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records,
                                record_ld, status3);
+}
+
+// The frame loop with the TRACKED contour in columns 0-1: the fused kernel at the caller's kmax into list buffers, the frame peaks
+// beside it, the pitch path behind it.  Everything is checked before anything is launched.
+static int analyze_tracked(vbx_ctx *ctx, const char *fn, const double *x, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
+                           const vbx_analysis_params *h_p, const vbx_pitch_track_params *h_track, const int64_t *h_seg_start,
+                           size_t n_segments, double *out_records, size_t record_ld, int32_t *status3, const vbx_pitch_track_outputs *h_out) {
+    if (!ctx) return fail(nullptr, VBX_E_INVALID, std::string(fn) + ": null context");
+    if (!h_track) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": null track parameters");
+    if (!h_p) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": null argument");
+    track_req_t tk{};
+    tk.kmax = h_track->kmax; tk.path = h_track->path;
+    if (h_out) tk.out = *h_out;
+    if (tk.path.time_step == 0.0) tk.path.time_step = (double)stride / h_p->sample_rate;      // the batch's own hop
+    int rc = check_pitch_path(ctx, fn, tk.path, n_frames, tk.kmax, true, h_seg_start, n_segments);
+    if (rc != VBX_SUCCESS) return rc;
+    return analyze_frames_impl(ctx, fn, x, pcm, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records, record_ld, status3, &tk);
+}
+
+int vbx_analyze_frames_tracked_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
+                                   const vbx_analysis_params *h_p, const vbx_pitch_track_params *h_track,
+                                   const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld,
+                                   int32_t *status3, const vbx_pitch_track_outputs *h_outputs) {
+    return analyze_tracked(ctx, __func__, x, nullptr, n_frames, frame_len, stride, h_p, h_track, h_seg_start, n_segments, out_records,
+                           record_ld, status3, h_outputs);
+}
+
+int vbx_analyze_frames_tracked_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
+                                     const vbx_analysis_params *h_p, const vbx_pitch_track_params *h_track,
+                                     const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld,
+                                     int32_t *status3, const vbx_pitch_track_outputs *h_outputs) {
+    if (n_frames != 0 && ctx && !pcm) return fail(ctx, VBX_E_INVALID, "vbx_analyze_frames_tracked_pcm16: null frame pointer");
+    return analyze_tracked(ctx, __func__, nullptr, pcm, n_frames, frame_len, stride, h_p, h_track, h_seg_start, n_segments, out_records,
+                           record_ld, status3, h_outputs);
 }
 
 // ---- Sample = f32, the WIDE forms --------------------------------------------
@@ -2211,6 +2321,27 @@ int vbx_frame_peak_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t fr
 #define VBX_PP_ROUNDS_LONG 8
 #endif
 
+#define VBX_PP_REQUIRE(cond, msg) \
+    do { if (!(cond)) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": " + (msg)); } while (0)
+
+static int check_pitch_path(vbx_ctx *ctx, const char *fn, const vbx_pitch_path_params &pr, size_t n_frames, size_t kmax, bool have_peak,
+                            const int64_t *h_seg_start, size_t n_segments) {
+    VBX_PP_REQUIRE(kmax >= 1 && kmax <= 63, "kmax must be in [1, 63] (at most 64 states per frame)");
+    for (double v : {pr.voicing_threshold, pr.silence_threshold, pr.octave_cost, pr.octave_jump_cost, pr.voiced_unvoiced_cost,
+                     pr.ceiling_hz, pr.time_step})
+        VBX_PP_REQUIRE(std::isfinite(v) && v >= 0.0, "every parameter must be finite and >= 0");
+    VBX_PP_REQUIRE(pr.time_step > 0.0 && pr.ceiling_hz > 0.0, "time_step and ceiling_hz must be > 0");
+    VBX_PP_REQUIRE(!(pr.silence_threshold > 0.0 && !have_peak), "silence_threshold > 0 needs local_peak");
+    VBX_PP_REQUIRE(n_frames <= 0x7fffffffull, "too many frames for one launch");
+    if (h_seg_start != nullptr && n_segments > 0) {            // the rules of vbx_analyze_frames_f64
+        VBX_PP_REQUIRE(h_seg_start[0] == 0, "seg_start[0] must be 0");
+        for (size_t i = 1; i < n_segments; i++)
+            VBX_PP_REQUIRE(h_seg_start[i] >= h_seg_start[i - 1] && (size_t)h_seg_start[i] <= n_frames, "seg_start must ascend within [0, n_frames]");
+    }
+    return VBX_SUCCESS;
+}
+#undef VBX_PP_REQUIRE
+
 int vbx_pitch_path_f64(vbx_ctx *ctx, const vbx_pitch *cand, const int32_t *count, const int32_t *status,
                        size_t n_frames, size_t kmax, const double *local_peak,
                        const int64_t *h_seg_start, size_t n_segments, const vbx_pitch_path_params *h_params,
@@ -2219,23 +2350,21 @@ int vbx_pitch_path_f64(vbx_ctx *ctx, const vbx_pitch *cand, const int32_t *count
     ctx->path_last = false;
     ctx->lpc_list_armed = false;
     VBX_REQUIRE(ctx, h_params != nullptr, "null params");
-    const vbx_pitch_path_params pr = *h_params;
-    VBX_REQUIRE(ctx, kmax >= 1 && kmax <= 63, "kmax must be in [1, 63] (at most 64 states per frame)");
-    for (double v : {pr.voicing_threshold, pr.silence_threshold, pr.octave_cost, pr.octave_jump_cost, pr.voiced_unvoiced_cost,
-                     pr.ceiling_hz, pr.time_step})
-        VBX_REQUIRE(ctx, std::isfinite(v) && v >= 0.0, "every parameter must be finite and >= 0");
-    VBX_REQUIRE(ctx, pr.time_step > 0.0 && pr.ceiling_hz > 0.0, "time_step and ceiling_hz must be > 0");
-    VBX_REQUIRE(ctx, !(pr.silence_threshold > 0.0 && local_peak == nullptr), "silence_threshold > 0 needs local_peak");
-    VBX_REQUIRE(ctx, n_frames <= 0x7fffffffull, "too many frames for one launch");
-    const bool segmented = h_seg_start != nullptr && n_segments > 0;
-    if (segmented) {                                           // the rules of vbx_analyze_frames_f64
-        VBX_REQUIRE(ctx, h_seg_start[0] == 0, "seg_start[0] must be 0");
-        for (size_t i = 1; i < n_segments; i++)
-            VBX_REQUIRE(ctx, h_seg_start[i] >= h_seg_start[i - 1] && (size_t)h_seg_start[i] <= n_frames, "seg_start must ascend within [0, n_frames]");
-    }
+    int rc = check_pitch_path(ctx, __func__, *h_params, n_frames, kmax, local_peak != nullptr, h_seg_start, n_segments);
+    if (rc != VBX_SUCCESS) return rc;
     if (n_frames == 0) { ctx->path_redone = nullptr; ctx->path_last = true; return VBX_SUCCESS; }
     VBX_REQUIRE(ctx, cand != nullptr && count != nullptr && out_path != nullptr, "null argument");
     VBX_HIP(ctx, hipSetDevice(ctx->device));
+    return run_pitch_path(ctx, ctx->stream, cand, count, status, n_frames, kmax, local_peak, h_seg_start, n_segments, *h_params,
+                          out_path, 2, out_index, __func__);
+}
+
+// the launches (arguments checked by the caller).  out_path rows lie path_ld doubles apart: 2 for the dense rows of vbx_pitch_path_f64,
+// record_ld for columns 0-1 of the frame records.  Leaves ctx->lpc_list_armed alone: the tracked frame loop reports its LPC probe.
+static int run_pitch_path(vbx_ctx *ctx, hipStream_t st, const vbx_pitch *cand, const int32_t *count, const int32_t *status,
+                          size_t n_frames, size_t kmax, const double *local_peak, const int64_t *h_seg_start, size_t n_segments,
+                          const vbx_pitch_path_params &pr, vbx_pitch *out_path, size_t path_ld, int32_t *out_index, const char *fn) {
+    const bool segmented = h_seg_start != nullptr && n_segments > 0;
     const long F = (long)n_frames, W = VBX_PP_WARM;
     const size_t nseg = segmented ? n_segments : 1;
     int G = 4;
@@ -2262,7 +2391,7 @@ int vbx_pitch_path_f64(vbx_ctx *ctx, const vbx_pitch *cand, const int32_t *count
     std::memcpy(tab.data(), chunks.data(), (size_t)nch * sizeof(pp_chunk_t));
     std::memcpy(tab.data() + (size_t)nch * sizeof(pp_chunk_t), seg_chunk0.data(), (nseg + 1) * sizeof(int64_t));
     void *dtab = nullptr;
-    int rc = stage_upload(ctx, 2, vbx_ctx::WS_PATH_TAB, tab.data(), tab.size(), ctx->stream, &dtab);
+    int rc = stage_upload(ctx, 2, vbx_ctx::WS_PATH_TAB, tab.data(), tab.size(), st, &dtab);
     if (rc != VBX_SUCCESS) return rc;
     const int64_t *d_seg_chunk0 = reinterpret_cast<const int64_t *>(static_cast<char *>(dtab) + (size_t)nch * sizeof(pp_chunk_t));
     // workspace: psi [F][G] uint8, per chunk entry / exit / wanted D, flags, maps; per segment leader and peak
@@ -2295,28 +2424,27 @@ int vbx_pitch_path_f64(vbx_ctx *ctx, const vbx_pitch *cand, const int32_t *count
     P.cvu = pr.voiced_unvoiced_cost * corr; P.cj = pr.octave_jump_cost * corr;
     P.Lc = std::log2(pr.ceiling_hz); P.q = pr.silence_threshold / (1.0 + pr.voicing_threshold);
     P.ch = reinterpret_cast<const pp_chunk_t *>(dtab); P.nch = nch;
-    hipStream_t st = ctx->stream;
     VBX_HIP(ctx, hipMemsetAsync(P.redone, 0, sizeof(unsigned long long), st));
-    if (P.use_u) { Prof pf(ctx, "pitch_path_peak"); launch_pitch_path_peak(st, P, d_seg_chunk0, (long)nseg, cpk); }
-    { Prof pf(ctx, "pitch_path_spec"); launch_pitch_path_spec(st, P, G, W); }
+    if (P.use_u) { Prof pf(ctx, "pitch_path_peak", st); launch_pitch_path_peak(st, P, d_seg_chunk0, (long)nseg, cpk); }
+    { Prof pf(ctx, "pitch_path_spec", st); launch_pitch_path_spec(st, P, G, W); }
     if (n_guessed > 0) {
         const int rounds = (F / (long)nseg > 8192) ? VBX_PP_ROUNDS_LONG : VBX_PP_ROUNDS;
         for (int r = 0; r < rounds; r++) {
-            { Prof pf(ctx, "pitch_path_check"); launch_pitch_path_check(st, P, G); }
-            { Prof pf(ctx, "pitch_path_repair"); launch_pitch_path_repair(st, P, G); }
+            { Prof pf(ctx, "pitch_path_check", st); launch_pitch_path_check(st, P, G); }
+            { Prof pf(ctx, "pitch_path_repair", st); launch_pitch_path_repair(st, P, G); }
         }
-        { Prof pf(ctx, "pitch_path_check"); launch_pitch_path_check(st, P, G); launch_pitch_path_mask(st, P); }
-        { Prof pf(ctx, "pitch_path_sweep"); launch_pitch_path_sweep(st, P, G, d_seg_chunk0, (long)nseg); }
+        { Prof pf(ctx, "pitch_path_check", st); launch_pitch_path_check(st, P, G); launch_pitch_path_mask(st, P); }
+        { Prof pf(ctx, "pitch_path_sweep", st); launch_pitch_path_sweep(st, P, G, d_seg_chunk0, (long)nseg); }
     }
-    { Prof pf(ctx, "pitch_path_backtrack"); launch_pitch_path_map(st, P, G, map_a); }
+    { Prof pf(ctx, "pitch_path_backtrack", st); launch_pitch_path_map(st, P, G, map_a); }
     for (long d = 1; d < max_per_seg; d <<= 1) {
-        { Prof pf(ctx, "pitch_path_compose"); launch_pitch_path_compose(st, nch, G, map_a, map_b, d); }
+        { Prof pf(ctx, "pitch_path_compose", st); launch_pitch_path_compose(st, nch, G, map_a, map_b, d); }
         std::swap(map_a, map_b);
     }
-    { Prof pf(ctx, "pitch_path_write"); launch_pitch_path_write(st, P, G, map_a, reinterpret_cast<pitch_t *>(out_path), out_index); }
+    { Prof pf(ctx, "pitch_path_write", st); launch_pitch_path_write(st, P, G, map_a, reinterpret_cast<pitch_t *>(out_path), (long)path_ld, out_index); }
     ctx->path_redone = P.redone;
     ctx->path_last = true;
-    return check_launch(ctx, __func__);
+    return check_launch(ctx, fn);
 }
 
 int vbx_internal_last_path_chunks_redone(vbx_ctx *ctx, int64_t *h_out) {

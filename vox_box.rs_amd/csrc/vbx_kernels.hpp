@@ -305,6 +305,8 @@ void launch_resample(hipStream_t s, const double *x, long F, int n, long stride,
                      const double *tab_frac, int m, double *out);
 void launch_ring_frames(hipStream_t s, const double *ring, long capacity, long head, long F, int n, long stride, double *out);
 void launch_pcm16(hipStream_t s, const int16_t *pcm, size_t n, double denom, double *out);
+// max |s| / 32767 per frame of 16-bit PCM: launch_frame_peak (k_pitch_path.hip) on the widened samples, bit for bit
+void launch_frame_peak_pcm16(hipStream_t s, const int16_t *pcm, long F, long n, long stride, double *out);
 void launch_rms(hipStream_t s, const double *x, long F, int n, long stride, const double *window, double *out);
 void launch_preemphasis(hipStream_t s, const double *x, long F, int n, long stride, double c, double *out);
 
@@ -355,6 +357,7 @@ void launch_pitch_path_mask(hipStream_t s, const pp_par_t &P);
 void launch_pitch_path_sweep(hipStream_t s, const pp_par_t &P, int G, const int64_t *seg_chunk0, long nseg);
 void launch_pitch_path_map(hipStream_t s, const pp_par_t &P, int G, uint8_t *map);
 void launch_pitch_path_compose(hipStream_t s, long nch, int G, const uint8_t *in, uint8_t *out, long d);
-void launch_pitch_path_write(hipStream_t s, const pp_par_t &P, int G, const uint8_t *map, pitch_t *out_path, int32_t *out_index);
+void launch_pitch_path_write(hipStream_t s, const pp_par_t &P, int G, const uint8_t *map, pitch_t *out_path,
+                             long ld /* doubles from one out_path row to the next: 2 = dense */, int32_t *out_index);
 
 }  // namespace vbx

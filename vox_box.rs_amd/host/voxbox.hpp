@@ -336,6 +336,29 @@ inline void analyze_frames_pcm16(Context &c, const int16_t *pcm, size_t n_frames
                                  Segments seg, double *records, size_t record_ld, int32_t *status3 = nullptr) {
     c.check(vbx_analyze_frames_pcm16(c.get(), pcm, n_frames, frame_len, stride, &p, seg.h_seg_start, seg.n, records, record_ld, status3));
 }
+// The frame loop with PitchExtractor's third pass run: columns 0-1 of the records hold the pitch path over the call's own kmax-entry
+// lists instead of candidates[0].  path.time_step == 0 (the helper's default) means stride / sample_rate.  outputs (optional device
+// arrays, any member null): the lists, counts, peaks and path indices, for another Pitched::pitch_path with other costs.
+using PitchTrackParams = vbx_pitch_track_params;
+using PitchTrackOutputs = vbx_pitch_track_outputs;
+inline PitchTrackParams pitch_track_params(size_t kmax = 15, const PitchPathParams &path = pitch_path_params(0.0)) {
+    PitchTrackParams t{};
+    t.kmax = kmax; t.path = path;
+    return t;
+}
+inline void analyze_frames_tracked(Context &c, const Frames &f, const AnalysisParams &p, const PitchTrackParams &track, Segments seg,
+                                   double *records, size_t record_ld, int32_t *status3 = nullptr,
+                                   const PitchTrackOutputs *outputs = nullptr) {
+    if (f.window != nullptr) throw Error(VBX_E_INVALID, "analyze_frames_tracked applies the windows itself: pass rectangular frames");
+    c.check(vbx_analyze_frames_tracked_f64(c.get(), f.x, f.n_frames, f.frame_len, f.stride, &p, &track, seg.h_seg_start, seg.n, records,
+                                           record_ld, status3, outputs));
+}
+inline void analyze_frames_tracked_pcm16(Context &c, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
+                                         const AnalysisParams &p, const PitchTrackParams &track, Segments seg, double *records,
+                                         size_t record_ld, int32_t *status3 = nullptr, const PitchTrackOutputs *outputs = nullptr) {
+    c.check(vbx_analyze_frames_tracked_pcm16(c.get(), pcm, n_frames, frame_len, stride, &p, &track, seg.h_seg_start, seg.n, records,
+                                             record_ld, status3, outputs));
+}
 
 // Frame-range sharding of one recording over the GPUs of a node (no counterpart in the reference) and the gather of the
 // per-frame records to one rank: grouped ncclSend / ncclRecv inside the library, one communicator per process.

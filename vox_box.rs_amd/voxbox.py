@@ -110,6 +110,22 @@ class PitchPathParams(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "chunk_frames"}
 
 
+class PitchTrackParams(C.Structure):
+    """vbx_pitch_track_params: the list length and path cost of vbx_analyze_frames_tracked_*.  path.time_step == 0 (make()'s
+    default here) means stride / sample_rate."""
+    _fields_ = [("kmax", C.c_size_t), ("path", PitchPathParams)]
+
+    @classmethod
+    def make(cls, kmax=15, path=None, **path_kw):
+        path_kw.setdefault("time_step", 0.0)
+        return cls(kmax, path if path is not None else PitchPathParams.make(**path_kw))
+
+
+class PitchTrackOutputs(C.Structure):
+    """vbx_pitch_track_outputs: optional device arrays of vbx_analyze_frames_tracked_* (any member may be NULL)."""
+    _fields_ = [("cand", C.c_void_p), ("count", C.c_void_p), ("peak", C.c_void_p), ("index", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -219,6 +235,10 @@ def load_library():
         "vbx_record_doubles": (sz, [C.POINTER(AnalysisParams)]),
         "vbx_analyze_frames_f64": (C.c_int, [vp, vp, sz, sz, sz, C.POINTER(AnalysisParams), vp, sz, vp, sz, vp]),
         "vbx_analyze_frames_pcm16": (C.c_int, [vp, vp, sz, sz, sz, C.POINTER(AnalysisParams), vp, sz, vp, sz, vp]),
+        "vbx_analyze_frames_tracked_f64": (C.c_int, [vp, vp, sz, sz, sz, C.POINTER(AnalysisParams), C.POINTER(PitchTrackParams),
+                                                     vp, sz, vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
+        "vbx_analyze_frames_tracked_pcm16": (C.c_int, [vp, vp, sz, sz, sz, C.POINTER(AnalysisParams), C.POINTER(PitchTrackParams),
+                                                       vp, sz, vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
         "vbx_shard_range": (C.c_int, [sz, i32, i32, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
         "vbx_shard_samples": (C.c_int, [sz, sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
         "vbx_shard_plan": (C.c_int, [sz, i32, i32, vp, sz, C.POINTER(ShardPlan)]),
@@ -1049,6 +1069,64 @@ class VoxBox:
             if d is not None:
                 d.free()
         return res
+
+    def _analyze_tracked(self, fn, ptr, F, N, S, params, track, seg_start, out, record_ld, status, lists, outputs, tmp):
+        rec = int(self.L.vbx_record_doubles(C.byref(params)))
+        ld = record_ld if record_ld is not None else rec + (rec & 1)
+        seg = None if seg_start is None else np.ascontiguousarray(seg_start, dtype=np.int64)
+        o = out if out is not None else self.empty((F, ld))
+        st = status if status is not None else (self.empty((3, F), np.int32) if out is None else None)
+        if lists and (out is not None or outputs is not None):
+            raise ValueError("lists=True returns host copies of library-allocated lists: it cannot be combined with out= or outputs= "
+                             "(pass device buffers through outputs= and read them yourself)")
+        own = []
+        if lists:
+            k = int(track.kmax)
+            own = [self.empty((F, k, 2)), self.empty(F, np.int32), self.empty(F), self.empty(F, np.int32)]
+            outputs = tuple(own)
+        po = None
+        if outputs is not None:
+            po = outputs if isinstance(outputs, PitchTrackOutputs) else PitchTrackOutputs(*[_ptr(a) for a in outputs])
+        try:
+            self._check(fn(self.ctx, ptr, F, N, S, C.byref(params), None if track is None else C.byref(track),
+                           None if seg is None else seg.ctypes.data, 0 if seg is None else seg.size,
+                           _ptr(o), ld, _ptr(st), None if po is None else C.byref(po)))
+            if out is not None:
+                return None
+            res = (o.numpy(), st.numpy())
+            if lists:
+                res = res + tuple(a.numpy() for a in own)
+            return res
+        finally:
+            for d in own + ([o, st] if out is None else []) + [tmp]:
+                if d is not None:
+                    d.free()
+
+    def analyze_frames_tracked(self, x, params, track, seg_start=None, frame_len=None, stride=None, n_frames=None, out=None,
+                               record_ld=None, status=None, lists=False, outputs=None):
+        """vbx_analyze_frames_tracked_f64: analyze_frames whose columns 0-1 hold the pitch path over the call's own kmax-entry
+        lists (track: PitchTrackParams).  Returns (records, status3), with lists=True also (cand [F, kmax, 2], count, peak,
+        index).  out / status: device buffers to write into (then returns None); outputs: a PitchTrackOutputs or a
+        (cand, count, peak, index) tuple of device buffers / None for the optional arrays.  lists=True with out= or outputs= is a
+        ValueError."""
+        ptr, F, N, S, tmp = self._frames(x, frame_len, stride, n_frames)
+        return self._analyze_tracked(self.L.vbx_analyze_frames_tracked_f64, ptr, F, N, S, params, track, seg_start, out, record_ld,
+                                     status, lists, outputs, tmp)
+
+    def analyze_frames_tracked_pcm16(self, pcm, params, track, seg_start=None, frame_len=None, stride=None, n_frames=None,
+                                     out=None, record_ld=None, status=None, lists=False, outputs=None):
+        """vbx_analyze_frames_tracked_pcm16: the same on 16-bit PCM samples (host int16 array or device buffer)."""
+        tmp = None
+        if isinstance(pcm, np.ndarray):
+            assert pcm.ndim == 1 and frame_len and stride
+            n_frames = frame_count(pcm.size, frame_len, stride) if n_frames is None else n_frames
+            tmp = self.to_device(pcm, np.int16)
+            ptr = tmp.ptr
+        else:
+            assert frame_len and stride and n_frames is not None
+            ptr = _ptr(pcm)
+        return self._analyze_tracked(self.L.vbx_analyze_frames_tracked_pcm16, ptr, int(n_frames), int(frame_len), int(stride), params,
+                                     track, seg_start, out, record_ld, status, lists, outputs, tmp)
 
     # -- spectrum.rs: MFCC ------------------------------------------------------------
     def mfcc(self, x, num_coeffs, freq_bounds, sample_rate, frame_len=None, stride=None, n_frames=None,
