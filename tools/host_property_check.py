@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Property test of the library's host-only entry points (csrc/vbx_host.cpp) on its AddressSanitizer + UBSan build
 (vox_box.rs_amd/lib/libvbx_host_asan.so; run with libasan preloaded -- tests/test_sanitizers.py does): random worlds, row
-counts, segment lists, window sizes and mel geometries, with the invariants each function documents.  Any sanitizer report
+counts, segment lists, window sizes, mel geometries and the builders of the device tables (into buffers with canaries on both
+sides), with the invariants each function documents.  Any sanitizer report
 aborts the process; the last line printed is "host property test: ok <n> cases"."""
 import ctypes as C
 import os
@@ -32,6 +33,7 @@ L.vbx_degree_c64.argtypes = [vp, sz]; L.vbx_degree_c64.restype = sz
 L.vbx_off_low_c64.argtypes = [vp, sz]; L.vbx_off_low_c64.restype = sz
 L.vbx_hz_to_mel.argtypes = [dbl]; L.vbx_hz_to_mel.restype = dbl
 L.vbx_mel_to_hz.argtypes = [dbl]; L.vbx_mel_to_hz.restype = dbl
+L.vbx_internal_host_table.argtypes = [i32, vp, vp, vp, vp, sz, vp]
 
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 1234)
 cases = 0
@@ -121,5 +123,58 @@ for _ in range(300):                                   # tables
     nz = np.nonzero(poly)[0]
     assert (d, o) == ((int(nz[-1]), int(nz[0])) if nz.size else (0, 0))
     assert abs(L.vbx_mel_to_hz(L.vbx_hz_to_mel(hi)) - hi) < 1e-9 * hi
+    cases += 1
+
+
+def host_table(kind, ip, dp=None, dtypes=(np.float64,), finite=True):
+    """one builder of the device tables (vbx_host.hpp) into a buffer with canaries on both sides -> its sub-tables"""
+    ip = np.asarray(ip, np.int64)
+    dp = None if dp is None else np.asarray(dp, np.float64)
+    sub, flags = np.zeros(4, np.uint64), np.zeros(1, np.int32)
+    args = (kind, ip.ctypes.data, None if dp is None else dp.ctypes.data, sub.ctypes.data)
+    assert L.vbx_internal_host_table(*args, None, 0, flags.ctypes.data) == 0
+    total = sum((int(b) + 15) & ~15 for b in sub)
+    buf = np.full(total + 32, 0xA5, np.uint8)                      # 16 canary bytes before and after (the tables are 16-byte aligned)
+    assert L.vbx_internal_host_table(*args, buf[16:].ctypes.data, total, flags.ctypes.data) == 0
+    assert np.all(buf[:16] == 0xA5) and np.all(buf[16 + total:] == 0xA5)
+    out, off = [], 16
+    for b, dt in zip(sub, dtypes):
+        out.append(buf[off:off + int(b)].view(dt))
+        assert not finite or np.all(np.isfinite(out[-1]))
+        off += (int(b) + 15) & ~15
+    return out, int(flags[0])
+
+
+for _ in range(150):                                   # the builders of the device tables, random parameters in their valid ranges
+    n = int(rng.integers(2, 4097))
+    (t,), f = host_table(0, [1, n], finite=False)       # the lag window with its reciprocals: every entry finite exactly when the flag says usable
+    r = np.abs(t[(n + 1) & ~1:])                        # (n >= 2: a one-sample Hanning ramp is 0 / 0)
+    assert t.size == ((n + 1) & ~1) + n and f == int(np.all(np.isfinite(r) & (r < 1e290) & (r > 1e-290))) and np.all(np.isfinite(t[:n]))
+    host_table(0, [int(rng.choice([0, 2, 3])), n])
+    (t32,), _ = host_table(1, [n], dtypes=(np.float32,))
+    assert t32.size == n
+    b_lo, nb = int(rng.integers(0, n)), int(rng.integers(0, 600))
+    (t,), _ = host_table(2, [n, b_lo, nb])              # Goertzel constants: 0 <= kappa <= 2 (+ rounding), sigma = +-1
+    assert t.size == 2 * max(nb, 1) and (nb == 0 or (np.all(np.abs(t[1::2]) == 1.0) and np.all((t[0::2] >= 0.0) & (t[0::2] <= 2.0000001))))
+    n1 = int(rng.integers(1, 129)); n2 = int(rng.integers(1, 257)); nc = (n1 + 3) & ~3
+    (ct, tw), _ = host_table(3, [n1 * n2, n1, nc], dtypes=(np.float64, np.float64))
+    assert ct.size == n1 * nc and tw.size == 2 * n1 * n2 and np.all(np.abs(ct) <= 1.0) and np.all(np.abs(tw) <= 1.0)
+    n1 = int(rng.integers(4, 64)); n2 = int(rng.integers(2, 65)); mt = (n2 + 15) // 16
+    ntd, ntm = (1, 0) if n1 <= 16 else (1, 1) if n1 <= 31 else (2, 0) if n1 == 32 else (2, 1) if n1 <= 47 else (2, 2)
+    tabs, _ = host_table(4, [n1 * n2, n1, n2, int(rng.integers(1, 9)), mt, ntd, ntm, 0, 1 if ntm == 2 else 0], dtypes=(np.float64,) * 4)
+    assert [a.size for a in tabs] == [((n1 + 3) & ~3) * 32 * ntd, mt * ntd * 512 + 2, mt * ntm * 512 + 2, 8 * mt * 64]
+    assert all(np.all(np.abs(a) <= 1.0) for a in tabs)
+    k = int(rng.integers(1, 65))
+    (t,), _ = host_table(5, [k])
+    assert t.size == k * k and np.all(np.abs(t) <= 1.0)
+    bins = np.cumsum(rng.integers(0, 40, k + 2))        # any ascending bins (neighbours may coincide)
+    (t,), _ = host_table(6, [k] + list(bins))
+    assert t.size == 2 * max(int(bins[-1] - bins[0]), 1) and np.all((t >= 0.0) & (t < 1.0))
+    ratio = float(rng.choice([0.5, 1.0, 1.5, 64.0, rng.uniform(0.01, 64.0)]))
+    m = L.vbx_resampled_len(n, ratio)
+    (idx, fr), _ = host_table(7, [m], [ratio], dtypes=(np.int32, np.float64))
+    assert idx.size == m and np.all(np.diff(idx) >= 0) and idx[0] == 0 and np.all((fr >= 0.0) & (fr < 1.0))
+    assert L.vbx_internal_host_table(5, np.array([0], np.int64).ctypes.data, None, np.zeros(4, np.uint64).ctypes.data, None, 0,
+                                     np.zeros(1, np.int32).ctypes.data) < 0                        # misuse is an error code
     cases += 1
 print("host property test: ok", cases, "cases")

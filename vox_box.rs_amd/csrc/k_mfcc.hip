@@ -288,7 +288,7 @@ void launch_mfcc(hipStream_t s, const double *x, long F, int n, long stride, con
     }
 }
 
-// ---- two-stage plan: geometry shared by the host (table builder in vbx_api.hip) and the launcher ----
+// ---- two-stage plan: geometry shared by the host (table builder: dft2_fill, vbx_host.cpp) and the launcher ----
 size_t mfcc_dft2_lds(const mfcc_plan_t &pl, int nb, int n, int waves) {
     const size_t xs_len = (size_t)((n > 2 * nb) ? n : 2 * nb);
     return ((size_t)pl.n1 * pl.nc + 2 * (size_t)n + (size_t)waves * (xs_len + (size_t)pl.n2 * pl.nc + 64)) * sizeof(double);

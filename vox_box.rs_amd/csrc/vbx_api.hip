@@ -4,18 +4,17 @@
 #include "../../include/voxbox_hip.h"
 #include "vbx_kernels.hpp"
 #include "vbx_host.hpp"
+#include "vbx_table_cache.hpp"
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
-#include <array>
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
 #include <map>
 #include <string>
-#include <tuple>
 #include <vector>
 
 using namespace vbx;
@@ -45,21 +44,10 @@ struct vbx_ctx {
     const int32_t *burg_list_count = nullptr;             // device counter of the last one-pass Burg call (tests)
     const int32_t *roots_list_count = nullptr;            // the same for the resonance kernel of find_formants
     size_t ws_bytes[WS_N] = {0};
-    // cached device tables
-    std::map<std::pair<int, size_t>, double *> windows;   // (kind, n)
-    std::map<size_t, bool> lag_rcp_ok;                    // n -> the lag window's table carries usable reciprocals (get_window_dev)
-    std::map<size_t, float *> lag_windows32;              // n -> the lag window table rounded to f32 (Pitched<f32, f32>)
-    std::map<std::tuple<size_t, int, int>, double *> goertzel;   // (n, b_lo, nb) -> [nb][2] kappa, sigma
-    std::map<size_t, double *> dct_tables;                // K -> [K][K]
-    std::map<std::pair<size_t, int>, std::pair<double *, double *>> dft2_tabs;   // (n, n1) -> (stage-1 table, twiddles)
-    std::map<std::tuple<size_t, int, int>, std::array<double *, 4>> mfma_tabs;   // (n, n1, k2) -> ctab, twd, twm, wm
-    std::map<std::tuple<size_t, int, int, int>, std::pair<double *, double *>> czt_tabs;   // (n, top, L, split length or 0) -> (chirp, FFT of the chirp segment(s))
+    device_tables_t tables;                               // every host-built device table (vbx_table_cache.hpp)
     bool pitch_whole_curve = false;                       // VBX_PITCH_CURVE_CUT=0: the pow2 kernels keep every lag of the curve in LDS (tests)
     bool mfcc_czt_split = false;                          // VBX_MFCC_CZT_SPLIT=1: the two-block form of the chirp-z kernel wherever it fits (tests)
     int mfcc_czt = -1;                                    // VBX_MFCC_CZT=0 / 1: never / wherever it fits (tests); -1: the measured choice
-    std::map<std::tuple<size_t, size_t, double, double, double>, int32_t *> bins_cache;
-    std::map<std::tuple<size_t, size_t, double, double, double>, double *> slopes_cache;   // [nb][2] i/up, i/down per bin
-    std::map<std::tuple<int, int, int, int>, std::pair<void *, mfcc_interp_t>> interp_cache;   // (plan, n, b_lo, nb) -> tables of the interpolated MFCC bins (first == nullptr: no such form)
     int last_mfcc_interp = 0;                             // the last vbx_mfcc_f64 call took the interpolated form (tests)
     int last_spectral_split = 0;                          // the last fused / pitch call ran as two kernels (tests)
     int last_mfcc_form = 0;                               // which kernel the last vbx_mfcc_f64 call launched: VBX_MFCC_FORM_* below (tests)
@@ -70,7 +58,6 @@ struct vbx_ctx {
     bool lpc_list_armed = false;                          // the last call that writes LPC rows from frames armed the probe's list (vbx_internal_last_lpc_exact_count)
     int pow2_split = -1;                                  // VBX_POW2_SPLIT=0: the 4096-point plan as ONE kernel (transforms and refinement fused, as before round 5; tests, A/B)
     int mfcc_interp = -1;                                 // VBX_MFCC_INTERP=0: never (the chirp-z kernel beside the fused one, as before round 5; tests, A/B)
-    std::map<std::pair<size_t, double>, std::pair<int32_t *, double *>> resample_tabs;   // (n, ratio) -> (index, fraction)
     // timing
     hipEvent_t t0 = nullptr, t1 = nullptr;
     bool prof = false;
@@ -81,7 +68,6 @@ struct vbx_ctx {
     std::vector<ProfRec> recs;
     std::map<std::string, std::pair<double, long>> prof_acc;
     std::map<std::string, int> prof_stream;               // name -> 0: the context's stream, 1: the side stream, 2: the tracker's
-    double *spectral_tab[SPECTRAL_PLANS] = {};             // twiddles of k_spectral*.hip, by plan
     bool pitch_force_mfma = false;                        // test hook: VBX_PITCH_MFMA=1 keeps the matrix-core pitch kernel on 1200-sample frames
     bool mfcc_force_goertzel = false;                     // test hooks: VBX_MFCC_GOERTZEL=1 / VBX_MFCC_DFT2=1 keep the
     bool mfcc_force_dft2 = false;                         //   fallback kernels covered on lengths the MFMA kernel takes
@@ -162,265 +148,13 @@ int ws_get(vbx_ctx *ctx, int slot, size_t bytes, void **out) {
     return VBX_SUCCESS;
 }
 
-// ---- host-built tables (the library's own statement of the sample-crate recurrences) --------
-
-// The lag window's table carries its entries' reciprocals behind them (each correctly rounded: the host's IEEE division), from
-// element (n + 1) & ~1 on, for the fused kernels' lag-window divide (quotient_by_table, vbx_spectral.hpp); ctx->lag_rcp_ok[n] says
-// whether they may be used (no zero, no entry whose reciprocal leaves the normal range).
-int get_window_dev(vbx_ctx *ctx, int kind, size_t n, const double **out) {
-    auto key = std::make_pair(kind, n);
-    auto it = ctx->windows.find(key);
-    if (it == ctx->windows.end()) {
-        const size_t off = (n + 1) & ~(size_t)1, total = (kind == VBX_WINDOW_HANNING_LAG) ? off + n : n;
-        std::vector<double> h(total, 0.0);
-        if (window_table_host(kind, n, h.data()) != VBX_SUCCESS) return fail(ctx, VBX_E_INVALID, "bad window kind");
-        if (kind == VBX_WINDOW_HANNING_LAG) {
-            bool usable = true;
-            for (size_t i = 0; i < n; i++) {
-                h[off + i] = 1.0 / h[i];
-                usable = usable && std::isfinite(h[off + i]) && std::fabs(h[off + i]) < 1e290 && std::fabs(h[off + i]) > 1e-290;
-            }
-            ctx->lag_rcp_ok[n] = usable;
-        }
-        double *d = nullptr;
-        VBX_HIP(ctx, hipMalloc((void **)&d, total * sizeof(double)));
-        VBX_HIP(ctx, hipMemcpy(d, h.data(), total * sizeof(double), hipMemcpyHostToDevice));
-        it = ctx->windows.emplace(key, d).first;
-    }
-    *out = it->second;
-    return VBX_SUCCESS;
-}
-
-// Goertzel-Reinsch constants of bins [b_lo, b_lo + nb) of an n-point DFT (k_mfcc.hip)
-int get_goertzel_dev(vbx_ctx *ctx, size_t n, int b_lo, int nb, const double **out) {
-    auto key = std::make_tuple(n, b_lo, nb);
-    auto it = ctx->goertzel.find(key);
-    if (it == ctx->goertzel.end()) {
-        std::vector<double> h(2 * (size_t)(nb > 0 ? nb : 1));
-        for (int i = 0; i < nb; i++) {
-            const double w = 2.0 * M_PI * (double)((size_t)(b_lo + i) % n) / (double)n;
-            if (std::cos(w) > 0.0) { const double sh = std::sin(0.5 * w); h[2 * i] = 4.0 * sh * sh; h[2 * i + 1] = 1.0; }
-            else { const double ch = std::cos(0.5 * w); h[2 * i] = 4.0 * ch * ch; h[2 * i + 1] = -1.0; }
-        }
-        double *d = nullptr;
-        VBX_HIP(ctx, hipMalloc((void **)&d, h.size() * sizeof(double)));
-        VBX_HIP(ctx, hipMemcpy(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-        it = ctx->goertzel.emplace(key, d).first;
-    }
-    *out = it->second;
-    return VBX_SUCCESS;
-}
-
-// tables of the two-stage MFCC DFT (k_mfcc.hip): ctab[i1][c] = cos / sin columns of the n1-point DFT,
-// twid[j] = (cos, sin)(2 pi j / n); evaluated in long double and rounded once
-int get_dft2_dev(vbx_ctx *ctx, size_t n, const mfcc_plan_t &pl, const double **ctab, const double **twid) {
-    auto key = std::make_pair(n, pl.n1);
-    auto it = ctx->dft2_tabs.find(key);
-    if (it == ctx->dft2_tabs.end()) {
-        const long double two_pi = 6.283185307179586476925286766559005768L;
-        const int n1 = pl.n1, nc = pl.nc, ncos = n1 / 2 + 1;
-        std::vector<double> hc((size_t)n1 * nc, 0.0), ht(2 * n);
-        for (int i1 = 0; i1 < n1; i1++)
-            for (int c = 0; c < n1; c++) {
-                const int k1 = (c < ncos) ? c : c - ncos + 1;
-                const long double ang = two_pi * (long double)((long)i1 * k1 % n1) / (long double)n1;
-                hc[(size_t)i1 * nc + c] = (double)((c < ncos) ? cosl(ang) : sinl(ang));
-            }
-        for (size_t j = 0; j < n; j++) {
-            const long double ang = two_pi * (long double)j / (long double)n;
-            ht[2 * j] = (double)cosl(ang); ht[2 * j + 1] = (double)sinl(ang);
-        }
-        double *dc = nullptr, *dt = nullptr;
-        VBX_HIP(ctx, hipMalloc((void **)&dc, hc.size() * sizeof(double)));
-        VBX_HIP(ctx, hipMalloc((void **)&dt, ht.size() * sizeof(double)));
-        VBX_HIP(ctx, hipMemcpy(dc, hc.data(), hc.size() * sizeof(double), hipMemcpyHostToDevice));
-        VBX_HIP(ctx, hipMemcpy(dt, ht.data(), ht.size() * sizeof(double), hipMemcpyHostToDevice));
-        it = ctx->dft2_tabs.emplace(key, std::make_pair(dc, dt)).first;
-    }
-    *ctab = it->second.first; *twid = it->second.second;
-    return VBX_SUCCESS;
-}
-
-// tables of the matrix-core MFCC kernel (k_mfcc_mfma.hip), evaluated in long double and rounded once
-int get_mfcc_mfma_dev(vbx_ctx *ctx, size_t n, const mfcc_mplan_t &pl, const double **ctab, const double **twd,
-                      const double **twm, const double **wm) {
-    auto key = std::make_tuple(n, pl.n1, pl.k2);
-    auto it = ctx->mfma_tabs.find(key);
-    if (it == ctx->mfma_tabs.end()) {
-        const long double two_pi = 6.283185307179586476925286766559005768L;
-        const int n1 = pl.n1, n2 = pl.n2, n1p = (n1 + 3) & ~3, nc = 32 * pl.ntd, mt = pl.mt;
-        std::vector<double> hc((size_t)n1p * nc, 0.0);
-        for (int i1 = 0; i1 < n1; i1++)
-            for (int c = 0; c < nc; c++) {
-                const bool is_sin = c >= 16 * pl.ntd;
-                const int k1 = is_sin ? c - 16 * pl.ntd : c;
-                if (k1 >= n1) continue;
-                const long double ang = two_pi * (long double)((long)i1 * k1 % n1) / (long double)n1;
-                hc[(size_t)i1 * nc + c] = (double)(is_sin ? sinl(ang) : cosl(ang));
-            }
-        auto twiddle = [&](int i2, int k1, double *dst) {
-            if (i2 >= n2 || k1 < 0 || k1 >= n1) { dst[0] = 0.0; dst[1] = 0.0; return; }
-            const long double ang = two_pi * (long double)((long)i2 * k1 % (long)n) / (long double)n;
-            dst[0] = (double)cosl(ang); dst[1] = (double)sinl(ang);
-        };
-        std::vector<double> hd((size_t)mt * pl.ntd * 4 * 128 + 2, 0.0), hm((size_t)mt * pl.ntm * 4 * 128 + 2, 0.0);
-        for (int m = 0; m < mt; m++)
-            for (int r = 0; r < 4; r++)
-                for (int l = 0; l < 64; l++) {
-                    const int i2 = 16 * m + 4 * r + (l >> 4), col = l & 15;
-                    for (int t = 0; t < pl.ntd; t++)
-                        twiddle(i2, 16 * t + col, &hd[((size_t)((m * pl.ntd + t) * 4 + r) * 64 + l) * 2]);
-                    for (int t = 0; t < pl.ntm; t++) {
-                        const int kp = 16 * (t == 0 ? pl.src0 : pl.src1) + col;
-                        twiddle(i2, (kp >= 1) ? n1 - kp : -1, &hm[((size_t)((m * pl.ntm + t) * 4 + r) * 64 + l) * 2]);
-                    }
-                }
-        // stage-2 A operand: Wm[2 k2 + p][kk], kk = Re rows i2 (0 .. 16 mt) then Im rows; lane l of K-step s holds
-        // Wm[l & 15][4 s + (l >> 4)]
-        std::vector<double> hw((size_t)8 * mt * 64, 0.0);
-        for (int s = 0; s < 8 * mt; s++)
-            for (int l = 0; l < 64; l++) {
-                const int rowm = l & 15, kk = 4 * s + (l >> 4);
-                const bool im_half = kk >= 16 * mt;
-                const int i2 = im_half ? kk - 16 * mt : kk, k2 = rowm >> 1, p = rowm & 1;
-                if (i2 >= n2 || k2 >= pl.k2) continue;
-                const long double ang = two_pi * (long double)((long)i2 * k2 % n2) / (long double)n2;
-                const long double c = cosl(ang), sn = sinl(ang);
-                // (Bre + i Bim)(c - i sn): Re = Bre c + Bim sn, Im = Bim c - Bre sn
-                hw[(size_t)s * 64 + l] = (double)(p == 0 ? (im_half ? sn : c) : (im_half ? c : -sn));
-            }
-        std::array<double *, 4> d{nullptr, nullptr, nullptr, nullptr};
-        const std::vector<double> *src[4] = {&hc, &hd, &hm, &hw};
-        for (int i = 0; i < 4; i++) {
-            VBX_HIP(ctx, hipMalloc((void **)&d[i], src[i]->size() * sizeof(double)));
-            VBX_HIP(ctx, hipMemcpy(d[i], src[i]->data(), src[i]->size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        it = ctx->mfma_tabs.emplace(key, d).first;
-    }
-    *ctab = it->second[0]; *twd = it->second[1]; *twm = it->second[2]; *wm = it->second[3];
-    return VBX_SUCCESS;
-}
-
-// tables of the chirp-z MFCC kernel (k_mfcc_czt.hip)
-int get_czt_dev(vbx_ctx *ctx, size_t n, int top, int L, int n1, const double **chirp, const double **bhat) {
-    auto key = std::make_tuple(n, top, L, n1);
-    auto it = ctx->czt_tabs.find(key);
-    if (it == ctx->czt_tabs.end()) {
-        const size_t nblk = (n1 > 0 && (size_t)n1 < n) ? (n + n1 - 1) / n1 : 1;
-        std::vector<double> hc(2 * n), hb(2 * (size_t)L * nblk);
-        mfcc_czt_fill_tabs((int)n, top, L, n1, hc.data(), hb.data());
-        double *dc = nullptr, *db = nullptr;
-        VBX_HIP(ctx, hipMalloc((void **)&dc, hc.size() * sizeof(double)));
-        VBX_HIP(ctx, hipMalloc((void **)&db, hb.size() * sizeof(double)));
-        VBX_HIP(ctx, hipMemcpy(dc, hc.data(), hc.size() * sizeof(double), hipMemcpyHostToDevice));
-        VBX_HIP(ctx, hipMemcpy(db, hb.data(), hb.size() * sizeof(double), hipMemcpyHostToDevice));
-        it = ctx->czt_tabs.emplace(key, std::make_pair(dc, db)).first;
-    }
-    *chirp = it->second.first; *bhat = it->second.second;
-    return VBX_SUCCESS;
-}
-
-int get_dct_dev(vbx_ctx *ctx, size_t k, const double **out) {
-    auto it = ctx->dct_tables.find(k);
-    if (it == ctx->dct_tables.end()) {
-        std::vector<double> h(k * k);
-        for (size_t kk = 0; kk < k; kk++)          // src/spectrum.rs:395
-            for (size_t n = 0; n < k; n++)
-                h[kk * k + n] = std::cos(M_PI * (double)kk * (2. * (double)n + 1.) / (2. * (double)k));
-        double *d = nullptr;
-        VBX_HIP(ctx, hipMalloc((void **)&d, k * k * sizeof(double)));
-        VBX_HIP(ctx, hipMemcpy(d, h.data(), k * k * sizeof(double), hipMemcpyHostToDevice));
-        it = ctx->dct_tables.emplace(k, d).first;
-    }
-    *out = it->second;
-    return VBX_SUCCESS;
-}
-
-// tables of the MFCC bins interpolated inside the fused kernel (mfcc_interp_t); *ok = false: the shape has no such form
-int get_interp_dev(vbx_ctx *ctx, int plan, int n, int b_lo, int nb, mfcc_interp_t *out, bool *ok) {
-    auto key = std::make_tuple(plan, n, b_lo, nb);
-    auto it = ctx->interp_cache.find(key);
-    if (it == ctx->interp_cache.end()) {
-        // a caller that sweeps frame lengths or bands would grow the cache without bound (48-200 KB of device memory per entry):
-        // past 64 entries everything is dropped (every stream drained first: a queued kernel may still read a table)
-        if (ctx->interp_cache.size() >= 64) {
-            VBX_HIP(ctx, hipDeviceSynchronize());
-            for (auto &kv : ctx->interp_cache) if (kv.second.first) (void)hipFree(kv.second.first);
-            ctx->interp_cache.clear();
-        }
-        mfcc_interp_t d{};
-        void *dev = nullptr;
-        {
-            const size_t bytes = mfcc_interp_table_bytes(plan, nb);
-            std::vector<char> h(bytes, 0);
-            if (mfcc_interp_fill(plan, n, b_lo, nb, h.data(), &d)) {
-                VBX_HIP(ctx, hipMalloc(&dev, bytes));
-                if (hipMemcpy(dev, h.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
-                    (void)hipFree(dev);
-                    return fail(ctx, VBX_E_RUNTIME, "get_interp_dev: hipMemcpy of the interpolation tables failed");
-                }
-                char *b = static_cast<char *>(dev);
-                d.rot = reinterpret_cast<const double *>(b);
-                d.coef = reinterpret_cast<const double *>(b + mfcc_interp_coef_offset(plan));
-                d.j0 = reinterpret_cast<const int32_t *>(b + mfcc_interp_j0_offset(plan, nb));
-            }
-        }
-        it = ctx->interp_cache.emplace(key, std::make_pair(dev, d)).first;
-    }
-    *ok = it->second.first != nullptr;
-    *out = it->second.second;
-    return VBX_SUCCESS;
-}
-
-// twiddles of the fused spectral kernels (k_spectral.hip, k_spectral_pow2.hip), one table per plan
-int get_spectral_tab(vbx_ctx *ctx, int plan, const double **out) {
-    if (!ctx->spectral_tab[plan]) {
-        std::vector<double> h(2 * (size_t)spectral_tab_complex(plan));
-        spectral_fill_tab(plan, h.data());
-        VBX_HIP(ctx, hipMalloc((void **)&ctx->spectral_tab[plan], h.size() * sizeof(double)));
-        VBX_HIP(ctx, hipMemcpy(ctx->spectral_tab[plan], h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    *out = ctx->spectral_tab[plan];
-    return VBX_SUCCESS;
-}
-
+// the mel bins: on the host on every call (the callers need them), their device copy from the context's tables
 int get_bins_dev(vbx_ctx *ctx, size_t n, size_t k, double lo, double hi, double sr,
                  const int32_t **out, std::vector<int32_t> &host_bins, bool &bad) {
     mel_bins_host(n, k, lo, hi, sr, host_bins, bad);
     for (size_t i = 0; i + 1 < host_bins.size(); i++) if (host_bins[i + 1] < host_bins[i]) bad = true;   // usize underflow panics
     if (host_bins.back() > (int32_t)n) bad = true;                                                    // spectrum[bin] out of bounds
-    auto key = std::make_tuple(n, k, lo, hi, sr);
-    auto it = ctx->bins_cache.find(key);
-    if (it == ctx->bins_cache.end()) {
-        int32_t *d = nullptr;
-        VBX_HIP(ctx, hipMalloc((void **)&d, host_bins.size() * sizeof(int32_t)));
-        VBX_HIP(ctx, hipMemcpy(d, host_bins.data(), host_bins.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        it = ctx->bins_cache.emplace(key, d).first;
-    }
-    *out = it->second;
-    return VBX_SUCCESS;
-}
-
-// src/spectrum.rs:424,430: the slope factor of every bin, (i as f64) / (up as f64) on the rising side of its
-// filter and i / down on the "falling" side (Q14: it rises too); one IEEE division each, as in the reference
-int get_slopes_dev(vbx_ctx *ctx, size_t n, size_t k, double lo, double hi, double sr,
-                   const std::vector<int32_t> &hb, const double **out) {
-    auto key = std::make_tuple(n, k, lo, hi, sr);
-    auto it = ctx->slopes_cache.find(key);
-    if (it == ctx->slopes_cache.end()) {
-        const int b_lo = hb.front(), nb = hb.back() - hb.front();
-        std::vector<double> h(2 * (size_t)(nb > 0 ? nb : 1), 0.0);
-        for (size_t w = 0; w < k; w++) {
-            const int up = hb[w + 1] - hb[w], down = hb[w + 2] - hb[w + 1];
-            for (int i = 0; i < up; i++) h[2 * (size_t)(hb[w] + i - b_lo)] = (double)i / (double)up;
-            for (int i = 0; i < down; i++) h[2 * (size_t)(hb[w + 1] + i - b_lo) + 1] = (double)i / (double)down;
-        }
-        double *d = nullptr;
-        VBX_HIP(ctx, hipMalloc((void **)&d, h.size() * sizeof(double)));
-        VBX_HIP(ctx, hipMemcpy(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-        it = ctx->slopes_cache.emplace(key, d).first;
-    }
-    *out = it->second;
+    VBX_HIP(ctx, ctx->tables.bins(n, k, lo, hi, sr, host_bins, out));
     return VBX_SUCCESS;
 }
 
@@ -569,18 +303,7 @@ void vbx_ctx_destroy(vbx_ctx *ctx) {
     for (int i = 0; i < vbx_ctx::WS_N; i++) if (ctx->ws[i]) hipFree(ctx->ws[i]);
     if (ctx->pitch_work) hipFree(ctx->pitch_work);
     if (ctx->stitch_state) hipFree(ctx->stitch_state);
-    for (double *t : ctx->spectral_tab) if (t) hipFree(t);
-    for (auto &kv : ctx->windows) hipFree(kv.second);
-    for (auto &kv : ctx->lag_windows32) hipFree(kv.second);
-    for (auto &kv : ctx->goertzel) hipFree(kv.second);
-    for (auto &kv : ctx->dct_tables) hipFree(kv.second);
-    for (auto &kv : ctx->dft2_tabs) { hipFree(kv.second.first); hipFree(kv.second.second); }
-    for (auto &kv : ctx->mfma_tabs) for (double *q : kv.second) hipFree(q);
-    for (auto &kv : ctx->czt_tabs) { hipFree(kv.second.first); hipFree(kv.second.second); }
-    for (auto &kv : ctx->bins_cache) hipFree(kv.second);
-    for (auto &kv : ctx->slopes_cache) hipFree(kv.second);
-    for (auto &kv : ctx->interp_cache) if (kv.second.first) hipFree(kv.second.first);
-    for (auto &kv : ctx->resample_tabs) { hipFree(kv.second.first); hipFree(kv.second.second); }
+    ctx->tables.clear();
     for (auto &r : ctx->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     if (ctx->side) { hipStreamSynchronize(ctx->side); hipStreamDestroy(ctx->side); }
     if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
@@ -762,8 +485,7 @@ static int run_autocorrelate(vbx_ctx *ctx, hipStream_t st, const double *x, size
         const double *tab = nullptr;
         spectral_launch_t L{};
         L.plan = spectral_plan((int)frame_len); L.n = (int)frame_len;
-        int rc = get_spectral_tab(ctx, L.plan, &tab);
-        if (rc != VBX_SUCCESS) return rc;
+        VBX_HIP(ctx, ctx->tables.spectral(L.plan, &tab));
         L.x = x; L.F = (long)n_frames; L.stride = (long)stride; L.window = window; L.tab = tab;
         L.out_r = out; L.n_lags = (int)n_lags;
         Prof p(ctx, "autocorr_fft", st);
@@ -928,9 +650,9 @@ static int run_pitch(vbx_ctx *ctx, hipStream_t st, const double *x, size_t n_fra
     VBX_REQUIRE(ctx, out_cand != nullptr, "null output");
     if (const char *e = pitch_shape_error(frame_len, kmax)) return fail(ctx, VBX_E_INVALID, std::string(__func__) + ": " + e);
     VBX_REQUIRE(ctx, cand_ld >= 2 * kmax && cand_ld % 2 == 0, "candidate rows must hold kmax entries and their leading dimension must be even");
-    const double *lagw = nullptr;
-    int rc = get_window_dev(ctx, VBX_WINDOW_HANNING_LAG, frame_len, &lagw);
-    if (rc != VBX_SUCCESS) return rc;
+    const double *lagw = nullptr; bool lag_rcp = false;
+    int rc;
+    VBX_HIP(ctx, ctx->tables.window(VBX_WINDOW_HANNING_LAG, frame_len, &lagw, &lag_rcp));
     if (frame_len > VBX_MAX_FRAME_LEN) {
         // a frame whose lag curve no LDS holds (k_long.hip): every lag by the chunked matrix-core tiles, the curve as an array in
         // HBM, peak scan -> improve_extremum per candidate -> rank sort; batches of frames so that the scratch stays <= 2 GiB
@@ -964,10 +686,9 @@ static int run_pitch(vbx_ctx *ctx, hipStream_t st, const double *x, size_t n_fra
         const double *tab = nullptr;
         spectral_launch_t L{};
         L.plan = spectral_plan((int)frame_len); L.n = (int)frame_len;
-        rc = get_spectral_tab(ctx, L.plan, &tab);
-        if (rc != VBX_SUCCESS) return rc;
+        VBX_HIP(ctx, ctx->tables.spectral(L.plan, &tab));
         L.x = x; L.F = (long)n_frames; L.stride = (long)stride; L.window = window; L.lag_window = lagw; L.tab = tab;
-        L.lag_rcp = ctx->lag_rcp_ok.count(frame_len) && ctx->lag_rcp_ok[frame_len];
+        L.lag_rcp = lag_rcp;
         L.sample_rate = sample_rate; L.threshold = threshold; L.fmin = fmin; L.fmax = fmax; L.kmax = (int)kmax;
         L.whole_curve = ctx->pitch_whole_curve;
         L.out_cand = (pitch_t *)out_cand; L.cand_ld = (long)cand_ld; L.out_count = out_count; L.pitch_status = status;
@@ -1357,8 +1078,7 @@ static int run_find_formants(vbx_ctx *ctx, hipStream_t stm, const double *x, siz
     int32_t *st = status;
     if (!st) { rc = ws_get(ctx, vbx_ctx::WS_STATUS, n_frames * sizeof(int32_t), &w); if (rc) return rc; st = (int32_t *)w; }
     const double *hann = nullptr;
-    rc = get_window_dev(ctx, VBX_WINDOW_HANNING_PERIODIC, frame_len, &hann);   // src/lib.rs:65-70
-    if (rc != VBX_SUCCESS) return rc;
+    VBX_HIP(ctx, ctx->tables.window(VBX_WINDOW_HANNING_PERIODIC, frame_len, &hann));   // src/lib.rs:65-70
     const int64_t *d_seg = nullptr; size_t nseg = 1; const res_t *d_est = nullptr;
     rc = upload_segments(ctx, stm, h_seg_start, n_segments, n_frames, &d_seg, &nseg);
     if (rc != VBX_SUCCESS) return rc;
@@ -1505,6 +1225,17 @@ int vbx_internal_mfcc_interp_table(size_t frame_len, int b_lo, int nb, int32_t *
     return 1;
 }
 
+// Host only: the plans whose fields the MFCC table builders of vbx_host.cpp take (vbx_internal_host_table; tests): out[0 .. 9) = the
+// matrix-core plan {ok, n1, n2, k2, mt, ntd, ntm, src0, src1}, out[9 .. 14) = the two-stage plan {ok, n1, n2, nc, tm}
+int vbx_internal_mfcc_table_plans(size_t frame_len, int b_lo, int nb, int32_t *out) {
+    if (!out || frame_len < 2 || frame_len > VBX_MAX_FRAME_LEN || b_lo < 0 || nb < 1 || nb > 4096) return VBX_E_INVALID;
+    const mfcc_mplan_t m = mfcc_mfma_plan((int)frame_len, b_lo, nb);
+    const mfcc_plan_t p = mfcc_plan((int)frame_len, nb);
+    const int32_t v[14] = {m.ok, m.n1, m.n2, m.k2, m.mt, m.ntd, m.ntm, m.src0, m.src1, p.ok, p.n1, p.n2, p.nc, p.tm};
+    std::memcpy(out, v, sizeof v);
+    return VBX_SUCCESS;
+}
+
 // ---- spectrum.rs: MFCC --------------------------------------------------------------------
 
 static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_frames, size_t frame_len, size_t stride,
@@ -1525,12 +1256,12 @@ static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_fra
     }
     const int nb = hb.back() - hb.front();
     const double *dct = nullptr, *slopes = nullptr;
-    rc = get_dct_dev(ctx, num_coeffs, &dct); if (rc != VBX_SUCCESS) return rc;
-    rc = get_slopes_dev(ctx, frame_len, num_coeffs, lo_hz, hi_hz, sample_rate, hb, &slopes); if (rc != VBX_SUCCESS) return rc;
+    VBX_HIP(ctx, ctx->tables.dct(num_coeffs, &dct));
+    VBX_HIP(ctx, ctx->tables.slopes(frame_len, num_coeffs, lo_hz, hi_hz, sample_rate, hb, &slopes));
     if (frame_len > VBX_MAX_FRAME_LEN) {          // a long frame: the Goertzel recurrence over HBM, the filter sums' inputs in a scratch (k_long.hip)
         VBX_REQUIRE(ctx, nb >= 1, "no mel bins");
         const double *tw = nullptr;
-        rc = get_goertzel_dev(ctx, frame_len, hb.front(), nb, &tw); if (rc != VBX_SUCCESS) return rc;
+        VBX_HIP(ctx, ctx->tables.goertzel(frame_len, hb.front(), nb, &tw));
         void *w = nullptr;
         rc = ws_get(ctx, vbx_ctx::WS_CZT, mfcc_long_scratch_bytes((long)n_frames, nb), &w); if (rc != VBX_SUCCESS) return rc;
         ctx->last_mfcc_form = 7;
@@ -1549,7 +1280,7 @@ static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_fra
             ((int)frame_len == spectral_plan_nc(plan) || (int)frame_len == 2 * spectral_plan_nc(plan)) &&
             num_coeffs <= 64 && nb >= 1 && hb.front() >= 0 && hb.front() + nb <= (int)frame_len / 2) {
             const double *tab = nullptr;
-            rc = get_spectral_tab(ctx, plan, &tab); if (rc != VBX_SUCCESS) return rc;
+            VBX_HIP(ctx, ctx->tables.spectral(plan, &tab));
             spectral_launch_t L{};
             L.plan = plan; L.n = (int)frame_len; L.mfcc_only = true;
             L.x = x; L.F = (long)n_frames; L.stride = (long)stride; L.window = window; L.tab = tab;
@@ -1578,11 +1309,11 @@ static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_fra
         bool ok = false;
         mfcc_interp_t ip{};
         if (plan != SPECTRAL_PLAN_NONE && (2 * spectral_plan_nc(plan)) % (int)frame_len != 0 && (int)frame_len < spectral_plan_nc(plan)) {
-            rc = get_interp_dev(ctx, plan, (int)frame_len, hb.front(), nb, &ip, &ok); if (rc != VBX_SUCCESS) return rc;
+            VBX_HIP(ctx, ctx->tables.interp(plan, (int)frame_len, hb.front(), nb, &ip, &ok));
         }
         if (ok) {
             const double *tab = nullptr;
-            rc = get_spectral_tab(ctx, plan, &tab); if (rc != VBX_SUCCESS) return rc;
+            VBX_HIP(ctx, ctx->tables.spectral(plan, &tab));
             spectral_launch_t L{};
             L.plan = plan; L.n = (int)frame_len; L.mfcc_only = true; L.interp = true; L.ip = ip;
             ctx->last_mfcc_interp = 1;
@@ -1624,8 +1355,8 @@ static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_fra
         const bool want = ctx->mfcc_czt == 1 || czt_over_mfma || (ctx->mfcc_czt == -1 && !forced && frame_len >= 600);
         if (cplan != SPECTRAL_PLAN_NONE && want) {
             const double *tab = nullptr, *chirp = nullptr, *bhat = nullptr;
-            rc = get_spectral_tab(ctx, cplan, &tab); if (rc != VBX_SUCCESS) return rc;
-            rc = get_czt_dev(ctx, frame_len, top, spectral_plan_nc(cplan), czt_n1, &chirp, &bhat); if (rc != VBX_SUCCESS) return rc;
+            VBX_HIP(ctx, ctx->tables.spectral(cplan, &tab));
+            VBX_HIP(ctx, ctx->tables.czt(frame_len, top, spectral_plan_nc(cplan), czt_n1, &chirp, &bhat));
             void *cw = nullptr;
             rc = ws_get(ctx, vbx_ctx::WS_CZT, (czt_n1 ? 4 : 2) * (size_t)spectral_plan_nc(cplan) * sizeof(double), &cw); if (rc != VBX_SUCCESS) return rc;
             ctx->last_mfcc_form = 3;
@@ -1637,14 +1368,14 @@ static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_fra
     }
     if (mp.ok) {
         const double *ctab = nullptr, *twd = nullptr, *twm = nullptr, *wm = nullptr;
-        rc = get_mfcc_mfma_dev(ctx, frame_len, mp, &ctab, &twd, &twm, &wm); if (rc != VBX_SUCCESS) return rc;
+        VBX_HIP(ctx, ctx->tables.mfma(frame_len, mp, &ctab, &twd, &twm, &wm));
         ctx->last_mfcc_form = 4;
         Prof p(ctx, "mfcc", stm);
         launch_mfcc_mfma(stm, x, (long)n_frames, (int)frame_len, (long)stride, window, mp, ctab, twd, twm, wm, d_bins,
                          slopes, dct, (int)num_coeffs, out, (long)out_ld, status, nb, ctx->cu_count);
     } else if (pl.ok) {
         const double *ctab = nullptr, *twid = nullptr;
-        rc = get_dft2_dev(ctx, frame_len, pl, &ctab, &twid); if (rc != VBX_SUCCESS) return rc;
+        VBX_HIP(ctx, ctx->tables.dft2(frame_len, pl, &ctab, &twid));
         ctx->last_mfcc_form = 5;
         Prof p(ctx, "mfcc", stm);
         launch_mfcc_dft2(stm, x, (long)n_frames, (int)frame_len, (long)stride, window, pl, ctab, twid, d_bins,
@@ -1652,7 +1383,7 @@ static int run_mfcc(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_fra
     } else {
         VBX_REQUIRE(ctx, mfcc_fits((int)frame_len, nb), "frame / bin range does not fit the LDS");
         const double *tw = nullptr;
-        rc = get_goertzel_dev(ctx, frame_len, hb.front(), nb, &tw); if (rc != VBX_SUCCESS) return rc;
+        VBX_HIP(ctx, ctx->tables.goertzel(frame_len, hb.front(), nb, &tw));
         ctx->last_mfcc_form = 6;
         Prof p(ctx, "mfcc", stm);
         launch_mfcc(stm, x, (long)n_frames, (int)frame_len, (long)stride, window, tw, d_bins, slopes, dct, (int)num_coeffs, out, (long)out_ld, status, nb);
@@ -1676,7 +1407,7 @@ int vbx_dct_f64(vbx_ctx *ctx, const double *in, size_t n_rows, size_t n, double 
     VBX_REQUIRE(ctx, in && out && n >= 1 && n <= 4096 && n_rows <= 0x7fffffffull, "bad argument");
     VBX_HIP(ctx, hipSetDevice(ctx->device));
     const double *dct = nullptr;
-    int rc = get_dct_dev(ctx, n, &dct); if (rc != VBX_SUCCESS) return rc;
+    VBX_HIP(ctx, ctx->tables.dct(n, &dct));
     { Prof p(ctx, "dct_rows"); launch_dct_rows(ctx->stream, in, (long)n_rows, (int)n, dct, out); }
     return check_launch(ctx, __func__);
 }
@@ -1742,30 +1473,9 @@ int vbx_resample_linear_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size
     const size_t m = vbx_resampled_len(frame_len, resample_ratio);
     VBX_REQUIRE(ctx, m >= 1 && m <= 0x3fffffff, "bad resampled length");
     VBX_HIP(ctx, hipSetDevice(ctx->device));
-    auto key = std::make_pair(frame_len, resample_ratio);
-    auto it = ctx->resample_tabs.find(key);
-    if (it == ctx->resample_tabs.end()) {
-        // sample 0.10 Converter: interpolation_value starts at 0, grows by 1/ratio per output, and every whole
-        // unit advances the (left, right) pair by one source sample; left starts at source index 0
-        std::vector<int32_t> hi(m);
-        std::vector<double> hf(m);
-        double value = 0.0;
-        const double step = 1.0 / resample_ratio;
-        long left = 0;
-        for (size_t k = 0; k < m; k++) {
-            while (value >= 1.0) { left++; value -= 1.0; }
-            hi[k] = (left > 0x3fffffff) ? 0x3fffffff : (int32_t)left;
-            hf[k] = value;
-            value += step;
-        }
-        int32_t *di = nullptr; double *df = nullptr;
-        VBX_HIP(ctx, hipMalloc((void **)&di, m * sizeof(int32_t)));
-        VBX_HIP(ctx, hipMalloc((void **)&df, m * sizeof(double)));
-        VBX_HIP(ctx, hipMemcpy(di, hi.data(), m * sizeof(int32_t), hipMemcpyHostToDevice));
-        VBX_HIP(ctx, hipMemcpy(df, hf.data(), m * sizeof(double), hipMemcpyHostToDevice));
-        it = ctx->resample_tabs.emplace(key, std::make_pair(di, df)).first;
-    }
-    { Prof p(ctx, "resample"); launch_resample(ctx->stream, x, (long)n_frames, (int)frame_len, (long)stride, it->second.first, it->second.second, (int)m, out); }
+    const int32_t *index = nullptr; const double *frac = nullptr;
+    VBX_HIP(ctx, ctx->tables.resample(frame_len, resample_ratio, m, &index, &frac));
+    { Prof p(ctx, "resample"); launch_resample(ctx->stream, x, (long)n_frames, (int)frame_len, (long)stride, index, frac, (int)m, out); }
     return check_launch(ctx, __func__);
 }
 
@@ -1844,8 +1554,7 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
     bool interp_mfcc = false;
     mfcc_interp_t ip{};
     if (fused && !fused_mfcc && !bad_bins && h_p->mfcc_coeffs && ctx->mfcc_interp != 0 && plan != SPECTRAL_PLAN_NONE && nb >= 1 && nb <= 4096 && hb.front() >= 0) {
-        rc = get_interp_dev(ctx, plan, (int)frame_len, hb.front(), nb, &ip, &interp_mfcc);
-        if (rc != VBX_SUCCESS) return rc;
+        VBX_HIP(ctx, ctx->tables.interp(plan, (int)frame_len, hb.front(), nb, &ip, &interp_mfcc));
         fused_mfcc = interp_mfcc;
     }
     // 16-bit PCM frames: the fused kernel of full 1200-sample frames, the pitch fallback and Burg read them directly;
@@ -1863,8 +1572,7 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
     }
     if (pcm_native) x = reinterpret_cast<const double *>(pcm16);          // the PCM kernels take the pointer through the f64 slot
     const double *hann = nullptr;
-    rc = get_window_dev(ctx, VBX_WINDOW_HANNING, frame_len, &hann);        // Windower::hanning frames (examples/pitch_detection.rs:23)
-    if (rc != VBX_SUCCESS) return rc;
+    VBX_HIP(ctx, ctx->tables.window(VBX_WINDOW_HANNING, frame_len, &hann));        // Windower::hanning frames (examples/pitch_detection.rs:23)
     // record columns
     const size_t c_form = 2, c_mfcc = c_form + (h_p->formant_order ? 2 * h_p->n_est : 0),
                  c_lpc = c_mfcc + h_p->mfcc_coeffs;
@@ -1944,13 +1652,12 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
     if (!h_p->mfcc_coeffs && st_mfcc) VBX_HIP(ctx, hipMemsetAsync(st_mfcc, 0, n_frames * sizeof(int32_t), side));
     VBX_HIP(ctx, hipEventRecord(ctx->ev_join, side));
     if (fused) {
-        const double *lagw = nullptr, *tab = nullptr;
-        rc = get_window_dev(ctx, VBX_WINDOW_HANNING_LAG, frame_len, &lagw); if (rc != VBX_SUCCESS) return rc;
-        rc = get_spectral_tab(ctx, plan, &tab); if (rc != VBX_SUCCESS) return rc;
+        const double *lagw = nullptr, *tab = nullptr; bool lag_rcp = false;
+        VBX_HIP(ctx, ctx->tables.window(VBX_WINDOW_HANNING_LAG, frame_len, &lagw, &lag_rcp));
+        VBX_HIP(ctx, ctx->tables.spectral(plan, &tab));
         if (fused_mfcc) {
-            rc = get_dct_dev(ctx, h_p->mfcc_coeffs, &dct); if (rc != VBX_SUCCESS) return rc;
-            rc = get_slopes_dev(ctx, frame_len, h_p->mfcc_coeffs, h_p->mfcc_lo_hz, h_p->mfcc_hi_hz, h_p->sample_rate, hb, &slopes);
-            if (rc != VBX_SUCCESS) return rc;
+            VBX_HIP(ctx, ctx->tables.dct(h_p->mfcc_coeffs, &dct));
+            VBX_HIP(ctx, ctx->tables.slopes(frame_len, h_p->mfcc_coeffs, h_p->mfcc_lo_hz, h_p->mfcc_hi_hz, h_p->sample_rate, hb, &slopes));
         }
         if (ctx->prof && !ctx->pitch_work) {
             const size_t wb = PITCH_WORK_WORDS * sizeof(unsigned long long);
@@ -1960,7 +1667,7 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
         spectral_launch_t L{};
         L.plan = plan; L.n = (int)frame_len;
         L.x = x; L.F = (long)n_frames; L.stride = (long)stride; L.window = hann; L.lag_window = lagw; L.tab = tab;
-        L.lag_rcp = ctx->lag_rcp_ok.count(frame_len) && ctx->lag_rcp_ok[frame_len];
+        L.lag_rcp = lag_rcp;
         L.sample_rate = h_p->sample_rate; L.threshold = h_p->pitch_threshold; L.fmin = h_p->pitch_fmin; L.fmax = h_p->pitch_fmax;
         L.kmax = 1;
         L.pcm = pcm_native;
@@ -2273,22 +1980,13 @@ int vbx_pitch_f32(vbx_ctx *ctx, const float *x, size_t n_frames, size_t frame_le
     VBX_REQUIRE(ctx, frame_len >= 4, "frame_len must be >= 4");
     VBX_REQUIRE(ctx, pitch_f32_exact_lds_bytes((int)frame_len, (int)kmax) + 16 <= 160 * 1024, "frame does not fit the LDS");
     VBX_HIP(ctx, hipSetDevice(ctx->device));
-    auto it = ctx->lag_windows32.find(frame_len);
-    if (it == ctx->lag_windows32.end()) {                   // w_lag as the f64 table of the reference's recurrence, each entry rounded to f32
-        std::vector<double> h(frame_len);
-        if (window_table_host(VBX_WINDOW_HANNING_LAG, frame_len, h.data()) != VBX_SUCCESS) return fail(ctx, VBX_E_INVALID, "lag window");
-        std::vector<float> hf(frame_len);
-        for (size_t i = 0; i < frame_len; i++) hf[i] = (float)h[i];
-        float *d = nullptr;
-        VBX_HIP(ctx, hipMalloc((void **)&d, frame_len * sizeof(float)));
-        VBX_HIP(ctx, hipMemcpy(d, hf.data(), frame_len * sizeof(float), hipMemcpyHostToDevice));
-        it = ctx->lag_windows32.emplace(frame_len, d).first;
-    }
+    const float *lagw32 = nullptr;
+    VBX_HIP(ctx, ctx->tables.lag_window_f32(frame_len, &lagw32));
     void *wo = nullptr;
     rc = ws_get(ctx, vbx_ctx::WS_F32_OUT, n_frames * kmax * sizeof(vbx_pitch), &wo);
     if (rc != VBX_SUCCESS) return rc;
     { Prof p(ctx, "pitch_f32_exact");
-      launch_pitch_f32_exact(ctx->stream, x, (long)n_frames, (int)frame_len, (long)stride, window, it->second, (double)sample_rate,
+      launch_pitch_f32_exact(ctx->stream, x, (long)n_frames, (int)frame_len, (long)stride, window, lagw32, (double)sample_rate,
                              (double)threshold, (double)fmin, (double)fmax, (int)kmax, (pitch_t *)wo, 2 * (long)kmax, out_count, status); }
     { Prof p(ctx, "narrow"); launch_narrow(ctx->stream, (const double *)wo, (long)(n_frames * kmax * 2), (float *)out_cand); }
     return check_launch(ctx, __func__);

@@ -1,6 +1,6 @@
 // vbx_host.cpp -- every entry point of the ABI that is plain host arithmetic: the window / lag-window tables by the sample
-// crate's recurrences, the mel bins, the work-size and frame-count formulas, and the geometry of a recording sharded over
-// ranks (frame ranges, warm-up, gather transfer list).  No HIP here: the same file is built into libvoxbox_hip.so and, under
+// crate's recurrences, the mel bins, the builders of the device tables the context caches (vbx_table_cache.hpp), the work-size and
+// frame-count formulas, and the geometry of a recording sharded over ranks (frame ranges, warm-up, gather transfer list).  No HIP here: the same file is built into libvoxbox_hip.so and, under
 // -fsanitize=address,undefined, into a host-only library that tests/test_sanitizers.py drives with random arguments
 // (tools/host_asan/Makefile).
 #include "../../include/voxbox_hip.h"
@@ -67,6 +67,139 @@ void mel_bins_host(size_t n, size_t k, double lo, double hi, double sr, std::vec
     }
 }
 
+// ---- device tables, host side (vbx_host.hpp) ----
+
+size_t window_dev_doubles(int kind, size_t n) { return (kind == VBX_WINDOW_HANNING_LAG) ? ((n + 1) & ~(size_t)1) + n : n; }
+
+int window_dev_fill(int kind, size_t n, double *h, bool *rcp_usable) {
+    *rcp_usable = false;
+    if (window_table_host(kind, n, h) != VBX_SUCCESS) return VBX_E_INVALID;
+    if (kind == VBX_WINDOW_HANNING_LAG) {
+        const size_t off = (n + 1) & ~(size_t)1;
+        bool usable = true;
+        for (size_t i = 0; i < n; i++) {
+            h[off + i] = 1.0 / h[i];
+            usable = usable && std::isfinite(h[off + i]) && std::fabs(h[off + i]) < 1e290 && std::fabs(h[off + i]) > 1e-290;
+        }
+        *rcp_usable = usable;
+    }
+    return VBX_SUCCESS;
+}
+
+size_t goertzel_doubles(int nb) { return 2 * (size_t)(nb > 0 ? nb : 1); }
+
+void goertzel_fill(size_t n, int b_lo, int nb, double *h) {
+    for (int i = 0; i < nb; i++) {
+        const double w = 2.0 * M_PI * (double)((size_t)(b_lo + i) % n) / (double)n;
+        if (std::cos(w) > 0.0) { const double sh = std::sin(0.5 * w); h[2 * i] = 4.0 * sh * sh; h[2 * i + 1] = 1.0; }
+        else { const double ch = std::cos(0.5 * w); h[2 * i] = 4.0 * ch * ch; h[2 * i + 1] = -1.0; }
+    }
+}
+
+size_t dft2_ctab_doubles(int n1, int nc) { return (size_t)n1 * nc; }
+size_t dft2_twid_doubles(size_t n) { return 2 * n; }
+
+// evaluated in long double and rounded once
+void dft2_fill(size_t n, int n1, int nc, double *hc, double *ht) {
+    const long double two_pi = 6.283185307179586476925286766559005768L;
+    const int ncos = n1 / 2 + 1;
+    for (int i1 = 0; i1 < n1; i1++)
+        for (int c = 0; c < n1; c++) {
+            const int k1 = (c < ncos) ? c : c - ncos + 1;
+            const long double ang = two_pi * (long double)((long)i1 * k1 % n1) / (long double)n1;
+            hc[(size_t)i1 * nc + c] = (double)((c < ncos) ? cosl(ang) : sinl(ang));
+        }
+    for (size_t j = 0; j < n; j++) {
+        const long double ang = two_pi * (long double)j / (long double)n;
+        ht[2 * j] = (double)cosl(ang); ht[2 * j + 1] = (double)sinl(ang);
+    }
+}
+
+void mfma_doubles(int n1, int mt, int ntd, int ntm, size_t doubles[4]) {
+    const int n1p = (n1 + 3) & ~3, nc = 32 * ntd;
+    doubles[0] = (size_t)n1p * nc;
+    doubles[1] = (size_t)mt * ntd * 4 * 128 + 2;
+    doubles[2] = (size_t)mt * ntm * 4 * 128 + 2;
+    doubles[3] = (size_t)8 * mt * 64;
+}
+
+// evaluated in long double and rounded once
+void mfma_fill(size_t n, int n1, int n2, int k2_plan, int mt, int ntd, int ntm, int src0, int src1,
+               double *hc, double *hd, double *hm, double *hw) {
+    const long double two_pi = 6.283185307179586476925286766559005768L;
+    const int nc = 32 * ntd;
+    for (int i1 = 0; i1 < n1; i1++)
+        for (int c = 0; c < nc; c++) {
+            const bool is_sin = c >= 16 * ntd;
+            const int k1 = is_sin ? c - 16 * ntd : c;
+            if (k1 >= n1) continue;
+            const long double ang = two_pi * (long double)((long)i1 * k1 % n1) / (long double)n1;
+            hc[(size_t)i1 * nc + c] = (double)(is_sin ? sinl(ang) : cosl(ang));
+        }
+    auto twiddle = [&](int i2, int k1, double *dst) {
+        if (i2 >= n2 || k1 < 0 || k1 >= n1) { dst[0] = 0.0; dst[1] = 0.0; return; }
+        const long double ang = two_pi * (long double)((long)i2 * k1 % (long)n) / (long double)n;
+        dst[0] = (double)cosl(ang); dst[1] = (double)sinl(ang);
+    };
+    for (int m = 0; m < mt; m++)
+        for (int r = 0; r < 4; r++)
+            for (int l = 0; l < 64; l++) {
+                const int i2 = 16 * m + 4 * r + (l >> 4), col = l & 15;
+                for (int t = 0; t < ntd; t++)
+                    twiddle(i2, 16 * t + col, &hd[((size_t)((m * ntd + t) * 4 + r) * 64 + l) * 2]);
+                for (int t = 0; t < ntm; t++) {
+                    const int kp = 16 * (t == 0 ? src0 : src1) + col;
+                    twiddle(i2, (kp >= 1) ? n1 - kp : -1, &hm[((size_t)((m * ntm + t) * 4 + r) * 64 + l) * 2]);
+                }
+            }
+    // stage-2 A operand: Wm[2 k2 + p][kk], kk = Re rows i2 (0 .. 16 mt) then Im rows; lane l of K-step s holds
+    // Wm[l & 15][4 s + (l >> 4)]
+    for (int s = 0; s < 8 * mt; s++)
+        for (int l = 0; l < 64; l++) {
+            const int rowm = l & 15, kk = 4 * s + (l >> 4);
+            const bool im_half = kk >= 16 * mt;
+            const int i2 = im_half ? kk - 16 * mt : kk, k2 = rowm >> 1, p = rowm & 1;
+            if (i2 >= n2 || k2 >= k2_plan) continue;
+            const long double ang = two_pi * (long double)((long)i2 * k2 % n2) / (long double)n2;
+            const long double c = cosl(ang), sn = sinl(ang);
+            // (Bre + i Bim)(c - i sn): Re = Bre c + Bim sn, Im = Bim c - Bre sn
+            hw[(size_t)s * 64 + l] = (double)(p == 0 ? (im_half ? sn : c) : (im_half ? c : -sn));
+        }
+}
+
+size_t dct_doubles(size_t k) { return k * k; }
+
+void dct_fill(size_t k, double *h) {
+    for (size_t kk = 0; kk < k; kk++)          // src/spectrum.rs:395
+        for (size_t n = 0; n < k; n++)
+            h[kk * k + n] = std::cos(M_PI * (double)kk * (2. * (double)n + 1.) / (2. * (double)k));
+}
+
+size_t slopes_doubles(const int32_t *hb, size_t k) { const int nb = hb[k + 1] - hb[0]; return 2 * (size_t)(nb > 0 ? nb : 1); }
+
+// one IEEE division each, as in the reference (Q14: the "falling" side rises too)
+void slopes_fill(const int32_t *hb, size_t k, double *h) {
+    const int b_lo = hb[0];
+    for (size_t w = 0; w < k; w++) {
+        const int up = hb[w + 1] - hb[w], down = hb[w + 2] - hb[w + 1];
+        for (int i = 0; i < up; i++) h[2 * (size_t)(hb[w] + i - b_lo)] = (double)i / (double)up;
+        for (int i = 0; i < down; i++) h[2 * (size_t)(hb[w + 1] + i - b_lo) + 1] = (double)i / (double)down;
+    }
+}
+
+// sample 0.10 Converter: interpolation_value starts at 0, grows by 1/ratio per output, and every whole
+// unit advances the (left, right) pair by one source sample; left starts at source index 0
+void resample_fill(size_t m, double resample_ratio, int32_t *hi, double *hf) {
+    double value = 0.0;
+    const double step = 1.0 / resample_ratio;
+    long left = 0;
+    for (size_t k = 0; k < m; k++) {
+        while (value >= 1.0) { left++; value -= 1.0; }
+        hi[k] = (left > 0x3fffffff) ? 0x3fffffff : (int32_t)left;
+        hf[k] = value;
+        value += step;
+    }
+}
 
 }  // namespace vbx
 
@@ -110,6 +243,84 @@ int vbx_window_table_f32(int kind, size_t n, float *h_out) {
     if (rc != VBX_SUCCESS) return rc;
     for (size_t i = 0; i < n; i++) h_out[i] = (float)t[i];
     return VBX_SUCCESS;
+}
+
+// Host only: the builders of the device tables (vbx_host.hpp) for tests and the sanitizer build.  kind: HOST_TABLE_*; ip / dp: its
+// integer / double parameters --
+//   WINDOW {window kind, n}   LAG_F32 {n}   GOERTZEL {n, b_lo, nb}   DFT2 {n, n1, nc}   DCT {k}   SLOPES {k, bins[0 .. k + 2)}
+//   MFMA {n, n1, n2, k2, mt, ntd, ntm, src0, src1}   RESAMPLE {m}, dp {ratio}
+// sub_bytes[4]: bytes of each sub-table (0: none); in buf each starts on the next multiple of 16 bytes after the one before, and what
+// the packing rules call padding stays zero.
+// *flags: bit 0 = the lag window's reciprocals are usable.  buf == nullptr: the sizes only.  VBX_E_INVALID: a parameter outside
+// what the library itself would pass, or cap too small.
+int vbx_internal_host_table(int kind, const int64_t *ip, const double *dp, size_t *sub_bytes, void *buf, size_t cap, int32_t *flags) {
+    if (!ip || !sub_bytes || !flags) return VBX_E_INVALID;
+    const int64_t big = 1 << 20;
+    auto in = [&](int i, int64_t lo, int64_t hi) { return ip[i] >= lo && ip[i] <= hi; };
+    size_t sz[4] = {0, 0, 0, 0};
+    double *b[4] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = VBX_SUCCESS;
+    *flags = 0;
+    auto place = [&]() {                       // the sizes are known: report them; true: the caller wants the tables, b[] says where
+        size_t total = 0, off[4];
+        for (int i = 0; i < 4; i++) { sub_bytes[i] = sz[i]; off[i] = total; total += (sz[i] + 15) & ~(size_t)15; }
+        if (buf && cap < total) rc = VBX_E_INVALID;
+        if (!buf || cap < total) return false;
+        std::memset(buf, 0, total);
+        for (int i = 0; i < 4; i++) b[i] = reinterpret_cast<double *>(static_cast<char *>(buf) + off[i]);
+        return true;
+    };
+    const size_t n = (size_t)ip[0];
+    switch (kind) {
+        case HOST_TABLE_WINDOW: {
+            if (!(in(0, 0, 3) && in(1, 1, big))) return VBX_E_INVALID;
+            bool usable = false;
+            sz[0] = window_dev_doubles((int)ip[0], (size_t)ip[1]) * sizeof(double);
+            if (place()) { rc = window_dev_fill((int)ip[0], (size_t)ip[1], b[0], &usable); *flags = usable ? 1 : 0; }
+            return rc;
+        }
+        case HOST_TABLE_LAG_F32:
+            if (!in(0, 1, big)) return VBX_E_INVALID;
+            sz[0] = n * sizeof(float);
+            if (place()) rc = vbx_window_table_f32(VBX_WINDOW_HANNING_LAG, n, reinterpret_cast<float *>(b[0]));
+            return rc;
+        case HOST_TABLE_GOERTZEL:
+            if (!(in(0, 1, big) && in(1, 0, big) && in(2, 0, big))) return VBX_E_INVALID;
+            sz[0] = goertzel_doubles((int)ip[2]) * sizeof(double);
+            if (place()) goertzel_fill(n, (int)ip[1], (int)ip[2], b[0]);
+            return rc;
+        case HOST_TABLE_DFT2:
+            if (!(in(0, 1, big) && in(1, 1, 128) && ip[0] % ip[1] == 0 && in(2, ip[1], 128))) return VBX_E_INVALID;
+            sz[0] = dft2_ctab_doubles((int)ip[1], (int)ip[2]) * sizeof(double); sz[1] = dft2_twid_doubles(n) * sizeof(double);
+            if (place()) dft2_fill(n, (int)ip[1], (int)ip[2], b[0], b[1]);
+            return rc;
+        case HOST_TABLE_MFMA:
+            if (!(in(1, 4, 63) && in(2, 2, 64) && ip[0] == ip[1] * ip[2] && in(3, 1, 8) && ip[4] == (ip[2] + 15) / 16 && in(5, 1, 2) && in(6, 0, 2) &&
+                  in(7, 0, 3) && in(8, 0, 3))) return VBX_E_INVALID;
+            mfma_doubles((int)ip[1], (int)ip[4], (int)ip[5], (int)ip[6], sz);
+            for (size_t &x : sz) x *= sizeof(double);
+            if (place()) mfma_fill(n, (int)ip[1], (int)ip[2], (int)ip[3], (int)ip[4], (int)ip[5], (int)ip[6], (int)ip[7], (int)ip[8], b[0], b[1], b[2], b[3]);
+            return rc;
+        case HOST_TABLE_DCT:
+            if (!in(0, 1, 64)) return VBX_E_INVALID;
+            sz[0] = dct_doubles(n) * sizeof(double);
+            if (place()) dct_fill(n, b[0]);
+            return rc;
+        case HOST_TABLE_SLOPES: {
+            if (!(in(0, 1, 64) && in(1, 0, big))) return VBX_E_INVALID;
+            for (size_t i = 1; i <= n + 1; i++) if (ip[i + 1] < ip[i] || ip[i + 1] > big) return VBX_E_INVALID;
+            const std::vector<int32_t> bins(ip + 1, ip + n + 3);
+            sz[0] = slopes_doubles(bins.data(), n) * sizeof(double);
+            if (place()) slopes_fill(bins.data(), n, b[0]);
+            return rc;
+        }
+        case HOST_TABLE_RESAMPLE:
+            if (!(dp && in(0, 1, 0x3fffffff) && dp[0] > 0.0 && dp[0] <= 64.0)) return VBX_E_INVALID;
+            sz[0] = n * sizeof(int32_t); sz[1] = n * sizeof(double);
+            if (place()) resample_fill(n, dp[0], reinterpret_cast<int32_t *>(b[0]), b[1]);
+            return rc;
+    }
+    return VBX_E_INVALID;
 }
 
 size_t vbx_degree_c64(const vbx_complex *h_poly, size_t len) {          // src/polynomial.rs:26-28
