@@ -1342,6 +1342,109 @@ pub fn gather_plan(rows: &[i64], rank: i32, dst: i32, row_doubles: usize) -> Gpu
     Ok((off, cnt, op))
 }
 
+/// Entries of the state and the back map that cross a shard cut (`VBX_PITCH_PATH_STATES`).
+pub const PITCH_PATH_STATES: usize = ffi::VBX_PITCH_PATH_STATES;
+
+/// One rank's part of the pitch path of a recording sharded by frame ranges (`vbx_pitch_path_shard_*_f64`; the protocol is in
+/// include/voxbox_hip.h, "The pitch path across a shard cut").  The rank's local frames are global frames `[lo - warm, hi)`
+/// of [`shard_plan`], `first = warm`.  The lists stay on the device and are borrowed until `finish`: the scan `begin` leaves
+/// in the context is what `enter` and `finish` continue, so no other path or frame-batch call may run on the `Gpu` in between
+/// (the library refuses `enter` / `finish` then).  Ranks call `begin` in any order, `enter` in rank order -- each passing its
+/// state on -- resolve the end states from the last rank backwards (`end[r] = back_map[r + 1][end[r + 1]]`), then `finish`.
+pub struct PathShard<'a, 'g: 'a> {
+    gpu: &'g Gpu,
+    n_frames: usize,
+    first: usize,
+    continues_prev: bool,
+    continues_next: bool,
+    _lists: PhantomData<&'a DeviceBuf<'g, ffi::VbxPitch>>,
+}
+
+/// The NaN-ignoring max of `local_peak` per local segment (`vbx_pitch_path_segment_peaks_f64`): the caller takes the max over
+/// the ranks that share a cut utterance and uploads the result as the `seg_peak` of [`PathShard::begin`].
+pub fn path_segment_peaks(gpu: &Gpu, local_peak: &DeviceBuf<f64>, seg_start: &[i64]) -> GpuResult<Vec<f64>> {
+    let (seg_ptr, n_seg) = if seg_start.is_empty() { (ptr::null(), 0) } else { (seg_start.as_ptr(), seg_start.len()) };
+    let out = gpu.alloc::<f64>(n_seg.max(1))?;
+    gpu.check(unsafe { ffi::vbx_pitch_path_segment_peaks_f64(gpu.raw, local_peak.as_ptr(), local_peak.len(), seg_ptr, n_seg, out.as_mut_ptr()) })?;
+    out.to_vec()
+}
+
+impl<'a, 'g: 'a> PathShard<'a, 'g> {
+    /// The speculative scan of the local frames (`vbx_pitch_path_shard_begin_f64`).  `cand`: `count.len() * kmax` entries;
+    /// `status`, `local_peak`, `seg_peak` (one entry per local segment: replaces P of every local segment) may be `None`.
+    #[allow(clippy::too_many_arguments)]
+    pub fn begin(gpu: &'g Gpu, cand: &'a DeviceBuf<'g, ffi::VbxPitch>, count: &'a DeviceBuf<'g, i32>, status: Option<&'a DeviceBuf<'g, i32>>,
+                 kmax: usize, local_peak: Option<&'a DeviceBuf<'g, f64>>, seg_peak: Option<&DeviceBuf<'g, f64>>, seg_start: &[i64],
+                 params: &PitchPathParams, plan: &ffi::VbxShardPlan) -> GpuResult<PathShard<'a, 'g>> {
+        let n_frames = count.len();
+        let (seg_ptr, n_seg) = if seg_start.is_empty() { (ptr::null(), 0) } else { (seg_start.as_ptr(), seg_start.len()) };
+        let raw = params.raw();
+        gpu.check(unsafe {
+            ffi::vbx_pitch_path_shard_begin_f64(
+                gpu.raw, cand.as_ptr(), count.as_ptr(), status.map_or(ptr::null(), |b| b.as_ptr()), n_frames, kmax,
+                local_peak.map_or(ptr::null(), |b| b.as_ptr()), seg_peak.map_or(ptr::null(), |b| b.as_ptr()), seg_ptr, n_seg, &raw,
+                plan.warm, plan.continues_prev, plan.continues_next,
+            )
+        })?;
+        Ok(PathShard { gpu, n_frames, first: plan.warm, continues_prev: plan.continues_prev != 0, continues_next: plan.continues_next != 0,
+                       _lists: PhantomData })
+    }
+
+    /// Step 2 (`vbx_pitch_path_shard_enter_f64`): `state_in` is the previous rank's `state_out` (`None` exactly when this rank
+    /// does not continue it).  Returns (state_out, back_map, chunks this call redid), each of `PITCH_PATH_STATES` entries.
+    pub fn enter(&self, state_in: Option<&[f64]>) -> GpuResult<(Vec<f64>, Vec<i32>, i32)> {
+        if state_in.is_some() != self.continues_prev || state_in.map_or(false, |s| s.len() != PITCH_PATH_STATES) {
+            return Err(GpuError { code: ffi::VBX_E_INVALID, message: "PathShard::enter: state_in must be 64 doubles exactly when the shard continues".into() });
+        }
+        let din = match state_in {
+            Some(s) => Some(self.gpu.upload(s)?),
+            None => None,
+        };
+        let state_out = self.gpu.alloc::<f64>(PITCH_PATH_STATES)?;
+        let back_map = self.gpu.alloc::<i32>(PITCH_PATH_STATES)?;
+        let changed = self.gpu.alloc::<i32>(1)?;
+        self.gpu.check(unsafe {
+            ffi::vbx_pitch_path_shard_enter_f64(
+                self.gpu.raw, din.as_ref().map_or(ptr::null(), |b| b.as_ptr()), state_out.as_mut_ptr(), back_map.as_mut_ptr(), changed.as_mut_ptr(),
+            )
+        })?;
+        Ok((state_out.to_vec()?, back_map.to_vec()?, changed.to_vec()?[0]))
+    }
+
+    /// Step 4 (`vbx_pitch_path_shard_finish_f64`): the rows of this rank's own frames `[first, n)` of the whole recording's
+    /// path and their list positions.  `end_state`: `None` exactly when the rank does not continue into the next.
+    pub fn finish(self, end_state: Option<i32>) -> GpuResult<(Vec<Pitch<f64>>, Vec<i32>)> {
+        if end_state.is_some() != self.continues_next {
+            return Err(GpuError { code: ffi::VBX_E_INVALID, message: "PathShard::finish: end_state must be given exactly when the shard continues".into() });
+        }
+        let dend = match end_state {
+            Some(e) => Some(self.gpu.upload(&[e])?),
+            None => None,
+        };
+        let path = self.gpu.alloc::<ffi::VbxPitch>(self.n_frames.max(1))?;
+        let index = self.gpu.alloc::<i32>(self.n_frames.max(1))?;
+        self.gpu.check(unsafe {
+            ffi::vbx_pitch_path_shard_finish_f64(self.gpu.raw, dend.as_ref().map_or(ptr::null(), |b| b.as_ptr()), path.as_mut_ptr(), 2, index.as_mut_ptr())
+        })?;
+        let (p, i) = (path.to_vec()?, index.to_vec()?);
+        Ok((p[self.first..self.n_frames].iter().map(|q| Pitch::new(q.frequency, q.strength)).collect(), i[self.first..self.n_frames].to_vec()))
+    }
+}
+
+/// Step 3 on the host: every rank's end state from the last rank backwards (`None`: the rank's last utterance ends at its own
+/// leader).  `back_maps[r]`: what rank `r`'s [`PathShard::enter`] returned.
+pub fn path_end_states(back_maps: &[Vec<i32>], plans: &[ffi::VbxShardPlan]) -> Vec<Option<i32>> {
+    let world = plans.len();
+    let mut end: Vec<Option<i32>> = vec![None; world];
+    for r in (0..world.saturating_sub(1)).rev() {
+        if plans[r].continues_next != 0 {
+            let e = end[r + 1].unwrap_or(0) as usize;
+            end[r] = Some(back_maps[r + 1][e % PITCH_PATH_STATES]);
+        }
+    }
+    end
+}
+
 /// This rank's RCCL communicator for the record gather (`vbx_comm_*`): one per process.  The 128-byte id comes from
 /// [`Comm::unique_id`] on rank 0 and travels to the other ranks by whatever the application has (MPI, a TCP store, a file).
 pub struct Comm<'g> {

@@ -561,7 +561,9 @@ int vbx_analyze_frames_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_frames, 
  * and a few hundred bytes per 256-frame chunk).  With silence_threshold == 0 and peak NULL no peak kernel runs.
  * VBX_E_INVALID, before anything is written and with the context left usable: a NULL h_track, kmax 0 or > 63, any path parameter
  * vbx_pitch_path_f64 rejects (other than time_step == 0), anything vbx_analyze_frames_f64 rejects.  n_frames == 0 succeeds.
- * Sharded runs (below): the path is NOT carried across a shard cut -- each rank's contour is the path of the frames it analysed.
+ * Sharded runs (below): by this call alone the path is NOT carried across a shard cut -- a rank's contour is the path of the frames it
+ * analysed.  vbx_pitch_path_shard_begin_f64 / _enter / _finish over the lists this call returns in h_outputs carry it: they turn
+ * columns 0-1 into the rows of the whole recording's path, bit for bit ("The pitch path across a shard cut", below).
  * Measured (one MI355X, 4.5 M frames of 1200 / 480 at 48 kHz, all parts on): 9.5 M frames/s at kmax 4, 5.0 M at kmax 15 (f64 and PCM
  * alike), against 7.9 M / 4.5 M for vbx_analyze_frames_f64 + vbx_pitch_f64(kmax) + vbx_frame_peak_f64 + vbx_pitch_path_f64: the
  * call saves the kmax = 1 pitch pass, ~90-100 ms of those frames; the list at kmax is what remains. */
@@ -617,8 +619,8 @@ int vbx_shard_samples(size_t lo, size_t hi, size_t frame_len, size_t hop, size_t
  * continues_next: the same for the next rank's first frame.
  * vbx_shard_local_segments: the utterance starts of frames [lo - warm, hi), re-based to the shard (first entry 0): the
  * h_seg_start of the rank's vbx_analyze_frames_f64 / vbx_find_formants_f64 call.  *n_out = entries needed (h_out may be NULL).
- * Only the formant track is carried across a cut.  The pitch path of vbx_analyze_frames_tracked_* is not: each rank's contour is the
- * path of the frames it analysed (its warm-up frames included), not a piece of the whole recording's path. */
+ * The formant track is carried across a cut by vbx_track_stitch_f64, the pitch path of vbx_pitch_path_f64 /
+ * vbx_analyze_frames_tracked_* by vbx_pitch_path_shard_*_f64 (further down), over the same plan. */
 #define VBX_SHARD_WARM_FRAMES 64
 typedef struct {
     size_t lo, hi, warm, stop;
@@ -634,6 +636,57 @@ int vbx_shard_local_segments(const vbx_shard_plan_t *h_plan, const int64_t *h_se
  * Alignment: formants as the call that wrote them took it (8 bytes for out_formants; the records' 16), d_state_in 8, d_changed 4. */
 int vbx_track_stitch_f64(vbx_ctx *ctx, vbx_resonance *formants, size_t n_frames, size_t formants_ld, size_t first, size_t stop,
                          const vbx_resonance *d_state_in, int32_t *d_changed);
+
+/* The pitch path across a shard cut (ABI 5, added): the rows every rank writes are those of vbx_pitch_path_f64 on the whole
+ * recording, bit for bit in out_path and equal in out_index, for any world size, cut positions, segment list, kmax and
+ * chunk_frames.  A rank analyses local frames [0, n) = global frames [lo - warm, hi) of vbx_shard_plan; first = warm: local
+ * frames [0, first) precede its range (they are analysed so that frame first - 1, the frame before the cut, has its list here:
+ * both ranks compute the list of a shared frame from the same samples with the same kernel, so its rows -- and with them the
+ * list positions the states are named by -- are the same bits on both; the formant stitch rests on the same property).
+ * Three small device arrays cross a cut:
+ *   state     VBX_PITCH_PATH_STATES doubles: the normalised D of ONE frame in that frame's state order (list positions
+ *             0..m-1, the appended unvoiced state at m), -inf where there is no state.  The frame is the one before the cut:
+ *             the sender's last (hi - 1), the receiver's local frame first - 1.
+ *   back map  VBX_PITCH_PATH_STATES int32: back_map[s] = the state of local frame first - 1 on the path that is in state s at
+ *             the rank's last frame n - 1 (constant when the utterance of frame first - 1 ends inside the shard; 0 beyond the
+ *             states; all 0 when first == 0).
+ *   end state one int32: the state of the rank's last frame on the whole recording's path.
+ * The silence term couples the ranks once more: u_t divides by P, the largest local_peak of the whole utterance.
+ * vbx_pitch_path_segment_peaks_f64 returns the NaN-ignoring max of local_peak per LOCAL segment (out_peak: device,
+ * n_segments entries, 1 when h_seg_start is NULL; NaN for an empty segment); the caller takes the max over the ranks that
+ * share a cut utterance and hands the result to _begin as seg_peak, which then REPLACES P of every local segment (NULL: P is
+ * the local max, as in vbx_pitch_path_f64).
+ * The protocol, every call asynchronous on the context's stream:
+ *   1. _begin on every rank, in any order: the speculative scan of all local frames, with nothing from another rank.
+ *      Arguments as vbx_pitch_path_f64; cand / count / status / local_peak must stay valid until _finish.  With continues_prev
+ *      local frame 0 is not the utterance's start.  VBX_E_INVALID: what vbx_pitch_path_f64 rejects, first > n_frames,
+ *      continues_prev with first == 0 or with an utterance start within [1, first], either flag with n_frames == 0,
+ *      continues_next with an empty last utterance.
+ *   2. _enter in rank order, each passing its d_state_out on as the next rank's d_state_in (NULL exactly when the rank was
+ *      begun without continues_prev): d_state_in is compared bit for bit with the scan's own D of frame first - 1; where they
+ *      differ the chunk that begins at `first` is redone from the true state and the repair is carried on, chunk by chunk,
+ *      inside that utterance only, until it meets states the scan already holds.  Then d_state_out (the D of frame n - 1;
+ *      d_state_in passed through when first == n_frames) and d_back_map are written; either may be NULL.
+ *      *d_changed (device, optional) = chunks this call redid.  d_state_out may be d_state_in.
+ *   3. on the host, from the last rank backwards: end[r] = back_map[r + 1][end[r + 1]] wherever rank r continues into r + 1.
+ *   4. _finish on every rank, in any order: d_end_state (device; NULL exactly when the rank was begun without
+ *      continues_next: its last utterance ends at its own leader) selects the path; rows [first, n) are written, row t at
+ *      out_path + t * path_ld doubles (path_ld = 2: dense rows; record_ld: columns 0-1 of frame records) and out_index[t]
+ *      (optional); rows [0, first) are not touched.  An end state outside the frame's states is taken modulo the row width.
+ * _enter and _finish continue the context's LAST _begin: after any other path or frame-batch call on the context they return
+ * VBX_E_INVALID (the rule of vbx_track_stitch_f64), as does _finish before _enter; nothing is written then and the context
+ * stays usable.  vbx_internal_last_path_chunks_redone reports the running count of _begin's and _enter's repairs. */
+#define VBX_PITCH_PATH_STATES 64
+int vbx_pitch_path_segment_peaks_f64(vbx_ctx *ctx, const double *local_peak, size_t n_frames, const int64_t *h_seg_start,
+                                     size_t n_segments, double *out_peak);
+int vbx_pitch_path_shard_begin_f64(vbx_ctx *ctx, const vbx_pitch *cand, const int32_t *count, const int32_t *status,
+                                   size_t n_frames, size_t kmax, const double *local_peak, const double *seg_peak,
+                                   const int64_t *h_seg_start, size_t n_segments, const vbx_pitch_path_params *h_params,
+                                   size_t first, int continues_prev, int continues_next);
+int vbx_pitch_path_shard_enter_f64(vbx_ctx *ctx, const double *d_state_in, double *d_state_out, int32_t *d_back_map,
+                                   int32_t *d_changed);
+int vbx_pitch_path_shard_finish_f64(vbx_ctx *ctx, const int32_t *d_end_state, vbx_pitch *out_path, size_t path_ld,
+                                    int32_t *out_index);
 
 typedef struct vbx_comm vbx_comm;
 #define VBX_UNIQUE_ID_BYTES 128

@@ -20,6 +20,9 @@
 //           pp_compose_kernel a log-depth suffix composition of those maps (the last chunk of a segment holds the constant
 //                             map to the segment's leader) gives every chunk's true end state.
 //           pp_write_kernel   per chunk, the group walks back from that state and writes out_path / out_index.
+//   shard   pp_enter_kernel / pp_open_map_kernel / pp_export_kernel / pp_select_kernel   the hand-off across a shard cut
+//                             (vbx_pitch_path_shard_*): the kernels above run unchanged on a rank's frames, these connect them to
+//                             the neighbouring ranks (at the end of the file).
 #include "vbx_kernels.hpp"
 
 #include <hip/hip_runtime.h>
@@ -371,7 +374,70 @@ __global__ __launch_bounds__(64) void pp_write_kernel(const pp_par_t P, const ui
     }
 }
 
+// ---- the shard hand-off (vbx_pitch_path_shard_*): a shard cut is a chunk boundary whose predecessor lives on another rank ------
+// The kernels above run unchanged on a rank's local frames; these four connect them to the neighbours.
+
+// enter: the chunk c0 that begins at local frame `first` against the TRUE state of frame first - 1 (64 doubles from the previous
+// rank, -inf where inactive).  Where the scan's own entry state is not that state bit for bit the chunk is redone from it, and
+// the repair is carried forward chunk by chunk (each redone chunk's exit against its successor's entry, whatever the exact flag
+// says: the scan's "exact" start of this utterance was local frame 0, itself a guess) until an exit state meets the entry the
+// next chunk already has, or the utterance ends at c1.  One group: the repair is sequential by nature.
+template <int G>
+__global__ __launch_bounds__(64) void pp_enter_kernel(const pp_par_t P, long c0, long c1, const double *__restrict__ state_in,
+                                                      int32_t *__restrict__ changed) {
+    __shared__ double2 lds[2][64];
+    const int s = threadIdx.x;                                 // blockDim.x == G: gbase 0
+    double D = state_in[s];
+    int n = 0;
+    for (long c = c0; c < c1; c++) {
+        const bool diff = __double_as_longlong(D) != __double_as_longlong(P.entry[c * G + s]);
+        if ((__ballot(diff) & pp_gmask<G>()) == 0ull) break;
+        P.entry[c * G + s] = D;
+        pp_run<G>(P, c, D, s, 0, lds);
+        D = P.exitd[c * G + s];                                // this lane's own store
+        n++;
+    }
+    if (s == 0 && changed != nullptr) *changed = n;
+}
+
+// the last chunk of an OPEN utterance (it continues on the next rank) ends in a state only that rank can name: the identity map
+// in place of the constant leader map, so that the suffix composition yields every chunk's map FROM the utterance's end state
+__global__ __launch_bounds__(64) void pp_open_map_kernel(uint8_t *__restrict__ map, long c, int G) {
+    if ((int)threadIdx.x < G) map[c * G + threadIdx.x] = (uint8_t)threadIdx.x;
+}
+
+// the two arrays that leave the rank, in their fixed 64-entry form: the exit state D of the last local frame (padded with -inf)
+// and the back map of the chunk that ends at frame first - 1 (padded with 0).  src: ns entries, map: G entries; NULL: all padding.
+// (src may be the caller's state_in, which state_out may alias: no __restrict__ on the two, each lane reads before it writes)
+__global__ __launch_bounds__(64) void pp_export_kernel(const double *src, int ns, const uint8_t *__restrict__ map, int G,
+                                                       double *state_out, int32_t *__restrict__ back_map) {
+    const int s = threadIdx.x;
+    const double d = (src != nullptr && s < ns) ? src[s] : -INFINITY;
+    if (state_out != nullptr) state_out[s] = d;
+    if (back_map != nullptr) back_map[s] = (map != nullptr && s < G) ? (int32_t)map[s] : 0;
+}
+
+// finish: sel[c][0] = map[c][end state] for the chunks from c0 on -- the form pp_write_kernel reads (a constant map's entry 0).
+// end_state: the state of the rank's last frame on the whole recording's path (device; NULL = 0: every map is constant then).
+__global__ __launch_bounds__(256) void pp_select_kernel(const uint8_t *__restrict__ map, long c0, long nch, int G,
+                                                        const int32_t *__restrict__ end_state, uint8_t *__restrict__ sel) {
+    const long c = c0 + (long)blockIdx.x * 256 + threadIdx.x;
+    if (c >= nch) return;
+    const int e = (end_state != nullptr) ? (*end_state & (G - 1)) : 0;     // never outside the row, whatever arrives
+    sel[c * G] = map[c * G + e];
+}
+
 // ---- launches ---------------------------------------------------------------------------------------------------------------
+void launch_pitch_path_open_map(hipStream_t s, uint8_t *map, long c, int G) {
+    hipLaunchKernelGGL(pp_open_map_kernel, dim3(1), dim3(64), 0, s, map, c, G);
+}
+void launch_pitch_path_export(hipStream_t s, const double *src, int ns, const uint8_t *map, int G, double *state_out, int32_t *back_map) {
+    hipLaunchKernelGGL(pp_export_kernel, dim3(1), dim3(64), 0, s, src, ns, map, G, state_out, back_map);
+}
+void launch_pitch_path_select(hipStream_t s, const uint8_t *map, long c0, long nch, int G, const int32_t *end_state, uint8_t *sel) {
+    hipLaunchKernelGGL(pp_select_kernel, dim3((unsigned)((nch - c0 + 255) / 256)), dim3(256), 0, s, map, c0, nch, G, end_state, sel);
+}
+
 void launch_pitch_path_peak(hipStream_t s, const pp_par_t &P, const int64_t *seg_chunk0, long nseg, double *cpk) {
     hipLaunchKernelGGL(pp_chunk_peak_kernel, dim3((unsigned)P.nch), dim3(64), 0, s, P.lpk, P.ch, P.nch, cpk);
     hipLaunchKernelGGL(pp_seg_peak_kernel, dim3((unsigned)nseg), dim3(64), 0, s, cpk, seg_chunk0, nseg, const_cast<double *>(P.spk));
@@ -411,6 +477,9 @@ void launch_pitch_path_compose(hipStream_t s, long nch, int G_, const uint8_t *i
 }
 void launch_pitch_path_write(hipStream_t s, const pp_par_t &P, int G_, const uint8_t *map, pitch_t *out_path, long ld, int32_t *out_index) {
     VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_write_kernel<G>, pp_group_grid(P.nch, G), dim3(64), 0, s, P, map, out_path, ld, out_index));
+}
+void launch_pitch_path_enter(hipStream_t s, const pp_par_t &P, int G_, long c0, long c1, const double *state_in, int32_t *changed) {
+    VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_enter_kernel<G>, dim3(1), dim3(G), 0, s, P, c0, c1, state_in, changed));
 }
 #undef VBX_PP_DISPATCH
 

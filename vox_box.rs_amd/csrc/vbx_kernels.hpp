@@ -359,5 +359,11 @@ void launch_pitch_path_map(hipStream_t s, const pp_par_t &P, int G, uint8_t *map
 void launch_pitch_path_compose(hipStream_t s, long nch, int G, const uint8_t *in, uint8_t *out, long d);
 void launch_pitch_path_write(hipStream_t s, const pp_par_t &P, int G, const uint8_t *map, pitch_t *out_path,
                              long ld /* doubles from one out_path row to the next: 2 = dense */, int32_t *out_index);
+// the shard hand-off (vbx_pitch_path_shard_*): chunks [c0, c1) are the rest of the utterance that is entered at chunk c0
+void launch_pitch_path_enter(hipStream_t s, const pp_par_t &P, int G, long c0, long c1, const double *state_in /* 64 */, int32_t *changed);
+void launch_pitch_path_open_map(hipStream_t s, uint8_t *map, long c, int G);
+void launch_pitch_path_export(hipStream_t s, const double *src /* ns or NULL */, int ns, const uint8_t *map /* G or NULL */, int G,
+                              double *state_out /* 64 or NULL */, int32_t *back_map /* 64 or NULL */);
+void launch_pitch_path_select(hipStream_t s, const uint8_t *map, long c0, long nch, int G, const int32_t *end_state, uint8_t *sel);
 
 }  // namespace vbx

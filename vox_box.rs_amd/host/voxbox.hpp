@@ -394,6 +394,34 @@ inline void track_stitch(Context &c, vbx_resonance *formants, size_t n_frames, s
                          const vbx_resonance *d_state_in, int32_t *d_changed = nullptr) {
     c.check(vbx_track_stitch_f64(c.get(), formants, n_frames, formants_ld, first, stop, d_state_in, d_changed));
 }
+// The pitch path across shard cuts (vbx_pitch_path_shard_*_f64; the protocol is in voxbox_hip.h, "The pitch path across a shard
+// cut"): begin on every rank, enter in rank order (each passing its state on), path_end_states on the host, finish on every rank.
+// Every pointer is a device pointer; state arrays hold VBX_PITCH_PATH_STATES entries.
+struct PitchPathShard {
+    static void segment_peaks(Context &c, const double *local_peak, size_t n_frames, Segments seg, double *out_peak) {
+        c.check(vbx_pitch_path_segment_peaks_f64(c.get(), local_peak, n_frames, seg.h_seg_start, seg.n, out_peak));
+    }
+    static void begin(Context &c, const Pitch *candidates, const int32_t *count, const int32_t *status, size_t kmax,
+                      const double *local_peak, const double *seg_peak, const ShardPlan &p, const PitchPathParams &params) {
+        c.check(vbx_pitch_path_shard_begin_f64(c.get(), candidates, count, status, p.n_frames(), kmax, local_peak, seg_peak,
+                                               p.local_seg_start.data(), p.local_seg_start.size(), &params, p.plan.warm,
+                                               p.plan.continues_prev, p.plan.continues_next));
+    }
+    static void enter(Context &c, const double *d_state_in, double *d_state_out, int32_t *d_back_map, int32_t *d_changed = nullptr) {
+        c.check(vbx_pitch_path_shard_enter_f64(c.get(), d_state_in, d_state_out, d_back_map, d_changed));
+    }
+    static void finish(Context &c, const int32_t *d_end_state, Pitch *out_path, size_t path_ld = 2, int32_t *out_index = nullptr) {
+        c.check(vbx_pitch_path_shard_finish_f64(c.get(), d_end_state, out_path, path_ld, out_index));
+    }
+    // end[r] = back_map[r + 1][end[r + 1]] from the last rank backwards; -1: rank r's last utterance ends at its own leader
+    // (pass NULL to finish).  back_maps[r]: rank r's back map on the host (unused where rank r does not continue r - 1).
+    static std::vector<int32_t> end_states(const std::vector<std::vector<int32_t>> &back_maps, const std::vector<ShardPlan> &plans) {
+        std::vector<int32_t> end(plans.size(), -1);
+        for (size_t r = plans.size(); r-- > 1;)
+            if (plans[r - 1].plan.continues_next) end[r - 1] = back_maps[r][end[r] < 0 ? 0 : end[r]];
+        return end;
+    }
+};
 
 class Comm {
 public:

@@ -3,7 +3,8 @@
 Frames are independent on the whole path except for the formant tracker, whose state is
 reset at utterance boundaries, so the batch splits by contiguous frame ranges with no
 data-path collective; the only exchange is one gather of fixed-size per-frame records to
-rank 0 (RCCL over xGMI when the tensors live on the GPUs, gloo in the CPU tests).
+rank 0 (RCCL over xGMI when the tensors live on the GPUs, gloo in the CPU tests).  Two sequential steps cross a cut inside
+an utterance: the formant tracker's state (plan, stitch_rows) and the pitch path's (path_end_states, stitch_path, path_handoff).
 """
 import numpy as np
 
@@ -151,3 +152,73 @@ def gather_records(local, counts, dst=0, group=None):
         return torch.cat([bufs[r][: counts[r]] for r in range(world)], dim=0)
     dist.gather(pad, None, dst=dst, group=group)
     return None
+
+
+# ---- the pitch path across shard cuts (include/voxbox_hip.h, "The pitch path across a shard cut") ----------------------------
+
+PATH_STATES = 64          # == VBX_PITCH_PATH_STATES
+
+
+def _plan_flag(pl, name):
+    return bool(pl[name] if isinstance(pl, dict) else getattr(pl, name))
+
+
+def path_end_states(back_maps, plans):
+    """Step 3 of the protocol on the host: the state of every rank's last frame on the whole recording's path, from the last
+    rank backwards -- end[r] = back_map[r + 1][end[r + 1]] wherever rank r continues into rank r + 1, None elsewhere (that
+    rank's last utterance ends at its own leader).  back_maps[r]: the 64 int32 vbx_pitch_path_shard_enter_f64 wrote on rank
+    r (None where rank r does not continue its predecessor); plans[r]: vbx_shard_plan of rank r (dict or ShardPlan).  Where
+    rank r + 1's utterance ends inside its shard its back map is constant: entry 0 is read."""
+    world = len(plans)
+    end = [None] * world
+    for r in range(world - 2, -1, -1):
+        if _plan_flag(plans[r], "continues_next"):
+            e = end[r + 1] if end[r + 1] is not None else 0
+            end[r] = int(back_maps[r + 1][e])
+    return end
+
+
+def stitch_path(enter, finish, plans):
+    """The protocol after every rank's begin, on one host (the counterpart of stitch_rows: the CPU tests pass the numpy model's
+    steps, a single-device run the VoxBox calls of one context per rank).  enter(r, state_in) -> (state_out [64] f64,
+    back_map [64] int32, chunks_redone) runs in rank order, state_in = rank r - 1's state_out when rank r continues it, else
+    None; finish(r, end_state) -> that rank's rows, end_state None where the rank does not continue into the next.
+    Returns ([rows of rank 0, rows of rank 1, ..], [chunks_redone per rank])."""
+    world = len(plans)
+    state, maps, changed = None, [], []
+    for r in range(world):
+        state, bm, n = enter(r, state if _plan_flag(plans[r], "continues_prev") else None)
+        maps.append(bm)
+        changed.append(int(n))
+    end = path_end_states(maps, plans)
+    return [finish(r, end[r]) for r in range(world)], changed
+
+
+def path_handoff(enter, plan, group=None, device=None):
+    """One rank's part of the protocol over a torch.distributed group (any backend with send / recv: gloo in the CPU test).
+    The states travel forward along the chain of ranks, the end states backward:
+      receive 64 doubles from rank - 1 when plan.continues_prev; enter(state_in or None) -> (state_out, back_map), tensors of
+      64 float64 / 64 int32 on `device` (what the backend moves: None = the CPU, for gloo); send state_out to rank + 1 when
+      plan.continues_next;
+      receive this rank's end state (one int32) from rank + 1 when plan.continues_next; send back_map[end state, or 0 when
+      the utterance ends here] to rank - 1 when plan.continues_prev.
+    Returns the end state for vbx_pitch_path_shard_finish_f64 as a one-element int32 tensor like back_map, or None."""
+    import torch
+    import torch.distributed as dist
+    rank = dist.get_rank(group)
+    prev, nxt = _plan_flag(plan, "continues_prev"), _plan_flag(plan, "continues_next")
+    state_in = None
+    if prev:
+        state_in = torch.empty(PATH_STATES, dtype=torch.float64, device=device)
+        dist.recv(state_in, src=rank - 1, group=group)
+    state_out, back_map = enter(state_in)
+    if nxt:
+        dist.send(state_out.contiguous(), dst=rank + 1, group=group)
+    end = None
+    if nxt:
+        end = torch.empty(1, dtype=torch.int32, device=device)
+        dist.recv(end, src=rank + 1, group=group)
+    if prev:
+        e = int(end.item()) if end is not None else 0
+        dist.send(back_map[e:e + 1].to(torch.int32).contiguous(), dst=rank - 1, group=group)
+    return end

@@ -185,6 +185,10 @@ def load_library():
         "vbx_frame_peak_f64": (C.c_int, [vp, vp, sz, sz, sz, vp]),
         "vbx_pitch_path_f64": (C.c_int, [vp, vp, vp, vp, sz, sz, vp, vp, sz, C.POINTER(PitchPathParams), vp, vp]),
         "vbx_internal_last_path_chunks_redone": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "vbx_pitch_path_segment_peaks_f64": (C.c_int, [vp, vp, sz, vp, sz, vp]),
+        "vbx_pitch_path_shard_begin_f64": (C.c_int, [vp, vp, vp, vp, sz, sz, vp, vp, vp, sz, C.POINTER(PitchPathParams), sz, i32, i32]),
+        "vbx_pitch_path_shard_enter_f64": (C.c_int, [vp, vp, vp, vp, vp]),
+        "vbx_pitch_path_shard_finish_f64": (C.c_int, [vp, vp, vp, sz, vp]),
         "vbx_lpc_f64": (C.c_int, [vp, vp, sz, sz, sz, vp]),
         "vbx_lpc_mut_f64": (C.c_int, [vp, vp, sz, sz, sz, vp, vp]),
         "vbx_window_table_f32": (C.c_int, [i32, sz, vp]),
@@ -748,6 +752,44 @@ class VoxBox:
         n = C.c_int64(0)
         self._check(self.L.vbx_internal_last_path_chunks_redone(self.ctx, C.byref(n)))
         return int(n.value)
+
+    # -- the pitch path across shard cuts (include/voxbox_hip.h, "The pitch path across a shard cut") -----------------
+    def pitch_path_segment_peaks(self, local_peak, n_frames, seg_start=None, out=None):
+        """vbx_pitch_path_segment_peaks_f64: the NaN-ignoring max of local_peak (device, [n_frames]) per local segment, as
+        numpy -- or into `out` (device, one double per segment).  The caller takes the max over the ranks that share a cut
+        utterance (np.fmax) and hands the result to pitch_path_shard_begin as seg_peak."""
+        seg = None if seg_start is None else np.ascontiguousarray(seg_start, dtype=np.int64)
+        nseg = 1 if seg is None or seg.size == 0 else seg.size
+        o = out if out is not None else self.empty(nseg)
+        rc = self.L.vbx_pitch_path_segment_peaks_f64(self.ctx, _ptr(local_peak), int(n_frames), None if seg is None else seg.ctypes.data,
+                                                     0 if seg is None else seg.size, _ptr(o))
+        try:
+            self._check(rc)
+            return None if out is not None else o.numpy()
+        finally:
+            if out is None:
+                o.free()
+
+    def pitch_path_shard_begin(self, cand, count, status, n_frames, kmax, local_peak=None, seg_peak=None, seg_start=None,
+                               params=None, first=0, continues_prev=False, continues_next=False):
+        """vbx_pitch_path_shard_begin_f64: the speculative scan of this rank's local frames [0, n_frames) (device buffers,
+        which must stay valid until pitch_path_shard_finish).  seg_peak: device, one double per local segment, or None."""
+        params = params if params is not None else PitchPathParams.make()
+        seg = None if seg_start is None else np.ascontiguousarray(seg_start, dtype=np.int64)
+        self._check(self.L.vbx_pitch_path_shard_begin_f64(
+            self.ctx, _ptr(cand), _ptr(count), _ptr(status), int(n_frames), int(kmax), _ptr(local_peak), _ptr(seg_peak),
+            None if seg is None else seg.ctypes.data, 0 if seg is None else seg.size, C.byref(params), int(first),
+            int(bool(continues_prev)), int(bool(continues_next))))
+
+    def pitch_path_shard_enter(self, state_in=None, state_out=None, back_map=None, changed=None):
+        """vbx_pitch_path_shard_enter_f64 on device buffers: state_in / state_out 64 doubles, back_map 64 int32, changed one
+        int32 (chunks redone by this call); state_in is None exactly when the rank was begun without continues_prev."""
+        self._check(self.L.vbx_pitch_path_shard_enter_f64(self.ctx, _ptr(state_in), _ptr(state_out), _ptr(back_map), _ptr(changed)))
+
+    def pitch_path_shard_finish(self, end_state, out_path, path_ld=2, out_index=None):
+        """vbx_pitch_path_shard_finish_f64: rows [first, n_frames) of out_path (rows path_ld doubles apart) and out_index;
+        end_state: device int32, None exactly when the rank was begun without continues_next."""
+        self._check(self.L.vbx_pitch_path_shard_finish_f64(self.ctx, _ptr(end_state), _ptr(out_path), int(path_ld), _ptr(out_index)))
 
     # -- spectrum.rs: LPC -------------------------------------------------------------
     def lpc(self, r, n_coeffs):
