@@ -906,8 +906,9 @@ impl<'b, 'g: 'b> ToResonance<f64> for RootRow<'b, 'g> {
 ///   not `Ok` leaves the state untouched, as `?` does at src/lib.rs:75.
 ///
 /// `resample_ratio != 1.0` runs the linear resampler of src/lib.rs:57-61 first (parity unpinned: the arithmetic
-/// lives in the un-vendored `sample 0.10` crate).  The reference's `resampled_buf` / `work` / `complex_work`
-/// arguments have no counterpart: the library owns its workspaces.
+/// lives in the un-vendored `sample 0.10` crate) -- inside Burg's kernels (`vbx_find_formants_resampled_f64`): the
+/// bits of [`FrameBatch::resample`] followed by this function on the dense batch, which never exists.  The
+/// reference's `resampled_buf` / `work` / `complex_work` arguments have no counterpart: the library owns its workspaces.
 pub fn find_formants(frames: &FrameBatch, sample_rate: f64, resample_ratio: f64, n_coeffs: usize, seg_start: &[i64], formants: &mut [Resonance<f64>]) -> VoxBoxResult<(Vec<Resonance<f64>>, Vec<FrameStatus>)> {
     let gpu = frames.gpu;
     let f = frames.n_frames;
@@ -915,28 +916,24 @@ pub fn find_formants(frames: &FrameBatch, sample_rate: f64, resample_ratio: f64,
     let gpu_err = |_e: GpuError| VoxBoxError::Workspace; // the reference's only non-algorithmic error (src/lib.rs:46-48)
     assert!(frames.window.is_none(), "find_formants applies its own window: pass rectangular frames (tests/lib.rs:71)");
 
-    // resample front end (src/lib.rs:42,57-61)
-    let resampled;
-    let (x, frame_len, stride) = if resample_ratio != 1.0 {
-        let m = unsafe { ffi::vbx_resampled_len(frames.frame_len, resample_ratio) };
-        resampled = gpu.alloc::<f64>(f * m).map_err(gpu_err)?;
-        gpu.check(unsafe {
-            ffi::vbx_resample_linear_f64(gpu.raw, frames.samples.as_ptr(), f, frames.frame_len, frames.stride, resample_ratio, resampled.as_mut_ptr())
-        })
-        .map_err(gpu_err)?;
-        (resampled.as_ptr(), m, m)
-    } else {
-        (frames.samples.as_ptr(), frames.frame_len, frames.stride)
-    };
-
+    let (x, frame_len, stride) = (frames.samples.as_ptr(), frames.frame_len, frames.stride);
     let track = gpu.alloc::<Resonance<f64>>(f * n_est).map_err(gpu_err)?;
     let status = gpu.alloc::<i32>(f).map_err(gpu_err)?;
     let (seg_ptr, n_seg) = if seg_start.is_empty() { (ptr::null(), 0) } else { (seg_start.as_ptr(), seg_start.len()) };
     gpu.check(unsafe {
-        ffi::vbx_find_formants_f64(
-            gpu.raw, x, f, frame_len, stride, sample_rate, n_coeffs, seg_ptr, n_seg, formants.as_ptr() as *const ffi::VbxResonance, n_est,
-            track.as_mut_ptr() as *mut ffi::VbxResonance, ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), status.as_mut_ptr(),
-        )
+        if resample_ratio != 1.0 {
+            // the resample front end (src/lib.rs:42,57-61) inside the call
+            ffi::vbx_find_formants_resampled_f64(
+                gpu.raw, x, f, frame_len, stride, sample_rate, resample_ratio, n_coeffs, seg_ptr, n_seg,
+                formants.as_ptr() as *const ffi::VbxResonance, n_est, track.as_mut_ptr() as *mut ffi::VbxResonance, ptr::null_mut(),
+                ptr::null_mut(), ptr::null_mut(), status.as_mut_ptr(),
+            )
+        } else {
+            ffi::vbx_find_formants_f64(
+                gpu.raw, x, f, frame_len, stride, sample_rate, n_coeffs, seg_ptr, n_seg, formants.as_ptr() as *const ffi::VbxResonance, n_est,
+                track.as_mut_ptr() as *mut ffi::VbxResonance, ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), status.as_mut_ptr(),
+            )
+        }
     })
     .map_err(gpu_err)?;
     let track = track.to_vec().map_err(gpu_err)?;
@@ -1111,6 +1108,28 @@ impl AnalysisParams {
     }
 }
 
+/// What examples/formant_extraction/src/main.rs:72-88 adds to the frame loop (`vbx_analysis_ext`): `find_formants` at
+/// `formant_resample_ratio` (0 or 1.0: none), given `formant_sample_rate` (0: `sample_rate * ratio`, formants in Hz of
+/// the recording), and with `rms` the frame's `RMS::rms` as the LAST column of the record.  `Default` asks for nothing.
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct AnalysisExt {
+    pub formant_resample_ratio: f64,
+    pub formant_sample_rate: f64,
+    pub rms: bool,
+}
+
+impl AnalysisExt {
+    /// The example itself: `find_formants(frame, new_rate, new_rate / recording_rate, ..)` and the RMS.  Pass `new_rate`
+    /// as `AnalysisParams::sample_rate` too to reproduce main.rs:76 literally (it hands `pitch` the new rate as well).
+    pub fn example(new_rate: f64, recording_rate: f64) -> AnalysisExt {
+        AnalysisExt { formant_resample_ratio: new_rate / recording_rate, formant_sample_rate: new_rate, rms: true }
+    }
+
+    fn to_ffi(&self) -> ffi::VbxAnalysisExt {
+        ffi::VbxAnalysisExt { formant_resample_ratio: self.formant_resample_ratio, formant_sample_rate: self.formant_sample_rate, rms: self.rms as i32 }
+    }
+}
+
 fn ffi_male_estimates() -> Vec<Resonance<f64>> {
     vox_box::MALE_FORMANT_ESTIMATES.iter().map(|&f| Resonance::new(f, 1.0)).collect()
 }
@@ -1194,6 +1213,48 @@ impl<'g> FrameBatch<'g> {
         })?;
         Ok((Records { data, status3, n_frames: self.n_frames, record_ld: ld }, index))
     }
+
+    /// The frame loop of examples/formant_extraction/src/main.rs:72-88 in one call (`vbx_analyze_frames_ex_f64`):
+    /// [`FrameBatch::analyze`] (`track` `None`) or [`FrameBatch::analyze_tracked`] (`track` = `(kmax, path)`) with
+    /// `find_formants` at `ext.formant_resample_ratio` -- the frames are resampled inside Burg's kernels, no dense
+    /// `[F, ceil(ratio * bin)]` batch exists -- and, with `ext.rms`, the frame's RMS as the record's last column
+    /// (`vbx_record_doubles_ex`).  Every other column keeps its offset; an `ext` that asks for nothing gives that call's
+    /// records bit for bit.  Returns the records and, for a tracked call, the path's list positions.
+    pub fn analyze_ex(&self, params: &AnalysisParams, ext: &AnalysisExt, track: Option<(usize, &PitchPathParams)>, seg_start: &[i64])
+                      -> GpuResult<(Records<'g>, Option<DeviceBuf<'g, i32>>)> {
+        assert!(self.window.is_none(), "analyze_ex applies the windows itself: pass a rectangular view (windower_rectangle)");
+        let gpu = self.gpu;
+        let (p, e) = (params.to_ffi(), ext.to_ffi());
+        let rec = unsafe { ffi::vbx_record_doubles_ex(&p, &e) };
+        let ld = rec + (rec & 1);
+        let data = gpu.alloc::<f64>(self.n_frames * ld)?;
+        let status3 = gpu.alloc::<i32>(3 * self.n_frames)?;
+        let (seg_ptr, n_seg) = if seg_start.is_empty() { (ptr::null(), 0) } else { (seg_start.as_ptr(), seg_start.len()) };
+        let tk = track.map(|(kmax, path)| ffi::VbxPitchTrackParams { kmax, path: path.raw() });
+        let index = if tk.is_some() { Some(gpu.alloc::<i32>(self.n_frames)?) } else { None };
+        let outputs = ffi::VbxPitchTrackOutputs {
+            cand: ptr::null_mut(), count: ptr::null_mut(), peak: ptr::null_mut(),
+            index: index.as_ref().map_or(ptr::null_mut(), |b| b.as_mut_ptr()),
+        };
+        gpu.check(unsafe {
+            ffi::vbx_analyze_frames_ex_f64(gpu.raw, self.samples.as_ptr(), self.n_frames, self.frame_len, self.stride, &p, &e,
+                                           tk.as_ref().map_or(ptr::null(), |t| t as *const _), seg_ptr, n_seg, data.as_mut_ptr(), ld,
+                                           status3.as_mut_ptr(), &outputs)
+        })?;
+        Ok((Records { data, status3, n_frames: self.n_frames, record_ld: ld }, index))
+    }
+
+    /// The resample front end of `find_formants` on its own (`vbx_resample_linear_f64`, src/lib.rs:42,57-61): the dense
+    /// `[F, vbx_resampled_len(bin, ratio)]` batch that [`find_formants`] and [`FrameBatch::analyze_ex`] never form.
+    pub fn resample(&self, resample_ratio: f64) -> GpuResult<FrameBatch<'g>> {
+        assert!(self.window.is_none(), "the resampler reads rectangular frames");
+        let m = unsafe { ffi::vbx_resampled_len(self.frame_len, resample_ratio) };
+        let out = self.gpu.alloc::<f64>(self.n_frames * m)?;
+        self.gpu.check(unsafe {
+            ffi::vbx_resample_linear_f64(self.gpu.raw, self.samples.as_ptr(), self.n_frames, self.frame_len, self.stride, resample_ratio, out.as_mut_ptr())
+        })?;
+        Ok(FrameBatch::new(self.gpu, out, None, self.n_frames, m, m))
+    }
 }
 
 /// 16-bit PCM samples on the device with a `Windower` view over them: what a WAV reader hands the reference's callers
@@ -1259,6 +1320,31 @@ impl<'g> PcmBatch<'g> {
         gpu.check(unsafe {
             ffi::vbx_analyze_frames_tracked_pcm16(gpu.raw, self.samples.as_ptr(), self.n_frames, self.frame_len, self.stride, &p, &track,
                                                   seg_ptr, n_seg, data.as_mut_ptr(), ld, status3.as_mut_ptr(), &outputs)
+        })?;
+        Ok((Records { data, status3, n_frames: self.n_frames, record_ld: ld }, index))
+    }
+
+    /// [`FrameBatch::analyze_ex`] reading the PCM directly (`vbx_analyze_frames_ex_pcm16`): bit-identical to
+    /// `self.widen()?.analyze_ex(..)`; neither Burg's resampled loaders nor the RMS need an f64 copy of the recording.
+    pub fn analyze_ex(&self, params: &AnalysisParams, ext: &AnalysisExt, track: Option<(usize, &PitchPathParams)>, seg_start: &[i64])
+                      -> GpuResult<(Records<'g>, Option<DeviceBuf<'g, i32>>)> {
+        let gpu = self.gpu;
+        let (p, e) = (params.to_ffi(), ext.to_ffi());
+        let rec = unsafe { ffi::vbx_record_doubles_ex(&p, &e) };
+        let ld = rec + (rec & 1);
+        let data = gpu.alloc::<f64>(self.n_frames * ld)?;
+        let status3 = gpu.alloc::<i32>(3 * self.n_frames)?;
+        let (seg_ptr, n_seg) = if seg_start.is_empty() { (ptr::null(), 0) } else { (seg_start.as_ptr(), seg_start.len()) };
+        let tk = track.map(|(kmax, path)| ffi::VbxPitchTrackParams { kmax, path: path.raw() });
+        let index = if tk.is_some() { Some(gpu.alloc::<i32>(self.n_frames)?) } else { None };
+        let outputs = ffi::VbxPitchTrackOutputs {
+            cand: ptr::null_mut(), count: ptr::null_mut(), peak: ptr::null_mut(),
+            index: index.as_ref().map_or(ptr::null_mut(), |b| b.as_mut_ptr()),
+        };
+        gpu.check(unsafe {
+            ffi::vbx_analyze_frames_ex_pcm16(gpu.raw, self.samples.as_ptr(), self.n_frames, self.frame_len, self.stride, &p, &e,
+                                           tk.as_ref().map_or(ptr::null(), |t| t as *const _), seg_ptr, n_seg, data.as_mut_ptr(), ld,
+                                           status3.as_mut_ptr(), &outputs)
         })?;
         Ok((Records { data, status3, n_frames: self.n_frames, record_ld: ld }, index))
     }

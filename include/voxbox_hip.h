@@ -588,6 +588,66 @@ int vbx_analyze_frames_tracked_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_
                                      double *out_records, size_t record_ld, int32_t *status3,
                                      const vbx_pitch_track_outputs *h_outputs);
 
+/* The frame loop of the reference's one complete program (ABI 5, added): examples/formant_extraction/src/main.rs:72-88 calls
+ * find_formants with resample_ratio = 10000 / 44100 (src/lib.rs:40-64: the frame is resampled to m = vbx_resampled_len(frame_len,
+ * ratio) samples before the periodic Hanning window and Burg) and keeps the frame's RMS next to the formants and the pitch
+ * (main.rs:84).  vbx_analyze_frames_ex_f64 / _pcm16 are vbx_analyze_frames_f64 / _pcm16 (h_track NULL: columns 0-1 = candidates[0])
+ * or vbx_analyze_frames_tracked_f64 / _pcm16 (h_track non-NULL) with that loop's two extras, from ONE call:
+ *   formant_resample_ratio  find_formants' resample_ratio.  The formant columns and the formant status row are those of
+ *                           vbx_resample_linear_f64 into a dense [F, m] batch followed by vbx_find_formants_f64 on it, BIT FOR BIT --
+ *                           but the batch never exists: Burg's kernels form each resampled, windowed sample in registers from the
+ *                           caller's hop-strided frames (f64, or 16-bit PCM widened in registers), for every resampled length
+ *                           2 <= m <= 1280 from frames of up to VBX_MAX_FRAME_LEN samples.  Other shapes (m > 1280, longer source
+ *                           frames) are resampled into a context-owned dense batch, a chunk of frames at a time: at most 256 MiB,
+ *                           or one resampled frame (8 m bytes) if that is more; PCM is then widened into the context-owned copy first.
+ *   formant_sample_rate     the sample_rate find_formants is given; 0: sample_rate * formant_resample_ratio, the true rate of the
+ *                           resampled frame (formants in Hz).
+ *   rms                     != 0: RMS::rms of the rectangular frame (src/waves.rs:10-23) -- exactly what vbx_rms_f64(window = NULL)
+ *                           returns on the f64 or widened samples -- as one more column, the LAST of the record:
+ *                             [ pitch | formants | mfcc | lpc | rms ],  vbx_record_doubles_ex(params, ext) doubles.
+ *                           It is taken on the context's second stream from the caller's own samples (a PCM recording is never widened
+ *                           for it); a tracked call that also needs local_peak reads the samples once for both.
+ * The example passes the NEW rate to pitch as well (main.rs:78-80): params.sample_rate = 10000 with formant_sample_rate = 10000
+ * reproduces it literally; a caller who wants true Hz passes the recording's rate as params.sample_rate and leaves
+ * formant_sample_rate 0.
+ * Every existing column keeps its offset; the alignment rules, status3, the state left for vbx_track_stitch_f64, the LPC probe's count
+ * and vbx_internal_last_burg_direct_count behave as in the plain and tracked calls.  With h_ext NULL or all zero (or a ratio of 1.0)
+ * the call IS the plain call (h_track NULL) or the tracked call (h_track non-NULL), bit for bit.
+ * VBX_E_INVALID, before anything is written and with the context left usable: a negative or non-finite ratio or rate, a ratio above
+ * 64 (the bound of vbx_resample_linear_f64), a resampled frame of fewer than 2 samples or an order Burg refuses on it, a ratio other
+ * than 0 / 1.0 with formant_order == 0, anything the plain or tracked call rejects.  n_frames == 0 succeeds.
+ * Measured (one MI355X, 4.5 M frames of 1200 / 480 at 48 kHz, all parts on, formants at ratio 10000 / 48000 and order 12, RMS on):
+ * 120.6 ms = 37.3 M frames/s (PCM: 121.3 ms) against 128.4 ms (PCM: 132.5 ms) for the calls it replaces -- vbx_analyze_frames_f64
+ * without formants, vbx_resample_linear_f64 into a 9 GB batch, vbx_find_formants_f64, vbx_rms_f64. */
+typedef struct {
+    double formant_resample_ratio;  /* find_formants' resample_ratio; 0 or 1.0: none (src/lib.rs:57,62-64) */
+    double formant_sample_rate;     /* the sample_rate find_formants is given; 0: sample_rate * ratio */
+    int32_t rms;                    /* != 0: one more column, the LAST of the record */
+} vbx_analysis_ext;
+size_t vbx_record_doubles_ex(const vbx_analysis_params *h_params, const vbx_analysis_ext *h_ext);
+int vbx_analyze_frames_ex_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
+                              const vbx_analysis_params *h_params, const vbx_analysis_ext *h_ext,
+                              const vbx_pitch_track_params *h_track /* NULL: columns 0-1 = candidates[0] */,
+                              const int64_t *h_seg_start, size_t n_segments,
+                              double *out_records, size_t record_ld, int32_t *status3,
+                              const vbx_pitch_track_outputs *h_outputs);
+int vbx_analyze_frames_ex_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
+                                const vbx_analysis_params *h_params, const vbx_analysis_ext *h_ext,
+                                const vbx_pitch_track_params *h_track /* NULL: columns 0-1 = candidates[0] */,
+                                const int64_t *h_seg_start, size_t n_segments,
+                                double *out_records, size_t record_ld, int32_t *status3,
+                                const vbx_pitch_track_outputs *h_outputs);
+/* vox_box::find_formants(buf, sample_rate, resample_ratio, ..) over F frames (src/lib.rs:40-116) with the ratio: all five outputs
+ * are those of vbx_resample_linear_f64 + vbx_find_formants_f64(sample_rate) on the dense batch, bit for bit, without the batch (the
+ * shapes and the fallback's workspace bound are those of vbx_analyze_frames_ex_f64).  sample_rate is what find_formants is given
+ * (the example: 10000).  resample_ratio 0 or 1.0: vbx_find_formants_f64 itself.  VBX_E_INVALID as above. */
+int vbx_find_formants_resampled_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
+                                    double sample_rate, double resample_ratio, size_t n_coeffs,
+                                    const int64_t *h_seg_start, size_t n_segments,
+                                    const vbx_resonance *h_est_init, size_t n_est,
+                                    vbx_resonance *out_formants, vbx_resonance *out_res, int32_t *out_res_count,
+                                    double *out_coeffs, int32_t *status);
+
 /* ------------------------------------------------------------------ multi-GPU: frame-range sharding */
 
 /* The reference has no distribution of any kind; frames are independent (the tracker per utterance), so a long

@@ -1,0 +1,8 @@
+// k_burg_resampled_p13.hip -- the one-pass Burg lag kernels on the resampled view at order 13 (vbx_burg_resampled.hpp)
+#include "vbx_burg_resampled.hpp"
+
+namespace vbx {
+
+VBX_BURG_RESAMPLED_INSTANTIATE(13)
+
+}  // namespace vbx

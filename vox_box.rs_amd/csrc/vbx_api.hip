@@ -51,7 +51,7 @@ struct vbx_ctx {
     std::string arch;
     int cu_count = 0;
     // workspaces (grown on demand, never shrunk)
-    enum { WS_COEFFS, WS_RES, WS_COUNT, WS_STATUS, WS_MISC, WS_SEG, WS_EST, WS_UNSURE, WS_F32_IN, WS_F32_OUT, WS_TRK, WS_BURG_LIST, WS_ROOTS_LIST, WS_LONG, WS_LONG2, WS_CZT, WS_CURVE, WS_LPC_LIST, WS_PATH, WS_PATH_TAB, WS_TRACK, WS_N };
+    enum { WS_COEFFS, WS_RES, WS_COUNT, WS_STATUS, WS_MISC, WS_SEG, WS_EST, WS_UNSURE, WS_F32_IN, WS_F32_OUT, WS_TRK, WS_BURG_LIST, WS_ROOTS_LIST, WS_LONG, WS_LONG2, WS_CZT, WS_CURVE, WS_LPC_LIST, WS_PATH, WS_PATH_TAB, WS_TRACK, WS_EX, WS_N };
     void *ws[WS_N] = {nullptr};
     const int32_t *burg_list_count = nullptr;             // device counter of the last one-pass Burg call (tests)
     const int32_t *roots_list_count = nullptr;            // the same for the resonance kernel of find_formants
@@ -835,8 +835,61 @@ static bool burg_order_ok(size_t frame_len, size_t n_coeffs) {
 
 // Burg on a batch: the one-pass form (k_burg_fast.hip) where it exists, the frames its guard turns away and every other
 // shape through the direct recursion (k_burg.hip)
+// rp (vbx_find_formants_resampled_f64, vbx_analyze_frames_ex_*): x / pcm hold the caller's frames of rp->n_src samples and Burg runs on
+// their RESAMPLED view -- n is then the resampled length m and window its periodic Hanning window.  The shapes the resampled
+// loaders take (k_burg_resampled.hip) never exist as a batch; the others are resampled into a context-owned dense batch, a
+// chunk of frames at a time, and take this function's plain form -- the same kernels at the same parameters either way.
+struct resample_plan_t { resample_src_t rs; size_t n_src, m; bool direct; };
+constexpr size_t EX_DENSE_BYTES = size_t(256) << 20;          // the dense fallback's batch: at most this, or one resampled frame
+
 static int run_burg(vbx_ctx *ctx, hipStream_t stm, const double *x, const int16_t *pcm, long F, int n, long stride,
-                    const double *window, int p, double *coeffs, int32_t *st, frame_map_t map = frame_map_t{0, 0, 0}) {
+                    const double *window, int p, double *coeffs, int32_t *st, frame_map_t map = frame_map_t{0, 0, 0},
+                    const resample_plan_t *rp = nullptr) {
+    if (rp && !rp->direct) {
+        // the dense fallback (f64 frames only: the callers widen PCM first; no time slices: run_find_formants)
+        long per = (long)(EX_DENSE_BYTES / ((size_t)n * sizeof(double)));
+        if (per < 1) per = 1;
+        if (per > F) per = F;
+        void *w = nullptr;
+        int rc = ws_get(ctx, vbx_ctx::WS_EX, 16 + (size_t)per * (size_t)n * sizeof(double), &w);
+        if (rc != VBX_SUCCESS) return rc;
+        int32_t *total = (int32_t *)w;                            // [1]: the guard's count over the whole call
+        double *dense = (double *)((char *)w + 16);
+        bool counted = false;
+        for (long f0 = 0; f0 < F; f0 += per) {
+            const long nf = (F - f0 < per) ? F - f0 : per;
+            { Prof pr(ctx, "resample", stm); launch_resample(stm, x + f0 * stride, nf, (int)rp->n_src, stride, rp->rs.li, rp->rs.frac, n, dense); }
+            rc = run_burg(ctx, stm, dense, nullptr, nf, n, (long)n, window, p, coeffs + f0 * (long)p, st + f0);
+            if (rc != VBX_SUCCESS) return rc;
+            if (ctx->burg_list_count) { launch_count_accumulate(stm, ctx->burg_list_count + 1, total + 1, f0 == 0); counted = true; }
+        }
+        if (counted) ctx->burg_list_count = total;
+        return VBX_SUCCESS;
+    }
+    if (rp) {
+        if (burg_fast_supported(n, p)) {
+            void *w = nullptr;
+            int rc = ws_get(ctx, vbx_ctx::WS_BURG_LIST, burg_fast_scratch_bytes(F, p), &w);
+            if (rc != VBX_SUCCESS) return rc;
+            int32_t *list = burg_fast_list(w, F, p);
+            ctx->burg_list_count = list;
+            VBX_HIP(ctx, hipMemsetAsync(list, 0, sizeof(int32_t), stm));
+            const long items = frame_map_items(map, F), chunk = burg_fast_chunk(F);
+            for (long i0 = 0; i0 < items; i0 += chunk) {
+                const long m = (items - i0 < chunk) ? items - i0 : chunk;
+                { Prof pr(ctx, "burg_lags_resampled", stm); launch_burg_lags_resampled(stm, x, pcm, F, n, stride, window, rp->rs, p, map, i0, m, w); }
+                { Prof pr(ctx, "burg_recursion", stm); launch_burg_recursion(stm, F, p, map, i0, m, coeffs, st, w); }
+            }
+            { Prof pr(ctx, "burg_direct_list_resampled", stm);
+              launch_burg_resampled_list(stm, x, pcm, F, n, stride, window, rp->rs, p, coeffs, st, list + 2, list); }
+            launch_count_accumulate(stm, list, list + 1, map.seg_len == 0 || map.t0 == 0);
+            return VBX_SUCCESS;
+        }
+        Prof pr(ctx, "burg_resampled", stm);
+        ctx->burg_list_count = nullptr;
+        launch_burg_resampled(stm, x, pcm, F, n, stride, window, rp->rs, p, coeffs, st, map);
+        return VBX_SUCCESS;
+    }
     if (n > VBX_MAX_FRAME_LEN) {
         // a frame longer than a wavefront's registers hold (tests/lib.rs:27-41 passes a whole file as one): one workgroup per
         // frame, the error arrays in an L2-resident scratch (k_long.hip); batches of frames so that the scratch stays <= 1 GiB
@@ -1076,8 +1129,10 @@ static int run_find_formants(vbx_ctx *ctx, hipStream_t stm, const double *x, siz
                              const int64_t *h_seg_start, size_t n_segments,
                              const vbx_resonance *h_est_init, size_t n_est,
                              vbx_resonance *out_formants, size_t formants_ld, vbx_resonance *out_res, int32_t *out_res_count,
-                             double *out_coeffs, int32_t *status, const int16_t *pcm = nullptr /* the frames as 16-bit PCM instead of x */) {
+                             double *out_coeffs, int32_t *status, const int16_t *pcm = nullptr /* the frames as 16-bit PCM instead of x */,
+                             const resample_plan_t *rp = nullptr /* find_formants on the frames' resampled view (run_burg) */) {
     VBX_REQUIRE(ctx, h_est_init && out_formants, "null argument");
+    if (rp) frame_len = rp->m;                                   // what Burg sees
     VBX_REQUIRE(ctx, burg_order_ok(frame_len, n_coeffs), "frame_len must be >= 2, order in [1, 62]");
     VBX_REQUIRE(ctx, n_est >= 1 && n_est <= VBX_FORMANT_SLOTS, "n_est must be in [1, 6]");
     VBX_REQUIRE(ctx, formants_ld >= 2 * n_est && formants_ld % 2 == 0, "formant rows must be 16-byte aligned and hold n_est entries");
@@ -1107,7 +1162,7 @@ static int run_find_formants(vbx_ctx *ctx, hipStream_t stm, const double *x, siz
     // round 3 only VBX_TRACKER_CHUNKED=0 reaches it (tracker_wants_chunks).
     long seg_len = 0;
     const bool chunked = tracker_wants_chunks(h_seg_start, n_segments, n_frames);   // long utterances: the chunked scan instead
-    if (!chunked && h_seg_start != nullptr && n_segments >= 64 && F >= 65536) {
+    if (!chunked && h_seg_start != nullptr && n_segments >= 64 && F >= 65536 && !(rp && !rp->direct)) {
         seg_len = (n_segments > 1) ? (long)h_seg_start[1] : 0;
         for (size_t i = 0; i < n_segments && seg_len > 0; i++) if (h_seg_start[i] != (int64_t)i * seg_len) seg_len = 0;
         // the slices cover t in [0, seg_len) of every utterance: a LAST utterance longer than the others (its end is
@@ -1125,7 +1180,7 @@ static int run_find_formants(vbx_ctx *ctx, hipStream_t stm, const double *x, siz
     ctx->last_track.res = res; ctx->last_track.cnt = cnt; ctx->last_track.st = st; ctx->last_track.F = F;
     ctx->last_track.n_est = (int)n_est; ctx->last_track.out = (res_t *)out_formants; ctx->last_track.out_ld = (long)formants_ld;
     if (n_slices == 1) {
-        rc = run_burg(ctx, stm, x, pcm, F, (int)frame_len, (long)stride, hann, p, coeffs, st);                                      // :75
+        rc = run_burg(ctx, stm, x, pcm, F, (int)frame_len, (long)stride, hann, p, coeffs, st, frame_map_t{0, 0, 0}, rp);           // :75
         if (rc != VBX_SUCCESS) return rc;
         rc = run_formant_resonances(ctx, stm, coeffs, F, p, sample_rate, res, cnt, st);                                            // :80-110
         if (rc != VBX_SUCCESS) return rc;
@@ -1141,7 +1196,7 @@ static int run_find_formants(vbx_ctx *ctx, hipStream_t stm, const double *x, siz
     }
     for (int j = 0; j < n_slices && j * tc < seg_len; j++) {
         const frame_map_t map{seg_len, j * tc, (seg_len - j * tc < tc) ? seg_len - j * tc : tc};   // the last slice may be shorter
-        rc = run_burg(ctx, stm, x, pcm, F, (int)frame_len, (long)stride, hann, p, coeffs, st, map);
+        rc = run_burg(ctx, stm, x, pcm, F, (int)frame_len, (long)stride, hann, p, coeffs, st, map, rp);
         if (rc != VBX_SUCCESS) return rc;
         rc = run_formant_resonances(ctx, stm, coeffs, F, p, sample_rate, res, cnt, st, map);
         if (rc != VBX_SUCCESS) return rc;
@@ -1515,27 +1570,30 @@ static int run_pitch_path(vbx_ctx *ctx, hipStream_t st, const vbx_pitch *cand, c
 
 // vbx_analyze_frames_tracked_*: columns 0-1 of the records are the pitch path over the call's own kmax-entry lists
 struct track_req_t { size_t kmax; vbx_pitch_path_params path; vbx_pitch_track_outputs out; };
+// vbx_analyze_frames_ex_*: find_formants on the frames' resampled view (rp non-null) at formant_rate, and the RMS column
+struct ex_req_t { const resample_plan_t *rp; double formant_rate; bool rms; };
 
 // x: the frames as f64 samples, or -- pcm16 non-null -- as 16-bit PCM (the kernels that have a PCM form read it directly:
 // 1200-sample frames through the fused spectral kernel, Burg at every length; every other shape is widened into a
 // context-owned f64 copy of the view first and takes the f64 path)
 static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, const int16_t *pcm16, size_t n_frames, size_t frame_len,
                                size_t stride, const vbx_analysis_params *h_p, const int64_t *h_seg_start, size_t n_segments,
-                               double *out_records, size_t record_ld, int32_t *status3, const track_req_t *tk = nullptr) {
+                               double *out_records, size_t record_ld, int32_t *status3, const track_req_t *tk = nullptr,
+                               const ex_req_t *ex = nullptr) {
     int rc = check_frames(ctx, fn, pcm16 ? (const void *)pcm16 : (const void *)x, n_frames, frame_len, stride, VBX_MAX_LONG_FRAME_LEN);
     if (rc == 1 && tk) { ctx->path_redone = nullptr; ctx->path_last = true; }      // an empty batch: an empty path
     if (rc != VBX_SUCCESS) return rc < 0 ? rc : VBX_SUCCESS;
     VBX_REQUIRE(ctx, h_p && out_records, "null argument");
-    const size_t rec = vbx_record_doubles(h_p);
+    const size_t c_rms = vbx_record_doubles(h_p), rec = c_rms + ((ex && ex->rms) ? 1 : 0);     // RMS: the record's last column
     VBX_REQUIRE(ctx, record_ld >= rec && record_ld % 2 == 0, "record_ld must be even and >= vbx_record_doubles(params)");
     VBX_REQUIRE(ctx, ((uintptr_t)out_records & 15) == 0, "records must be 16-byte aligned");
     VBX_REQUIRE(ctx, !h_p->formant_order || (h_p->n_est >= 1 && h_p->n_est <= VBX_FORMANT_SLOTS), "n_est must be in [1, 6]");
-    if (tk) {
+    if (tk || ex) {
         // The tracked form writes its peaks before the parts below look at their own arguments: what they would reject is asked first,
         // through the predicates those parts use themselves.  (The unfused MFCC kernels choose their form from the geometry: the tracked
         // form queues them FIRST on the side stream, below, so that their rejection also precedes every write.)
-        if (const char *e = pitch_shape_error(frame_len, tk->kmax)) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": " + e);
-        VBX_REQUIRE(ctx, !h_p->formant_order || burg_order_ok(frame_len, h_p->formant_order), "frame_len must be >= 2, order in [1, 62]");
+        if (const char *e = pitch_shape_error(frame_len, tk ? tk->kmax : 1)) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": " + e);
+        VBX_REQUIRE(ctx, !h_p->formant_order || burg_order_ok((ex && ex->rp) ? ex->rp->m : frame_len, h_p->formant_order), "frame_len must be >= 2, order in [1, 62]");
         VBX_REQUIRE(ctx, !h_p->lpc_order || lpc_order_ok(frame_len, h_p->lpc_order), "bad order");
     }
     VBX_HIP(ctx, hipSetDevice(ctx->device));
@@ -1576,7 +1634,8 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
     // anything that would send another kernel over the samples takes one widening pass into a context-owned f64 copy
     const int16_t *const pcm_in = pcm16;                                   // (the peak kernel reads the caller's PCM whichever form the rest takes)
     const bool pcm_native = pcm16 != nullptr && fused && frame_len == (size_t)SPECTRAL_N &&
-                            (!h_p->lpc_order || fused_lpc) && (!h_p->mfcc_coeffs || fused_mfcc);
+                            (!h_p->lpc_order || fused_lpc) && (!h_p->mfcc_coeffs || fused_mfcc) &&
+                            !(ex && ex->rp && !ex->rp->direct);            // (the dense fallback resamples f64 frames)
     if (pcm16 != nullptr && !pcm_native) {
         const size_t ns = (n_frames - 1) * stride + frame_len;
         void *w = nullptr;
@@ -1624,7 +1683,15 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
                       h_p->sample_rate, out_records + c_mfcc, record_ld, st_mfcc);
         if (rc != VBX_SUCCESS) return rc;
     }
-    if (tk_peak) {
+    // RMS::rms of the rectangular frame (examples/formant_extraction/src/main.rs:84), from the caller's own samples -- a PCM
+    // recording is never widened for it.  A tracked call that needs the frame peaks takes both from one read, here; otherwise
+    // the RMS kernel is the side stream's LAST launch, behind everything that may still reject the call.
+    const bool want_rms = ex && ex->rms;
+    if (tk_peak && want_rms) {
+        { Prof p(ctx, "frame_rms_peak", side);
+          launch_frame_rms(side, pcm_in ? nullptr : x, pcm_in, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, tk_peak); }
+        VBX_HIP(ctx, hipEventRecord(ctx->ev_peak, side));
+    } else if (tk_peak) {
         // max |x| per frame, first on the side stream: HBM-bound, beside the FP64-bound kernel; the path waits for ev_peak
         if (pcm_in) { Prof p(ctx, "frame_peak_pcm16", side); launch_frame_peak_pcm16(side, pcm_in, (long)n_frames, (long)frame_len, (long)stride, tk_peak); }
         else { Prof p(ctx, "frame_peak", side); launch_frame_peak(side, x, (long)n_frames, (long)frame_len, (long)stride, tk_peak); }
@@ -1633,9 +1700,9 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
     if (h_p->formant_order) {
         vbx_resonance est[VBX_FORMANT_SLOTS];
         for (size_t e = 0; e < h_p->n_est; e++) est[e] = h_p->est_init[e];
-        rc = run_find_formants(ctx, side, x, n_frames, frame_len, stride, h_p->sample_rate, h_p->formant_order,
+        rc = run_find_formants(ctx, side, x, n_frames, frame_len, stride, ex ? ex->formant_rate : h_p->sample_rate, h_p->formant_order,
                                h_seg_start, n_segments, est, h_p->n_est, (vbx_resonance *)(out_records + c_form), record_ld,
-                               nullptr, nullptr, nullptr, st_form, pcm_native ? pcm16 : nullptr);
+                               nullptr, nullptr, nullptr, st_form, pcm_native ? pcm16 : nullptr, ex ? ex->rp : nullptr);
         if (rc != VBX_SUCCESS) return rc;
     } else {
         ctx->last_track.res = nullptr;                        // no tracks in these records: nothing for vbx_track_stitch_f64 to continue
@@ -1665,6 +1732,10 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
         }
     }
     if (!h_p->mfcc_coeffs && st_mfcc) VBX_HIP(ctx, hipMemsetAsync(st_mfcc, 0, n_frames * sizeof(int32_t), side));
+    if (want_rms && !tk_peak) {
+        Prof p(ctx, "frame_rms", side);
+        launch_frame_rms(side, pcm_in ? nullptr : x, pcm_in, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, nullptr);
+    }
     VBX_HIP(ctx, hipEventRecord(ctx->ev_join, side));
     if (fused) {
         const double *lagw = nullptr, *tab = nullptr; bool lag_rcp = false;
@@ -1763,6 +1834,95 @@ int vbx_analyze_frames_tracked_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_
     if (n_frames != 0 && ctx && !pcm) return fail(ctx, VBX_E_INVALID, "vbx_analyze_frames_tracked_pcm16: null frame pointer");
     return analyze_tracked(ctx, __func__, nullptr, pcm, n_frames, frame_len, stride, h_p, h_track, h_seg_start, n_segments, out_records,
                            record_ld, status3, h_outputs);
+}
+
+// find_formants' resample_ratio (src/lib.rs:40-64) as a plan: the checks every entry point that takes a ratio shares, the
+// resampled length, the context's (li, frac) table and whether the resampled loaders take the shape.  *have = false: no
+// resampling (ratio 0 or 1.0: src/lib.rs:57 compares with 1.0).
+static int make_resample_plan(vbx_ctx *ctx, const char *fn, double ratio, size_t frame_len, size_t order, resample_plan_t *rp, bool *have) {
+    *have = false;
+    if (!(ratio >= 0.0) || !std::isfinite(ratio)) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": resample_ratio must be finite and >= 0");
+    if (ratio == 0.0 || ratio == 1.0) return VBX_SUCCESS;
+    if (ratio > 64.0) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": resample_ratio must be in (0, 64]");
+    if (order == 0) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": a resample_ratio needs a formant order");
+    const size_t m = vbx_resampled_len(frame_len, ratio);
+    if (m > 0x3fffffff) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": bad resampled length");
+    if (!burg_order_ok(m, order)) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": the resampled frame must have >= 2 samples, order in [1, 62]");
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    rp->n_src = frame_len; rp->m = m; rp->rs.n_src = (int)frame_len;
+    VBX_HIP(ctx, ctx->tables.resample(frame_len, ratio, m, &rp->rs.li, &rp->rs.frac));
+    rp->direct = frame_len <= VBX_MAX_FRAME_LEN && burg_resampled_supported((int)frame_len, (int)m, (int)order);
+    *have = true;
+    return VBX_SUCCESS;
+}
+
+// The frame loop of examples/formant_extraction/src/main.rs:72-88: find_formants at a resample_ratio, the frame's RMS as the
+// record's last column.  Everything is checked before anything is launched; an h_ext that asks for nothing is the plain /
+// tracked call itself.
+static int analyze_ex(vbx_ctx *ctx, const char *fn, const double *x, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
+                      const vbx_analysis_params *h_p, const vbx_analysis_ext *h_ext, const vbx_pitch_track_params *h_track,
+                      const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld, int32_t *status3,
+                      const vbx_pitch_track_outputs *h_out) {
+    if (!ctx) return fail(nullptr, VBX_E_INVALID, std::string(fn) + ": null context");
+    if (!h_p) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": null argument");
+    resample_plan_t rp{}; ex_req_t ex{nullptr, h_p->sample_rate, false};
+    const ex_req_t *exp = nullptr;
+    if (h_ext) {
+        const double ratio = h_ext->formant_resample_ratio, rate = h_ext->formant_sample_rate;
+        if (!(rate >= 0.0) || !std::isfinite(rate)) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": formant_sample_rate must be finite and >= 0");
+        bool have = false;
+        if (n_frames != 0 && frame_len >= 1 && frame_len <= VBX_MAX_LONG_FRAME_LEN) {      // (any other frame_len is rejected below)
+            int rc = make_resample_plan(ctx, fn, ratio, frame_len, h_p->formant_order, &rp, &have);
+            if (rc != VBX_SUCCESS) return rc;
+        } else if (!(ratio >= 0.0) || !std::isfinite(ratio) || ratio > 64.0) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": resample_ratio must be in [0, 64]");
+        ex.rp = have ? &rp : nullptr;
+        ex.formant_rate = rate != 0.0 ? rate : (have ? h_p->sample_rate * ratio : h_p->sample_rate);
+        ex.rms = h_ext->rms != 0;
+        if (have || ex.rms || rate != 0.0) exp = &ex;
+    }
+    if (!h_track) return analyze_frames_impl(ctx, fn, x, pcm, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records, record_ld,
+                                             status3, nullptr, exp);
+    track_req_t tk{};
+    tk.kmax = h_track->kmax; tk.path = h_track->path;
+    if (h_out) tk.out = *h_out;
+    if (tk.path.time_step == 0.0) tk.path.time_step = (double)stride / h_p->sample_rate;      // the batch's own hop
+    int rc = check_pitch_path(ctx, fn, tk.path, n_frames, tk.kmax, true, h_seg_start, n_segments);
+    if (rc != VBX_SUCCESS) return rc;
+    return analyze_frames_impl(ctx, fn, x, pcm, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records, record_ld, status3, &tk, exp);
+}
+
+int vbx_analyze_frames_ex_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
+                              const vbx_analysis_params *h_p, const vbx_analysis_ext *h_ext, const vbx_pitch_track_params *h_track,
+                              const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld,
+                              int32_t *status3, const vbx_pitch_track_outputs *h_outputs) {
+    return analyze_ex(ctx, __func__, x, nullptr, n_frames, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, out_records,
+                      record_ld, status3, h_outputs);
+}
+
+int vbx_analyze_frames_ex_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
+                                const vbx_analysis_params *h_p, const vbx_analysis_ext *h_ext, const vbx_pitch_track_params *h_track,
+                                const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld,
+                                int32_t *status3, const vbx_pitch_track_outputs *h_outputs) {
+    if (n_frames != 0 && ctx && !pcm) return fail(ctx, VBX_E_INVALID, "vbx_analyze_frames_ex_pcm16: null frame pointer");
+    return analyze_ex(ctx, __func__, nullptr, pcm, n_frames, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, out_records,
+                      record_ld, status3, h_outputs);
+}
+
+int vbx_find_formants_resampled_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
+                                    double sample_rate, double resample_ratio, size_t n_coeffs,
+                                    const int64_t *h_seg_start, size_t n_segments, const vbx_resonance *h_est_init, size_t n_est,
+                                    vbx_resonance *out_formants, vbx_resonance *out_res, int32_t *out_res_count,
+                                    double *out_coeffs, int32_t *status) {
+    int rc = check_frames(ctx, __func__, x, n_frames, frame_len, stride, VBX_MAX_LONG_FRAME_LEN);
+    if (rc != VBX_SUCCESS) return rc < 0 ? rc : VBX_SUCCESS;
+    VBX_REQUIRE(ctx, n_coeffs >= 1, "frame_len must be >= 2, order in [1, 62]");
+    resample_plan_t rp{}; bool have = false;
+    rc = make_resample_plan(ctx, __func__, resample_ratio, frame_len, n_coeffs, &rp, &have);
+    if (rc != VBX_SUCCESS) return rc;
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    return run_find_formants(ctx, ctx->stream, x, n_frames, frame_len, stride, sample_rate, n_coeffs, h_seg_start, n_segments,
+                             h_est_init, n_est, out_formants, 2 * n_est, out_res, out_res_count, out_coeffs, status, nullptr,
+                             have ? &rp : nullptr);
 }
 
 // ---- Sample = f32, the WIDE forms --------------------------------------------

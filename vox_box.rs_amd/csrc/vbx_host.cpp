@@ -347,6 +347,11 @@ size_t vbx_record_doubles(const vbx_analysis_params *h_p) {
     return n;
 }
 
+size_t vbx_record_doubles_ex(const vbx_analysis_params *h_p, const vbx_analysis_ext *h_ext) {
+    if (!h_p) return 0;
+    return vbx_record_doubles(h_p) + ((h_ext && h_ext->rms) ? 1 : 0);     // RMS: the LAST column
+}
+
 int vbx_gather_plan(const int64_t *h_rows, int world, int rank, int dst, size_t row_doubles,
                     int64_t *h_offset, int64_t *h_count, int32_t *h_op) {
     if (!h_rows || world < 1 || rank < 0 || rank >= world || dst < 0 || dst >= world || row_doubles < 1)

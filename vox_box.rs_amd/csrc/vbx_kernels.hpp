@@ -80,6 +80,19 @@ void launch_burg_recursion(hipStream_t s, long F, int p, frame_map_t map, long i
 
 void launch_count_accumulate(hipStream_t s, const int32_t *count, int32_t *total, bool reset);   // total = (reset ? 0 : total) + count
 
+// k_burg_resampled.hip: launch_burg / launch_burg_list / launch_burg_lags on the RESAMPLED view of the frames (find_formants with a
+// resample_ratio): x (or pcm, if non-null) holds the caller's frames of rs.n_src samples; m: the resampled length; window: the
+// periodic Hanning window of length m; rs: the (li, frac) table of vbx_resample_linear_f64.  Bit for bit the dense launchers on
+// the [F, m] batch that entry point writes.  launch_burg_recursion runs behind launch_burg_lags_resampled unchanged.
+struct resample_src_t { const int32_t *li; const double *frac; int n_src; };
+bool burg_resampled_supported(int n_src, int m, int p);
+void launch_burg_resampled(hipStream_t s, const double *x, const int16_t *pcm, long F, int m, long stride, const double *window,
+                           resample_src_t rs, int p, double *out, int32_t *status, frame_map_t map);
+void launch_burg_resampled_list(hipStream_t s, const double *x, const int16_t *pcm, long F, int m, long stride, const double *window,
+                                resample_src_t rs, int p, double *out, int32_t *status, const int32_t *list, const int32_t *count);
+void launch_burg_lags_resampled(hipStream_t s, const double *x, const int16_t *pcm, long F, int m, long stride, const double *window,
+                                resample_src_t rs, int p, frame_map_t map, long i0, long n_items, void *ws);
+
 // k_roots.hip
 void launch_find_roots(hipStream_t s, cplx_t *polys, long F, int len, int32_t *status);
 void launch_laguerre(hipStream_t s, const cplx_t *polys, long F, int len, cplx_t start, cplx_t *out);
@@ -309,6 +322,11 @@ void launch_pcm16(hipStream_t s, const int16_t *pcm, size_t n, double denom, dou
 void launch_frame_peak_pcm16(hipStream_t s, const int16_t *pcm, long F, long n, long stride, double *out);
 void launch_rms(hipStream_t s, const double *x, long F, int n, long stride, const double *window, double *out);
 void launch_preemphasis(hipStream_t s, const double *x, long F, int n, long stride, double c, double *out);
+
+// k_front_ex.hip: RMS::rms of the rectangular frame (launch_rms with a null window, bit for bit) from the f64 view or from 16-bit
+// PCM, written at out_rms + f * rms_ld; out_peak non-null: launch_frame_peak / launch_frame_peak_pcm16 from the same read
+void launch_frame_rms(hipStream_t s, const double *x, const int16_t *pcm, long F, int n, long stride, double *out_rms, long rms_ld,
+                      double *out_peak);
 
 // k_long.hip: frames of more than VBX_MAX_FRAME_LEN_K samples (tiles out of HBM / L2 instead of registers / LDS)
 size_t burg_long_scratch_bytes(long frames, long n);

@@ -298,14 +298,11 @@ inline void find_formants(Context &c, const Frames &f, double sample_rate, size_
                           Resonance *resonances = nullptr, int32_t *res_count = nullptr, double *lpc_coeffs = nullptr,
                           int32_t *status = nullptr, double resample_ratio = 1.0) {
     if (f.window != nullptr) throw Error(VBX_E_INVALID, "find_formants applies its own periodic Hanning (lib.rs:65-70): pass rectangular frames");
-    if (resample_ratio != 1.0) {   // lib.rs:57-61 (sample-crate arithmetic: parity unpinned), then the same chain on the dense batch
-        const size_t m = vbx_resampled_len(f.frame_len, resample_ratio);
-        DeviceVec<double> dense(c, f.n_frames * m);
-        c.check(vbx_resample_linear_f64(c.get(), f.x, f.n_frames, f.frame_len, f.stride, resample_ratio, dense.data()));
-        c.check(vbx_find_formants_f64(c.get(), dense.data(), f.n_frames, m, m, sample_rate, n_coeffs, seg.h_seg_start,
-                                      seg.n, starting_estimates.data(), starting_estimates.size(), formants, resonances,
-                                      res_count, lpc_coeffs, status));
-        c.sync();
+    if (resample_ratio != 1.0) {   // lib.rs:57-61 (sample-crate arithmetic: parity unpinned): resampled inside Burg's kernels, the
+                                   // bits of vbx_resample_linear_f64 into a dense batch + the same chain on it, without the batch
+        c.check(vbx_find_formants_resampled_f64(c.get(), f.x, f.n_frames, f.frame_len, f.stride, sample_rate, resample_ratio, n_coeffs,
+                                                seg.h_seg_start, seg.n, starting_estimates.data(), starting_estimates.size(), formants,
+                                                resonances, res_count, lpc_coeffs, status));
         return;
     }
     c.check(vbx_find_formants_f64(c.get(), f.x, f.n_frames, f.frame_len, f.stride, sample_rate, n_coeffs, seg.h_seg_start,
@@ -358,6 +355,31 @@ inline void analyze_frames_tracked_pcm16(Context &c, const int16_t *pcm, size_t 
                                          size_t record_ld, int32_t *status3 = nullptr, const PitchTrackOutputs *outputs = nullptr) {
     c.check(vbx_analyze_frames_tracked_pcm16(c.get(), pcm, n_frames, frame_len, stride, &p, &track, seg.h_seg_start, seg.n, records,
                                              record_ld, status3, outputs));
+}
+// The frame loop of examples/formant_extraction/src/main.rs:72-88: find_formants at ext.formant_resample_ratio (given
+// ext.formant_sample_rate; 0: sample_rate * ratio) and, with ext.rms, the frame's RMS as the LAST column of the record
+// (record_doubles(params, ext) doubles).  track null: columns 0-1 = candidates[0] (analyze_frames); non-null: the pitch path
+// (analyze_frames_tracked).  An ext that asks for nothing is that call itself, bit for bit.
+using AnalysisExt = vbx_analysis_ext;
+inline AnalysisExt analysis_ext(double formant_resample_ratio = 0.0, bool rms = false, double formant_sample_rate = 0.0) {
+    AnalysisExt e{};
+    e.formant_resample_ratio = formant_resample_ratio; e.formant_sample_rate = formant_sample_rate; e.rms = rms ? 1 : 0;
+    return e;
+}
+inline size_t record_doubles(const AnalysisParams &p, const AnalysisExt &ext) { return vbx_record_doubles_ex(&p, &ext); }
+inline void analyze_frames_ex(Context &c, const Frames &f, const AnalysisParams &p, const AnalysisExt &ext, const PitchTrackParams *track,
+                              Segments seg, double *records, size_t record_ld, int32_t *status3 = nullptr,
+                              const PitchTrackOutputs *outputs = nullptr) {
+    if (f.window != nullptr) throw Error(VBX_E_INVALID, "analyze_frames_ex applies the windows itself: pass rectangular frames");
+    c.check(vbx_analyze_frames_ex_f64(c.get(), f.x, f.n_frames, f.frame_len, f.stride, &p, &ext, track, seg.h_seg_start, seg.n, records,
+                                      record_ld, status3, outputs));
+}
+inline void analyze_frames_ex_pcm16(Context &c, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
+                                    const AnalysisParams &p, const AnalysisExt &ext, const PitchTrackParams *track, Segments seg,
+                                    double *records, size_t record_ld, int32_t *status3 = nullptr,
+                                    const PitchTrackOutputs *outputs = nullptr) {
+    c.check(vbx_analyze_frames_ex_pcm16(c.get(), pcm, n_frames, frame_len, stride, &p, &ext, track, seg.h_seg_start, seg.n, records,
+                                        record_ld, status3, outputs));
 }
 
 // Frame-range sharding of one recording over the GPUs of a node (no counterpart in the reference) and the gather of the

@@ -126,6 +126,17 @@ class PitchTrackOutputs(C.Structure):
     _fields_ = [("cand", C.c_void_p), ("count", C.c_void_p), ("peak", C.c_void_p), ("index", C.c_void_p)]
 
 
+class AnalysisExt(C.Structure):
+    """vbx_analysis_ext: what examples/formant_extraction/src/main.rs adds to the frame loop (vbx_analyze_frames_ex_*) --
+    find_formants' resample_ratio (0 or 1.0: none), the sample_rate find_formants is given (0: sample_rate * ratio) and the
+    frame's RMS as the record's last column."""
+    _fields_ = [("formant_resample_ratio", C.c_double), ("formant_sample_rate", C.c_double), ("rms", C.c_int32)]
+
+    @classmethod
+    def make(cls, formant_resample_ratio=0.0, formant_sample_rate=0.0, rms=False):
+        return cls(formant_resample_ratio, formant_sample_rate, 1 if rms else 0)
+
+
 _lib = None
 
 
@@ -243,6 +254,12 @@ def load_library():
                                                      vp, sz, vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
         "vbx_analyze_frames_tracked_pcm16": (C.c_int, [vp, vp, sz, sz, sz, C.POINTER(AnalysisParams), C.POINTER(PitchTrackParams),
                                                        vp, sz, vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
+        "vbx_record_doubles_ex": (sz, [C.POINTER(AnalysisParams), C.POINTER(AnalysisExt)]),
+        "vbx_analyze_frames_ex_f64": (C.c_int, [vp, vp, sz, sz, sz, C.POINTER(AnalysisParams), C.POINTER(AnalysisExt),
+                                                C.POINTER(PitchTrackParams), vp, sz, vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
+        "vbx_analyze_frames_ex_pcm16": (C.c_int, [vp, vp, sz, sz, sz, C.POINTER(AnalysisParams), C.POINTER(AnalysisExt),
+                                                  C.POINTER(PitchTrackParams), vp, sz, vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
+        "vbx_find_formants_resampled_f64": (C.c_int, [vp, vp, sz, sz, sz, dbl, dbl, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp]),
         "vbx_shard_range": (C.c_int, [sz, i32, i32, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
         "vbx_shard_samples": (C.c_int, [sz, sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
         "vbx_shard_plan": (C.c_int, [sz, i32, i32, vp, sz, C.POINTER(ShardPlan)]),
@@ -943,8 +960,9 @@ class VoxBox:
         return out
 
     def find_formants(self, x, sample_rate, n_coeffs, est_init, seg_start=None, frame_len=None, stride=None,
-                      n_frames=None, out=None, want=("formants", "res", "count", "coeffs", "status")):
-        """vox_box::find_formants over a batch (resample_ratio = 1.0).  est_init: [n_est, 2]."""
+                      n_frames=None, out=None, want=("formants", "res", "count", "coeffs", "status"), resample_ratio=1.0):
+        """vox_box::find_formants over a batch.  est_init: [n_est, 2].  resample_ratio other than 1.0: the frames are resampled
+        inside Burg's kernels (vbx_find_formants_resampled_f64); sample_rate is what find_formants is given either way."""
         ptr, F, N, S, tmp = self._frames(x, frame_len, stride, n_frames)
         e = np.ascontiguousarray(est_init, dtype=np.float64)
         n_est = e.shape[0]
@@ -959,11 +977,13 @@ class VoxBox:
             }
         else:
             bufs = out
-        self._check(self.L.vbx_find_formants_f64(
-            self.ctx, ptr, F, N, S, sample_rate, n_coeffs,
-            None if seg is None else seg.ctypes.data, 0 if seg is None else seg.size,
-            e.ctypes.data, n_est, _ptr(bufs["formants"]), _ptr(bufs.get("res")), _ptr(bufs.get("count")),
-            _ptr(bufs.get("coeffs")), _ptr(bufs.get("status"))))
+        tail = (None if seg is None else seg.ctypes.data, 0 if seg is None else seg.size,
+                e.ctypes.data, n_est, _ptr(bufs["formants"]), _ptr(bufs.get("res")), _ptr(bufs.get("count")),
+                _ptr(bufs.get("coeffs")), _ptr(bufs.get("status")))
+        if resample_ratio == 1.0:
+            self._check(self.L.vbx_find_formants_f64(self.ctx, ptr, F, N, S, sample_rate, n_coeffs, *tail))
+        else:
+            self._check(self.L.vbx_find_formants_resampled_f64(self.ctx, ptr, F, N, S, sample_rate, resample_ratio, n_coeffs, *tail))
         if out is not None:
             return None
         res = {k: (v.numpy() if v is not None else None) for k, v in bufs.items()}
@@ -1112,8 +1132,16 @@ class VoxBox:
                 d.free()
         return res
 
-    def _analyze_tracked(self, fn, ptr, F, N, S, params, track, seg_start, out, record_ld, status, lists, outputs, tmp):
-        rec = int(self.L.vbx_record_doubles(C.byref(params)))
+    def _analyze_tracked(self, fn, ptr, F, N, S, params, track, seg_start, out, record_ld, status, lists, outputs, tmp, ext=False):
+        # ext: False = the tracked entry points; an AnalysisExt or None = the _ex ones (one more argument, one more column)
+        head = [self.ctx, ptr, F, N, S, C.byref(params)]
+        if ext is False:
+            rec = int(self.L.vbx_record_doubles(C.byref(params)))
+        else:
+            head.append(None if ext is None else C.byref(ext))
+            rec = int(self.L.vbx_record_doubles_ex(C.byref(params), head[-1]))
+        if lists and track is None:
+            raise ValueError("lists=True returns the pitch path's lists: it needs track=")
         ld = record_ld if record_ld is not None else rec + (rec & 1)
         seg = None if seg_start is None else np.ascontiguousarray(seg_start, dtype=np.int64)
         o = out if out is not None else self.empty((F, ld))
@@ -1130,7 +1158,7 @@ class VoxBox:
         if outputs is not None:
             po = outputs if isinstance(outputs, PitchTrackOutputs) else PitchTrackOutputs(*[_ptr(a) for a in outputs])
         try:
-            self._check(fn(self.ctx, ptr, F, N, S, C.byref(params), None if track is None else C.byref(track),
+            self._check(fn(*head, None if track is None else C.byref(track),
                            None if seg is None else seg.ctypes.data, 0 if seg is None else seg.size,
                            _ptr(o), ld, _ptr(st), None if po is None else C.byref(po)))
             if out is not None:
@@ -1169,6 +1197,30 @@ class VoxBox:
             ptr = _ptr(pcm)
         return self._analyze_tracked(self.L.vbx_analyze_frames_tracked_pcm16, ptr, int(n_frames), int(frame_len), int(stride), params,
                                      track, seg_start, out, record_ld, status, lists, outputs, tmp)
+
+    def analyze_frames_ex(self, x, params, ext=None, track=None, seg_start=None, frame_len=None, stride=None, n_frames=None,
+                          out=None, record_ld=None, status=None, lists=False, outputs=None):
+        """vbx_analyze_frames_ex_f64: the frame loop of examples/formant_extraction -- analyze_frames (track None) or
+        analyze_frames_tracked (track: PitchTrackParams) with find_formants at ext.formant_resample_ratio and, with ext.rms, the
+        frame's RMS as the record's last column (ext: AnalysisExt; None: the plain / tracked call itself)."""
+        ptr, F, N, S, tmp = self._frames(x, frame_len, stride, n_frames)
+        return self._analyze_tracked(self.L.vbx_analyze_frames_ex_f64, ptr, F, N, S, params, track, seg_start, out, record_ld,
+                                     status, lists, outputs, tmp, ext=ext)
+
+    def analyze_frames_ex_pcm16(self, pcm, params, ext=None, track=None, seg_start=None, frame_len=None, stride=None,
+                                n_frames=None, out=None, record_ld=None, status=None, lists=False, outputs=None):
+        """vbx_analyze_frames_ex_pcm16: the same on 16-bit PCM samples (host int16 array or device buffer)."""
+        tmp = None
+        if isinstance(pcm, np.ndarray):
+            assert pcm.ndim == 1 and frame_len and stride
+            n_frames = frame_count(pcm.size, frame_len, stride) if n_frames is None else n_frames
+            tmp = self.to_device(pcm, np.int16)
+            ptr = tmp.ptr
+        else:
+            assert frame_len and stride and n_frames is not None
+            ptr = _ptr(pcm)
+        return self._analyze_tracked(self.L.vbx_analyze_frames_ex_pcm16, ptr, int(n_frames), int(frame_len), int(stride), params,
+                                     track, seg_start, out, record_ld, status, lists, outputs, tmp, ext=ext)
 
     # -- spectrum.rs: MFCC ------------------------------------------------------------
     def mfcc(self, x, num_coeffs, freq_bounds, sample_rate, frame_len=None, stride=None, n_frames=None,
