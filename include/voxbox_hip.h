@@ -25,7 +25,17 @@
  *    frames in, float results out; vbx_*_c32: Complex<f32> Polynomial) widens on load, computes in f64 and rounds
  *    each result to f32 once -- except the Complex<f32> root finder, which follows the reference's f32 arithmetic
  *    step by step because its iteration counts and root ORDER depend on it.
- *  - calls are asynchronous on the context's HIP stream; vbx_sync() waits.
+ *  - calls are asynchronous on the context's HIP stream; vbx_sync() waits.  Stream order is the whole contract: a call reads
+ *    its device inputs and writes its device outputs in the order of the context's stream, so a producer queued on that stream
+ *    before the call and a consumer queued on it after the call need no host wait (the streams and events the library uses
+ *    inside are joined into the context's stream before the call returns; tests/test_gpu_stream_order.py).  HOST arrays
+ *    (h_ parameters) are read before the call returns.  The host is blocked only by: the first call of a shape (its tables are
+ *    built and its workspaces grown, which drains the context's streams); a call whose h_seg_start, h_est_init or pitch path
+ *    chunk table differs from the previous call's WHILE that previous call's upload of it is still queued (it waits until the
+ *    upload has left the pinned staging buffer, i.e. for the work queued ahead of it -- a first change behind idle uploads and
+ *    identical content do not wait; tests/test_gpu_stream_order.py test_host_blocks_only_as_documented); and the calls that
+ *    return a value to the host: vbx_sync, vbx_memcpy_h2d / _d2h, vbx_free, vbx_timer_end, vbx_profile_enable / _reset / _get /
+ *    _stream / _names / _pitch_work, vbx_internal_last_*_count, vbx_internal_last_path_chunks_redone.
  *  - a context (stream, cached tables, scratch) is not internally synchronised: one host thread per context at
  *    a time.  Contexts are independent of each other and cheap; use one per thread / stream.
  *  - return value: 0 ok, <0 API misuse / runtime failure (vbx_last_error()).
@@ -94,8 +104,14 @@ extern const double VBX_FEMALE_FORMANT_ESTIMATES[4];
 /* ------------------------------------------------------------------ context */
 
 int vbx_abi_version(void);
-/* device: HIP device ordinal.  hip_stream: a hipStream_t to launch on (e.g. torch's
- * current stream), or NULL to let the context create and own one. */
+/* device: HIP device ordinal.  hip_stream: a hipStream_t to launch on (e.g. a torch.cuda.Stream's handle), or NULL to let
+ * the context create and own one.  NULL ALWAYS means "own stream" (non-blocking: not ordered with the null stream either) --
+ * it never means the runtime's default stream.  Any non-NULL handle is used as given, the runtime's special handles
+ * (hipStreamLegacy, hipStreamPerThread; hip_runtime_api.h) included -- but those are the runtime's business: on ROCm 7.2 a
+ * process whose context ran on hipStreamLegacy died with a segmentation fault, so pass a stream the caller created.  PyTorch
+ * reports its default stream's handle as 0, so `torch.cuda.current_stream().cuda_stream` must not be passed on blindly:
+ * VoxBox.from_torch (vox_box.rs_amd/voxbox.py) refuses it with an error that asks for a torch.cuda.Stream to be made current
+ * (INTEGRATION.md section 3). */
 int vbx_ctx_create(vbx_ctx **out, int device, void *hip_stream);
 void vbx_ctx_destroy(vbx_ctx *ctx);
 int vbx_sync(vbx_ctx *ctx);

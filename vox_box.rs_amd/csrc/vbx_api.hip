@@ -190,8 +190,10 @@ int check_frames(vbx_ctx *ctx, const char *fn, const void *x, size_t n_frames, s
 }
 
 // Small host array -> ctx-owned device buffer through pinned staging.  The caller's array may be freed on return
-// (the copy below reads the staging buffer, not the caller's memory), the host is not blocked behind queued work,
-// and identical content (the usual case: the same segments / estimates every call) is not uploaded again.
+// (the copy below reads the staging buffer, not the caller's memory), and identical content (the usual case: the same
+// segments / estimates every call) is not uploaded again and never waits.  Changed content reuses the one staging buffer:
+// the host waits until the PREVIOUS upload of that array has left it -- at once if that upload has long run, behind the
+// queued work if it is still queued (two changes in one queue; include/voxbox_hip.h lists it among the calls that block).
 int stage_upload(vbx_ctx *ctx, int which, int ws_slot, const void *h_src, size_t bytes, hipStream_t st, void **d_out) {
     void *d = nullptr;
     const bool grown = ctx->ws_bytes[ws_slot] < bytes;
@@ -337,6 +339,10 @@ void vbx_ctx_destroy(vbx_ctx *ctx) {
 int vbx_sync(vbx_ctx *ctx) {
     if (!ctx) return fail(nullptr, VBX_E_INVALID, "vbx_sync: null context");
     VBX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // every call joins its inner streams into ctx->stream before it returns, so they are idle by now; draining them as well
+    // costs nothing and makes "after vbx_sync nothing of this context runs" hold by construction (buffers may be freed)
+    if (ctx->side) VBX_HIP(ctx, hipStreamSynchronize(ctx->side));
+    if (ctx->trk) VBX_HIP(ctx, hipStreamSynchronize(ctx->trk));
     return VBX_SUCCESS;
 }
 

@@ -492,9 +492,27 @@ class VoxBox:
             msg = self.L.vbx_last_error(None)
             raise VoxBoxError(f"vbx_ctx_create failed ({rc}): {msg.decode() if msg else ''}")
         self.ctx = ctx
+        self.stream_handle = int(stream or 0)   # what vbx_ctx_create was given (0: the context created and owns its stream)
         self._tables = {}
         if lpc_policy is not None:
             self.lpc_policy = lpc_policy
+
+    @classmethod
+    def from_torch(cls, device=None, lpc_policy=None):
+        """A context ordered with PyTorch's CURRENT stream on `device` (None: torch's current device): producers and consumers
+        torch queues on that stream around a call need no host wait.  A torch.cuda.Stream must be current: torch reports its
+        default stream's handle as 0, which vbx_ctx_create reads as NULL = "create and own a stream" -- a context that is not
+        ordered with torch's work at all -- so with the default stream current this raises VoxBoxError instead of handing out an
+        unordered context.  (The runtime's legacy-default-stream handle, hipStreamLegacy, is not a way out: a process that
+        passed it as the context's stream died with a segmentation fault on ROCm 7.2.)"""
+        import torch
+        s = torch.cuda.current_stream(device)
+        handle = int(s.cuda_stream)
+        if handle == 0:
+            raise VoxBoxError("VoxBox.from_torch: torch's default stream is current; its handle is 0, which the library reads as "
+                              "\"create and own a stream\" (not ordered with torch's work).  Make a torch.cuda.Stream current "
+                              "(`with torch.cuda.stream(torch.cuda.Stream()):`) and call VoxBox.from_torch() inside it")
+        return cls(s.device.index, handle, lpc_policy)
 
     @property
     def lpc_policy(self):
