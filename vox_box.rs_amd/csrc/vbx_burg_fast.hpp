@@ -27,8 +27,10 @@
 // wavefront's batch would run it.  The scratch (312 B per frame at order 12) is why the batch is cut into chunks of BF_CHUNK frames.
 //
 // Accuracy.  num and den are differences of terms of size c[0] |A|^2: the lag sums' own rounding (~eps c[0]) reaches mu
-// amplified by kappa = c[0] |A|_1^2 / den.  On speech kappa eps is ~1e-12 (coefficients within ~1e-11 of the row's largest);
-// the direct recursion of k_burg.hip is exact to ~eps.  The kernel therefore evaluates the bound itself: a frame whose
+// amplified by kappa = c[0] |A|_1^2 / den.  On speech kappa eps is ~1e-12 (coefficients within ~1e-11 of the row's largest;
+// measured against long double, tests/test_gpu_accuracy.py: 1e-13 .. 1.2e-12); the direct recursion of k_burg.hip is exact to ~eps
+// where it sums every denominator (measured 2e-16 .. 5e-16) and within 2.4e-13 at one frame per wavefront, where it carries the
+// denominator from order to order.  The kernel therefore evaluates the bound itself: a frame whose
 // coefficients could be off by more than BF_TARGET in the parity metric of tests/ (|d| <= 1e-6 max(|a_j|, 1e-6 max|a|)) --
 // a badly conditioned frame, or one with a coefficient that happens to be tiny -- or whose denominator is not positive
 // (the reference's Err(LPC), NaN input) is NOT written: its index goes to a list, and the direct kernel runs on the list
