@@ -1350,6 +1350,62 @@ impl<'g> PcmBatch<'g> {
     }
 }
 
+/// float32 samples on the device with a `Windower` view over them: what `hound`'s float WAVs, `torchaudio` / `soundfile` tensors
+/// and model outputs are.  Half the bytes of the f64 view, and the fused frame loop reads them without an f64 copy.
+pub struct F32Batch<'g> {
+    gpu: &'g Gpu,
+    samples: DeviceBuf<'g, f32>,
+    n_frames: usize,
+    frame_len: usize,
+    stride: usize,
+}
+
+impl<'g> F32Batch<'g> {
+    /// `Windower::rectangle(samples, bin, hop)` semantics (frame t = samples[t*hop .. t*hop+bin] while bin <= remaining).
+    pub fn windower(gpu: &'g Gpu, samples: &[f32], bin: usize, hop: usize) -> GpuResult<F32Batch<'g>> {
+        let n_frames = unsafe { ffi::vbx_frame_count(samples.len(), bin, hop) };
+        Ok(F32Batch { gpu, samples: gpu.upload(samples)?, n_frames, frame_len: bin, stride: hop })
+    }
+
+    pub fn n_frames(&self) -> usize {
+        self.n_frames
+    }
+
+    /// `samples as f64` for every sample, on the device (`vbx_f32_to_f64`; exact): the f64 batch of the same view.
+    pub fn widen(&self) -> GpuResult<FrameBatch<'g>> {
+        let out = self.gpu.alloc::<f64>(self.samples.len())?;
+        self.gpu.check(unsafe { ffi::vbx_f32_to_f64(self.gpu.raw, self.samples.as_ptr(), self.samples.len(), out.as_mut_ptr()) })?;
+        Ok(FrameBatch::new(self.gpu, out, None, self.n_frames, self.frame_len, self.stride))
+    }
+
+    /// [`FrameBatch::analyze_ex`] reading the floats directly (`vbx_analyze_frames_ex_f32in`): bit-identical to
+    /// `self.widen()?.analyze_ex(..)`.  `ext` `None` and `track` `None`: the plain loop; `track` `Some`: the tracked loop.
+    pub fn analyze_ex_f32in(&self, params: &AnalysisParams, ext: Option<&AnalysisExt>, track: Option<(usize, &PitchPathParams)>,
+                            seg_start: &[i64]) -> GpuResult<(Records<'g>, Option<DeviceBuf<'g, i32>>)> {
+        let gpu = self.gpu;
+        let p = params.to_ffi();
+        let e = ext.map(|x| x.to_ffi());
+        let e_ptr = e.as_ref().map_or(ptr::null(), |x| x as *const _);
+        let rec = unsafe { ffi::vbx_record_doubles_ex(&p, e_ptr) };
+        let ld = rec + (rec & 1);
+        let data = gpu.alloc::<f64>(self.n_frames * ld)?;
+        let status3 = gpu.alloc::<i32>(3 * self.n_frames)?;
+        let (seg_ptr, n_seg) = if seg_start.is_empty() { (ptr::null(), 0) } else { (seg_start.as_ptr(), seg_start.len()) };
+        let tk = track.map(|(kmax, path)| ffi::VbxPitchTrackParams { kmax, path: path.raw() });
+        let index = if tk.is_some() { Some(gpu.alloc::<i32>(self.n_frames)?) } else { None };
+        let outputs = ffi::VbxPitchTrackOutputs {
+            cand: ptr::null_mut(), count: ptr::null_mut(), peak: ptr::null_mut(),
+            index: index.as_ref().map_or(ptr::null_mut(), |b| b.as_mut_ptr()),
+        };
+        gpu.check(unsafe {
+            ffi::vbx_analyze_frames_ex_f32in(gpu.raw, self.samples.as_ptr(), self.n_frames, self.frame_len, self.stride, &p, e_ptr,
+                                             tk.as_ref().map_or(ptr::null(), |t| t as *const _), seg_ptr, n_seg, data.as_mut_ptr(), ld,
+                                             status3.as_mut_ptr(), &outputs)
+        })?;
+        Ok((Records { data, status3, n_frames: self.n_frames, record_ld: ld }, index))
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // multi-GPU: frame-range sharding and the record gather (one process per GPU, RCCL inside the library)
 // ---------------------------------------------------------------------------------------------------------------

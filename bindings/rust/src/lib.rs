@@ -29,5 +29,5 @@ pub mod ffi;
 pub mod gpu;
 
 pub use gpu::{find_formants, gather_plan, path_end_states, path_segment_peaks, shard_range, shard_samples, AnalysisExt, AnalysisParams, Comm, DeviceBuf,
-              FormantExtractor, FrameBatch, FrameStatus, Frames, Gpu, GpuError, GpuEstimates, GpuFrame, LpcPolicy, PathShard, PcmBatch,
+              F32Batch, FormantExtractor, FrameBatch, FrameStatus, Frames, Gpu, GpuError, GpuEstimates, GpuFrame, LpcPolicy, PathShard, PcmBatch,
               PitchPathParams, PolyBatch, Records, ResonanceRows, RootRow, RootRows, PITCH_PATH_STATES};

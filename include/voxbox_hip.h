@@ -432,6 +432,12 @@ int vbx_dct_f64(vbx_ctx *ctx, const double *in, size_t n_rows, size_t n, double 
  * (stride = hop) view of `out`: window::Windower::{rectangle,hanning} without copying frames. */
 int vbx_pcm16_to_f64(vbx_ctx *ctx, const int16_t *pcm, size_t n_samples, double *out);
 
+/* float samples -> f64, exactly (every float is a double: subnormals, -0.0, infinities and NaNs arrive as the same values): the
+ * counterpart of vbx_pcm16_to_f64 for the float32 tensors that torchaudio / soundfile, float WAVs and model outputs hand over.
+ * x: n float samples on the device (4-byte aligned); out: n doubles.  The fused frame loop does not need it: see
+ * vbx_analyze_frames_ex_f32in. */
+int vbx_f32_to_f64(vbx_ctx *ctx, const float *x, size_t n_samples, double *out);
+
 /* RMS::rms per frame (src/waves.rs:10-23).  out: [F]. */
 int vbx_rms_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
                 const double *window, double *out);
@@ -648,6 +654,31 @@ int vbx_analyze_frames_ex_f64(vbx_ctx *ctx, const double *x, size_t n_frames, si
                               double *out_records, size_t record_ld, int32_t *status3,
                               const vbx_pitch_track_outputs *h_outputs);
 int vbx_analyze_frames_ex_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
+                                const vbx_analysis_params *h_params, const vbx_analysis_ext *h_ext,
+                                const vbx_pitch_track_params *h_track /* NULL: columns 0-1 = candidates[0] */,
+                                const int64_t *h_seg_start, size_t n_segments,
+                                double *out_records, size_t record_ld, int32_t *status3,
+                                const vbx_pitch_track_outputs *h_outputs);
+/* vbx_analyze_frames_ex_f64 on FLOAT32 samples: frame t is x[t*stride .. +frame_len).  The suffix is _f32in, not _f32: only the INPUT
+ * is float -- the records, the candidate lists, the peaks, the arithmetic and everything else written stay f64 (elsewhere in this
+ * header _f32 means float results too).  One call covers three forms: h_ext NULL and h_track NULL is the plain loop, h_track non-NULL
+ * the tracked loop.
+ * Every byte the call writes -- the records, status3, all four h_outputs arrays -- and everything it leaves behind (the state for
+ * vbx_track_stitch_f64, the vbx_internal_last_* counts, vbx_internal_last_path_chunks_redone) is what vbx_f32_to_f64 into a caller-owned
+ * buffer followed by vbx_analyze_frames_ex_f64 on that buffer gives, BIT FOR BIT, at every shape, parameter set and LPC policy that
+ * call accepts: widening is exact, so a NaN frame reports VBX_FRAME_ERR_NAN exactly as there.
+ * Which shapes read the floats directly (the rule of the PCM form): full 1200-sample frames through the fused spectral kernel with
+ * lpc_order 0 or 12 and MFCC fused -- under every LPC policy: the pitch fallback list, the double-double LPC list and the REFERENCE
+ * rows have float forms --, with the formant chain at any order, resampled (the shapes Burg's resampled loaders take) or not.  There
+ * the f64 copy never exists: 4 B per sample resident instead of 4 + 8, and no widening pass.  Every other shape takes ONE widening
+ * pass of the view into a context-owned f64 copy (8 B per sample of the view, kept for the next call), queued on the context's stream
+ * ahead of the fork, and runs the f64 path from there.  The RMS column and local_peak are always taken from the caller's floats, on
+ * the context's second stream (the peak as a float max widened once: the same bits).
+ * x needs 4-byte alignment only: wider loads are taken where a frame's own address allows them (8 bytes in the fused kernel: an odd
+ * stride alternates frame by frame), with the same bits either way.  It takes no stream or event of its own.
+ * VBX_E_INVALID, before anything is written: what vbx_analyze_frames_ex_f64 rejects, and a NULL x with n_frames > 0.  n_frames == 0
+ * succeeds.  Measured: DESIGN.md section 5d. */
+int vbx_analyze_frames_ex_f32in(vbx_ctx *ctx, const float *x, size_t n_frames, size_t frame_len, size_t stride,
                                 const vbx_analysis_params *h_params, const vbx_analysis_ext *h_ext,
                                 const vbx_pitch_track_params *h_track /* NULL: columns 0-1 = candidates[0] */,
                                 const int64_t *h_seg_start, size_t n_segments,

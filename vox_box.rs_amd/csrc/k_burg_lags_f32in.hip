@@ -1,0 +1,34 @@
+// k_burg_lags_f32in.hip -- dispatch of the one-pass Burg lag kernels on FLOAT32 samples by order (k_burg_fast.hip's and
+// k_burg_resampled.hip's, for float; the instantiations live in k_burg_lags_f32in_a.hip / _b.hip; launch_burg_recursion runs
+// behind either unchanged)
+#include "vbx_burg_resampled.hpp"
+
+namespace vbx {
+
+// false: no instantiation at this order, NOTHING was launched (the caller fails the call: burg_fast_supported's list of orders,
+// k_burg_fast.hip, and this one have drifted apart, and the recursion behind would read scratch that no kernel wrote)
+#define VBX_BF32_DISPATCH(CALL)                                   \
+    switch (p) {                                                  \
+        case 8: CALL(8); return true;                             \
+        case 10: CALL(10); return true;                           \
+        case 12: CALL(12); return true;                           \
+        case 13: CALL(13); return true;                           \
+        case 14: CALL(14); return true;                           \
+        case 16: CALL(16); return true;                           \
+        default: return false;                                    \
+    }
+
+bool launch_burg_lags_f32in(hipStream_t s, const float *x, long F, int n, long stride, const double *window, int p,
+                            frame_map_t map, long i0, long m, void *ws) {
+#define VBX_BF_CALL(PP) launch_burg_lags_p<PP, float>(s, x, F, n, stride, window, map, i0, m, (double *)ws)
+    VBX_BF32_DISPATCH(VBX_BF_CALL)
+#undef VBX_BF_CALL
+}
+bool launch_burg_lags_resampled_f32in(hipStream_t s, const float *x, long F, int m, long stride, const double *window,
+                                      resample_src_t rs, int p, frame_map_t map, long i0, long n_items, void *ws) {
+#define VBX_BF_CALL(PP) launch_burg_lags_resampled_p<PP, float>(s, x, F, m, stride, window, rs, map, i0, n_items, (double *)ws)
+    VBX_BF32_DISPATCH(VBX_BF_CALL)
+#undef VBX_BF_CALL
+}
+
+}  // namespace vbx

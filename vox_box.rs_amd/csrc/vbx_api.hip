@@ -627,7 +627,10 @@ static int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, c
         // 4 ms to come and go with nothing to do, beside 13.5 ms of the analysis itself.  One per CU where the state is large.
         const int cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
         const int grid = pitch_lds_bytes(L.n) > 24 * 1024 ? cus : cus * 4;
-        launch_pitch_list(st, L.unsure_list, L.unsure_count, grid, L.x, L.n, L.stride, L.window, L.lag_window,
+        if (L.f32in) launch_pitch_list_f32in(st, L.unsure_list, L.unsure_count, grid, reinterpret_cast<const float *>(L.x), L.n, L.stride, L.window,
+                                             L.lag_window, L.sample_rate, L.threshold, L.fmin, L.fmax, L.kmax, L.out_cand, L.cand_ld, L.out_count,
+                                             L.pitch_status, L.work);
+        else launch_pitch_list(st, L.unsure_list, L.unsure_count, grid, L.x, L.n, L.stride, L.window, L.lag_window,
                           L.sample_rate, L.threshold, L.fmin, L.fmax, L.kmax, L.out_cand, L.cand_ld, L.out_count,
                           L.pitch_status, L.work, L.pcm);
     }
@@ -640,14 +643,18 @@ static int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, c
         if (L.lpc_list != nullptr) {
             Prof p(ctx, "lpc_exact_list", st);
             const int cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
-            launch_lpc_exact_list(st, L.lpc_list, L.lpc_count, cus, L.x, L.n, L.stride, L.window, L.pcm, SPECTRAL_LPC_ORDER, L.out_lpc, L.lpc_ld);
+            if (L.f32in) launch_lpc_exact_list_f32in(st, L.lpc_list, L.lpc_count, cus, reinterpret_cast<const float *>(L.x), L.n, L.stride, L.window,
+                                                     SPECTRAL_LPC_ORDER, L.out_lpc, L.lpc_ld);
+            else launch_lpc_exact_list(st, L.lpc_list, L.lpc_count, cus, L.x, L.n, L.stride, L.window, L.pcm, SPECTRAL_LPC_ORDER, L.out_lpc, L.lpc_ld);
         }
         if (ctx->lpc_policy == VBX_LPC_POLICY_REFERENCE) {
             // the crate's rows (k_lpc_ref.hip) over the column, after the kernels above on the same stream: the fused kernel and the
             // Levinson pass run as under every policy (their instantiations, and so every other column, unchanged), only the LPC
             // row is replaced
             Prof p(ctx, "lpc_ref", st);
-            launch_lpc_ref(st, L.x, L.pcm != 0, L.F, L.n, L.stride, L.window, SPECTRAL_LPC_ORDER + 1, SPECTRAL_LPC_ORDER, 0, nullptr, 0,
+            if (L.f32in) launch_lpc_ref_f32in(st, reinterpret_cast<const float *>(L.x), L.F, L.n, L.stride, L.window, SPECTRAL_LPC_ORDER + 1,
+                                              SPECTRAL_LPC_ORDER, 0, nullptr, 0, L.out_lpc, L.lpc_ld);
+            else launch_lpc_ref(st, L.x, L.pcm != 0, L.F, L.n, L.stride, L.window, SPECTRAL_LPC_ORDER + 1, SPECTRAL_LPC_ORDER, 0, nullptr, 0,
                            L.out_lpc, L.lpc_ld);
         }
     }
@@ -850,7 +857,7 @@ constexpr size_t EX_DENSE_BYTES = size_t(256) << 20;          // the dense fallb
 
 static int run_burg(vbx_ctx *ctx, hipStream_t stm, const double *x, const int16_t *pcm, long F, int n, long stride,
                     const double *window, int p, double *coeffs, int32_t *st, frame_map_t map = frame_map_t{0, 0, 0},
-                    const resample_plan_t *rp = nullptr) {
+                    const resample_plan_t *rp = nullptr, const float *f32 = nullptr /* the frames as float32 samples instead of x / pcm */) {
     if (rp && !rp->direct) {
         // the dense fallback (f64 frames only: the callers widen PCM first; no time slices: run_find_formants)
         long per = (long)(EX_DENSE_BYTES / ((size_t)n * sizeof(double)));
@@ -883,17 +890,22 @@ static int run_burg(vbx_ctx *ctx, hipStream_t stm, const double *x, const int16_
             const long items = frame_map_items(map, F), chunk = burg_fast_chunk(F);
             for (long i0 = 0; i0 < items; i0 += chunk) {
                 const long m = (items - i0 < chunk) ? items - i0 : chunk;
-                { Prof pr(ctx, "burg_lags_resampled", stm); launch_burg_lags_resampled(stm, x, pcm, F, n, stride, window, rp->rs, p, map, i0, m, w); }
+                { Prof pr(ctx, "burg_lags_resampled", stm);
+                  if (f32) { if (!launch_burg_lags_resampled_f32in(stm, f32, F, n, stride, window, rp->rs, p, map, i0, m, w))
+                                 return fail(ctx, VBX_E_RUNTIME, "burg_lags_resampled: no float32 lag kernel at order " + std::to_string(p)); }
+                  else launch_burg_lags_resampled(stm, x, pcm, F, n, stride, window, rp->rs, p, map, i0, m, w); }
                 { Prof pr(ctx, "burg_recursion", stm); launch_burg_recursion(stm, F, p, map, i0, m, coeffs, st, w); }
             }
             { Prof pr(ctx, "burg_direct_list_resampled", stm);
-              launch_burg_resampled_list(stm, x, pcm, F, n, stride, window, rp->rs, p, coeffs, st, list + 2, list); }
+              if (f32) launch_burg_resampled_f32in_list(stm, f32, F, n, stride, window, rp->rs, p, coeffs, st, list + 2, list);
+              else launch_burg_resampled_list(stm, x, pcm, F, n, stride, window, rp->rs, p, coeffs, st, list + 2, list); }
             launch_count_accumulate(stm, list, list + 1, map.seg_len == 0 || map.t0 == 0);
             return VBX_SUCCESS;
         }
         Prof pr(ctx, "burg_resampled", stm);
         ctx->burg_list_count = nullptr;
-        launch_burg_resampled(stm, x, pcm, F, n, stride, window, rp->rs, p, coeffs, st, map);
+        if (f32) launch_burg_resampled_f32in(stm, f32, F, n, stride, window, rp->rs, p, coeffs, st, map);
+        else launch_burg_resampled(stm, x, pcm, F, n, stride, window, rp->rs, p, coeffs, st, map);
         return VBX_SUCCESS;
     }
     if (n > VBX_MAX_FRAME_LEN) {
@@ -922,12 +934,15 @@ static int run_burg(vbx_ctx *ctx, hipStream_t stm, const double *x, const int16_
         for (long i0 = 0; i0 < items; i0 += chunk) {
             const long m = (items - i0 < chunk) ? items - i0 : chunk;
             { Prof pr(ctx, "burg_lags", stm);
-              if (pcm) launch_burg_lags_pcm16(stm, pcm, F, n, stride, window, p, map, i0, m, w);
+              if (f32) { if (!launch_burg_lags_f32in(stm, f32, F, n, stride, window, p, map, i0, m, w))
+                             return fail(ctx, VBX_E_RUNTIME, "burg_lags: no float32 lag kernel at order " + std::to_string(p)); }
+              else if (pcm) launch_burg_lags_pcm16(stm, pcm, F, n, stride, window, p, map, i0, m, w);
               else launch_burg_lags(stm, x, F, n, stride, window, p, map, i0, m, w); }
             { Prof pr(ctx, "burg_recursion", stm); launch_burg_recursion(stm, F, p, map, i0, m, coeffs, st, w); }
         }
         { Prof pr(ctx, "burg_direct_list", stm);
-          if (pcm) launch_burg_pcm16_list(stm, pcm, F, n, stride, window, p, coeffs, st, list + 2, list);
+          if (f32) launch_burg_f32in_list(stm, f32, F, n, stride, window, p, coeffs, st, list + 2, list);
+          else if (pcm) launch_burg_pcm16_list(stm, pcm, F, n, stride, window, p, coeffs, st, list + 2, list);
           else launch_burg_list(stm, x, F, n, stride, window, p, coeffs, st, list + 2, list); }
         // the probe (vbx_internal_last_burg_direct_count) reports the whole CALL: list[0] restarts with every time slice of
         // find_formants, list[1] adds the slices up (reset with the call's first slice)
@@ -936,7 +951,8 @@ static int run_burg(vbx_ctx *ctx, hipStream_t stm, const double *x, const int16_
     }
     Prof pr(ctx, "burg", stm);
     ctx->burg_list_count = nullptr;
-    if (pcm) launch_burg_pcm16(stm, pcm, F, n, stride, window, p, coeffs, st, map);
+    if (f32) launch_burg_f32in(stm, f32, F, n, stride, window, p, coeffs, st, map);
+    else if (pcm) launch_burg_pcm16(stm, pcm, F, n, stride, window, p, coeffs, st, map);
     else launch_burg(stm, x, F, n, stride, window, p, coeffs, st, map);
     return VBX_SUCCESS;
 }
@@ -1136,7 +1152,8 @@ static int run_find_formants(vbx_ctx *ctx, hipStream_t stm, const double *x, siz
                              const vbx_resonance *h_est_init, size_t n_est,
                              vbx_resonance *out_formants, size_t formants_ld, vbx_resonance *out_res, int32_t *out_res_count,
                              double *out_coeffs, int32_t *status, const int16_t *pcm = nullptr /* the frames as 16-bit PCM instead of x */,
-                             const resample_plan_t *rp = nullptr /* find_formants on the frames' resampled view (run_burg) */) {
+                             const resample_plan_t *rp = nullptr /* find_formants on the frames' resampled view (run_burg) */,
+                             const float *f32 = nullptr /* the frames as float32 samples instead of x / pcm */) {
     VBX_REQUIRE(ctx, h_est_init && out_formants, "null argument");
     if (rp) frame_len = rp->m;                                   // what Burg sees
     VBX_REQUIRE(ctx, burg_order_ok(frame_len, n_coeffs), "frame_len must be >= 2, order in [1, 62]");
@@ -1186,7 +1203,7 @@ static int run_find_formants(vbx_ctx *ctx, hipStream_t stm, const double *x, siz
     ctx->last_track.res = res; ctx->last_track.cnt = cnt; ctx->last_track.st = st; ctx->last_track.F = F;
     ctx->last_track.n_est = (int)n_est; ctx->last_track.out = (res_t *)out_formants; ctx->last_track.out_ld = (long)formants_ld;
     if (n_slices == 1) {
-        rc = run_burg(ctx, stm, x, pcm, F, (int)frame_len, (long)stride, hann, p, coeffs, st, frame_map_t{0, 0, 0}, rp);           // :75
+        rc = run_burg(ctx, stm, x, pcm, F, (int)frame_len, (long)stride, hann, p, coeffs, st, frame_map_t{0, 0, 0}, rp, f32);      // :75
         if (rc != VBX_SUCCESS) return rc;
         rc = run_formant_resonances(ctx, stm, coeffs, F, p, sample_rate, res, cnt, st);                                            // :80-110
         if (rc != VBX_SUCCESS) return rc;
@@ -1202,7 +1219,7 @@ static int run_find_formants(vbx_ctx *ctx, hipStream_t stm, const double *x, siz
     }
     for (int j = 0; j < n_slices && j * tc < seg_len; j++) {
         const frame_map_t map{seg_len, j * tc, (seg_len - j * tc < tc) ? seg_len - j * tc : tc};   // the last slice may be shorter
-        rc = run_burg(ctx, stm, x, pcm, F, (int)frame_len, (long)stride, hann, p, coeffs, st, map, rp);
+        rc = run_burg(ctx, stm, x, pcm, F, (int)frame_len, (long)stride, hann, p, coeffs, st, map, rp, f32);
         if (rc != VBX_SUCCESS) return rc;
         rc = run_formant_resonances(ctx, stm, coeffs, F, p, sample_rate, res, cnt, st, map);
         if (rc != VBX_SUCCESS) return rc;
@@ -1499,6 +1516,15 @@ int vbx_pcm16_to_f64(vbx_ctx *ctx, const int16_t *pcm, size_t n_samples, double 
     return check_launch(ctx, __func__);
 }
 
+int vbx_f32_to_f64(vbx_ctx *ctx, const float *x, size_t n_samples, double *out) {
+    VBX_REQUIRE(ctx, ctx != nullptr, "null context");
+    if (n_samples == 0) return VBX_SUCCESS;
+    VBX_REQUIRE(ctx, x && out, "null argument");
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    { Prof p(ctx, "f32_to_f64"); launch_f32_to_f64(ctx->stream, x, n_samples, out); }
+    return check_launch(ctx, __func__);
+}
+
 int vbx_rms_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
                 const double *window, double *out) {
     int rc = check_frames(ctx, __func__, x, n_frames, frame_len, stride, VBX_MAX_LONG_FRAME_LEN);
@@ -1581,12 +1607,13 @@ struct ex_req_t { const resample_plan_t *rp; double formant_rate; bool rms; };
 
 // x: the frames as f64 samples, or -- pcm16 non-null -- as 16-bit PCM (the kernels that have a PCM form read it directly:
 // 1200-sample frames through the fused spectral kernel, Burg at every length; every other shape is widened into a
-// context-owned f64 copy of the view first and takes the f64 path)
+// context-owned f64 copy of the view first and takes the f64 path), or -- f32 non-null -- as float32 samples, by the same rule (the
+// kernels that have a float form read them directly, every other shape takes one widening pass into that copy first)
 static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, const int16_t *pcm16, size_t n_frames, size_t frame_len,
                                size_t stride, const vbx_analysis_params *h_p, const int64_t *h_seg_start, size_t n_segments,
                                double *out_records, size_t record_ld, int32_t *status3, const track_req_t *tk = nullptr,
-                               const ex_req_t *ex = nullptr) {
-    int rc = check_frames(ctx, fn, pcm16 ? (const void *)pcm16 : (const void *)x, n_frames, frame_len, stride, VBX_MAX_LONG_FRAME_LEN);
+                               const ex_req_t *ex = nullptr, const float *f32 = nullptr) {
+    int rc = check_frames(ctx, fn, f32 ? (const void *)f32 : pcm16 ? (const void *)pcm16 : (const void *)x, n_frames, frame_len, stride, VBX_MAX_LONG_FRAME_LEN);
     if (rc == 1 && tk) { ctx->path_redone = nullptr; ctx->path_last = true; }      // an empty batch: an empty path
     if (rc != VBX_SUCCESS) return rc < 0 ? rc : VBX_SUCCESS;
     VBX_REQUIRE(ctx, h_p && out_records, "null argument");
@@ -1651,6 +1678,20 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
         x = (const double *)w; pcm16 = nullptr;
     }
     if (pcm_native) x = reinterpret_cast<const double *>(pcm16);          // the PCM kernels take the pointer through the f64 slot
+    // float32 frames, by the same rule: the shapes whose every kernel over the samples has a float form read the caller's floats
+    const float *const f32_in = f32;                                       // (the RMS / peak kernel reads them whichever form the rest takes)
+    const bool f32_native = f32 != nullptr && fused && frame_len == (size_t)SPECTRAL_N &&
+                            (!h_p->lpc_order || fused_lpc) && (!h_p->mfcc_coeffs || fused_mfcc) &&
+                            !(ex && ex->rp && !ex->rp->direct);
+    if (f32 != nullptr && !f32_native) {
+        const size_t ns = (n_frames - 1) * stride + frame_len;
+        void *w = nullptr;
+        rc = ws_get(ctx, vbx_ctx::WS_F32_IN, ns * sizeof(double), &w);
+        if (rc != VBX_SUCCESS) return rc;
+        { Prof p(ctx, "f32_to_f64"); launch_f32_to_f64(ctx->stream, f32, ns, (double *)w); }
+        x = (const double *)w; f32 = nullptr;
+    }
+    if (f32_native) x = reinterpret_cast<const double *>(f32);            // the float kernels take the pointer through the f64 slot
     const double *hann = nullptr;
     VBX_HIP(ctx, ctx->tables.window(VBX_WINDOW_HANNING, frame_len, &hann));        // Windower::hanning frames (examples/pitch_detection.rs:23)
     // record columns
@@ -1695,11 +1736,13 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
     const bool want_rms = ex && ex->rms;
     if (tk_peak && want_rms) {
         { Prof p(ctx, "frame_rms_peak", side);
-          launch_frame_rms(side, pcm_in ? nullptr : x, pcm_in, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, tk_peak); }
+          if (f32_in) launch_frame_rms_f32in(side, f32_in, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, tk_peak);
+          else launch_frame_rms(side, pcm_in ? nullptr : x, pcm_in, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, tk_peak); }
         VBX_HIP(ctx, hipEventRecord(ctx->ev_peak, side));
     } else if (tk_peak) {
         // max |x| per frame, first on the side stream: HBM-bound, beside the FP64-bound kernel; the path waits for ev_peak
-        if (pcm_in) { Prof p(ctx, "frame_peak_pcm16", side); launch_frame_peak_pcm16(side, pcm_in, (long)n_frames, (long)frame_len, (long)stride, tk_peak); }
+        if (f32_in) { Prof p(ctx, "frame_peak_f32in", side); launch_frame_peak_f32in(side, f32_in, (long)n_frames, (long)frame_len, (long)stride, tk_peak); }
+        else if (pcm_in) { Prof p(ctx, "frame_peak_pcm16", side); launch_frame_peak_pcm16(side, pcm_in, (long)n_frames, (long)frame_len, (long)stride, tk_peak); }
         else { Prof p(ctx, "frame_peak", side); launch_frame_peak(side, x, (long)n_frames, (long)frame_len, (long)stride, tk_peak); }
         VBX_HIP(ctx, hipEventRecord(ctx->ev_peak, side));
     }
@@ -1708,7 +1751,7 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
         for (size_t e = 0; e < h_p->n_est; e++) est[e] = h_p->est_init[e];
         rc = run_find_formants(ctx, side, x, n_frames, frame_len, stride, ex ? ex->formant_rate : h_p->sample_rate, h_p->formant_order,
                                h_seg_start, n_segments, est, h_p->n_est, (vbx_resonance *)(out_records + c_form), record_ld,
-                               nullptr, nullptr, nullptr, st_form, pcm_native ? pcm16 : nullptr, ex ? ex->rp : nullptr);
+                               nullptr, nullptr, nullptr, st_form, pcm_native ? pcm16 : nullptr, ex ? ex->rp : nullptr, f32_native ? f32 : nullptr);
         if (rc != VBX_SUCCESS) return rc;
     } else {
         ctx->last_track.res = nullptr;                        // no tracks in these records: nothing for vbx_track_stitch_f64 to continue
@@ -1740,7 +1783,8 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
     if (!h_p->mfcc_coeffs && st_mfcc) VBX_HIP(ctx, hipMemsetAsync(st_mfcc, 0, n_frames * sizeof(int32_t), side));
     if (want_rms && !tk_peak) {
         Prof p(ctx, "frame_rms", side);
-        launch_frame_rms(side, pcm_in ? nullptr : x, pcm_in, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, nullptr);
+        if (f32_in) launch_frame_rms_f32in(side, f32_in, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, nullptr);
+        else launch_frame_rms(side, pcm_in ? nullptr : x, pcm_in, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, nullptr);
     }
     VBX_HIP(ctx, hipEventRecord(ctx->ev_join, side));
     if (fused) {
@@ -1763,6 +1807,7 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
         L.sample_rate = h_p->sample_rate; L.threshold = h_p->pitch_threshold; L.fmin = h_p->pitch_fmin; L.fmax = h_p->pitch_fmax;
         L.kmax = 1;
         L.pcm = pcm_native;
+        L.f32in = f32_native;
         L.whole_curve = ctx->pitch_whole_curve;
         L.out_cand = (pitch_t *)out_records; L.cand_ld = (long)record_ld; L.out_count = nullptr; L.pitch_status = st_pitch;
         if (tk) { L.kmax = (int)tk->kmax; L.out_cand = (pitch_t *)tk_cand; L.cand_ld = 2 * (long)tk->kmax; L.out_count = tk_count; }
@@ -1868,7 +1913,7 @@ static int make_resample_plan(vbx_ctx *ctx, const char *fn, double ratio, size_t
 static int analyze_ex(vbx_ctx *ctx, const char *fn, const double *x, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
                       const vbx_analysis_params *h_p, const vbx_analysis_ext *h_ext, const vbx_pitch_track_params *h_track,
                       const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld, int32_t *status3,
-                      const vbx_pitch_track_outputs *h_out) {
+                      const vbx_pitch_track_outputs *h_out, const float *f32 = nullptr /* the frames as float32 samples instead of x / pcm */) {
     if (!ctx) return fail(nullptr, VBX_E_INVALID, std::string(fn) + ": null context");
     if (!h_p) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": null argument");
     resample_plan_t rp{}; ex_req_t ex{nullptr, h_p->sample_rate, false};
@@ -1887,14 +1932,14 @@ static int analyze_ex(vbx_ctx *ctx, const char *fn, const double *x, const int16
         if (have || ex.rms || rate != 0.0) exp = &ex;
     }
     if (!h_track) return analyze_frames_impl(ctx, fn, x, pcm, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records, record_ld,
-                                             status3, nullptr, exp);
+                                             status3, nullptr, exp, f32);
     track_req_t tk{};
     tk.kmax = h_track->kmax; tk.path = h_track->path;
     if (h_out) tk.out = *h_out;
     if (tk.path.time_step == 0.0) tk.path.time_step = (double)stride / h_p->sample_rate;      // the batch's own hop
     int rc = check_pitch_path(ctx, fn, tk.path, n_frames, tk.kmax, true, h_seg_start, n_segments);
     if (rc != VBX_SUCCESS) return rc;
-    return analyze_frames_impl(ctx, fn, x, pcm, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records, record_ld, status3, &tk, exp);
+    return analyze_frames_impl(ctx, fn, x, pcm, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records, record_ld, status3, &tk, exp, f32);
 }
 
 int vbx_analyze_frames_ex_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
@@ -1912,6 +1957,15 @@ int vbx_analyze_frames_ex_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_frame
     if (n_frames != 0 && ctx && !pcm) return fail(ctx, VBX_E_INVALID, "vbx_analyze_frames_ex_pcm16: null frame pointer");
     return analyze_ex(ctx, __func__, nullptr, pcm, n_frames, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, out_records,
                       record_ld, status3, h_outputs);
+}
+
+int vbx_analyze_frames_ex_f32in(vbx_ctx *ctx, const float *x, size_t n_frames, size_t frame_len, size_t stride,
+                                const vbx_analysis_params *h_p, const vbx_analysis_ext *h_ext, const vbx_pitch_track_params *h_track,
+                                const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld,
+                                int32_t *status3, const vbx_pitch_track_outputs *h_outputs) {
+    if (n_frames != 0 && ctx && !x) return fail(ctx, VBX_E_INVALID, "vbx_analyze_frames_ex_f32in: null frame pointer");
+    return analyze_ex(ctx, __func__, nullptr, nullptr, n_frames, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, out_records,
+                      record_ld, status3, h_outputs, x);
 }
 
 int vbx_find_formants_resampled_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,

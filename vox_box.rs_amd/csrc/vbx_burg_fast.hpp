@@ -139,7 +139,8 @@ __device__ __forceinline__ bool burg_from_lags(const double *c_, const double *h
     return ok && (BF_KAPPA_EPS * kappa * big <= BF_TARGET * floor_j);               // false for NaN
 }
 
-// EPL: samples per lane (frame_len <= 64 EPL).  P: the order.  TIN: double, or int16_t = 16-bit PCM widened in registers.
+// EPL: samples per lane (frame_len <= 64 EPL).  P: the order.  TIN: double, int16_t = 16-bit PCM widened in registers, or float =
+// float32 samples (k_burg_lags_f32in*.hip), widened -- exactly -- when the window product is formed.
 // One wavefront works through BF_FPW frames as autocorr_fewlags_kernel does (k_lpc.hip: EPL samples per lane in registers,
 // neighbour samples by DPP wave shifts, one transposing reduction through LDS for all P + 1 lag sums).
 // scratch: tiles of [3 (P + 1)][64] doubles, 64 consecutive items per tile.
@@ -151,8 +152,10 @@ __global__ __launch_bounds__(64) void burg_lags_kernel(
     constexpr int NL = P + 1;
     constexpr int TS = NL | 1;
     constexpr bool PCM = sizeof(TIN) == 2;
-    constexpr int RAW = PCM ? EPL / 2 : EPL;         // registers of a frame in flight: packed pairs of PCM samples, or doubles
+    constexpr bool F32 = std::is_same<TIN, float>::value;
+    constexpr int RAW = PCM ? EPL / 2 : EPL;         // registers of a frame in flight: packed pairs of PCM samples, or doubles / floats
     static_assert(EPL % 2 == 0 && EPL >= 2, "pairs of samples per lane");
+    static_assert(!F32 || EPL % 4 == 0, "float samples: 16-byte loads of four");
     __shared__ double TR[64 * TS];                   // per-frame transpose buffer [lane][lag]
     __shared__ double REC[3 * NL * FPW];             // [value][frame of the batch]: C, then HD, then TL
     const int lane = lane_id();
@@ -168,9 +171,10 @@ __global__ __launch_bounds__(64) void burg_lags_kernel(
     }
     const bool whole = (n % EPL == 0);               // no lane straddles the frame's end
     const bool mine = lane * EPL < n;
-    using raw_t = typename std::conditional<PCM, uint32_t, double>::type;
-    // 16-byte loads of doubles / 4-byte loads of PCM pairs where every row allows them
+    using raw_t = typename std::conditional<PCM, uint32_t, typename std::conditional<F32, float, double>::type>::type;
+    // 16-byte loads of doubles (of four floats) / 4-byte loads of PCM pairs where every row allows them
     const bool wide = whole && (PCM ? ((((uintptr_t)x) & 3) == 0 && (stride & 1) == 0)
+                              : F32 ? ((((uintptr_t)x) & 15) == 0 && (stride & 3) == 0)
                                     : ((((uintptr_t)x) & 15) == 0 && (stride & 1) == 0));
     auto load_frame = [&](int g, raw_t (&dst)[RAW]) {
         const long f = frame_map(map, i0 + g, n_frames);
@@ -189,6 +193,19 @@ __global__ __launch_bounds__(64) void burg_lags_kernel(
                     const uint32_t hi = (f >= 0 && j + 1 < n) ? (uint16_t)xf[2 * e + 1] : 0u;
                     dst[e] = lo | (hi << 16);
                 }
+            }
+        } else if constexpr (F32) {
+            if (wide) {
+                const float4 *xv = reinterpret_cast<const float4 *>(xf);
+#pragma unroll
+                for (int e = 0; e < EPL; e += 4) {
+                    float4 v; v.x = 0.0f; v.y = 0.0f; v.z = 0.0f; v.w = 0.0f;
+                    if (have) v = xv[e / 4];
+                    dst[e] = v.x; dst[e + 1] = v.y; dst[e + 2] = v.z; dst[e + 3] = v.w;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < EPL; e++) dst[e] = (f >= 0 && lane * EPL + e < n) ? xf[e] : 0.0f;
             }
         } else {
             if (wide) {
@@ -222,7 +239,7 @@ __global__ __launch_bounds__(64) void burg_lags_kernel(
             }
         } else {
 #pragma unroll
-            for (int e = 0; e < EPL; e++) ext[e] = cur[e] * wreg[e];
+            for (int e = 0; e < EPL; e++) ext[e] = (double)cur[e] * wreg[e];
         }
 #pragma unroll
         for (int e = EPL; e < EPL + NL - 1; e++) ext[e] = from_next_lane(ext[e - EPL]);
@@ -432,7 +449,8 @@ template <int P>
 void launch_burg_recursion_p(hipStream_t s, const double *scratch, long F, frame_map_t map, long i0, long m,
                              double *out, int32_t *status, int32_t *list);
 
-#define VBX_BURG_FAST_INSTANTIATE(P)                                                                                          \
+// (the definition of launch_burg_lags_p apart, for the translation units that instantiate it for another sample type)
+#define VBX_BURG_FAST_DEFINE_LAGS                                                                                             \
     template <int PP, typename TIN>                                                                                           \
     void launch_burg_lags_p(hipStream_t s, const TIN *x, long F, int n, long stride, const double *window,                   \
                             frame_map_t map, long i0, long m, double *scratch) {                                              \
@@ -444,7 +462,10 @@ void launch_burg_recursion_p(hipStream_t s, const double *scratch, long F, frame
         else if constexpr (std::is_same<TIN, double>::value) {                                                                \
             hipLaunchKernelGGL((burg_lags_seg_kernel<PP>), grid, b, 0, s, x, F, n, stride, window, map, i0, m, scratch);      \
         } else hipLaunchKernelGGL((burg_lags_kernel<32, PP, TIN>), grid, b, 0, s, x, F, n, stride, window, map, i0, m, scratch);                \
-    }                                                                                                                         \
+    }
+
+#define VBX_BURG_FAST_INSTANTIATE(P)                                                                                          \
+    VBX_BURG_FAST_DEFINE_LAGS                                                                                                 \
     template <int PP>                                                                                                         \
     void launch_burg_recursion_p(hipStream_t s, const double *scratch, long F, frame_map_t map, long i0, long m,              \
                                  double *out, int32_t *status, int32_t *list) {                                               \

@@ -26,7 +26,7 @@ namespace vbx {
 constexpr bool BURG_RS_LDS = VBX_BURG_RS_GATHER == 0;        // the resampled frame through LDS (default), or per-lane gathers
 
 // sample k of the resampled frame (resample_src_t, vbx_kernels.hpp: li / frac = the context's resample table, n_src = the
-// caller's frame length); TIN = int16_t: 16-bit PCM widened by pcm16_value first
+// caller's frame length); TIN = int16_t: 16-bit PCM widened by pcm16_value first; TIN = float: float32 samples, widened as they are
 template <typename TIN>
 __device__ __forceinline__ double resampled_sample(const TIN *__restrict__ xf, const resample_src_t &rs, int k) {
 #pragma clang fp contract(off)   // (diff * value) + left, two roundings as resample_kernel
@@ -165,7 +165,8 @@ template <int P, typename TIN>
 void launch_burg_lags_resampled_p(hipStream_t s, const TIN *x, long F, int m_len, long stride, const double *window,
                                   resample_src_t rs, frame_map_t map, long i0, long m, double *scratch);
 
-#define VBX_BURG_RESAMPLED_INSTANTIATE(P)                                                                                     \
+// (the definition apart, for the translation units that instantiate it for another sample type)
+#define VBX_BURG_RESAMPLED_DEFINE                                                                                             \
     template <int PP, typename TIN>                                                                                           \
     void launch_burg_lags_resampled_p(hipStream_t s, const TIN *x, long F, int n, long stride, const double *window,         \
                                       resample_src_t rs, frame_map_t map, long i0, long m, double *scratch) {                 \
@@ -174,7 +175,10 @@ void launch_burg_lags_resampled_p(hipStream_t s, const TIN *x, long F, int m_len
         if (n <= 64 * 8) hipLaunchKernelGGL((burg_lags_resampled_kernel<8, PP, TIN>), grid8, b, 0, s, x, F, n, stride, window, rs, map, i0, m, scratch);       \
         else if (n <= 64 * 16) hipLaunchKernelGGL((burg_lags_resampled_kernel<16, PP, TIN>), grid, b, 0, s, x, F, n, stride, window, rs, map, i0, m, scratch); \
         else hipLaunchKernelGGL((burg_lags_resampled_kernel<20, PP, TIN>), grid, b, 0, s, x, F, n, stride, window, rs, map, i0, m, scratch);                   \
-    }                                                                                                                         \
+    }
+
+#define VBX_BURG_RESAMPLED_INSTANTIATE(P)                                                                                     \
+    VBX_BURG_RESAMPLED_DEFINE                                                                                                 \
     template void launch_burg_lags_resampled_p<P, double>(hipStream_t, const double *, long, int, long, const double *, resample_src_t, frame_map_t, long, long, double *);   \
     template void launch_burg_lags_resampled_p<P, int16_t>(hipStream_t, const int16_t *, long, int, long, const double *, resample_src_t, frame_map_t, long, long, double *);
 

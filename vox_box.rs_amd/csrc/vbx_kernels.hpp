@@ -234,6 +234,7 @@ struct spectral_launch_t {
     bool mfcc_only;                                              // MFCC::mfcc alone (n == the plan's Nc): no pitch, no LPC
     double *out_r; int n_lags;                                   // non-NULL: Autocorrelate::autocorrelate(n_lags) alone, [F, n_lags]
     bool pcm;                                                    // x points to int16 PCM samples (n == 1200 only)
+    bool f32in;                                                  // x points to float32 samples (n == 1200 only; k_spectral_f32in.hip)
     bool whole_curve;                                            // keep every lag of the curve in LDS (VBX_PITCH_CURVE_CUT=0; tests)
     bool interp; mfcc_interp_t ip;                               // MFCC by interpolation of the transform's bins (device pointers)
     double *curve_ws; size_t curve_ws_bytes;                     // scratch for the split form of the 4096-point plan (lag curves between its two kernels); NULL: fused
@@ -327,6 +328,37 @@ void launch_preemphasis(hipStream_t s, const double *x, long F, int n, long stri
 // PCM, written at out_rms + f * rms_ld; out_peak non-null: launch_frame_peak / launch_frame_peak_pcm16 from the same read
 void launch_frame_rms(hipStream_t s, const double *x, const int16_t *pcm, long F, int n, long stride, double *out_rms, long rms_ld,
                       double *out_peak);
+
+// k_front_f32in.hip, k_burg_f32in.hip, k_burg_lags_f32in*.hip, k_lists_f32in.hip (and k_spectral_f32in.hip, declared in vbx_spectral.hpp):
+// the kernels above that read a frame's samples, on FLOAT32 samples (vbx_analyze_frames_ex_f32in).  Each widens a sample in registers
+// before its first use -- every float is a double, so the frame is the one launch_f32_to_f64 would have written and every result
+// is the f64 launcher's on that copy, bit for bit; windows, tables and results stay f64.
+void launch_f32_to_f64(hipStream_t s, const float *x, size_t n, double *out);
+// max |x| per frame taken in float and widened once: launch_frame_peak on the widened samples (NaNs ignored, as there)
+void launch_frame_peak_f32in(hipStream_t s, const float *x, long F, long n, long stride, double *out);
+void launch_frame_rms_f32in(hipStream_t s, const float *x, long F, int n, long stride, double *out_rms, long rms_ld, double *out_peak);
+void launch_pitch_list_f32in(hipStream_t s, const int32_t *frame_list, const int32_t *list_count, int grid,
+                             const float *x, int n, long stride, const double *window,
+                             const double *lag_window, double sample_rate, double threshold, double fmin, double fmax,
+                             int kmax, pitch_t *out_cand, long cand_ld, int32_t *out_count, int32_t *status,
+                             unsigned long long *work);
+void launch_lpc_exact_list_f32in(hipStream_t s, const int32_t *frame_list, const int32_t *list_count, int cus, const float *x, int n,
+                                 long stride, const double *window, int p, double *out_lpc, long lpc_ld);
+void launch_lpc_ref_f32in(hipStream_t s, const float *x, long F, int n, long stride, const double *window, int n_lags, int p,
+                          int normalize, double *out_r, long r_ld, double *out_lpc, long lpc_ld);
+void launch_burg_f32in(hipStream_t s, const float *x, long F, int n, long stride, const double *window,
+                       int p, double *out, int32_t *status, frame_map_t map = frame_map_t{0, 0, 0});
+void launch_burg_f32in_list(hipStream_t s, const float *x, long F, int n, long stride, const double *window,
+                            int p, double *out, int32_t *status, const int32_t *list, const int32_t *count);
+// the two lag launchers: false when the order has no float instantiation (nothing launched)
+bool launch_burg_lags_f32in(hipStream_t s, const float *x, long F, int n, long stride, const double *window, int p,
+                            frame_map_t map, long i0, long m, void *ws);
+void launch_burg_resampled_f32in(hipStream_t s, const float *x, long F, int m, long stride, const double *window,
+                                 resample_src_t rs, int p, double *out, int32_t *status, frame_map_t map);
+void launch_burg_resampled_f32in_list(hipStream_t s, const float *x, long F, int m, long stride, const double *window,
+                                      resample_src_t rs, int p, double *out, int32_t *status, const int32_t *list, const int32_t *count);
+bool launch_burg_lags_resampled_f32in(hipStream_t s, const float *x, long F, int m, long stride, const double *window,
+                                      resample_src_t rs, int p, frame_map_t map, long i0, long n_items, void *ws);
 
 // k_long.hip: frames of more than VBX_MAX_FRAME_LEN_K samples (tiles out of HBM / L2 instead of registers / LDS)
 size_t burg_long_scratch_bytes(long frames, long n);

@@ -145,6 +145,9 @@ constexpr int SP_LPC_P = SPECTRAL_LPC_ORDER;
 // conditioning probe + double-double redo of ill-conditioned rows (k_lpc_exact.hip) ride on that kernel for nothing.
 
 // k_spectral_pow2.hip
+// k_spectral_f32in.hip: the fused analysis of full 1200-sample frames whose samples are float32 (a.frames carries the float pointer);
+// launch_analyze calls it with the geometry it worked out for the f64 form
+void launch_analyze_f32in(hipStream_t s, const spectral_args_t &a, unsigned grid, size_t lds, bool lpc, bool mfcc, bool waves3);
 int launch_analyze_pow2(hipStream_t s, const spectral_launch_t &L, spectral_args_t &a);      // 1: ran in the split form
 
 }  // namespace vbx

@@ -153,6 +153,8 @@ struct Filter {          // waves.rs:82-96 (result in a dense [F, N] batch: stri
 
 // hound-style ingestion of 16-bit PCM (tests/lib.rs:17-19): sample / 32767
 inline void pcm16_to_f64(Context &c, const int16_t *pcm, size_t n, double *out) { c.check(vbx_pcm16_to_f64(c.get(), pcm, n, out)); }
+// float32 samples -> f64, exactly (every float is a double)
+inline void f32_to_f64(Context &c, const float *x, size_t n, double *out) { c.check(vbx_f32_to_f64(c.get(), x, n, out)); }
 
 struct Normalize {       // waves.rs:60-76
     static void normalize(Context &c, double *rows, size_t n_rows, size_t n) { c.check(vbx_normalize_f64(c.get(), rows, n_rows, n)); }
@@ -379,6 +381,15 @@ inline void analyze_frames_ex_pcm16(Context &c, const int16_t *pcm, size_t n_fra
                                     double *records, size_t record_ld, int32_t *status3 = nullptr,
                                     const PitchTrackOutputs *outputs = nullptr) {
     c.check(vbx_analyze_frames_ex_pcm16(c.get(), pcm, n_frames, frame_len, stride, &p, &ext, track, seg.h_seg_start, seg.n, records,
+                                        record_ld, status3, outputs));
+}
+// The same on float32 samples (only the input is float: records and everything else written are analyze_frames_ex's on the exactly
+// widened samples, bit for bit; full 1200-sample frames are read without an f64 copy).  ext null: the plain / tracked call.
+inline void analyze_frames_ex_f32in(Context &c, const float *x, size_t n_frames, size_t frame_len, size_t stride,
+                                    const AnalysisParams &p, const AnalysisExt *ext, const PitchTrackParams *track, Segments seg,
+                                    double *records, size_t record_ld, int32_t *status3 = nullptr,
+                                    const PitchTrackOutputs *outputs = nullptr) {
+    c.check(vbx_analyze_frames_ex_f32in(c.get(), x, n_frames, frame_len, stride, &p, ext, track, seg.h_seg_start, seg.n, records,
                                         record_ld, status3, outputs));
 }
 

@@ -234,6 +234,7 @@ def load_library():
         "vbx_resampled_len": (sz, [sz, dbl]),
         "vbx_resample_linear_f64": (C.c_int, [vp, vp, sz, sz, sz, dbl, vp]),
         "vbx_pcm16_to_f64": (C.c_int, [vp, vp, sz, vp]),
+        "vbx_f32_to_f64": (C.c_int, [vp, vp, sz, vp]),
         "vbx_rms_f64": (C.c_int, [vp, vp, sz, sz, sz, vp, vp]),
         "vbx_preemphasis_f64": (C.c_int, [vp, vp, sz, sz, sz, dbl, vp]),
         "vbx_synth_speech_f64": (C.c_int, [vp, vp, sz, C.c_uint64, dbl, C.c_uint64]),
@@ -258,6 +259,8 @@ def load_library():
         "vbx_analyze_frames_ex_f64": (C.c_int, [vp, vp, sz, sz, sz, C.POINTER(AnalysisParams), C.POINTER(AnalysisExt),
                                                 C.POINTER(PitchTrackParams), vp, sz, vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
         "vbx_analyze_frames_ex_pcm16": (C.c_int, [vp, vp, sz, sz, sz, C.POINTER(AnalysisParams), C.POINTER(AnalysisExt),
+                                                  C.POINTER(PitchTrackParams), vp, sz, vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
+        "vbx_analyze_frames_ex_f32in": (C.c_int, [vp, vp, sz, sz, sz, C.POINTER(AnalysisParams), C.POINTER(AnalysisExt),
                                                   C.POINTER(PitchTrackParams), vp, sz, vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
         "vbx_find_formants_resampled_f64": (C.c_int, [vp, vp, sz, sz, sz, dbl, dbl, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp]),
         "vbx_shard_range": (C.c_int, [sz, i32, i32, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
@@ -1240,6 +1243,27 @@ class VoxBox:
         return self._analyze_tracked(self.L.vbx_analyze_frames_ex_pcm16, ptr, int(n_frames), int(frame_len), int(stride), params,
                                      track, seg_start, out, record_ld, status, lists, outputs, tmp, ext=ext)
 
+    def analyze_frames_ex_f32in(self, x, params, ext=None, track=None, seg_start=None, frame_len=None, stride=None,
+                                n_frames=None, out=None, record_ld=None, status=None, lists=False, outputs=None):
+        """vbx_analyze_frames_ex_f32in: analyze_frames_ex on float32 samples (host float32 array, uploaded as it is; a float32
+        DeviceArray; or a raw device address).  Only the input is float: the records and everything else written are the f64 call's
+        on the exactly widened samples, bit for bit, and full 1200-sample frames are read without an f64 copy."""
+        tmp = None
+        if isinstance(x, np.ndarray):
+            assert x.ndim == 1 and x.dtype == np.float32 and frame_len and stride
+            n_frames = frame_count(x.size, frame_len, stride) if n_frames is None else n_frames
+            tmp = self.to_device(x, np.float32)
+            ptr = tmp.ptr
+        else:
+            assert frame_len and stride
+            if n_frames is None:
+                assert isinstance(x, DeviceArray) and len(x.shape) == 1
+                n_frames = frame_count(x.shape[0], frame_len, stride)
+            assert not isinstance(x, DeviceArray) or x.dtype == np.float32
+            ptr = _ptr(x)
+        return self._analyze_tracked(self.L.vbx_analyze_frames_ex_f32in, ptr, int(n_frames), int(frame_len), int(stride), params,
+                                     track, seg_start, out, record_ld, status, lists, outputs, tmp, ext=ext)
+
     # -- spectrum.rs: MFCC ------------------------------------------------------------
     def mfcc(self, x, num_coeffs, freq_bounds, sample_rate, frame_len=None, stride=None, n_frames=None,
              window=None, out=None):
@@ -1278,6 +1302,25 @@ class VoxBox:
             n, ptr = out.shape[0], _ptr(pcm)
         o = out if out is not None else self.empty(n)
         self._check(self.L.vbx_pcm16_to_f64(self.ctx, ptr, n, _ptr(o)))
+        if tmp is not None:
+            self.sync()
+            tmp.free()
+        return o
+
+    def f32_to_f64(self, x, out=None):
+        """float32 samples (host array, float32 DeviceArray, or a raw address + n via `out`) -> f64 on the device, exactly."""
+        tmp = None
+        if isinstance(x, np.ndarray):
+            assert x.dtype == np.float32
+            tmp = self.to_device(x, np.float32)
+            n, ptr = x.size, tmp.ptr
+        elif isinstance(x, DeviceArray):
+            assert x.dtype == np.float32
+            n, ptr = int(np.prod(x.shape)), x.ptr
+        else:
+            n, ptr = out.shape[0], _ptr(x)
+        o = out if out is not None else self.empty(n)
+        self._check(self.L.vbx_f32_to_f64(self.ctx, ptr, n, _ptr(o)))
         if tmp is not None:
             self.sync()
             tmp.free()
