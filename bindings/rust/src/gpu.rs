@@ -253,6 +253,62 @@ impl Gpu {
         Ok(buf)
     }
 
+    /// One channel of interleaved sample frames on the device, as the type the frame loop reads natively (`vbx_unpack_samples`):
+    /// `format` is a `VBX_SAMPLE_*`; `dst` holds `n_sample_frames` elements of i16 (PCM16), f32 (F32) or f64 (PCM24 / PCM32 / F64).
+    /// 24- and 32-bit PCM become `s / 8388607` and `s / 2147483647`, correctly rounded.
+    pub fn unpack_samples<S: Copy, D: Copy>(&self, src: &DeviceBuf<S>, n_sample_frames: usize, format: i32, channels: i32, channel: i32,
+                                            dst: &DeviceBuf<D>) -> GpuResult<()> {
+        let src_bytes = match format { ffi::VBX_SAMPLE_PCM16 => 2, ffi::VBX_SAMPLE_PCM24 => 3, ffi::VBX_SAMPLE_F64 => 8, _ => 4 };
+        let dst_bytes = match format { ffi::VBX_SAMPLE_PCM16 => 2, ffi::VBX_SAMPLE_F32 => 4, _ => 8 };
+        assert!(channels >= 1 && src.len() * std::mem::size_of::<S>() >= n_sample_frames * channels as usize * src_bytes, "source too small");
+        assert!(dst.len() * std::mem::size_of::<D>() >= n_sample_frames * dst_bytes, "destination too small");
+        self.check(unsafe {
+            ffi::vbx_unpack_samples(self.raw, src.as_ptr() as *const c_void, n_sample_frames, format, channels, channel,
+                                    dst.as_mut_ptr() as *mut c_void)
+        })
+    }
+
+    /// The frame loop on a recording in HOST memory, of any length, from one call (`vbx_analyze_host`): the samples are uploaded
+    /// chunk by chunk beside the analysis and are never resident on the device; only the records are.  `channel` of `channels`
+    /// interleaved channels is analysed; `chunk_frames` 0 takes the library's default.  The records, status rows and (tracked) the
+    /// path's list positions are those of the resident call on the whole channel, bit for bit.
+    #[allow(clippy::too_many_arguments)]
+    pub fn analyze_host(&self, audio: HostSamples, channels: usize, channel: usize, chunk_frames: usize, frame_len: usize, stride: usize,
+                        params: &AnalysisParams, ext: Option<&AnalysisExt>, track: Option<(usize, &PitchPathParams)>, seg_start: &[i64])
+                        -> GpuResult<(Records, Option<DeviceBuf<i32>>)> {
+        assert!(channels >= 1 && channel < channels, "need channels >= 1 and channel < channels");
+        let (format, addr, n_samples) = match audio {
+            HostSamples::Pcm16(a) => (ffi::VBX_SAMPLE_PCM16, a.as_ptr() as *const c_void, a.len()),
+            HostSamples::Pcm24(a) => (ffi::VBX_SAMPLE_PCM24, a.as_ptr() as *const c_void, a.len() / 3),
+            HostSamples::Pcm32(a) => (ffi::VBX_SAMPLE_PCM32, a.as_ptr() as *const c_void, a.len()),
+            HostSamples::F32(a) => (ffi::VBX_SAMPLE_F32, a.as_ptr() as *const c_void, a.len()),
+            HostSamples::F64(a) => (ffi::VBX_SAMPLE_F64, a.as_ptr() as *const c_void, a.len()),
+        };
+        let n_sample_frames = n_samples / channels;
+        let fmt = ffi::VbxHostAudio { format, channels: channels as i32, channel: channel as i32, reserved: 0, chunk_frames };
+        let n_frames = unsafe { ffi::vbx_frame_count(n_sample_frames, frame_len, stride) };
+        let p = params.to_ffi();
+        let e = ext.map(|x| x.to_ffi());
+        let e_ptr = e.as_ref().map_or(ptr::null(), |x| x as *const _);
+        let rec = unsafe { ffi::vbx_record_doubles_ex(&p, e_ptr) };
+        let ld = rec + (rec & 1);
+        let data = self.alloc::<f64>(n_frames * ld)?;
+        let status3 = self.alloc::<i32>(3 * n_frames)?;
+        let (seg_ptr, n_seg) = if seg_start.is_empty() { (ptr::null(), 0) } else { (seg_start.as_ptr(), seg_start.len()) };
+        let tk = track.map(|(kmax, path)| ffi::VbxPitchTrackParams { kmax, path: path.raw() });
+        let index = if tk.is_some() { Some(self.alloc::<i32>(n_frames)?) } else { None };
+        let outputs = ffi::VbxPitchTrackOutputs {
+            cand: ptr::null_mut(), count: ptr::null_mut(), peak: ptr::null_mut(),
+            index: index.as_ref().map_or(ptr::null_mut(), |b| b.as_mut_ptr()),
+        };
+        self.check(unsafe {
+            ffi::vbx_analyze_host(self.raw, addr, n_sample_frames, &fmt, frame_len, stride, &p, e_ptr,
+                                  tk.as_ref().map_or(ptr::null(), |t| t as *const _), seg_ptr, n_seg, data.as_mut_ptr(), ld,
+                                  status3.as_mut_ptr(), &outputs)
+        })?;
+        Ok((Records { data, status3, n_frames, record_ld: ld }, index))
+    }
+
     /// `sample::window` tables built on the host with the reference's recurrences (`VBX_WINDOW_*`).
     pub fn window_table(kind: i32, n: usize) -> GpuResult<Vec<f64>> {
         let mut t = vec![0f64; n];
@@ -277,6 +333,17 @@ fn last_error(ctx: *const ffi::VbxCtx) -> String {
     } else {
         unsafe { CStr::from_ptr(p) }.to_string_lossy().into_owned()
     }
+}
+
+/// A recording in host memory as a WAV reader hands it over ([`Gpu::analyze_host`]): interleaved when it has more than one
+/// channel; 24-bit PCM as packed 3-byte little-endian samples.
+#[derive(Clone, Copy, Debug)]
+pub enum HostSamples<'a> {
+    Pcm16(&'a [i16]),
+    Pcm24(&'a [u8]),
+    Pcm32(&'a [i32]),
+    F32(&'a [f32]),
+    F64(&'a [f64]),
 }
 
 /// `len` elements of `T` in HBM, freed on drop.
@@ -1444,6 +1511,20 @@ pub fn shard_plan(n_frames: usize, world: i32, rank: i32, seg_start: &[i64]) -> 
         return Err(GpuError { code: rc, message: last_error(ptr::null()) });
     }
     Ok(plan)
+}
+
+/// Chunk `c` of a host-resident recording cut every `chunk_frames` frames (`vbx_host_chunk_plan`; host arithmetic only): the
+/// plan of its frames -- `continues_prev` is set for every cut inside an utterance -- and the sample frames `[s0, s1)` it uploads.
+pub fn host_chunk_plan(n_frames: usize, chunk_frames: usize, c: usize, frame_len: usize, stride: usize, seg_start: &[i64])
+                       -> GpuResult<(ffi::VbxShardPlan, usize, usize)> {
+    let mut plan = ffi::VbxShardPlan::default();
+    let (mut s0, mut s1) = (0usize, 0usize);
+    let (seg_ptr, n_seg) = if seg_start.is_empty() { (ptr::null(), 0) } else { (seg_start.as_ptr(), seg_start.len()) };
+    let rc = unsafe { ffi::vbx_host_chunk_plan(n_frames, chunk_frames, c, frame_len, stride, seg_ptr, n_seg, &mut plan, &mut s0, &mut s1) };
+    if rc != ffi::VBX_SUCCESS {
+        return Err(GpuError { code: rc, message: last_error(ptr::null()) });
+    }
+    Ok((plan, s0, s1))
 }
 
 /// Utterance starts of the frames `[lo - warm, hi)` of a plan, re-based to the shard (`vbx_shard_local_segments`): the

@@ -28,6 +28,6 @@
 pub mod ffi;
 pub mod gpu;
 
-pub use gpu::{find_formants, gather_plan, path_end_states, path_segment_peaks, shard_range, shard_samples, AnalysisExt, AnalysisParams, Comm, DeviceBuf,
-              F32Batch, FormantExtractor, FrameBatch, FrameStatus, Frames, Gpu, GpuError, GpuEstimates, GpuFrame, LpcPolicy, PathShard, PcmBatch,
+pub use gpu::{find_formants, gather_plan, host_chunk_plan, path_end_states, path_segment_peaks, shard_range, shard_samples, AnalysisExt, AnalysisParams, Comm, DeviceBuf,
+              F32Batch, FormantExtractor, FrameBatch, FrameStatus, Frames, Gpu, GpuError, HostSamples, GpuEstimates, GpuFrame, LpcPolicy, PathShard, PcmBatch,
               PitchPathParams, PolyBatch, Records, ResonanceRows, RootRow, RootRows, PITCH_PATH_STATES};

@@ -33,7 +33,8 @@
  *    built and its workspaces grown, which drains the context's streams); a call whose h_seg_start, h_est_init or pitch path
  *    chunk table differs from the previous call's WHILE that previous call's upload of it is still queued (it waits until the
  *    upload has left the pinned staging buffer, i.e. for the work queued ahead of it -- a first change behind idle uploads and
- *    identical content do not wait; tests/test_gpu_stream_order.py test_host_blocks_only_as_documented); and the calls that
+ *    identical content do not wait; tests/test_gpu_stream_order.py test_host_blocks_only_as_documented); vbx_analyze_host, until
+ *    the last byte of its h_audio has been read (its uploads wait for the chunks queued ahead of them); and the calls that
  *    return a value to the host: vbx_sync, vbx_memcpy_h2d / _d2h, vbx_free, vbx_timer_end, vbx_profile_enable / _reset / _get /
  *    _stream / _names / _pitch_work, vbx_internal_last_*_count, vbx_internal_last_path_chunks_redone.
  *  - a context (stream, cached tables, scratch) is not internally synchronised: one host thread per context at
@@ -695,6 +696,83 @@ int vbx_find_formants_resampled_f64(vbx_ctx *ctx, const double *x, size_t n_fram
                                     vbx_resonance *out_formants, vbx_resonance *out_res, int32_t *out_res_count,
                                     double *out_coeffs, int32_t *status);
 
+/* ------------------------------------------------------------------ host-resident recordings (ABI 5, added) */
+
+/* What a WAV reader hands over, as the type the frame loop reads natively: channel `channel` of n_sample_frames interleaved sample
+ * frames of `channels` samples each (element i * channels + channel), d_src and d_out on the device.
+ *   VBX_SAMPLE_PCM16  int16                           -> int16, copied (the frame loop's PCM kernels divide by 32767: vbx_pcm16_to_f64)
+ *   VBX_SAMPLE_PCM24  packed 3-byte LE two's complement -> double, s / 8388607    (tests/lib.rs:17-19 at bits_per_sample = 24)
+ *   VBX_SAMPLE_PCM32  int32                           -> double, s / 2147483647
+ *   VBX_SAMPLE_F32    float                           -> float, as it is (bit patterns are copied: NaN payloads, -0.0, subnormals survive)
+ *   VBX_SAMPLE_F64    double                          -> double, as it is
+ * PCM24 and PCM32 results are the correctly rounded quotient (IEEE division), bit for bit numpy.float64(s) / denom.
+ * Alignment: a PCM24 source may sit at any byte address; every other source and every destination needs its type's natural
+ * alignment.  A 16-byte aligned destination is written by 16-byte stores, a mono source of matching alignment read by the widest
+ * loads; the results are the same bits either way.  channels == 1 with PCM16, F32 or F64 is a plain copy.  One pass, asynchronous
+ * on the context's stream; profiled as unpack_pcm16 / unpack_pcm24 / unpack_pcm32 / unpack_f32 / unpack_f64.
+ * VBX_E_INVALID: an unknown format, channels < 1, channel outside [0, channels), a NULL pointer with n_sample_frames > 0, a
+ * misaligned pointer.  n_sample_frames == 0 succeeds. */
+#define VBX_SAMPLE_PCM16 1
+#define VBX_SAMPLE_PCM24 2
+#define VBX_SAMPLE_PCM32 3
+#define VBX_SAMPLE_F32 4
+#define VBX_SAMPLE_F64 5
+int vbx_unpack_samples(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames, int format, int channels, int channel, void *d_out);
+
+/* The frame loop on a recording that lives in HOST memory, of any length, from one call: vbx_analyze_frames_ex_* fed chunk by chunk.
+ * h_audio holds n_sample_frames interleaved sample frames in h_fmt->format; channel h_fmt->channel is analysed;
+ * F = vbx_frame_count(n_sample_frames, frame_len, stride) frames.  out_records [F, record_ld], status3 [3, F] (optional) and the
+ * h_outputs arrays (F rows each) are DEVICE memory: the recording itself is never resident, only the records are (288 B per frame
+ * with all parts on).
+ * Contract: every byte written to out_records, status3 and the four h_outputs arrays equals, bit for bit, what the resident call
+ * writes on the whole selected channel -- vbx_analyze_frames_ex_pcm16 for PCM16, vbx_analyze_frames_ex_f32in for F32,
+ * vbx_analyze_frames_ex_f64 on the converted samples (vbx_unpack_samples) for PCM24, PCM32 and F64 -- for every
+ * chunk_frames >= VBX_SHARD_WARM_FRAMES, every segment list, the plain, tracked and ext forms, every LPC policy, pinned and pageable
+ * h_audio (tests/test_gpu_analyze_host.py).  Where the mono PCM16 / F32 call reads the samples without a copy (1200-sample frames:
+ * the rule of vbx_analyze_frames_pcm16) the chunks do too; elsewhere the widening pass runs per chunk into the context-owned copy,
+ * which is then chunk-sized.
+ * How.  Chunk c covers frames [lo, hi) = [c * chunk_frames, ...) (vbx_host_chunk_plan).  Its sample frames -- those of frames
+ * [lo - warm, hi), i.e. with the frame_len - stride halo -- are uploaded on a context-owned copy stream into one of two raw staging
+ * slots; the upload of chunk c + 1 is issued before chunk c's analysis is queued.  On the context's stream, behind the upload:
+ * vbx_unpack_samples into a typed chunk buffer (skipped for mono PCM16 / F32 / F64: the slot is read as it is), the frame loop on
+ * frames [lo - warm, hi) into chunk-local records and status rows, the formant tracker's stitch from row lo - 1 of out_records
+ * when the cut lies inside an utterance (vbx_track_stitch_f64: the warm-up and the exact repair of the sharded runs below), and a
+ * copy of the chunk's own rows into place.  The tracked form writes each chunk's candidate lists, counts and peaks at their global
+ * offsets -- the caller's h_outputs arrays, or a context workspace of F * (16 kmax + 16) bytes -- and runs the pitch path ONCE over
+ * the whole recording behind the last chunk, straight into columns 0-1: the lists are per frame and all there, so the contour is
+ * vbx_pitch_path_f64's by construction.
+ * Device memory in use: the two raw slots, the typed chunk buffer, the chunk-local records and status rows, the frame loop's own
+ * chunk-sized workspaces, the caller's outputs.
+ * Host timing: the call returns when the last byte of h_audio has been read (the caller may free or overwrite it); kernels may still
+ * be running, and the outputs are ordered on the context's stream like every call's.  Pinned h_audio (vbx_malloc_host) is uploaded
+ * beside the previous chunk's analysis; pageable memory works, but nothing overlaps.  vbx_sync drains the copy stream too.
+ * Host calls may follow one another on a context with no wait between them (the channels of a stereo file are two calls): every
+ * upload waits for its staging slot's last reader, the previous call's included.
+ * Afterwards the vbx_internal_last_* probes describe the LAST chunk's call only (not part of the contract), and the context holds
+ * no state for vbx_track_stitch_f64, which returns VBX_E_INVALID.  Not capturable into a graph.
+ * h_fmt->chunk_frames: analysis frames per chunk; 0 = the library's default, 250,000 frames (120 M samples at a 480-sample hop).
+ * VBX_E_INVALID, before anything is written and with the context left usable: a NULL h_fmt, an unknown format, channels < 1,
+ * channel outside [0, channels), reserved != 0, a NULL h_audio with F > 0, 0 < chunk_frames < VBX_SHARD_WARM_FRAMES, anything the
+ * resident call rejects.  F == 0 succeeds. */
+typedef struct {
+    int32_t format;        /* VBX_SAMPLE_* */
+    int32_t channels;      /* >= 1, interleaved */
+    int32_t channel;       /* the one analysed, < channels */
+    int32_t reserved;      /* 0 */
+    size_t  chunk_frames;  /* analysis frames per chunk; 0: the library's default (250,000) */
+} vbx_host_audio;
+#define VBX_HOST_DEFAULT_CHUNK_FRAMES 250000
+
+int vbx_analyze_host(vbx_ctx *ctx, const void *h_audio, size_t n_sample_frames, const vbx_host_audio *h_fmt,
+                     size_t frame_len, size_t stride,
+                     const vbx_analysis_params *h_params, const vbx_analysis_ext *h_ext, const vbx_pitch_track_params *h_track,
+                     const int64_t *h_seg_start, size_t n_segments,
+                     double *out_records /* device */, size_t record_ld, int32_t *status3 /* device, [3, F] */,
+                     const vbx_pitch_track_outputs *h_outputs /* device arrays of F rows */);
+/* pinned host memory for h_audio (hipHostMalloc / hipHostFree): uploads from it overlap the analysis */
+int vbx_malloc_host(vbx_ctx *ctx, void **out, size_t bytes);
+int vbx_free_host(vbx_ctx *ctx, void *p);
+
 /* ------------------------------------------------------------------ multi-GPU: frame-range sharding */
 
 /* The reference has no distribution of any kind; frames are independent (the tracker per utterance), so a long
@@ -736,6 +814,15 @@ typedef struct {
 int vbx_shard_plan(size_t n_frames, int world, int rank, const int64_t *h_seg_start, size_t n_segments, vbx_shard_plan_t *h_out);
 int vbx_shard_local_segments(const vbx_shard_plan_t *h_plan, const int64_t *h_seg_start, size_t n_segments,
                              int64_t *h_out, size_t cap, size_t *n_out);
+/* Pure host arithmetic: chunk c of a host-resident recording of n_frames frames cut every chunk_frames frames (vbx_analyze_host).
+ * h_out: lo, hi = the chunk's own frames [c * chunk_frames, min(n_frames, (c + 1) * chunk_frames)); warm = min(frames since the
+ * utterance of frame lo began, VBX_SHARD_WARM_FRAMES) frames analysed before them; stop = index, counted from frame lo - warm, at
+ * which that utterance ends inside the chunk (or the chunk's end); continues_prev: frame lo is not an utterance start (the tracker's
+ * state comes from row lo - 1; with warm < VBX_SHARD_WARM_FRAMES the warm-up began at the utterance's start and the stitch changes
+ * nothing); continues_next: the same for frame hi.  [*s0, *s1): the sample frames of frames [lo - warm, hi), what the chunk uploads.
+ * VBX_E_INVALID: a NULL output, chunk_frames 0, frame_len or stride 0, c beyond the last chunk, a bad segment list. */
+int vbx_host_chunk_plan(size_t n_frames, size_t chunk_frames, size_t c, size_t frame_len, size_t stride,
+                        const int64_t *h_seg_start, size_t n_segments, vbx_shard_plan_t *h_out, size_t *s0, size_t *s1);
 /* Step 2 on one device: `formants` are the rows the LAST vbx_find_formants_f64 (out_formants, formants_ld = 2 n_est) or
  * vbx_analyze_frames_* call (out_records + 2, formants_ld = record_ld) on this context wrote, n_frames of them (call it right
  * after that call: it reads the resonance rows the context still holds); d_state_in (device, n_est entries) is the true state

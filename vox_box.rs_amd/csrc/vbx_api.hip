@@ -51,7 +51,7 @@ struct vbx_ctx {
     std::string arch;
     int cu_count = 0;
     // workspaces (grown on demand, never shrunk)
-    enum { WS_COEFFS, WS_RES, WS_COUNT, WS_STATUS, WS_MISC, WS_SEG, WS_EST, WS_UNSURE, WS_F32_IN, WS_F32_OUT, WS_TRK, WS_BURG_LIST, WS_ROOTS_LIST, WS_LONG, WS_LONG2, WS_CZT, WS_CURVE, WS_LPC_LIST, WS_PATH, WS_PATH_TAB, WS_TRACK, WS_EX, WS_N };
+    enum { WS_COEFFS, WS_RES, WS_COUNT, WS_STATUS, WS_MISC, WS_SEG, WS_EST, WS_UNSURE, WS_F32_IN, WS_F32_OUT, WS_TRK, WS_BURG_LIST, WS_ROOTS_LIST, WS_LONG, WS_LONG2, WS_CZT, WS_CURVE, WS_LPC_LIST, WS_PATH, WS_PATH_TAB, WS_TRACK, WS_EX, WS_HOST, WS_HOST_TYPED, WS_N };
     void *ws[WS_N] = {nullptr};
     const int32_t *burg_list_count = nullptr;             // device counter of the last one-pass Burg call (tests)
     const int32_t *roots_list_count = nullptr;            // the same for the resonance kernel of find_formants
@@ -106,6 +106,13 @@ struct vbx_ctx {
     bool path_last = false;
     // the scan vbx_pitch_path_shard_begin_f64 left in WS_PATH for _enter / _finish; any other path or frame-batch call ends it
     struct { bool live = false, entered = false; pp_plan_t S; int prev = 0, next = 0; } shard;
+    // vbx_analyze_host: the copy stream, the two raw staging slots of a chunk's bytes and their events -- ready: the upload has
+    // landed (the context's stream waits for it); freed: the slot's last reader on the context's stream is through (the copy stream
+    // waits for it before the next upload into the slot)
+    hipStream_t copy = nullptr;
+    void *host_raw[2] = {nullptr, nullptr};
+    size_t host_raw_bytes = 0;
+    hipEvent_t host_ready[2] = {nullptr, nullptr}, host_freed[2] = {nullptr, nullptr};
 };
 
 namespace {
@@ -329,6 +336,12 @@ void vbx_ctx_destroy(vbx_ctx *ctx) {
     for (auto &e : ctx->ev_slice) if (e) hipEventDestroy(e);
     if (ctx->ev_trk) hipEventDestroy(ctx->ev_trk);
     if (ctx->trk) { hipStreamSynchronize(ctx->trk); hipStreamDestroy(ctx->trk); }
+    if (ctx->copy) { hipStreamSynchronize(ctx->copy); hipStreamDestroy(ctx->copy); }
+    for (int i = 0; i < 2; i++) {
+        if (ctx->host_raw[i]) hipFree(ctx->host_raw[i]);
+        if (ctx->host_ready[i]) hipEventDestroy(ctx->host_ready[i]);
+        if (ctx->host_freed[i]) hipEventDestroy(ctx->host_freed[i]);
+    }
     for (int i = 0; i < 3; i++) { if (ctx->stage[i]) hipHostFree(ctx->stage[i]); if (ctx->stage_ev[i]) hipEventDestroy(ctx->stage_ev[i]); }
     if (ctx->t0) hipEventDestroy(ctx->t0);
     if (ctx->t1) hipEventDestroy(ctx->t1);
@@ -343,6 +356,7 @@ int vbx_sync(vbx_ctx *ctx) {
     // costs nothing and makes "after vbx_sync nothing of this context runs" hold by construction (buffers may be freed)
     if (ctx->side) VBX_HIP(ctx, hipStreamSynchronize(ctx->side));
     if (ctx->trk) VBX_HIP(ctx, hipStreamSynchronize(ctx->trk));
+    if (ctx->copy) VBX_HIP(ctx, hipStreamSynchronize(ctx->copy));       // (vbx_analyze_host's uploads: idle once that call has returned)
     return VBX_SUCCESS;
 }
 
@@ -1601,7 +1615,8 @@ static int run_pitch_path(vbx_ctx *ctx, hipStream_t st, const vbx_pitch *cand, c
                           const vbx_pitch_path_params &pr, vbx_pitch *out_path, size_t path_ld, int32_t *out_index, const char *fn);
 
 // vbx_analyze_frames_tracked_*: columns 0-1 of the records are the pitch path over the call's own kmax-entry lists
-struct track_req_t { size_t kmax; vbx_pitch_path_params path; vbx_pitch_track_outputs out; };
+// (defer_path: the lists, counts and peaks only -- vbx_analyze_host runs ONE path over the whole recording behind its last chunk)
+struct track_req_t { size_t kmax; vbx_pitch_path_params path; vbx_pitch_track_outputs out; bool defer_path; };
 // vbx_analyze_frames_ex_*: find_formants on the frames' resampled view (rp non-null) at formant_rate, and the RMS column
 struct ex_req_t { const resample_plan_t *rp; double formant_rate; bool rms; };
 
@@ -1827,7 +1842,7 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
                        h_p->pitch_fmin, h_p->pitch_fmax, 1, (vbx_pitch *)out_records, record_ld, nullptr, st_pitch);
     }
     if (rc != VBX_SUCCESS) return rc;
-    if (tk) {
+    if (tk && !tk->defer_path) {
         // the path over those lists, on the context's stream behind the kernel that wrote them: its rows are columns 0-1 of the records
         if (tk_peak) VBX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_peak, 0));
         rc = run_pitch_path(ctx, ctx->stream, tk_cand, tk_count, st_pitch, n_frames, tk->kmax, tk_peak, h_seg_start, n_segments, tk->path,
@@ -1913,7 +1928,8 @@ static int make_resample_plan(vbx_ctx *ctx, const char *fn, double ratio, size_t
 static int analyze_ex(vbx_ctx *ctx, const char *fn, const double *x, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
                       const vbx_analysis_params *h_p, const vbx_analysis_ext *h_ext, const vbx_pitch_track_params *h_track,
                       const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld, int32_t *status3,
-                      const vbx_pitch_track_outputs *h_out, const float *f32 = nullptr /* the frames as float32 samples instead of x / pcm */) {
+                      const vbx_pitch_track_outputs *h_out, const float *f32 = nullptr /* the frames as float32 samples instead of x / pcm */,
+                      bool defer_path = false /* vbx_analyze_host's chunks: track_req_t */) {
     if (!ctx) return fail(nullptr, VBX_E_INVALID, std::string(fn) + ": null context");
     if (!h_p) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": null argument");
     resample_plan_t rp{}; ex_req_t ex{nullptr, h_p->sample_rate, false};
@@ -1936,6 +1952,7 @@ static int analyze_ex(vbx_ctx *ctx, const char *fn, const double *x, const int16
     track_req_t tk{};
     tk.kmax = h_track->kmax; tk.path = h_track->path;
     if (h_out) tk.out = *h_out;
+    tk.defer_path = defer_path;
     if (tk.path.time_step == 0.0) tk.path.time_step = (double)stride / h_p->sample_rate;      // the batch's own hop
     int rc = check_pitch_path(ctx, fn, tk.path, n_frames, tk.kmax, true, h_seg_start, n_segments);
     if (rc != VBX_SUCCESS) return rc;
@@ -1966,6 +1983,219 @@ int vbx_analyze_frames_ex_f32in(vbx_ctx *ctx, const float *x, size_t n_frames, s
     if (n_frames != 0 && ctx && !x) return fail(ctx, VBX_E_INVALID, "vbx_analyze_frames_ex_f32in: null frame pointer");
     return analyze_ex(ctx, __func__, nullptr, nullptr, n_frames, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, out_records,
                       record_ld, status3, h_outputs, x);
+}
+
+// ---- host-resident recordings (header: "host-resident recordings") ---------------------------
+
+static const char *const k_unpack_names[6] = {"", "unpack_pcm16", "unpack_pcm24", "unpack_pcm32", "unpack_f32", "unpack_f64"};
+static bool sample_format_ok(int f) { return f >= VBX_SAMPLE_PCM16 && f <= VBX_SAMPLE_F64; }
+static size_t sample_src_bytes(int f) { return f == VBX_SAMPLE_PCM16 ? 2 : f == VBX_SAMPLE_PCM24 ? 3 : f == VBX_SAMPLE_F64 ? 8 : 4; }
+static size_t sample_out_bytes(int f) { return f == VBX_SAMPLE_PCM16 ? 2 : f == VBX_SAMPLE_F32 ? 4 : 8; }
+
+int vbx_unpack_samples(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames, int format, int channels, int channel, void *d_out) {
+    VBX_REQUIRE(ctx, ctx != nullptr, "null context");
+    VBX_REQUIRE(ctx, sample_format_ok(format), "unknown sample format");
+    VBX_REQUIRE(ctx, channels >= 1 && channel >= 0 && channel < channels, "need channels >= 1 and 0 <= channel < channels");
+    if (n_sample_frames == 0) return VBX_SUCCESS;
+    VBX_REQUIRE(ctx, d_src && d_out, "null argument");
+    VBX_REQUIRE(ctx, format == VBX_SAMPLE_PCM24 || (uintptr_t)d_src % sample_src_bytes(format) == 0, "the source needs its type's alignment");
+    VBX_REQUIRE(ctx, (uintptr_t)d_out % sample_out_bytes(format) == 0, "the destination needs its type's alignment");
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    { Prof p(ctx, k_unpack_names[format]); launch_unpack(ctx->stream, format, d_src, n_sample_frames, (size_t)channels, (size_t)channel, d_out); }
+    return check_launch(ctx, __func__);
+}
+
+int vbx_malloc_host(vbx_ctx *ctx, void **out, size_t bytes) {
+    VBX_REQUIRE(ctx, ctx && out, "null argument");
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    VBX_HIP(ctx, hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault));
+    return VBX_SUCCESS;
+}
+
+int vbx_free_host(vbx_ctx *ctx, void *p) {
+    VBX_REQUIRE(ctx, ctx != nullptr, "null context");
+    if (!p) return VBX_SUCCESS;
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    VBX_HIP(ctx, hipHostFree(p));
+    return VBX_SUCCESS;
+}
+
+// the copy stream, the slots' events and the two raw slots of `bytes` each (grown on demand: both streams are drained first)
+static int ensure_host_slots(vbx_ctx *ctx, size_t bytes) {
+    if (!ctx->copy) {
+        VBX_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy, hipStreamNonBlocking));
+        for (int i = 0; i < 2; i++) {
+            VBX_HIP(ctx, hipEventCreateWithFlags(&ctx->host_ready[i], hipEventDisableTiming));
+            VBX_HIP(ctx, hipEventCreateWithFlags(&ctx->host_freed[i], hipEventDisableTiming));
+        }
+    }
+    if (ctx->host_raw_bytes >= bytes) return VBX_SUCCESS;
+    VBX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    VBX_HIP(ctx, hipStreamSynchronize(ctx->copy));
+    for (int i = 0; i < 2; i++) if (ctx->host_raw[i]) { VBX_HIP(ctx, hipFree(ctx->host_raw[i])); ctx->host_raw[i] = nullptr; }
+    ctx->host_raw_bytes = 0;
+    const size_t cap = bytes + bytes / 8;
+    for (int i = 0; i < 2; i++) VBX_HIP(ctx, hipMalloc(&ctx->host_raw[i], cap));
+    ctx->host_raw_bytes = cap;
+    return VBX_SUCCESS;
+}
+
+int vbx_analyze_host(vbx_ctx *ctx, const void *h_audio, size_t n_sample_frames, const vbx_host_audio *h_fmt, size_t frame_len, size_t stride,
+                     const vbx_analysis_params *h_p, const vbx_analysis_ext *h_ext, const vbx_pitch_track_params *h_track,
+                     const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld, int32_t *status3,
+                     const vbx_pitch_track_outputs *h_outputs) {
+    const char *fn = __func__;
+    if (!ctx) return fail(nullptr, VBX_E_INVALID, "vbx_analyze_host: null context");
+    VBX_REQUIRE(ctx, h_fmt != nullptr, "null format");
+    VBX_REQUIRE(ctx, sample_format_ok(h_fmt->format), "unknown sample format");
+    VBX_REQUIRE(ctx, h_fmt->channels >= 1 && h_fmt->channel >= 0 && h_fmt->channel < h_fmt->channels, "need channels >= 1 and 0 <= channel < channels");
+    VBX_REQUIRE(ctx, h_fmt->reserved == 0, "reserved must be 0");
+    VBX_REQUIRE(ctx, h_fmt->chunk_frames == 0 || h_fmt->chunk_frames >= (size_t)VBX_SHARD_WARM_FRAMES, "chunk_frames must be 0 or >= VBX_SHARD_WARM_FRAMES");
+    VBX_REQUIRE(ctx, h_p != nullptr, "null argument");
+    const size_t F = vbx_frame_count(n_sample_frames, frame_len, stride);
+    if (F == 0)                                           // the resident call's empty batch: its checks, its state
+        return analyze_ex(ctx, fn, nullptr, nullptr, 0, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, out_records, record_ld,
+                          status3, h_outputs);
+    // what the resident call rejects from its arguments alone, asked first: nothing is uploaded or written for such a call.  (What
+    // only the parts themselves know -- orders, the resampled shape, the MFCC geometry -- is rejected by the first chunk's call,
+    // which has written nothing of the caller's by then: its records are chunk-local.)
+    VBX_REQUIRE(ctx, h_audio != nullptr, "null audio");
+    VBX_REQUIRE(ctx, frame_len <= VBX_MAX_LONG_FRAME_LEN, "frame_len must be in [1, 67108864]");
+    VBX_REQUIRE(ctx, F <= 0x7fffffffull, "too many frames for one launch");
+    VBX_REQUIRE(ctx, out_records != nullptr, "null argument");
+    const size_t rec = vbx_record_doubles_ex(h_p, h_ext);
+    VBX_REQUIRE(ctx, record_ld >= rec && record_ld % 2 == 0, "record_ld must be even and >= vbx_record_doubles(params)");
+    VBX_REQUIRE(ctx, ((uintptr_t)out_records & 15) == 0, "records must be 16-byte aligned");
+    VBX_REQUIRE(ctx, !h_p->formant_order || (h_p->n_est >= 1 && h_p->n_est <= VBX_FORMANT_SLOTS), "n_est must be in [1, 6]");
+    const bool segmented = h_seg_start != nullptr && n_segments > 0;
+    if (segmented) {
+        VBX_REQUIRE(ctx, h_seg_start[0] == 0, "seg_start[0] must be 0");
+        for (size_t i = 1; i < n_segments; i++)
+            VBX_REQUIRE(ctx, h_seg_start[i] >= h_seg_start[i - 1] && (size_t)h_seg_start[i] <= F, "seg_start must ascend within [0, n_frames]");
+    }
+    vbx_pitch_path_params path{};
+    size_t kmax = 0;
+    bool need_peak = false;
+    if (h_track) {
+        kmax = h_track->kmax; path = h_track->path;
+        if (path.time_step == 0.0) path.time_step = (double)stride / h_p->sample_rate;        // the batch's own hop
+        int rc = check_pitch_path(ctx, fn, path, F, kmax, true, h_seg_start, n_segments);
+        if (rc != VBX_SUCCESS) return rc;
+        need_peak = path.silence_threshold != 0.0 || (h_outputs && h_outputs->peak);
+    }
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+
+    const int fmt = h_fmt->format;
+    const size_t C = (size_t)h_fmt->channels, ch = (size_t)h_fmt->channel;
+    size_t cf = h_fmt->chunk_frames ? h_fmt->chunk_frames : (size_t)VBX_HOST_DEFAULT_CHUNK_FRAMES;
+    if (cf > F) cf = F;                                   // one chunk (and no overflow in the sizes below)
+    const size_t nc = (F + cf - 1) / cf;
+    const size_t nmax = (nc == 1) ? F : (cf + VBX_SHARD_WARM_FRAMES < F ? cf + VBX_SHARD_WARM_FRAMES : F);
+    const size_t ns_max = (nmax - 1) * stride + frame_len;                    // sample frames of the largest chunk
+    const size_t sf_bytes = C * sample_src_bytes(fmt);                        // one interleaved sample frame
+    // mono PCM16 / F32 / F64: the slot holds the frame loop's type already
+    const bool unpack = !(C == 1 && (fmt == VBX_SAMPLE_PCM16 || fmt == VBX_SAMPLE_F32 || fmt == VBX_SAMPLE_F64));
+    int rc = ensure_host_slots(ctx, ns_max * sf_bytes);
+    if (rc != VBX_SUCCESS) return rc;
+    void *typed = nullptr;
+    if (unpack) {
+        rc = ws_get(ctx, vbx_ctx::WS_HOST_TYPED, ns_max * sample_out_bytes(fmt), &typed);
+        if (rc != VBX_SUCCESS) return rc;
+    }
+    // chunk-local records and status rows; the tracked form's whole-recording arrays where the caller keeps none
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t ld_c = rec + (rec & 1);
+    const size_t b_rec = up(nmax * ld_c * sizeof(double)), b_st = up(3 * nmax * sizeof(int32_t));
+    const size_t b_cand = (h_track && !(h_outputs && h_outputs->cand)) ? up(F * kmax * sizeof(vbx_pitch)) : 0,
+                 b_peak = (need_peak && !(h_outputs && h_outputs->peak)) ? up(F * sizeof(double)) : 0,
+                 b_count = (h_track && !(h_outputs && h_outputs->count)) ? up(F * sizeof(int32_t)) : 0,
+                 b_gst = (h_track && !status3) ? up(3 * F * sizeof(int32_t)) : 0;
+    void *w = nullptr;
+    rc = ws_get(ctx, vbx_ctx::WS_HOST, b_rec + b_st + b_cand + b_peak + b_count + b_gst, &w);
+    if (rc != VBX_SUCCESS) return rc;
+    char *q = static_cast<char *>(w);
+    double *c_rec = reinterpret_cast<double *>(q); q += b_rec;
+    int32_t *c_st = reinterpret_cast<int32_t *>(q); q += b_st;
+    vbx_pitch *g_cand = h_outputs ? h_outputs->cand : nullptr;
+    double *g_peak = (h_outputs && need_peak) ? h_outputs->peak : nullptr;
+    int32_t *g_count = h_outputs ? h_outputs->count : nullptr, *g_st = status3;
+    if (b_cand) { g_cand = reinterpret_cast<vbx_pitch *>(q); q += b_cand; }
+    if (b_peak) { g_peak = reinterpret_cast<double *>(q); q += b_peak; }
+    if (b_count) { g_count = reinterpret_cast<int32_t *>(q); q += b_count; }
+    if (b_gst) g_st = reinterpret_cast<int32_t *>(q);
+
+    vbx_shard_plan_t pl{};
+    size_t s0 = 0, s1 = 0;
+    auto upload = [&](size_t c) -> int {                  // chunk c's bytes into slot c & 1, on the copy stream
+        vbx_shard_plan_t p{}; size_t a = 0, b = 0;
+        if (vbx_host_chunk_plan(F, cf, c, frame_len, stride, h_seg_start, n_segments, &p, &a, &b) != VBX_SUCCESS)
+            return fail(ctx, VBX_E_INVALID, std::string(fn) + ": bad chunk plan");
+        const int slot = (int)(c & 1);
+        // behind the slot's last reader -- chunk c - 2's, or for the first two chunks the PREVIOUS call's last chunks, whose kernels may
+        // still be queued when this call begins (an event that was never recorded is complete)
+        VBX_HIP(ctx, hipStreamWaitEvent(ctx->copy, ctx->host_freed[slot], 0));
+        VBX_HIP(ctx, hipMemcpyAsync(ctx->host_raw[slot], static_cast<const char *>(h_audio) + a * sf_bytes, (b - a) * sf_bytes,
+                                    hipMemcpyHostToDevice, ctx->copy));
+        VBX_HIP(ctx, hipEventRecord(ctx->host_ready[slot], ctx->copy));
+        return VBX_SUCCESS;
+    };
+    auto bail = [&](int code) { hipStreamSynchronize(ctx->copy); return code; };      // h_audio is not read after the call returns
+    std::vector<int64_t> lseg;
+    rc = upload(0);
+    if (rc != VBX_SUCCESS) return bail(rc);
+    for (size_t c = 0; c < nc; c++) {
+        // the next chunk's upload is issued first: this chunk's analysis may block the host on its segment list's upload
+        if (c + 1 < nc) { rc = upload(c + 1); if (rc != VBX_SUCCESS) return bail(rc); }
+        if (vbx_host_chunk_plan(F, cf, c, frame_len, stride, h_seg_start, n_segments, &pl, &s0, &s1) != VBX_SUCCESS)
+            return bail(fail(ctx, VBX_E_INVALID, std::string(fn) + ": bad chunk plan"));
+        const int slot = (int)(c & 1);
+        const size_t first = pl.lo - pl.warm, n = pl.hi - first, own = pl.hi - pl.lo;
+        VBX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->host_ready[slot], 0));
+        const void *xs = ctx->host_raw[slot];
+        if (unpack) {
+            { Prof p(ctx, k_unpack_names[fmt]); launch_unpack(ctx->stream, fmt, ctx->host_raw[slot], s1 - s0, C, ch, typed); }
+            VBX_HIP(ctx, hipEventRecord(ctx->host_freed[slot], ctx->stream));
+            xs = typed;
+        }
+        const int64_t *seg_c = nullptr; size_t nseg_c = 0;
+        if (segmented) {
+            size_t need = 0;
+            vbx_shard_local_segments(&pl, h_seg_start, n_segments, nullptr, 0, &need);
+            lseg.resize(need);
+            if (vbx_shard_local_segments(&pl, h_seg_start, n_segments, lseg.data(), need, &need) != VBX_SUCCESS)
+                return bail(fail(ctx, VBX_E_INVALID, std::string(fn) + ": bad chunk plan"));
+            seg_c = lseg.data(); nseg_c = need;
+        }
+        vbx_pitch_track_outputs to{};
+        if (h_track) { to.cand = g_cand + first * kmax; to.count = g_count + first; to.peak = g_peak ? g_peak + first : nullptr; }
+        const bool as_pcm = fmt == VBX_SAMPLE_PCM16, as_f32 = fmt == VBX_SAMPLE_F32;
+        rc = analyze_ex(ctx, fn, (as_pcm || as_f32) ? nullptr : static_cast<const double *>(xs), as_pcm ? static_cast<const int16_t *>(xs) : nullptr,
+                        n, frame_len, stride, h_p, h_ext, h_track, seg_c, nseg_c, c_rec, ld_c, c_st, h_track ? &to : nullptr,
+                        as_f32 ? static_cast<const float *>(xs) : nullptr, true);
+        if (rc != VBX_SUCCESS) return bail(rc);
+        if (!unpack) VBX_HIP(ctx, hipEventRecord(ctx->host_freed[slot], ctx->stream));
+        // a cut inside an utterance: the tracker continues from the true state, the row before the cut (already in place)
+        if (pl.continues_prev && h_p->formant_order) {
+            rc = vbx_internal_track_stitch(ctx, nullptr, reinterpret_cast<vbx_resonance *>(c_rec + 2), n, ld_c, pl.warm, pl.stop,
+                                           out_records + (pl.lo - 1) * record_ld + 2, nullptr);
+            if (rc != VBX_SUCCESS) return bail(rc);
+        }
+        { Prof p(ctx, "host_rows");
+          launch_host_rows(ctx->stream, c_rec, ld_c, pl.warm, own, h_track ? 2 : 0, rec, out_records + pl.lo * record_ld, record_ld,
+                           c_st, n, g_st ? g_st + pl.lo : nullptr, F); }
+    }
+    rc = check_launch(ctx, fn);
+    if (rc != VBX_SUCCESS) return bail(rc);
+    if (h_track) {
+        // ONE path over the whole recording's lists, behind the last chunk, straight into columns 0-1
+        rc = run_pitch_path(ctx, ctx->stream, g_cand, g_count, g_st, F, kmax, g_peak, h_seg_start, n_segments, path,
+                            reinterpret_cast<vbx_pitch *>(out_records), record_ld, h_outputs ? h_outputs->index : nullptr, fn);
+        if (rc != VBX_SUCCESS) return bail(rc);
+    }
+    ctx->last_track.res = nullptr;                        // the chunk-local rows are no track of the caller's: nothing to stitch
+    ctx->last_track.n_est = 0;
+    VBX_HIP(ctx, hipEventSynchronize(ctx->host_ready[(nc - 1) & 1]));      // the last byte of h_audio has been read
+    return VBX_SUCCESS;
 }
 
 int vbx_find_formants_resampled_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,

@@ -460,5 +460,29 @@ int vbx_shard_samples(size_t lo, size_t hi, size_t frame_len, size_t hop, size_t
     return VBX_SUCCESS;
 }
 
+// Chunk c of a host-resident recording (vbx_analyze_host): the shard plan's arithmetic on cuts every chunk_frames frames.  Unlike
+// vbx_shard_plan, continues_prev is set for EVERY cut inside an utterance, a short warm-up included: the previous chunk's rows are at
+// hand on the same device, so the stitch always runs there (and finds nothing to redo when the warm-up began at the utterance's start).
+int vbx_host_chunk_plan(size_t n_frames, size_t chunk_frames, size_t c, size_t frame_len, size_t stride,
+                        const int64_t *h_seg_start, size_t n_segments, vbx_shard_plan_t *out, size_t *s0, size_t *s1) {
+    if (!out || !s0 || !s1 || chunk_frames < 1 || frame_len < 1 || stride < 1) return fail(nullptr, VBX_E_INVALID, "vbx_host_chunk_plan: bad argument");
+    if (h_seg_start && n_segments > 0) {
+        if (h_seg_start[0] != 0) return fail(nullptr, VBX_E_INVALID, "vbx_host_chunk_plan: seg_start[0] must be 0");
+        for (size_t i = 1; i < n_segments; i++)
+            if (h_seg_start[i] < h_seg_start[i - 1]) return fail(nullptr, VBX_E_INVALID, "vbx_host_chunk_plan: seg_start must ascend");
+    }
+    if (c >= n_frames / chunk_frames + (n_frames % chunk_frames != 0)) return fail(nullptr, VBX_E_INVALID, "vbx_host_chunk_plan: no such chunk");
+    const size_t lo = c * chunk_frames, hi = (n_frames - lo > chunk_frames) ? lo + chunk_frames : n_frames;
+    auto inside = [&](size_t f) { return f > 0 && f < n_frames && seg_start_of(h_seg_start, n_segments, f) != f; };
+    const size_t back = lo - seg_start_of(h_seg_start, n_segments, lo);
+    out->lo = lo; out->hi = hi;
+    out->warm = back < (size_t)VBX_SHARD_WARM_FRAMES ? back : (size_t)VBX_SHARD_WARM_FRAMES;
+    out->continues_prev = inside(lo) ? 1 : 0;
+    out->continues_next = inside(hi) ? 1 : 0;
+    const size_t next = seg_start_after(h_seg_start, n_segments, lo, n_frames);
+    out->stop = ((next < hi) ? next : hi) - (lo - out->warm);
+    return vbx_shard_samples(lo - out->warm, hi, frame_len, stride, s0, s1);
+}
+
 
 }  // extern "C"

@@ -324,6 +324,16 @@ void launch_frame_peak_pcm16(hipStream_t s, const int16_t *pcm, long F, long n, 
 void launch_rms(hipStream_t s, const double *x, long F, int n, long stride, const double *window, double *out);
 void launch_preemphasis(hipStream_t s, const double *x, long F, int n, long stride, double c, double *out);
 
+// k_reader.hip: channel `channel` of n interleaved sample frames of `channels` samples each, as the type the frame loop reads natively
+// (format = VBX_SAMPLE_* of the C header: out is int16 for PCM16, float for F32, double for PCM24 / PCM32 / F64; PCM24 / PCM32 are
+// divided by 8388607 / 2147483647 with IEEE division).  A PCM24 source may sit at any byte address, the others need their type's.
+enum { UNPACK_PCM16 = 1, UNPACK_PCM24 = 2, UNPACK_PCM32 = 3, UNPACK_F32 = 4, UNPACK_F64 = 5 };
+void launch_unpack(hipStream_t s, int format, const void *src, size_t n, size_t channels, size_t channel, void *out);
+// vbx_analyze_host: rows [row0, row0 + rows) x columns [c0, c1) of a chunk's records and of its [3, src_n] status rows into the caller's
+// (dst, dst_st point at the chunk's first own row / column; dst_st may be null)
+void launch_host_rows(hipStream_t s, const double *src, size_t src_ld, size_t row0, size_t rows, size_t c0, size_t c1, double *dst,
+                      size_t dst_ld, const int32_t *src_st, size_t src_n, int32_t *dst_st, size_t dst_n);
+
 // k_front_ex.hip: RMS::rms of the rectangular frame (launch_rms with a null window, bit for bit) from the f64 view or from 16-bit
 // PCM, written at out_rms + f * rms_ld; out_peak non-null: launch_frame_peak / launch_frame_peak_pcm16 from the same read
 void launch_frame_rms(hipStream_t s, const double *x, const int16_t *pcm, long F, int n, long stride, double *out_rms, long rms_ld,

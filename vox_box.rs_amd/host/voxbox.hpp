@@ -392,6 +392,28 @@ inline void analyze_frames_ex_f32in(Context &c, const float *x, size_t n_frames,
     c.check(vbx_analyze_frames_ex_f32in(c.get(), x, n_frames, frame_len, stride, &p, ext, track, seg.h_seg_start, seg.n, records,
                                         record_ld, status3, outputs));
 }
+// The frame loop on a recording in HOST memory, of any length (vbx_analyze_host): h_audio holds n_sample_frames interleaved sample
+// frames in fmt.format, uploaded chunk by chunk beside the analysis; records / status3 / outputs are device memory and hold what the
+// resident call on the whole selected channel writes, bit for bit.  host_audio(): mono, the library's default chunk.
+using HostAudio = vbx_host_audio;
+inline HostAudio host_audio(int format, int channels = 1, int channel = 0, size_t chunk_frames = 0) {
+    HostAudio a{};
+    a.format = format; a.channels = channels; a.channel = channel; a.chunk_frames = chunk_frames;
+    return a;
+}
+inline void analyze_host(Context &c, const void *h_audio, size_t n_sample_frames, const HostAudio &fmt, size_t frame_len, size_t stride,
+                         const AnalysisParams &p, const AnalysisExt *ext, const PitchTrackParams *track, Segments seg,
+                         double *records, size_t record_ld, int32_t *status3 = nullptr, const PitchTrackOutputs *outputs = nullptr) {
+    c.check(vbx_analyze_host(c.get(), h_audio, n_sample_frames, &fmt, frame_len, stride, &p, ext, track, seg.h_seg_start, seg.n, records,
+                             record_ld, status3, outputs));
+}
+// one channel of interleaved sample frames on the device, as the type the frame loop reads (vbx_unpack_samples)
+inline void unpack_samples(Context &c, const void *d_src, size_t n_sample_frames, int format, int channels, int channel, void *d_out) {
+    c.check(vbx_unpack_samples(c.get(), d_src, n_sample_frames, format, channels, channel, d_out));
+}
+// pinned host memory for analyze_host's h_audio (vbx_malloc_host / vbx_free_host)
+inline void *malloc_host(Context &c, size_t bytes) { void *p = nullptr; c.check(vbx_malloc_host(c.get(), &p, bytes)); return p; }
+inline void free_host(Context &c, void *p) { c.check(vbx_free_host(c.get(), p)); }
 
 // Frame-range sharding of one recording over the GPUs of a node (no counterpart in the reference) and the gather of the
 // per-frame records to one rank: grouped ncclSend / ncclRecv inside the library, one communicator per process.

@@ -137,6 +137,26 @@ class AnalysisExt(C.Structure):
         return cls(formant_resample_ratio, formant_sample_rate, 1 if rms else 0)
 
 
+SAMPLE_PCM16, SAMPLE_PCM24, SAMPLE_PCM32, SAMPLE_F32, SAMPLE_F64 = 1, 2, 3, 4, 5
+_SAMPLE_OF_DTYPE = {np.dtype(np.int16): SAMPLE_PCM16, np.dtype(np.int32): SAMPLE_PCM32, np.dtype(np.float32): SAMPLE_F32,
+                    np.dtype(np.float64): SAMPLE_F64}
+_SAMPLE_SRC_BYTES = {SAMPLE_PCM16: 2, SAMPLE_PCM24: 3, SAMPLE_PCM32: 4, SAMPLE_F32: 4, SAMPLE_F64: 8}
+_SAMPLE_OUT_DTYPE = {SAMPLE_PCM16: np.int16, SAMPLE_PCM24: np.float64, SAMPLE_PCM32: np.float64, SAMPLE_F32: np.float32,
+                     SAMPLE_F64: np.float64}
+HOST_DEFAULT_CHUNK_FRAMES = 250000
+
+
+class HostAudio(C.Structure):
+    """vbx_host_audio: what vbx_analyze_host is handed -- the sample format (SAMPLE_*), the interleaved channel count, the channel
+    analysed, and the analysis frames per chunk (0: the library's default, HOST_DEFAULT_CHUNK_FRAMES)."""
+    _fields_ = [("format", C.c_int32), ("channels", C.c_int32), ("channel", C.c_int32), ("reserved", C.c_int32),
+                ("chunk_frames", C.c_size_t)]
+
+    @classmethod
+    def make(cls, format, channels=1, channel=0, chunk_frames=0):
+        return cls(int(format), int(channels), int(channel), 0, int(chunk_frames))
+
+
 _lib = None
 
 
@@ -262,6 +282,12 @@ def load_library():
                                                   C.POINTER(PitchTrackParams), vp, sz, vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
         "vbx_analyze_frames_ex_f32in": (C.c_int, [vp, vp, sz, sz, sz, C.POINTER(AnalysisParams), C.POINTER(AnalysisExt),
                                                   C.POINTER(PitchTrackParams), vp, sz, vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
+        "vbx_unpack_samples": (C.c_int, [vp, vp, sz, i32, i32, i32, vp]),
+        "vbx_analyze_host": (C.c_int, [vp, vp, sz, C.POINTER(HostAudio), sz, sz, C.POINTER(AnalysisParams), C.POINTER(AnalysisExt),
+                                       C.POINTER(PitchTrackParams), vp, sz, vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
+        "vbx_malloc_host": (C.c_int, [vp, C.POINTER(vp), sz]),
+        "vbx_free_host": (C.c_int, [vp, vp]),
+        "vbx_host_chunk_plan": (C.c_int, [sz, sz, sz, sz, sz, vp, sz, C.POINTER(ShardPlan), C.POINTER(sz), C.POINTER(sz)]),
         "vbx_find_formants_resampled_f64": (C.c_int, [vp, vp, sz, sz, sz, dbl, dbl, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp]),
         "vbx_shard_range": (C.c_int, [sz, i32, i32, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
         "vbx_shard_samples": (C.c_int, [sz, sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
@@ -372,6 +398,19 @@ def shard_local_segments(plan, seg_start=None):
     if L.vbx_shard_local_segments(C.byref(plan), sp, sn, out.ctypes.data, out.size, C.byref(n)) != 0:
         raise VoxBoxError("vbx_shard_local_segments: bad argument")
     return out
+
+
+def host_chunk_plan(n_frames, chunk_frames, c, frame_len, stride, seg_start=None):
+    """vbx_host_chunk_plan: chunk `c` of a host-resident recording cut every chunk_frames frames -- (plan, s0, s1): its own frames
+    [plan.lo, plan.hi), the warm-up before them, where the cut utterance ends, the continues_prev / continues_next flags, and the
+    sample frames [s0, s1) it uploads."""
+    plan, s0, s1 = ShardPlan(), C.c_size_t(), C.c_size_t()
+    seg = None if seg_start is None else np.ascontiguousarray(seg_start, dtype=np.int64)
+    rc = load_library().vbx_host_chunk_plan(n_frames, chunk_frames, c, frame_len, stride, None if seg is None else seg.ctypes.data,
+                                            0 if seg is None else seg.size, C.byref(plan), C.byref(s0), C.byref(s1))
+    if rc != 0:
+        raise VoxBoxError("vbx_host_chunk_plan: bad argument")
+    return plan, s0.value, s1.value
 
 
 def shard_samples(lo, hi, frame_len, hop):
@@ -489,6 +528,7 @@ class VoxBox:
     def __init__(self, device=0, stream=None, lpc_policy=None):
         self.L = load_library()
         self._allocs = set()
+        self._host_allocs = {}                  # pinned host memory of malloc_host: address -> the buffer object numpy views
         ctx = C.c_void_p()
         rc = self.L.vbx_ctx_create(C.byref(ctx), device, stream)
         if rc != 0:
@@ -539,6 +579,9 @@ class VoxBox:
         if getattr(self, "ctx", None):
             for a in list(self._allocs):
                 a.free()
+            for addr in list(self._host_allocs):
+                self._host_allocs.pop(addr)
+                self.L.vbx_free_host(self.ctx, addr)
             self.L.vbx_ctx_destroy(self.ctx)
             self.ctx = None
 
@@ -1263,6 +1306,73 @@ class VoxBox:
             ptr = _ptr(x)
         return self._analyze_tracked(self.L.vbx_analyze_frames_ex_f32in, ptr, int(n_frames), int(frame_len), int(stride), params,
                                      track, seg_start, out, record_ld, status, lists, outputs, tmp, ext=ext)
+
+    # -- host-resident recordings ------------------------------------------------------
+    def malloc_host(self, shape, dtype=np.uint8):
+        """vbx_malloc_host: pinned host memory as a numpy array (uploads from it overlap the analysis).  Release it with
+        free_host(array) once no view of it is in use; the context frees what is left when it closes."""
+        shape = (int(shape),) if np.isscalar(shape) else tuple(int(v) for v in shape)
+        dt = np.dtype(dtype)
+        nbytes = int(np.prod(shape)) * dt.itemsize
+        p = C.c_void_p()
+        self._check(self.L.vbx_malloc_host(self.ctx, C.byref(p), nbytes))
+        buf = (C.c_char * max(nbytes, 1)).from_address(p.value)
+        a = np.frombuffer(buf, dtype=dt, count=int(np.prod(shape))).reshape(shape)
+        self._host_allocs[p.value] = buf
+        return a
+
+    def free_host(self, a):
+        addr = a if isinstance(a, int) else a.ctypes.data
+        if self._host_allocs.pop(addr, None) is None:
+            raise ValueError("not an array malloc_host returned")
+        self._check(self.L.vbx_free_host(self.ctx, addr))
+
+    def unpack_samples(self, src, n_sample_frames, format, channels=1, channel=0, out=None):
+        """vbx_unpack_samples: channel `channel` of n interleaved sample frames on the device, as the type the frame loop reads
+        (int16 for PCM16, float32 for F32, float64 for PCM24 / PCM32 / F64).  src / out: device buffers or raw addresses."""
+        n = int(n_sample_frames)
+        o = out if out is not None else self.empty(n, _SAMPLE_OUT_DTYPE[format])
+        self._check(self.L.vbx_unpack_samples(self.ctx, _ptr(src), n, int(format), int(channels), int(channel), _ptr(o)))
+        return o
+
+    def analyze_host(self, audio, params, ext=None, track=None, format=None, channels=1, channel=0, chunk_frames=0, seg_start=None,
+                     frame_len=None, stride=None, n_sample_frames=None, out=None, record_ld=None, status=None, lists=False,
+                     outputs=None):
+        """vbx_analyze_host: the frame loop on a recording in HOST memory, chunk by chunk with the uploads overlapped; the recording
+        is never resident on the device, the records are.  audio: a numpy array of int16 / int32 / float32 / float64 shaped [T] or
+        [T, C] (format and channels follow from it); bytes / bytearray / a uint8 array of packed 24-bit PCM (format=SAMPLE_PCM24,
+        channels=); or a raw host address with format=, channels= and n_sample_frames=.  Returns what analyze_frames_ex returns."""
+        assert frame_len and stride
+        keep = audio
+        if isinstance(audio, (bytes, bytearray, memoryview)):
+            keep = np.frombuffer(audio, dtype=np.uint8)
+        if isinstance(keep, np.ndarray):
+            if keep.dtype == np.uint8:
+                fmt = SAMPLE_PCM24 if format is None else int(format)
+                assert fmt == SAMPLE_PCM24 and keep.ndim == 1
+                keep = np.ascontiguousarray(keep)
+                T = keep.size // (3 * int(channels))
+            else:
+                fmt = _SAMPLE_OF_DTYPE[keep.dtype]
+                assert format is None or int(format) == fmt
+                assert keep.ndim in (1, 2)
+                if keep.ndim == 2:
+                    channels = keep.shape[1]
+                keep = np.ascontiguousarray(keep)
+                T = keep.shape[0]
+            addr = keep.ctypes.data
+            n_sample_frames = T if n_sample_frames is None else int(n_sample_frames)
+            assert n_sample_frames <= T
+        else:
+            assert isinstance(audio, int) and format is not None and n_sample_frames is not None
+            fmt, addr = int(format), audio
+        hf = HostAudio.make(fmt, channels, channel, chunk_frames)
+        F = frame_count(int(n_sample_frames), int(frame_len), int(stride))
+
+        def fn(ctx, ptr, F_, N, S, *rest):
+            return self.L.vbx_analyze_host(ctx, ptr, int(n_sample_frames), C.byref(hf), N, S, *rest)
+        return self._analyze_tracked(fn, addr, F, int(frame_len), int(stride), params, track, seg_start, out, record_ld, status, lists,
+                                     outputs, None, ext=ext)
 
     # -- spectrum.rs: MFCC ------------------------------------------------------------
     def mfcc(self, x, num_coeffs, freq_bounds, sample_rate, frame_len=None, stride=None, n_frames=None,
