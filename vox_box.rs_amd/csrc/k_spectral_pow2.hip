@@ -83,7 +83,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
     wave_sync();
     pitch_params_t pp = a.pp;
     pp.ncurve = nst;
-    pitch_refine_store<2>(smem, a.n, pp, f, a.out_cand, a.cand_ld, a.out_count, a.pitch_status, a.work, 0.0, nullptr, &ncand, a.cand_cap);
+    pitch_refine_store<2, REFINE_LIST_CELL_NB>(smem, a.n, pp, f, a.out_cand, a.cand_ld, a.out_count, a.pitch_status, a.work, 0.0, nullptr, &ncand, a.cand_cap);
 }
 
 // the frames of far_list: the whole stored curve, every stage (what the fused kernel does after its transforms); a fixed grid over a count
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(64) void refine_far_kernel(const spectral_args_t a)
         for (int j = lane; j < (nst + Y_PAD + 1) / 2; j += 64) ys2[j] = row[j];
         const double unc_tol = a.curve_tol[fb];
         wave_sync();
-        if (!pitch_refine_store(smem, a.n, a.pp, f, a.out_cand, a.cand_ld, a.out_count, a.pitch_status, a.work, unc_tol, nullptr)) {
+        if (!pitch_refine_store<0, PITCH_CELL_NB>(smem, a.n, a.pp, f, a.out_cand, a.cand_ld, a.out_count, a.pitch_status, a.work, unc_tol, nullptr)) {
             if (lane == 0) a.unsure_list[atomicAdd(a.unsure_count, 1)] = (int32_t)f;
         }
     }

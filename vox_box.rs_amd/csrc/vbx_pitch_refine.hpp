@@ -133,11 +133,10 @@ __device__ __forceinline__ void sinc_stream_init(sinc_stream_t &s, const double 
     s.acc0 = 0.0; s.acc1 = 0.0;
 }
 
-// four terms; step = +-NSTEP (the side's direction)
+// four terms on samples the caller holds (s.yp is neither read nor stepped)
 template <int NSTEP>
-__device__ __forceinline__ void sinc_stream_block4(sinc_stream_t &s, const int step) {
+__device__ __forceinline__ void sinc_stream_block4(sinc_stream_t &s, const double y0, const double y1, const double y2, const double y3) {
     constexpr double S = (double)NSTEP;
-    const double y0 = s.yp[0], y1 = s.yp[step], y2 = s.yp[2 * step], y3 = s.yp[3 * step];
     const double p0 = s.pn, p1 = s.pn + S, p2 = s.pn + 2.0 * S, p3 = s.pn + 3.0 * S;
     const double q01 = p0 * p1, q23 = p2 * p3;
     const double r = rcp_nr1(q01 * q23);
@@ -152,14 +151,19 @@ __device__ __forceinline__ void sinc_stream_block4(sinc_stream_t &s, const int s
     s.acc0 += t3; s.acc1 = fma(t3, s.C, s.acc1);
     s.C += s.d; s.d = fma(-s.kappa, s.C, s.d);
     s.pn += 4.0 * S;
+}
+// the same on the stream's own samples; step = +-NSTEP (the side's direction)
+template <int NSTEP>
+__device__ __forceinline__ void sinc_stream_block4(sinc_stream_t &s, const int step) {
+    const double y0 = s.yp[0], y1 = s.yp[step], y2 = s.yp[2 * step], y3 = s.yp[3 * step];
+    sinc_stream_block4<NSTEP>(s, y0, y1, y2, y3);
     s.yp += 4 * step;
 }
 
-// 1..3 terms left: one more block, padded with zero-weight terms
+// 1..3 terms left: one more block, padded with zero-weight terms (the samples of the terms that are not there: 0.0)
 template <int NSTEP>
-__device__ __forceinline__ void sinc_stream_tail(sinc_stream_t &s, const int step, const int rem) {
+__device__ __forceinline__ void sinc_stream_tail(sinc_stream_t &s, const double y0, const double y1, const double y2) {
     constexpr double S = (double)NSTEP;
-    const double y0 = s.yp[0], y1 = (rem > 1) ? s.yp[step] : 0.0, y2 = (rem > 2) ? s.yp[2 * step] : 0.0;
     const double p0 = s.pn, p1 = s.pn + S, p2 = s.pn + 2.0 * S;
     const double q01 = p0 * p1;
     const double r = rcp_nr1(q01 * p2);
@@ -170,6 +174,11 @@ __device__ __forceinline__ void sinc_stream_tail(sinc_stream_t &s, const int ste
     s.acc0 += t1; s.acc1 = fma(t1, s.C, s.acc1);
     s.C += s.d;
     s.acc0 += t2; s.acc1 = fma(t2, s.C, s.acc1);
+}
+template <int NSTEP>
+__device__ __forceinline__ void sinc_stream_tail(sinc_stream_t &s, const int step, const int rem) {
+    const double y0 = s.yp[0], y1 = (rem > 1) ? s.yp[step] : 0.0, y2 = (rem > 2) ? s.yp[2 * step] : 0.0;
+    sinc_stream_tail<NSTEP>(s, y0, y1, y2);
 }
 
 // the lane's partial sum, scaled and ROUNDED before the cross-lane sum (vbx_device.hpp); k = sin(pi*ph) / pi * 0.5 (the taper's)
@@ -413,6 +422,10 @@ __device__ __forceinline__ void improve_extremum_sinc(const double *y, int nvali
 // The Brent state (v, w, x, fv, fw, fx) lives in SCALAR registers: each abscissa is read from lane 0 once (the values of an
 // evaluation arrive in scalar registers anyway, group_sum<64> ends in a lane read), so the rotations v = w; w = x; x = t
 // are scalar moves, which cost no vector issue, and the vector unit only sees the iteration's arithmetic.
+// NB > 0: the lane's samples of the first NB whole blocks of each kept cell, and the four slots after the cell's last whole
+// block, stay in REGISTERS from the cell's first evaluation to the end of the run (cell_set_t below).  NB = 0: every
+// evaluation reads them from LDS.  A compile-time number per kernel instance: what its register budget holds.
+template <int NB = 0>
 __device__ __forceinline__ bool improve_extremum_sinc_wave(const double *y, int nvalid, int ylen, int offset, int nx,
                                                            double ixmid, int depth, double &xmid, double &ymid,
                                                            unsigned &terms, unsigned &evals, double bar, bool &pruned) {
@@ -462,8 +475,65 @@ __device__ __forceinline__ bool improve_extremum_sinc_wave(const double *y, int 
     //    their sin(delta / 2) from lanes 56..59 (four lanes on: the same side, the same value);
     //  * a lane's block count is nblk or nblk + 1: nblk blocks run unmasked on a scalar counter (no per-lane compare, no
     //    per-lane counter), then at most one more under the lanes' mask, then the tail.
+    // NB > 0.  A Brent run evaluates its ~25 abscissae in two cells, changing cell on almost every second one, and the samples
+    // a lane multiplies depend on the cell alone: each of the two kept cells has a register set of its own, filled once.
+    //   yb: the lane's samples of the cell's first NB whole blocks (those of them the cell has);
+    //   yt: the four slots after the LAST whole block, yp0 + (4 nblk + i) step: the masked extra block of the lanes with four
+    //       more terms, or the tail; a slot whose term the lane does not have holds the 0.0 sinc_stream_tail pads with, and its
+    //       address is never formed (the load goes to y[0]).
+    // `sel` (scalar) names the set of the last evaluation; the other one is the older: a third cell refills it.  Nothing is
+    // ever moved between the sets: the evaluation has one chain of blocks per set, so every register index is static.
+    // Whole blocks beyond NB continue from LDS as before.
+    constexpr int NSTEP = 32;
+    static_assert(NB >= 0 && NB <= 4, "cell sets of up to four whole blocks");
+    struct cell_set_t { int nl, nblk; unsigned tinc; double dmd; int rest; const double *yp0; double yb[NB > 0 ? 4 * NB : 1], yt[4]; };
+    cell_set_t c0, c1;
+    c0.nl = c1.nl = -0x7fffffff;
+    int sel = 0;
+    auto fill_set = [&](cell_set_t &c, int nl) __attribute__((always_inline)) {         // nl: scalar
+        c.nl = nl;
+        const int nr = nl + 1;
+        int md = depth;
+        if ((offset + nr) < md) md = offset + nr;                                                // :46-52 (offset + nr >= 1 here)
+        if ((offset + nl + md) >= nx) md = nx - offset + nl - 1;                                 // :55-57
+        c.tinc = 2u * (unsigned)(md + 1);
+        c.dmd = readfirstlane_f64((double)md);
+        c.nblk = ((31 <= md) ? (md - 31) / 32 + 1 : 0) >> 2;
+        c.rest = ((n0 <= md) ? (md - n0) / 32 + 1 : 0) - 4 * c.nblk;  // 0..4 (a lane with n0 below another's has at most one term more)
+        c.yp0 = y + (side ? (offset + nl + n0) : (offset + nr - n0));
+        const int step = side ? NSTEP : -NSTEP;
+        // (every index below is a constant in the source, not a loop counter: the sets must be plain registers from the
+        // compiler's first pass on, before it gets to merge the two copies of this code into one that writes through a pointer)
+#define VBX_CELL_FILL(J)                                                                                                 \
+        if constexpr (NB > J) if (c.nblk > J) {                                                                          \
+            c.yb[4 * J] = c.yp0[(4 * J) * step]; c.yb[4 * J + 1] = c.yp0[(4 * J + 1) * step];                          \
+            c.yb[4 * J + 2] = c.yp0[(4 * J + 2) * step]; c.yb[4 * J + 3] = c.yp0[(4 * J + 3) * step];                  \
+        }
+        VBX_CELL_FILL(0) VBX_CELL_FILL(1) VBX_CELL_FILL(2) VBX_CELL_FILL(3)
+#undef VBX_CELL_FILL
+        const double *yt0 = c.yp0 + 4 * c.nblk * step;
+        auto slot = [&](int i) __attribute__((always_inline)) {
+            const bool in = i < c.rest;
+            const double v = *(in ? yt0 + i * step : y);
+            return in ? v : 0.0;
+        };
+        c.yt[0] = slot(0); c.yt[1] = slot(1); c.yt[2] = slot(2); c.yt[3] = slot(3);
+    };
+    auto run_set = [&](sinc_stream_t &s, const cell_set_t &c) __attribute__((always_inline)) {
+#define VBX_CELL_RUN(J)                                                                                                  \
+        if constexpr (NB > J) if (c.nblk > J) sinc_stream_block4<NSTEP>(s, c.yb[4 * J], c.yb[4 * J + 1], c.yb[4 * J + 2], c.yb[4 * J + 3]);
+        VBX_CELL_RUN(0) VBX_CELL_RUN(1) VBX_CELL_RUN(2) VBX_CELL_RUN(3)
+#undef VBX_CELL_RUN
+        if (c.nblk > NB) {
+            const int step = side ? NSTEP : -NSTEP;
+            s.yp = c.yp0 + 4 * NB * step;
+            for (int j = NB; j < c.nblk; j++) sinc_stream_block4<NSTEP>(s, step);
+        }
+        if (c.rest >= 4) sinc_stream_block4<NSTEP>(s, c.yt[0], c.yt[1], c.yt[2], c.yt[3]);
+        if (c.rest & 3) sinc_stream_tail<NSTEP>(s, c.yt[0], c.yt[1], c.yt[2]);
+    };
     unsigned nterms_s = 0u, nevals_s = 1u;       // the work counters of this run, in scalar registers; handed over at the end
-    auto eval = [&](double x) -> double {
+    auto eval = [&](double x) __attribute__((always_inline)) -> double {
         const double fl = floor(x);
         int nlv = (int)fl;
         asm("" : "+v"(nlv));                                      // convert once, in the vector unit, then read the lane
@@ -471,17 +541,32 @@ __device__ __forceinline__ bool improve_extremum_sinc_wave(const double *y, int 
         const double phil = x - fl, phir = 1.0 - phil;
         if (__any(phil < 1.0e-10)) return readfirstlane_f64(y[offset + nl]);                     // :41
         if (__any(phir < 1.0e-10)) return readfirstlane_f64(y[offset + nl + 1]);                 // :42
-        if (nl != cur.nl) {
-            if (nl != oth.nl) fill(oth, nl);
-            const cell_t t = cur; cur = oth; oth = t;
+        double dmd;
+        if constexpr (NB == 0) {
+            if (nl != cur.nl) {
+                if (nl != oth.nl) fill(oth, nl);
+                const cell_t t = cur; cur = oth; oth = t;
+            }
+            nterms_s += cur.tinc;
+            dmd = cur.dmd;
+        } else {
+            if (nl != (sel ? c1.nl : c0.nl)) {
+                if (nl != (sel ? c0.nl : c1.nl)) {
+                    // (the two arms end differently on purpose: ending alike, the compiler merges their last stores into one
+                    // through a selected pointer, and what it writes that way it keeps in memory)
+                    if (sel) { fill_set(c0, nl); asm volatile("; cell set 0"); }
+                    else { fill_set(c1, nl); asm volatile("; cell set 1"); }
+                }
+                sel ^= 1;
+            }
+            nterms_s += sel ? c1.tinc : c0.tinc;
+            dmd = sel ? c1.dmd : c0.dmd;
         }
-        nterms_s += cur.tinc;
-        constexpr int NSTEP = 32;
         constexpr double S = (double)NSTEP;
         const int step = side ? NSTEP : -NSTEP;
         sinc_stream_t s;
         const double ph = side ? phir : phil;
-        const double h2 = M_PI * rcp_nr2(ph + cur.dmd);           // theta = h2 * (ph + n)  in [0, pi]
+        const double h2 = M_PI * rcp_nr2(ph + dmd);               // theta = h2 * (ph + n)  in [0, pi]
         s.pn = ph + (double)n0;
         const double delta = h2 * S;
         // cos(theta0) = -sin(theta0 - pi/2) and cos(theta0 + delta) - cos(theta0), theta0 = h2 * pn
@@ -497,12 +582,15 @@ __device__ __forceinline__ bool improve_extremum_sinc_wave(const double *y, int 
         const double k = readlane_f64(sn * (0.5 * 0.31830988618379067154), 63);
         const double sh = dpp_f64_into<DPP_ROW_SHR4, 0x8, 0x8>(sn, sn);                          // lanes 60..63 <- 56..59
         s.kappa = 4.0 * sh * sh;
-        s.yp = cur.yp0;
         s.acc0 = 0.0; s.acc1 = 0.0;
-        for (int j = 0; j < cur.nblk; j++) sinc_stream_block4<NSTEP>(s, step);
-        const int rest = cur.nterms - 4 * cur.nblk;               // 0..4 (a lane with n0 below another's has at most one term more)
-        if (rest >= 4) sinc_stream_block4<NSTEP>(s, step);
-        if (rest & 3) sinc_stream_tail<NSTEP>(s, step, rest & 3);
+        if constexpr (NB == 0) {
+            s.yp = cur.yp0;
+            for (int j = 0; j < cur.nblk; j++) sinc_stream_block4<NSTEP>(s, step);
+            const int rest = cur.nterms - 4 * cur.nblk;           // 0..4 (a lane with n0 below another's has at most one term more)
+            if (rest >= 4) sinc_stream_block4<NSTEP>(s, step);
+            if (rest & 3) sinc_stream_tail<NSTEP>(s, step, rest & 3);
+        } else if (sel) run_set(s, c1);
+        else run_set(s, c0);
         const double acc = s.acc0 + s.acc1;
         const double signed_acc = __hiloint2double(__double2hiint(acc) ^ sign_bit, __double2loint(acc));
         return group_sum<64>(signed_acc * k);
@@ -915,7 +1003,18 @@ __host__ __device__ constexpr int pitch_full_list_entries(int n) { return n / 4 
 // curve in MEMORY: only the list is written); 2 = everything AFTER them, from a list
 // a STAGE-1 call left (*io_ncand entries; keys / list regions of cand_cap entries; ys then only needs the lags a candidate's
 // refinement reads, pp.ncurve = pitch_curve_reach).  The same statements in the same order: 1 then 2 is 0, bit for bit.
-template <int STAGE = 0>
+// NB: whole blocks of samples per cell the one-candidate refinement keeps in registers (improve_extremum_sinc_wave<NB>).
+// PITCH_CELL_NB: what the kernels outside the 1200-point fused one pass: 0 for pitch_kernel / pitch_list_kernel, the power-of-two
+// plans' fused kernels and refine_far_kernel (at 3 several of them spill more than at 0 and refine_far_kernel drops to one
+// wavefront per SIMD; 1 and 2 have not been tried there); refine_list_kernel, which is the refinement and nothing else, holds three (REFINE_LIST_CELL_NB).
+#ifndef VBX_EXP_CELL_NB_PITCH
+#define VBX_EXP_CELL_NB_PITCH 0
+#endif
+#ifndef VBX_EXP_CELL_NB_REFINE_LIST
+#define VBX_EXP_CELL_NB_REFINE_LIST 3
+#endif
+constexpr int PITCH_CELL_NB = VBX_EXP_CELL_NB_PITCH, REFINE_LIST_CELL_NB = VBX_EXP_CELL_NB_REFINE_LIST;
+template <int STAGE = 0, int NB = 0>
 __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitch_params_t &pp, long f,
                                                    double *__restrict__ out_cand, long cand_ld,
                                                    int32_t *__restrict__ out_count, int32_t *__restrict__ status,
@@ -1099,18 +1198,8 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
     unsigned nterms = 0, nevals = 0;                // group path: work executed (group leaders' counts are summed)
     int group_lanes = RG;
     if (ncand <= GROUP_PATH_MIN_CAND && !(kmax >= VBX_EXP_GROUP_KMAX && ncand >= 4)) {
-        for (;;) {
-            const double bar = VBX_BAR();
-            const int c = in_order ? next_full-- : pick_best_pred(keys, cand_list, ys, ncand, bar, lane);
-            if (c < 0) break;
-            double freq, nn, xmid, ymid;
-            cand_from_peak(ys, cand_list[c], sample_rate, offset, freq, nn, f32);
-            bool dropped = false;
-#ifndef VBX_EXP_NO_WAVE_BRENT
-            if (!improve_extremum_sinc_wave(ys, nvalid, ylen, offset, nx, nn, 1200, xmid, ymid, cterms, cevals, bar, dropped))
-#endif
-                improve_extremum_sinc<64>(ys, nvalid, ylen, offset, nx, nn, 1200, true, xmid, ymid, st, &cterms, &cevals, bar, &dropped);
-            if (dropped) continue;
+        // a refined candidate -> the sorted list
+        auto enter = [&](int c, double xmid, double ymid) __attribute__((always_inline)) {
             double xm, ym;
             {
 #pragma clang fp contract(off)
@@ -1121,6 +1210,43 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
                 if (f32) { xm = (double)(float)xm; ym = (double)(float)ym; }  // Pitch<f32>
             }
             insert(xm, ym, c);
+        };
+        // The loop of the frames this path is for holds the wave-wide form ALONE.  A candidate that form does not take (an
+        // early-out of :193-194, a bracket that is not trusted: next to none) ends it, and that candidate and whatever the frame
+        // still has take the general form in a loop of their own, below: bit for bit the same values either way.  With the
+        // general form as a branch of the first loop, its constants and addresses (hoisted out of its own loops: some forty
+        // registers) stayed allocated across every evaluation of the wave-wide form, which left that form's sample cache
+        // sixteen registers.
+        int c_general = -1;
+#ifndef VBX_EXP_NO_WAVE_BRENT
+        for (;;) {
+            const double bar = VBX_BAR();
+            const int c = in_order ? next_full-- : pick_best_pred(keys, cand_list, ys, ncand, bar, lane);
+            if (c < 0) break;
+            double freq, nn, xmid, ymid;
+            cand_from_peak(ys, cand_list[c], sample_rate, offset, freq, nn, f32);
+            bool dropped = false;
+            if (__builtin_expect(!improve_extremum_sinc_wave<NB>(ys, nvalid, ylen, offset, nx, nn, 1200, xmid, ymid, cterms, cevals, bar, dropped), 0)) {
+                c_general = c;
+                break;
+            }
+            if (dropped) continue;
+            enter(c, xmid, ymid);
+        }
+        if (c_general >= 0)
+#endif
+        for (;;) {
+            const double bar = VBX_BAR();
+            int c = c_general;
+            c_general = -1;
+            if (c < 0) c = in_order ? next_full-- : pick_best_pred(keys, cand_list, ys, ncand, bar, lane);
+            if (c < 0) break;
+            double freq, nn, xmid, ymid;
+            cand_from_peak(ys, cand_list[c], sample_rate, offset, freq, nn, f32);
+            bool dropped = false;
+            improve_extremum_sinc<64>(ys, nvalid, ylen, offset, nx, nn, 1200, true, xmid, ymid, st, &cterms, &cevals, bar, &dropped);
+            if (dropped) continue;
+            enter(c, xmid, ymid);
         }
     } else {
       // PG lanes per candidate; DUAL: each of them stands in for two lanes of a group of 2 PG (sinc_terms_fast_dual)

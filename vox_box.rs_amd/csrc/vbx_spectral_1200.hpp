@@ -216,6 +216,16 @@ __device__ __forceinline__ void fft1200(double (&re)[20], double (&im)[20], doub
 // a.pcm -- 16-bit PCM.  float (k_spectral_f32in.hip only): float32 samples, widened in registers before the window product (every float
 // is a double: the frame is the one vbx_f32_to_f64 would have written, bit for bit).  A compile-time choice, so that the f64 / PCM
 // instantiations are instruction for instruction what they were before the float form existed.  Full frames only.
+// Whole blocks of samples per cell the one-candidate refinement keeps in registers (improve_extremum_sinc_wave<NB>): the most
+// at which no instance of this kernel, at two or three wavefronts, f64 / PCM or float samples, uses a register or a byte of
+// scratch more than at 0 (tools/resource_usage.sh; at 4 the three-wavefront instances spill 17-52 registers).
+#ifndef VBX_EXP_CELL_NB
+#define VBX_EXP_CELL_NB 3
+#endif
+#ifndef VBX_EXP_CELL_NB_F32IN
+#define VBX_EXP_CELL_NB_F32IN VBX_EXP_CELL_NB
+#endif
+__host__ __device__ constexpr int sp_cell_blocks(int waves, bool f32) { return f32 ? VBX_EXP_CELL_NB_F32IN : VBX_EXP_CELL_NB; }
 template <bool LPC, bool MFCC, bool FULL, int MODE = SP_ANALYZE, int WAVES = VBX_SPECTRAL_WAVES, typename TIN = double>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_only(MODE) ? 2 : WAVES, sp_is_mfcc_only(MODE) ? 4 : WAVES))) void analyze_kernel(const spectral_args_t a) {
     constexpr bool F32 = std::is_same<TIN, float>::value;
@@ -635,7 +645,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_o
     const double unc_tol = SP_UNC_EPS * fabs(s0) * scale;
     double2 *full = a.pp.full_off > 0 ? reinterpret_cast<double2 *>(reinterpret_cast<char *>(smem) + a.pp.full_off)
                   : a.pp.full_off < 0 ? reinterpret_cast<double2 *>(a.out_cand + f * a.cand_ld) : nullptr;
-    if (!pitch_refine_store(ys, n, a.pp, f, a.out_cand, a.cand_ld, a.out_count, a.pitch_status, a.work, unc_tol, full)) {
+    if (!pitch_refine_store<0, sp_cell_blocks(WAVES, F32)>(ys, n, a.pp, f, a.out_cand, a.cand_ld, a.out_count, a.pitch_status, a.work, unc_tol, full)) {
         if (lane == 0) a.unsure_list[atomicAdd(a.unsure_count, 1)] = (int32_t)f;
     }
 }

@@ -681,7 +681,7 @@ void analyze_pow2_kernel(const spectral_args_t a) {
     wave_sync();
     const double unc_tol = SP_UNC_EPS * fabs(s0) * scale;
     double2 *full = a.pp.full_off ? reinterpret_cast<double2 *>(reinterpret_cast<char *>(smem) + a.pp.full_off) : nullptr;
-    if (!pitch_refine_store(ys, n, a.pp, f, a.out_cand, a.cand_ld, a.out_count, a.pitch_status, a.work, unc_tol, full)) {
+    if (!pitch_refine_store<0, PITCH_CELL_NB>(ys, n, a.pp, f, a.out_cand, a.cand_ld, a.out_count, a.pitch_status, a.work, unc_tol, full)) {
         if (lane == 0) a.unsure_list[atomicAdd(a.unsure_count, 1)] = (int32_t)f;
     }
 }
