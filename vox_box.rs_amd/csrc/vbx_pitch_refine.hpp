@@ -686,6 +686,10 @@ constexpr int RG = VBX_EXP_RG;                  // lanes per candidate on the gr
 #endif
 constexpr int DUAL_MIN_CAND = VBX_EXP_DUAL_MIN_CAND;   // unpruned frames with at least this many candidates: 8 groups, two lanes in one
 
+// the abscissa the refinement starts from, from the parabolic lag's frequency (T = f64)
+__device__ __forceinline__ double nn_from_freq(double sample_rate, double freq, int offset) {
+    return sample_rate / freq - (double)offset;                      // :432, :443
+}
 __device__ __forceinline__ void cand_from_peak(const double *ys, int kk, double sample_rate, int offset,
                                                double &freq, double &nn, const bool f32 = false) {
     const double peak = ys[kk], peak_rev = ys[kk - 1], peak_fwd = ys[kk + 1];
@@ -700,7 +704,7 @@ __device__ __forceinline__ void cand_from_peak(const double *ys, int kk, double 
     const double dr = 0.5 * (peak_fwd - peak_rev);                    // :423
     const double d2r = 2. * peak - (peak_rev - peak_fwd);             // :424 (Q5)
     freq = sample_rate / ((double)kk + dr / d2r);                     // :425
-    nn = sample_rate / freq - (double)offset;                         // :432, :443
+    nn = nn_from_freq(sample_rate, freq, offset);
 }
 
 constexpr int BOUND_HEAD = 8;                   // nearest terms per side evaluated by the first-evaluation bound
@@ -916,8 +920,24 @@ __device__ __forceinline__ int pick_best(float *keys, int ncand, double bar, int
 // evaluations instead of being refined to the end first (replay on the oracle, 172 voiced frames: 28.2 -> 25.3 evaluations
 // per frame; refining the best candidate alone takes 24.7).  The order changes nothing that is returned: a candidate that
 // is never picked has a bound below the final bar, one that is abandoned has a running minimum below it.
+// EARLY (pitch_refine_store<.., ONCE>): with at most 64 candidates a lane's one key stays in its register and a ballot of the
+// eligibility answers "nothing is left" before the two gathers, wave_max and the index reduction: the call that ends a voiced
+// frame's loop.  -1 exactly when the full search returns it (no lane eligible), keys[] untouched; otherwise the same search.
+template <bool EARLY = false>
 __device__ __forceinline__ int pick_best_pred(float *keys, const cand_t *cand_list, const double *ys, int ncand, double bar, int lane) {
     double bv = -__builtin_inf(); int bi = 0x7fffffff;
+    if (EARLY && ncand <= 64) {
+        const float kv = (lane < ncand) ? keys[lane] : -__builtin_inff();
+        const bool eligible = kv > -__builtin_inff() && (double)kv >= bar;
+        if (!__any(eligible)) return -1;
+        if (eligible) {
+            const int k = (int)cand_list[lane];
+            double p = fmin(ys[k - 1], ys[k + 1]);
+            if (!(p == p)) p = __builtin_inf();
+            bv = p; bi = lane;
+        }
+    } else {                                                  // (more than 64, noise-like frames: a pass over the keys alone first
+                                                              // was measured and costs more than it saves -- most picks there find one)
     for (int i = lane; i < ncand; i += 64) {
         const float kv = keys[i];                             // -inf: retired (the bar itself is -inf until kmax are kept)
         if (kv > -__builtin_inff() && (double)kv >= bar) {
@@ -926,6 +946,7 @@ __device__ __forceinline__ int pick_best_pred(float *keys, const cand_t *cand_li
             if (!(p == p)) p = __builtin_inf();               // NaN data: such a candidate is refined like any other
             if (bi == 0x7fffffff || p > bv) { bv = p; bi = i; }
         }
+    }
     }
     const double gm = wave_max(bv);
     int pick = (bi != 0x7fffffff && bv == gm) ? bi : 0x7fffffff;
@@ -1014,7 +1035,20 @@ __host__ __device__ constexpr int pitch_full_list_entries(int n) { return n / 4 
 #define VBX_EXP_CELL_NB_REFINE_LIST 3
 #endif
 constexpr int PITCH_CELL_NB = VBX_EXP_CELL_NB_PITCH, REFINE_LIST_CELL_NB = VBX_EXP_CELL_NB_REFINE_LIST;
-template <int STAGE = 0, int NB = 0>
+// experiment builds (tools/experiments/front_end_split.sh): -DVBX_EXP_STOP=k ends pitch_refine_store after 1 the peak scan, 2 the
+// frequency filter, 3 the |y| prefix sums, 4 the first-evaluation bounds, 5 the first pick (written to the frame's count so that it
+// is computed); 6 goes from the bounds straight to the store.  Counter passes of these forms, subtracted, are the front end's split.
+#ifndef VBX_EXP_STOP
+#define VBX_EXP_STOP 0
+#endif
+#define VBX_STOP_AT(k_) do { if (VBX_EXP_STOP == (k_)) return true; } while (0)
+#define VBX_STOP_AT_PICK(k_, c_) do { if (VBX_EXP_STOP == (k_)) { if (lane == 0 && out_count != nullptr) out_count[f] = (c_); return true; } } while (0)
+// ONCE: the candidate front end computes each of its values once (the 1200-point fused kernel; the other callers keep the
+// forms they were measured with): a block's |y| sum stays in a register between the lane totals and the prefix written back,
+// the quad bound pass leaves the abscissa nn of candidates 0..15 in lane 4c for the refinement to read back instead of running
+// cand_from_peak again, and pick_best_pred answers "nothing left" from a ballot.  Every operation on every value is the one
+// the plain form does, in the same order: keys[], the picks and the outputs keep every bit.
+template <int STAGE = 0, int NB = 0, bool ONCE = false>
 __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitch_params_t &pp, long f,
                                                    double *__restrict__ out_cand, long cand_ld,
                                                    int32_t *__restrict__ out_count, int32_t *__restrict__ status,
@@ -1038,6 +1072,17 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
     const int ylen = 2 * n;                         // :411
     const int nvalid = nst + Y_PAD;
 
+    // ONCE: the filter has just computed nn for every peak; it parks the first NN_PARKED candidates' in the head of the keys region,
+    // which nobody has written yet, and the quad bound pass's first round -- the only one in a voiced frame -- reads them back
+    // BEFORE it writes its keys (the same wave, LDS operations in order) instead of three samples and three divisions in four
+    // lanes each.  The same function on the same samples: the same bits.  Frames with more than 64 peaks (noise-like: three passes
+    // of the filter, candidates the quad pass mostly does not serve) do not park: there it cost 19 instructions per pass.
+    constexpr int NN_PARKED = 16;
+    constexpr bool NN_PARK = ONCE && STAGE == 0;
+    // (The region is read as double here and written as float by the bound pass.  The order holds because the round's only float
+    // store, keys[c], is computed from the double it loaded; a reordering of that loop must keep the round's loads before its stores.)
+    double *nn_park = reinterpret_cast<double *>(keys);       // 8-byte aligned: p16 + an even count
+    bool parked = false;                                      // uniform: this frame's filter parked them
     VBX_PHASE_INIT();
     int ncand = 0;
     if constexpr (STAGE == 2) ncand = *io_ncand;
@@ -1062,15 +1107,22 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
     wave_sync();
     if (unc_tol > 0.0 && __any(unsure)) return false;
     VBX_PHASE(work, f, 6);
+    VBX_STOP_AT(1);
     unsure = false;
+    parked = NN_PARK && !f32 && npeak <= 64 && n / 4 + 8 >= 2 * NN_PARKED;   // one pass of the filter (voiced frames), and the region holds them
     for (int base = 0; base < npeak; base += 64) {  // in place: the write position never passes the read position
         const int i = base + lane;
         bool pass = false;
         int k = 0;
+        double nn_i = 0.0;
         if (i < npeak) {
             k = cand_list[i];
             double freq, nn;
             cand_from_peak(ys, k, sample_rate, offset, freq, nn, f32);
+            // (the filter itself needs the frequency alone, and the abscissa's division is dead code in it.  Written as its own
+            // expression under the uniform test, not as nn_i = nn: with the latter the division ran in every frame's filter,
+            // +57 instructions per noise-like frame, measured)
+            if (parked) nn_i = nn_from_freq(sample_rate, freq, offset);
             pass = (freq == 0.0) || (freq > fmin && freq < fmax);             // :439
             if (unc_tol > 0.0) {
                 // the filter is a discrete decision too: the parabolic lag k + dr / d2r inherits the curve's error (each of
@@ -1083,13 +1135,16 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
         }
         wave_sync();                                // all reads of this pass before its writes
         const unsigned long long mask = __ballot(pass);
-        if (pass) cand_list[ncand + __popcll(mask & ((1ull << lane) - 1ull))] = (cand_t)k;
+        const int ci = ncand + __popcll(mask & ((1ull << lane) - 1ull));
+        if (pass) cand_list[ci] = (cand_t)k;
+        if (parked && pass && ci < NN_PARKED) nn_park[ci] = nn_i;
         ncand += __popcll(mask);
         wave_sync();
     }
 
     if (unc_tol > 0.0 && __any(unsure)) return false;         // a frequency within the curve's error of fmin / fmax
     VBX_PHASE(work, f, 7);
+    VBX_STOP_AT(2);
     }
     if constexpr (STAGE == 1) { *io_ncand = ncand; return true; }
 
@@ -1098,9 +1153,34 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
     // (not when nothing can be pruned -- the whole Vec, a list that never fills, T = f32: the candidates are then taken in
     // index order, below)
     const bool in_order = full != nullptr || kmax > ncand || f32;
+    double nn_kept = 0.0;                           // ONCE: lane 4c holds nn of candidate c < n_kept (the quad pass's first round)
+    int n_kept = 0;
     if (!in_order) {
         // lane l owns the consecutive blocks [l*per, (l+1)*per): local sums, one scan over the lanes, prefix written back
         const int per = (nblk + 63) >> 6;
+        constexpr int PER_REG = 4;                           // block sums a lane keeps (ONCE): curves of up to 64 * 4 * PB lags
+        if (ONCE && per <= PER_REG) {
+            double bs[PER_REG];
+            double tot = 0.0;
+#pragma unroll
+            for (int q = 0; q < PER_REG; q++) {
+                const int j = lane * per + q;
+                const bool in = q < per && j < nblk;
+                bs[q] = in ? block_abs_sum(ys + PB * j) : 0.0;
+                if (in) tot += bs[q];
+            }
+            const double incl = wave_inclusive_scan(tot);
+            double run = incl - tot;
+            if (lane == 0) p16[0] = 0.0;
+#pragma unroll
+            for (int q = 0; q < PER_REG; q++) {
+                const int j = lane * per + q;
+                if (q < per && j < nblk) {
+                    run += bs[q];
+                    p16[j + 1] = run;
+                }
+            }
+        } else {
         double tot = 0.0;
         for (int q = 0; q < per; q++) {
             const int j = lane * per + q;
@@ -1116,7 +1196,9 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
                 p16[j + 1] = run;
             }
         }
+        }
         wave_sync();
+        VBX_STOP_AT(3);
         // one lane per candidate, or -- when that would leave most lanes idle -- four lanes per candidate
         // (cost model: 16 candidates per pass at about 7/25 of the cost of a 64-candidate pass)
         const bool quad = ((ncand + 15) / 16) * 7 < ((ncand + 63) / 64) * 25;
@@ -1125,7 +1207,9 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
                 const int c = base + (lane >> 2);
                 const bool have = c < ncand;
                 double freq = 0., nn = 0.;
-                if (have) cand_from_peak(ys, cand_list[c], sample_rate, offset, freq, nn, f32);
+                if (parked && base == 0) { if (have) nn = nn_park[c]; }
+                else if (have) cand_from_peak(ys, cand_list[c], sample_rate, offset, freq, nn, f32);
+                if (ONCE && base == 0) { nn_kept = nn; n_kept = (ncand < 16) ? ncand : 16; }
                 const double ub = first_eval_bound_quad(ys, p16, nblk, nvalid, ylen, offset, nx, nn, 1200, lane & 3, have);
                 const double kb = (ub <= 1.) ? ub : ((ub != ub) ? __builtin_inf() : ((ub == __builtin_inf()) ? ub : 1.));
                 if (have && (lane & 3) == 0) keys[c] = __double2float_ru(kb);
@@ -1143,6 +1227,7 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
     }
 
     VBX_PHASE(work, f, 8);
+    VBX_STOP_AT(4);
     int st = 0;
     int kept = 0;
     double lf = 0.0, ls = 0.0;                      // lane j holds sorted candidate j
@@ -1197,7 +1282,8 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
     int next_full = ncand - 1;
     unsigned nterms = 0, nevals = 0;                // group path: work executed (group leaders' counts are summed)
     int group_lanes = RG;
-    if (ncand <= GROUP_PATH_MIN_CAND && !(kmax >= VBX_EXP_GROUP_KMAX && ncand >= 4)) {
+    if (VBX_EXP_STOP == 6) { }                      // bounds, then straight to the store: no pick, no evaluation
+    else if (ncand <= GROUP_PATH_MIN_CAND && !(kmax >= VBX_EXP_GROUP_KMAX && ncand >= 4)) {
         // a refined candidate -> the sorted list
         auto enter = [&](int c, double xmid, double ymid) __attribute__((always_inline)) {
             double xm, ym;
@@ -1221,10 +1307,12 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
 #ifndef VBX_EXP_NO_WAVE_BRENT
         for (;;) {
             const double bar = VBX_BAR();
-            const int c = in_order ? next_full-- : pick_best_pred(keys, cand_list, ys, ncand, bar, lane);
+            const int c = in_order ? next_full-- : pick_best_pred<ONCE>(keys, cand_list, ys, ncand, bar, lane);
+            VBX_STOP_AT_PICK(5, c);
             if (c < 0) break;
             double freq, nn, xmid, ymid;
-            cand_from_peak(ys, cand_list[c], sample_rate, offset, freq, nn, f32);
+            if (ONCE && c < n_kept) nn = readlane_f64(nn_kept, 4 * __builtin_amdgcn_readfirstlane(c));
+            else cand_from_peak(ys, cand_list[c], sample_rate, offset, freq, nn, f32);
             bool dropped = false;
             if (__builtin_expect(!improve_extremum_sinc_wave<NB>(ys, nvalid, ylen, offset, nx, nn, 1200, xmid, ymid, cterms, cevals, bar, dropped), 0)) {
                 c_general = c;
@@ -1239,7 +1327,7 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
             const double bar = VBX_BAR();
             int c = c_general;
             c_general = -1;
-            if (c < 0) c = in_order ? next_full-- : pick_best_pred(keys, cand_list, ys, ncand, bar, lane);
+            if (c < 0) c = in_order ? next_full-- : pick_best_pred<ONCE>(keys, cand_list, ys, ncand, bar, lane);
             if (c < 0) break;
             double freq, nn, xmid, ymid;
             cand_from_peak(ys, cand_list[c], sample_rate, offset, freq, nn, f32);
@@ -1294,8 +1382,8 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
             {   // 2. hand the next candidates to the idle groups, in group order
                 unsigned long long im = __ballot(ci < 0) & LEADERS;
                 while (im != 0ull && !exhausted) {
-                    const int c = in_order ? next_full-- : pick_best_pred(keys, cand_list, ys, ncand, VBX_BAR(), lane);
-                    if (c < 0) { exhausted = true; break; }
+                    const int c = in_order ? next_full-- : pick_best_pred<ONCE>(keys, cand_list, ys, ncand, VBX_BAR(), lane);
+                    if (VBX_EXP_STOP == 5 || c < 0) { exhausted = true; break; }     // (stop 5: the first pick, then the store)
                     const int g = __builtin_ctzll(im) / PG;
                     im &= im - 1ull;
                     if (gid == g) {

@@ -225,6 +225,15 @@ __device__ __forceinline__ void fft1200(double (&re)[20], double (&im)[20], doub
 #ifndef VBX_EXP_CELL_NB_F32IN
 #define VBX_EXP_CELL_NB_F32IN VBX_EXP_CELL_NB
 #endif
+// The candidate front end with its values computed once (pitch_refine_store<.., ONCE>): every instance of this kernel but the
+// three-wavefront forms of full f64 / PCM frames without MFCC, which spill two to four registers more with it (4 -> 8 and 4 -> 6,
+// tools/resource_usage.sh) and keep the plain form; no other instance uses a register or a byte of scratch more.
+#ifndef VBX_EXP_FRONT_END_ONCE
+#define VBX_EXP_FRONT_END_ONCE 1
+#endif
+__host__ __device__ constexpr bool sp_front_end_once(bool mfcc, bool full, int waves, bool f32) {
+    return VBX_EXP_FRONT_END_ONCE != 0 && !(!mfcc && full && waves >= 3 && !f32);
+}
 __host__ __device__ constexpr int sp_cell_blocks(int waves, bool f32) { return f32 ? VBX_EXP_CELL_NB_F32IN : VBX_EXP_CELL_NB; }
 template <bool LPC, bool MFCC, bool FULL, int MODE = SP_ANALYZE, int WAVES = VBX_SPECTRAL_WAVES, typename TIN = double>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_only(MODE) ? 2 : WAVES, sp_is_mfcc_only(MODE) ? 4 : WAVES))) void analyze_kernel(const spectral_args_t a) {
@@ -645,7 +654,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_o
     const double unc_tol = SP_UNC_EPS * fabs(s0) * scale;
     double2 *full = a.pp.full_off > 0 ? reinterpret_cast<double2 *>(reinterpret_cast<char *>(smem) + a.pp.full_off)
                   : a.pp.full_off < 0 ? reinterpret_cast<double2 *>(a.out_cand + f * a.cand_ld) : nullptr;
-    if (!pitch_refine_store<0, sp_cell_blocks(WAVES, F32)>(ys, n, a.pp, f, a.out_cand, a.cand_ld, a.out_count, a.pitch_status, a.work, unc_tol, full)) {
+    if (!pitch_refine_store<0, sp_cell_blocks(WAVES, F32), sp_front_end_once(MFCC, FULL, WAVES, F32)>(ys, n, a.pp, f, a.out_cand, a.cand_ld, a.out_count, a.pitch_status, a.work, unc_tol, full)) {
         if (lane == 0) a.unsure_list[atomicAdd(a.unsure_count, 1)] = (int32_t)f;
     }
 }
