@@ -309,6 +309,71 @@ impl Gpu {
         Ok((Records { data, status3, n_frames, record_ld: ld }, index))
     }
 
+    /// The selected channels of interleaved sample frames on the device in ONE pass (`vbx_unpack_channels`): plane `k` is channel
+    /// `select[k]`, `n_sample_frames` elements from element `k * plane_ld` of `dst`, bit for bit what [`Gpu::unpack_samples`] writes
+    /// for that channel.  `select` holds distinct channels in any order, at most `VBX_HOST_MAX_CHANNELS` of them.
+    #[allow(clippy::too_many_arguments)]
+    pub fn unpack_channels<S: Copy, D: Copy>(&self, src: &DeviceBuf<S>, n_sample_frames: usize, format: i32, channels: i32, select: &[i32],
+                                             dst: &DeviceBuf<D>, plane_ld: usize) -> GpuResult<()> {
+        let src_bytes = match format { ffi::VBX_SAMPLE_PCM16 => 2, ffi::VBX_SAMPLE_PCM24 => 3, ffi::VBX_SAMPLE_F64 => 8, _ => 4 };
+        let dst_bytes = match format { ffi::VBX_SAMPLE_PCM16 => 2, ffi::VBX_SAMPLE_F32 => 4, _ => 8 };
+        assert!(channels >= 1 && src.len() * std::mem::size_of::<S>() >= n_sample_frames * channels as usize * src_bytes, "source too small");
+        assert!(!select.is_empty() && select.len() <= ffi::VBX_HOST_MAX_CHANNELS && plane_ld >= n_sample_frames, "bad selection or plane_ld");
+        assert!(dst.len() * std::mem::size_of::<D>() >= ((select.len() - 1) * plane_ld + n_sample_frames) * dst_bytes, "destination too small");
+        self.check(unsafe {
+            ffi::vbx_unpack_channels(self.raw, src.as_ptr() as *const c_void, n_sample_frames, format, channels, select.as_ptr(), select.len(),
+                                     dst.as_mut_ptr() as *mut c_void, plane_ld)
+        })
+    }
+
+    /// [`Gpu::analyze_host`] for several channels of one recording from ONE upload per chunk (`vbx_analyze_host_channels`): a stereo
+    /// file, a microphone array.  `select` holds distinct channels in any order (at most `VBX_HOST_MAX_CHANNELS`); entry `k` of the
+    /// result is what `analyze_host` returns for channel `select[k]`, bit for bit.  One parameter set and one segment list for all.
+    #[allow(clippy::too_many_arguments)]
+    pub fn analyze_host_channels(&self, audio: HostSamples, channels: usize, select: &[i32], chunk_frames: usize, frame_len: usize,
+                                 stride: usize, params: &AnalysisParams, ext: Option<&AnalysisExt>, track: Option<(usize, &PitchPathParams)>,
+                                 seg_start: &[i64]) -> GpuResult<Vec<(Records, Option<DeviceBuf<i32>>)>> {
+        assert!(channels >= 1 && !select.is_empty() && select.len() <= channels.min(ffi::VBX_HOST_MAX_CHANNELS), "bad selection");
+        let (format, addr, n_samples) = match audio {
+            HostSamples::Pcm16(a) => (ffi::VBX_SAMPLE_PCM16, a.as_ptr() as *const c_void, a.len()),
+            HostSamples::Pcm24(a) => (ffi::VBX_SAMPLE_PCM24, a.as_ptr() as *const c_void, a.len() / 3),
+            HostSamples::Pcm32(a) => (ffi::VBX_SAMPLE_PCM32, a.as_ptr() as *const c_void, a.len()),
+            HostSamples::F32(a) => (ffi::VBX_SAMPLE_F32, a.as_ptr() as *const c_void, a.len()),
+            HostSamples::F64(a) => (ffi::VBX_SAMPLE_F64, a.as_ptr() as *const c_void, a.len()),
+        };
+        let n_sample_frames = n_samples / channels;
+        let fmt = ffi::VbxHostAudio { format, channels: channels as i32, channel: 0, reserved: 0, chunk_frames };
+        let n_frames = unsafe { ffi::vbx_frame_count(n_sample_frames, frame_len, stride) };
+        let p = params.to_ffi();
+        let e = ext.map(|x| x.to_ffi());
+        let e_ptr = e.as_ref().map_or(ptr::null(), |x| x as *const _);
+        let rec = unsafe { ffi::vbx_record_doubles_ex(&p, e_ptr) };
+        let ld = rec + (rec & 1);
+        let (seg_ptr, n_seg) = if seg_start.is_empty() { (ptr::null(), 0) } else { (seg_start.as_ptr(), seg_start.len()) };
+        let tk = track.map(|(kmax, path)| ffi::VbxPitchTrackParams { kmax, path: path.raw() });
+        let mut results = Vec::with_capacity(select.len());
+        let mut outputs = Vec::with_capacity(select.len());
+        for _ in select {
+            let data = self.alloc::<f64>(n_frames * ld)?;
+            let status3 = self.alloc::<i32>(3 * n_frames)?;
+            let index = if tk.is_some() { Some(self.alloc::<i32>(n_frames)?) } else { None };
+            outputs.push(ffi::VbxPitchTrackOutputs {
+                cand: ptr::null_mut(), count: ptr::null_mut(), peak: ptr::null_mut(),
+                index: index.as_ref().map_or(ptr::null_mut(), |b| b.as_mut_ptr()),
+            });
+            results.push((Records { data, status3, n_frames, record_ld: ld }, index));
+        }
+        // (`outputs` is complete before its entries' addresses are taken: it does not move again)
+        let entries: Vec<ffi::VbxChannelOutputs> = results.iter().zip(outputs.iter())
+            .map(|((r, _), o)| ffi::VbxChannelOutputs { records: r.data.as_mut_ptr(), status3: r.status3.as_mut_ptr(), outputs: o as *const _ })
+            .collect();
+        self.check(unsafe {
+            ffi::vbx_analyze_host_channels(self.raw, addr, n_sample_frames, &fmt, select.as_ptr(), select.len(), frame_len, stride, &p, e_ptr,
+                                           tk.as_ref().map_or(ptr::null(), |t| t as *const _), seg_ptr, n_seg, entries.as_ptr(), ld)
+        })?;
+        Ok(results)
+    }
+
     /// `sample::window` tables built on the host with the reference's recurrences (`VBX_WINDOW_*`).
     pub fn window_table(kind: i32, n: usize) -> GpuResult<Vec<f64>> {
         let mut t = vec![0f64; n];

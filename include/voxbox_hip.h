@@ -746,7 +746,8 @@ int vbx_unpack_samples(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames, 
  * Host timing: the call returns when the last byte of h_audio has been read (the caller may free or overwrite it); kernels may still
  * be running, and the outputs are ordered on the context's stream like every call's.  Pinned h_audio (vbx_malloc_host) is uploaded
  * beside the previous chunk's analysis; pageable memory works, but nothing overlaps.  vbx_sync drains the copy stream too.
- * Host calls may follow one another on a context with no wait between them (the channels of a stereo file are two calls): every
+ * Host calls may follow one another on a context with no wait between them (several channels of one file from one upload:
+ * vbx_analyze_host_channels, below): every
  * upload waits for its staging slot's last reader, the previous call's included.
  * Afterwards the vbx_internal_last_* probes describe the LAST chunk's call only (not part of the contract), and the context holds
  * no state for vbx_track_stitch_f64, which returns VBX_E_INVALID.  Not capturable into a graph.
@@ -772,6 +773,65 @@ int vbx_analyze_host(vbx_ctx *ctx, const void *h_audio, size_t n_sample_frames, 
 /* pinned host memory for h_audio (hipHostMalloc / hipHostFree): uploads from it overlap the analysis */
 int vbx_malloc_host(vbx_ctx *ctx, void **out, size_t bytes);
 int vbx_free_host(vbx_ctx *ctx, void *p);
+
+/* vbx_unpack_samples for n_sel selected channels in ONE pass over the interleaved sample frames: plane k is n_sample_frames elements
+ * of the format's output type (int16 for PCM16, float for F32, double for PCM24, PCM32 and F64) starting at element k * plane_ld of
+ * d_out, and equals, bit for bit, what vbx_unpack_samples(..., channel = h_channels[k], ...) writes -- the correctly rounded PCM24 /
+ * PCM32 quotients, the copied bit patterns of floats.  Elements [n_sample_frames, plane_ld) of a plane are not written.
+ * h_channels is HOST memory: n_sel distinct values in [0, channels), in any order, 1 <= n_sel <= min(channels,
+ * VBX_HOST_MAX_CHANNELS); the selection travels as a kernel argument, so the call allocates and uploads nothing.
+ * How: a block stages a tile of whole sample frames in LDS by contiguous 16-byte loads (dword loads for a source on a dword boundary
+ * only), and each lane gathers the 16 output bytes it owns in one plane and stores them at once: the interleaved frames are read
+ * from memory once, whatever n_sel.  The per-element form takes over -- same bits -- for a source off a dword boundary (PCM24 at an
+ * odd byte address, PCM16 at an odd element), a destination off a 16-byte boundary or a plane_ld that leaves a later plane off one,
+ * a sample frame too wide for 16 of them to fit a tile, and the tail behind the last whole tile; channels == 1 is
+ * vbx_unpack_samples itself.  The per-element form is correct but slow (scalar stores, a division per element): keep d_out 16-byte
+ * aligned and choose plane_ld as a multiple of 8 elements (n_sample_frames rounded up), which keeps every plane on the tiled form.
+ * Measured rates, subsets included: DESIGN.md section 5f.  Asynchronous on the context's stream; profiled as unpack_all_pcm16 / unpack_all_pcm24 /
+ * unpack_all_pcm32 / unpack_all_f32 / unpack_all_f64.
+ * VBX_E_INVALID, with nothing written: an unknown format, channels < 1, n_sel outside [1, min(channels, VBX_HOST_MAX_CHANNELS)], a
+ * NULL h_channels, a repeated or out-of-range channel, plane_ld < n_sample_frames, a NULL pointer with n_sample_frames > 0, a pointer
+ * that breaks its type's natural alignment (a PCM24 source has none).  n_sample_frames == 0 succeeds. */
+#define VBX_HOST_MAX_CHANNELS 64
+int vbx_unpack_channels(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames, int format, int channels,
+                        const int32_t *h_channels, size_t n_sel, void *d_out, size_t plane_ld);
+
+/* vbx_analyze_host for n_sel channels of one recording from ONE upload per chunk (a stereo file, a microphone array): every chunk's
+ * interleaved bytes cross the bus once, one vbx_unpack_channels launch turns them into n_sel typed planes, and the channels are then
+ * analysed one after another on the context's stream.  h_fmt->channel must be 0; the selection is h_channels (as for
+ * vbx_unpack_channels).  All channels share one parameter set, one segment list and one record_ld; h_out holds n_sel entries, entry k
+ * the device outputs of channel h_channels[k]: records [F, record_ld] (16-byte aligned), status3 [3, F] (optional), outputs (optional:
+ * device arrays of F rows, as h_outputs of vbx_analyze_host).
+ * Contract: every byte written through h_out[k] equals, bit for bit, what vbx_analyze_host writes with h_fmt->channel = h_channels[k]
+ * and the same other arguments -- by that call's contract the resident call's output -- for every chunk_frames >=
+ * VBX_SHARD_WARM_FRAMES, every segment list, the plain, tracked and ext forms, every LPC policy, pinned and pageable h_audio
+ * (tests/test_gpu_analyze_host_channels.py).
+ * How.  Chunks, the two raw slots, their ready / freed events and the overlapped upload are vbx_analyze_host's (a slot holds all
+ * `channels` channels, as it does there).  Per chunk: one unpack launch into n_sel planes whose pitch keeps every plane 256-byte
+ * aligned (each is read as a resident recording would be: 1200-sample PCM16 / F32 frames without a widening copy), the slot's freed
+ * event right behind it; then per selected channel the frame loop on its plane into the chunk-local records and status rows (reused
+ * from channel to channel), the tracker's stitch from row lo - 1 of THAT channel's records, and the copy of the chunk's own rows into
+ * h_out[k].  channels == 1: the slot is read as it is for PCM16, F32 and F64.  The tracked form keeps each channel's candidate lists,
+ * counts, peaks and status rows for the whole recording until the end -- in the caller's arrays where h_out[k] supplies them, else in
+ * the context workspace, which then grows to n_sel * F * (16 kmax + 16) bytes -- and runs the pitch path once per channel behind the
+ * last chunk, into columns 0-1 of that channel's records.
+ * Device memory in use: the two raw slots, n_sel typed planes, one set of chunk-local records and status rows, the frame loop's
+ * chunk-sized workspaces, the tracked form's per-channel lists, the caller's outputs.
+ * Host timing, vbx_sync, calls that follow one another with no wait between them, "not capturable into a graph" and the state left
+ * behind (the probes describe the last chunk's last channel; none for vbx_track_stitch_f64) are as for vbx_analyze_host.
+ * VBX_E_INVALID, before anything is written and with the context left usable: everything vbx_analyze_host rejects; a bad selection
+ * (as vbx_unpack_channels); h_fmt->channel != 0; a NULL h_out; an entry whose records are NULL or not 16-byte aligned; two entries
+ * whose [F, record_ld] record ranges overlap.  F == 0 succeeds. */
+typedef struct {
+    double  *records;                        /* device, [F, record_ld], 16-byte aligned */
+    int32_t *status3;                        /* device, [3, F], optional */
+    const vbx_pitch_track_outputs *outputs;  /* optional; device arrays of F rows, as in vbx_analyze_host */
+} vbx_channel_outputs;
+int vbx_analyze_host_channels(vbx_ctx *ctx, const void *h_audio, size_t n_sample_frames, const vbx_host_audio *h_fmt,
+                              const int32_t *h_channels, size_t n_sel, size_t frame_len, size_t stride,
+                              const vbx_analysis_params *h_params, const vbx_analysis_ext *h_ext,
+                              const vbx_pitch_track_params *h_track, const int64_t *h_seg_start, size_t n_segments,
+                              const vbx_channel_outputs *h_out /* n_sel entries */, size_t record_ld);
 
 /* ------------------------------------------------------------------ multi-GPU: frame-range sharding */
 

@@ -9,6 +9,8 @@
 // fetches: a mono source on a dword boundary is staged through LDS -- the block reads a tile's dwords as contiguous spans, each lane
 // then picks its two samples out of LDS -- and every other 24-bit source is read byte by byte.  The quotients are IEEE divisions:
 // div_exact_small (vbx_device.hpp) is proven for 16-bit numerators only, and the divide hides behind the memory traffic.
+// unpack_all_*: every selected channel of the interleaved frames in one pass (vbx_unpack_channels, and the per-chunk step of
+// vbx_analyze_host_channels): tiles of whole sample frames through LDS, see there.
 // host_rows_kernel: a chunk's own record rows and its three status rows, copied from the chunk-local buffers into the caller's.
 #include "vbx_device.hpp"
 #include "vbx_kernels.hpp"
@@ -18,11 +20,12 @@ namespace vbx {
 namespace {
 
 template <int FMT> struct reader_t;
-template <> struct reader_t<UNPACK_PCM16> { using out_t = uint16_t; static constexpr int G = 8; };
-template <> struct reader_t<UNPACK_PCM24> { using out_t = double;   static constexpr int G = 2; };
-template <> struct reader_t<UNPACK_PCM32> { using out_t = double;   static constexpr int G = 2; };
-template <> struct reader_t<UNPACK_F32>   { using out_t = uint32_t; static constexpr int G = 4; };
-template <> struct reader_t<UNPACK_F64>   { using out_t = uint64_t; static constexpr int G = 2; };
+// out_t: what is written; G: elements in a lane's 16 output bytes; B: bytes of a source sample
+template <> struct reader_t<UNPACK_PCM16> { using out_t = uint16_t; static constexpr int G = 8; static constexpr int B = 2; };
+template <> struct reader_t<UNPACK_PCM24> { using out_t = double;   static constexpr int G = 2; static constexpr int B = 3; };
+template <> struct reader_t<UNPACK_PCM32> { using out_t = double;   static constexpr int G = 2; static constexpr int B = 4; };
+template <> struct reader_t<UNPACK_F32>   { using out_t = uint32_t; static constexpr int G = 4; static constexpr int B = 4; };
+template <> struct reader_t<UNPACK_F64>   { using out_t = uint64_t; static constexpr int G = 2; static constexpr int B = 8; };
 
 __device__ __forceinline__ int sext24(uint32_t v) { return (int)(v << 8) >> 8; }
 __device__ __forceinline__ double pcm24_value(int s) { return (double)s / 8388607.0; }
@@ -100,6 +103,93 @@ __global__ __launch_bounds__(256) void unpack_pcm24_tiled_kernel(const uint32_t 
     }
 }
 
+// ---- every selected channel in one pass (vbx_unpack_channels) ----
+// The tiled form of unpack_pcm24_tiled_kernel for any format and channel count: a block stages a tile of T WHOLE sample frames
+// (T * channels * B bytes <= UNPACK_ALL_TILE_BYTES, T a multiple of 16, so a tile is whole 16-byte words and whole lane groups of
+// every output type) in LDS by contiguous 16-byte loads -- dword loads where the source sits on a dword boundary only -- and a lane
+// then owns 16 consecutive output bytes of ONE plane: it gathers its G elements from LDS (channels * B bytes apart) and stores them
+// with one 16-byte store.  The interleaved frames are read from memory once, whatever the number of planes.
+// LDS reads: the work items of a tile are numbered with the plane FASTEST, so neighbouring lanes read neighbouring samples of one
+// sample frame (the same or adjacent dwords; identical addresses broadcast) and the next G sample frames follow n_sel lanes later.
+// Lanes that all walked one plane would be G * channels * B bytes apart: 8 dwords for 16-bit stereo, an 8-way conflict in a
+// 32-lane group.  Spread over the planes the 32 lanes touch at most 32 / n_sel such spans; with EVERY channel selected that is, for
+// 16-bit words, 4-way at worst (channels 2, 4, 8) and 2-way for 3, 5, 6 -- at 128 B per two clocks conflict-free, a quarter of the
+// LDS rate is still several times what HBM delivers per CU, so the tile is not padded (padding would break the 16-byte LDS stores
+// of the staging loop).  A SUBSET leaves fewer planes to spread over: one channel of 16-bit stereo is the 8-way case above, one of
+// eight puts all 32 lanes on one bank (32 dwords apart).  The bits are the same, and the measured rates do not show the difference: one
+// channel of two or of eight runs at 0.62-0.66 of the HBM roof in every format.
+// 8 KiB tiles: eight blocks per CU keep 64 KiB of loads in flight and use 8 x (8208 + 256) B = 66 of the 160 KiB of LDS.
+#define UNPACK_ALL_TILE_BYTES 8192
+static_assert(UNPACK_ALL_TILE_BYTES / 16 <= 2 * 256, "the staging loop is two 16-byte loads per lane");
+
+// the sample at byte b of the tile (b is a multiple of B: the tile starts on a sample frame)
+template <int FMT>
+__device__ __forceinline__ typename reader_t<FMT>::out_t lds_one(const uint32_t *tile, unsigned b) {
+    if constexpr (FMT == UNPACK_PCM16) return (uint16_t)(tile[b >> 2] >> ((b & 2) * 8));      // (a dword read: lanes on the two halves of one dword broadcast)
+    else if constexpr (FMT == UNPACK_PCM24) {                // three bytes at any byte offset: out of the two dwords that hold them
+        const uint64_t w = (uint64_t)tile[b >> 2] | ((uint64_t)tile[(b >> 2) + 1] << 32);
+        return pcm24_value(sext24((uint32_t)(w >> ((b & 3) * 8))));
+    } else if constexpr (FMT == UNPACK_PCM32) return pcm32_value((int)tile[b >> 2]);
+    else if constexpr (FMT == UNPACK_F32) return tile[b >> 2];
+    else return reinterpret_cast<const uint64_t *>(tile)[b >> 3];
+}
+
+// n_tiles whole tiles of T sample frames; src on a dword boundary at least, out 16-byte aligned, plane_ld a multiple of G
+template <int FMT>
+__global__ __launch_bounds__(256) void unpack_all_tiled_kernel(const unsigned char *__restrict__ src, size_t n_tiles, unsigned T, unsigned channels,
+                                                               unpack_sel_t sel, unsigned n_sel,
+                                                               typename reader_t<FMT>::out_t *__restrict__ out, size_t plane_ld) {
+    using R = reader_t<FMT>;
+    using out_t = typename R::out_t;
+    __shared__ __attribute__((aligned(16))) uint32_t tile[UNPACK_ALL_TILE_BYTES / 4 + 4];      // (+ the dword a last 24-bit sample's read touches)
+    __shared__ int s_sel[UNPACK_MAX_SEL];
+    const unsigned t = threadIdx.x;
+    if (t < n_sel) s_sel[t] = sel.ch[t];                                        // (read behind the first barrier)
+    const unsigned fb = channels * R::B, tile_bytes = T * fb, items = (T / R::G) * n_sel;
+    const bool wide = (reinterpret_cast<uintptr_t>(src) & 15) == 0;             // kernel-uniform; tile_bytes is a multiple of 16
+    for (size_t k = blockIdx.x; k < n_tiles; k += gridDim.x) {                  // (block-uniform trip count: the barriers are safe)
+        const unsigned char *w = src + k * tile_bytes;
+        if (wide) {                                                             // at most 512 words of 16 bytes: both loads of a lane in flight
+            const uint4 *w4 = reinterpret_cast<const uint4 *>(w);
+            uint4 *tile4 = reinterpret_cast<uint4 *>(tile);
+            const unsigned n16 = tile_bytes / 16;
+            const bool two = t + 256 < n16;
+            uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0;
+            if (t < n16) q0 = w4[t];
+            if (two) q1 = w4[t + 256];
+            if (t < n16) tile4[t] = q0;
+            if (two) tile4[t + 256] = q1;
+        } else for (unsigned i = t; i < tile_bytes / 4; i += 256) tile[i] = reinterpret_cast<const uint32_t *>(w)[i];
+        __syncthreads();
+        for (unsigned it = t; it < items; it += 256) {
+            const unsigned gl = it / n_sel, p = it - gl * n_sel;                // lane group gl of plane p
+            const unsigned b = (gl * R::G * channels + (unsigned)s_sel[p]) * R::B;
+            alignas(16) out_t v[R::G];
+#pragma unroll
+            for (int j = 0; j < R::G; j++) v[j] = lds_one<FMT>(tile, b + j * fb);
+            uint4 q;
+            __builtin_memcpy(&q, v, 16);
+            *reinterpret_cast<uint4 *>(out + p * plane_ld + k * T + (size_t)gl * R::G) = q;
+        }
+        __syncthreads();
+    }
+}
+
+// the per-element form over all planes: element e of plane p is source element e * channels + sel.ch[p]
+template <int FMT>
+__global__ __launch_bounds__(256) void unpack_all_elem_kernel(const unsigned char *__restrict__ src, size_t n, size_t channels, unpack_sel_t sel,
+                                                              size_t n_sel, typename reader_t<FMT>::out_t *__restrict__ out, size_t plane_ld) {
+    __shared__ int s_sel[UNPACK_MAX_SEL];
+    if (threadIdx.x < n_sel) s_sel[threadIdx.x] = sel.ch[threadIdx.x];
+    __syncthreads();
+    const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = t0; i < n * n_sel; i += step) {
+        const size_t p = i / n, e = i - p * n;
+        out[p * plane_ld + e] = read_one<FMT>(src, e * channels + (size_t)s_sel[p]);
+    }
+}
+
 // rows [row0, row0 + rows) of src (src_ld doubles apart), columns [c0, c1), to dst rows [0, rows) (dst_ld apart); and the same rows
 // of the three status rows: src_st [3, src_n] from column row0 to dst_st [3, dst_n] (dst_st already points at the first column)
 __global__ __launch_bounds__(256) void host_rows_kernel(const double *__restrict__ src, size_t src_ld, size_t row0, size_t rows, size_t c0,
@@ -129,6 +219,32 @@ void launch_unpack_as(hipStream_t s, const void *src, size_t n, size_t channels,
                        channel, static_cast<typename R::out_t *>(out));
 }
 
+template <int FMT>
+void launch_unpack_all_as(hipStream_t s, const void *src, size_t n, size_t channels, const unpack_sel_t &sel, size_t n_sel, void *out, size_t plane_ld) {
+    using R = reader_t<FMT>;
+    using out_t = typename R::out_t;
+    const unsigned char *in = static_cast<const unsigned char *>(src);
+    out_t *o = static_cast<out_t *>(out);
+    // whole tiles through LDS where a tile holds at least 16 sample frames, the source can be read by dwords and every lane's 16
+    // output bytes are aligned in every plane; the tail -- or everything -- by the element kernel
+    const size_t fb = channels * R::B;
+    const size_t T = fb <= UNPACK_ALL_TILE_BYTES / 16 ? (UNPACK_ALL_TILE_BYTES / fb) & ~(size_t)15 : 0;
+    const bool tiled = T != 0 && n >= T && ((uintptr_t)src & 3) == 0 && ((uintptr_t)out & 15) == 0 && plane_ld % R::G == 0;
+    size_t done = 0;
+    if (tiled) {
+        const size_t n_tiles = n / T, blocks = n_tiles < 256 * 8 ? n_tiles : 256 * 8;
+        hipLaunchKernelGGL(unpack_all_tiled_kernel<FMT>, dim3((unsigned)blocks), dim3(256), 0, s, in, n_tiles, (unsigned)T, (unsigned)channels, sel,
+                           (unsigned)n_sel, o, plane_ld);
+        done = n_tiles * T;
+    }
+    if (done < n) {
+        size_t blocks = ((n - done) * n_sel + 255) / 256;
+        if (blocks > 256 * 32) blocks = 256 * 32;
+        hipLaunchKernelGGL(unpack_all_elem_kernel<FMT>, dim3((unsigned)blocks), dim3(256), 0, s, in + done * fb, n - done, channels, sel, n_sel,
+                           o + done, plane_ld);
+    }
+}
+
 }  // namespace
 
 void launch_unpack(hipStream_t s, int format, const void *src, size_t n, size_t channels, size_t channel, void *out) {
@@ -147,6 +263,19 @@ void launch_unpack(hipStream_t s, int format, const void *src, size_t n, size_t 
         case UNPACK_PCM32: launch_unpack_as<UNPACK_PCM32>(s, src, n, channels, channel, out); break;
         case UNPACK_F32: launch_unpack_as<UNPACK_F32>(s, src, n, channels, channel, out); break;
         case UNPACK_F64: launch_unpack_as<UNPACK_F64>(s, src, n, channels, channel, out); break;
+    }
+}
+
+void launch_unpack_all(hipStream_t s, int format, const void *src, size_t n, size_t channels, const unpack_sel_t &sel, size_t n_sel, void *out,
+                       size_t plane_ld) {
+    if (n == 0) return;
+    if (channels == 1) { launch_unpack(s, format, src, n, 1, 0, out); return; }        // one plane, the mono forms (wide loads, the 24-bit tiles)
+    switch (format) {
+        case UNPACK_PCM16: launch_unpack_all_as<UNPACK_PCM16>(s, src, n, channels, sel, n_sel, out, plane_ld); break;
+        case UNPACK_PCM24: launch_unpack_all_as<UNPACK_PCM24>(s, src, n, channels, sel, n_sel, out, plane_ld); break;
+        case UNPACK_PCM32: launch_unpack_all_as<UNPACK_PCM32>(s, src, n, channels, sel, n_sel, out, plane_ld); break;
+        case UNPACK_F32: launch_unpack_all_as<UNPACK_F32>(s, src, n, channels, sel, n_sel, out, plane_ld); break;
+        case UNPACK_F64: launch_unpack_all_as<UNPACK_F64>(s, src, n, channels, sel, n_sel, out, plane_ld); break;
     }
 }
 

@@ -329,6 +329,13 @@ void launch_preemphasis(hipStream_t s, const double *x, long F, int n, long stri
 // divided by 8388607 / 2147483647 with IEEE division).  A PCM24 source may sit at any byte address, the others need their type's.
 enum { UNPACK_PCM16 = 1, UNPACK_PCM24 = 2, UNPACK_PCM32 = 3, UNPACK_F32 = 4, UNPACK_F64 = 5 };
 void launch_unpack(hipStream_t s, int format, const void *src, size_t n, size_t channels, size_t channel, void *out);
+// the same for n_sel selected channels in ONE pass over the interleaved frames (vbx_unpack_channels): plane k = channel sel.ch[k], n
+// elements from element k * plane_ld of out, bit for bit what launch_unpack writes for that channel.  The selection travels as a
+// kernel argument (UNPACK_MAX_SEL == VBX_HOST_MAX_CHANNELS).  channels == 1 is launch_unpack itself.
+#define UNPACK_MAX_SEL 64
+struct unpack_sel_t { int32_t ch[UNPACK_MAX_SEL]; };
+void launch_unpack_all(hipStream_t s, int format, const void *src, size_t n, size_t channels, const unpack_sel_t &sel, size_t n_sel,
+                       void *out, size_t plane_ld);
 // vbx_analyze_host: rows [row0, row0 + rows) x columns [c0, c1) of a chunk's records and of its [3, src_n] status rows into the caller's
 // (dst, dst_st point at the chunk's first own row / column; dst_st may be null)
 void launch_host_rows(hipStream_t s, const double *src, size_t src_ld, size_t row0, size_t rows, size_t c0, size_t c1, double *dst,

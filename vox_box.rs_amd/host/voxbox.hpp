@@ -411,6 +411,21 @@ inline void analyze_host(Context &c, const void *h_audio, size_t n_sample_frames
 inline void unpack_samples(Context &c, const void *d_src, size_t n_sample_frames, int format, int channels, int channel, void *d_out) {
     c.check(vbx_unpack_samples(c.get(), d_src, n_sample_frames, format, channels, channel, d_out));
 }
+// the selected channels in one pass (vbx_unpack_channels): plane k = channel h_channels[k], from element k * plane_ld of d_out
+inline void unpack_channels(Context &c, const void *d_src, size_t n_sample_frames, int format, int channels, const int32_t *h_channels,
+                            size_t n_sel, void *d_out, size_t plane_ld) {
+    c.check(vbx_unpack_channels(c.get(), d_src, n_sample_frames, format, channels, h_channels, n_sel, d_out, plane_ld));
+}
+// analyze_host for n_sel channels of one recording from ONE upload per chunk (vbx_analyze_host_channels): fmt.channel stays 0, the
+// selection is h_channels; out[k] holds the device outputs of channel h_channels[k], each what analyze_host writes for that channel,
+// bit for bit.  One parameter set, one segment list and one record_ld for all channels; n_sel <= VBX_HOST_MAX_CHANNELS.
+using ChannelOutputs = vbx_channel_outputs;
+inline void analyze_host_channels(Context &c, const void *h_audio, size_t n_sample_frames, const HostAudio &fmt, const int32_t *h_channels,
+                                  size_t n_sel, size_t frame_len, size_t stride, const AnalysisParams &p, const AnalysisExt *ext,
+                                  const PitchTrackParams *track, Segments seg, const ChannelOutputs *out, size_t record_ld) {
+    c.check(vbx_analyze_host_channels(c.get(), h_audio, n_sample_frames, &fmt, h_channels, n_sel, frame_len, stride, &p, ext, track,
+                                      seg.h_seg_start, seg.n, out, record_ld));
+}
 // pinned host memory for analyze_host's h_audio (vbx_malloc_host / vbx_free_host)
 inline void *malloc_host(Context &c, size_t bytes) { void *p = nullptr; c.check(vbx_malloc_host(c.get(), &p, bytes)); return p; }
 inline void free_host(Context &c, void *p) { c.check(vbx_free_host(c.get(), p)); }

@@ -157,6 +157,15 @@ class HostAudio(C.Structure):
         return cls(int(format), int(channels), int(channel), 0, int(chunk_frames))
 
 
+HOST_MAX_CHANNELS = 64
+
+
+class ChannelOutputs(C.Structure):
+    """vbx_channel_outputs: one selected channel's device outputs of vbx_analyze_host_channels -- records [F, record_ld], status3
+    [3, F] (optional) and the tracked form's optional arrays (a pointer to a PitchTrackOutputs, or NULL)."""
+    _fields_ = [("records", C.c_void_p), ("status3", C.c_void_p), ("outputs", C.POINTER(PitchTrackOutputs))]
+
+
 _lib = None
 
 
@@ -285,6 +294,9 @@ def load_library():
         "vbx_unpack_samples": (C.c_int, [vp, vp, sz, i32, i32, i32, vp]),
         "vbx_analyze_host": (C.c_int, [vp, vp, sz, C.POINTER(HostAudio), sz, sz, C.POINTER(AnalysisParams), C.POINTER(AnalysisExt),
                                        C.POINTER(PitchTrackParams), vp, sz, vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
+        "vbx_unpack_channels": (C.c_int, [vp, vp, sz, i32, i32, vp, sz, vp, sz]),
+        "vbx_analyze_host_channels": (C.c_int, [vp, vp, sz, C.POINTER(HostAudio), vp, sz, sz, sz, C.POINTER(AnalysisParams),
+                                                C.POINTER(AnalysisExt), C.POINTER(PitchTrackParams), vp, sz, C.POINTER(ChannelOutputs), sz]),
         "vbx_malloc_host": (C.c_int, [vp, C.POINTER(vp), sz]),
         "vbx_free_host": (C.c_int, [vp, vp]),
         "vbx_host_chunk_plan": (C.c_int, [sz, sz, sz, sz, sz, vp, sz, C.POINTER(ShardPlan), C.POINTER(sz), C.POINTER(sz)]),
@@ -1343,6 +1355,19 @@ class VoxBox:
         [T, C] (format and channels follow from it); bytes / bytearray / a uint8 array of packed 24-bit PCM (format=SAMPLE_PCM24,
         channels=); or a raw host address with format=, channels= and n_sample_frames=.  Returns what analyze_frames_ex returns."""
         assert frame_len and stride
+        keep, fmt, addr, channels, n_sample_frames = self._host_audio(audio, format, channels, n_sample_frames)
+        hf = HostAudio.make(fmt, channels, channel, chunk_frames)
+        F = frame_count(int(n_sample_frames), int(frame_len), int(stride))
+
+        def fn(ctx, ptr, F_, N, S, *rest):
+            return self.L.vbx_analyze_host(ctx, ptr, int(n_sample_frames), C.byref(hf), N, S, *rest)
+        return self._analyze_tracked(fn, addr, F, int(frame_len), int(stride), params, track, seg_start, out, record_ld, status, lists,
+                                     outputs, None, ext=ext)
+
+    @staticmethod
+    def _host_audio(audio, format, channels, n_sample_frames):
+        # what analyze_host / analyze_host_channels are handed -> (the object that keeps the memory alive, format, host address,
+        # channels, n_sample_frames)
         keep = audio
         if isinstance(audio, (bytes, bytearray, memoryview)):
             keep = np.frombuffer(audio, dtype=np.uint8)
@@ -1366,13 +1391,79 @@ class VoxBox:
         else:
             assert isinstance(audio, int) and format is not None and n_sample_frames is not None
             fmt, addr = int(format), audio
-        hf = HostAudio.make(fmt, channels, channel, chunk_frames)
-        F = frame_count(int(n_sample_frames), int(frame_len), int(stride))
+        return keep, fmt, addr, int(channels), int(n_sample_frames)
 
-        def fn(ctx, ptr, F_, N, S, *rest):
-            return self.L.vbx_analyze_host(ctx, ptr, int(n_sample_frames), C.byref(hf), N, S, *rest)
-        return self._analyze_tracked(fn, addr, F, int(frame_len), int(stride), params, track, seg_start, out, record_ld, status, lists,
-                                     outputs, None, ext=ext)
+    def unpack_channels(self, src, n_sample_frames, format, channels, select=None, out=None, plane_ld=None):
+        """vbx_unpack_channels: the selected channels (select: distinct channel numbers in any order; None = every channel) of n
+        interleaved sample frames on the device, in one pass, as planes of the type the frame loop reads: plane k starts at element
+        k * plane_ld of out (plane_ld None: n rounded up to a multiple of 128 elements, which keeps the planes 256-byte aligned).
+        src / out: device buffers or raw addresses.  Returns out (a [n_sel, plane_ld] DeviceArray where it was allocated here)."""
+        n = int(n_sample_frames)
+        sel = np.ascontiguousarray(np.arange(int(channels)) if select is None else select, dtype=np.int32)
+        ld = int(plane_ld) if plane_ld is not None else (n + 127) // 128 * 128
+        o = out if out is not None else self.empty((max(sel.size, 1), ld), _SAMPLE_OUT_DTYPE[format])
+        self._check(self.L.vbx_unpack_channels(self.ctx, _ptr(src), n, int(format), int(channels), sel.ctypes.data, sel.size, _ptr(o), ld))
+        return o
+
+    def analyze_host_channels(self, audio, params, ext=None, track=None, format=None, channels=1, select=None, chunk_frames=0,
+                              seg_start=None, frame_len=None, stride=None, n_sample_frames=None, out=None, record_ld=None, status=None,
+                              lists=False, outputs=None):
+        """vbx_analyze_host_channels: analyze_host for several channels of one recording from ONE upload per chunk.  audio is what
+        analyze_host takes ([T, C] arrays, packed 24-bit bytes with channels=, or a raw host address with format=, channels= and
+        n_sample_frames=); select: distinct channel numbers in any order (None = every channel).  Returns a list with one entry per
+        selected channel, each what analyze_host(channel=c) returns.  out / status / outputs: one entry per selected channel (device
+        buffers; outputs entries as in analyze_frames_tracked, or None) to write into; the call then returns None."""
+        assert frame_len and stride
+        keep, fmt, addr, channels, n_sample_frames = self._host_audio(audio, format, channels, n_sample_frames)
+        sel = np.ascontiguousarray(np.arange(channels) if select is None else select, dtype=np.int32)
+        K = int(sel.size)
+        hf = HostAudio.make(fmt, channels, 0, chunk_frames)
+        N, S = int(frame_len), int(stride)
+        F = frame_count(n_sample_frames, N, S)
+        e_ref = None if ext is None else C.byref(ext)
+        rec = int(self.L.vbx_record_doubles_ex(C.byref(params), e_ref))
+        ld = record_ld if record_ld is not None else rec + (rec & 1)
+        if lists and track is None:
+            raise ValueError("lists=True returns the pitch path's lists: it needs track=")
+        if lists and (out is not None or outputs is not None):
+            raise ValueError("lists=True returns host copies of library-allocated lists: it cannot be combined with out= or outputs=")
+        for per_channel in (out, status, outputs):
+            assert per_channel is None or len(per_channel) == K, "out / status / outputs take one entry per selected channel"
+        seg = None if seg_start is None else np.ascontiguousarray(seg_start, dtype=np.int64)
+        own = []
+
+        def mine(shape, dtype=np.float64):
+            own.append(self.empty(shape, dtype))
+            return own[-1]
+        try:
+            recs = list(out) if out is not None else [mine((F, ld)) for _ in range(K)]
+            sts = list(status) if status is not None else ([mine((3, F), np.int32) for _ in range(K)] if out is None else [None] * K)
+            outs = list(outputs) if outputs is not None else [None] * K
+            if lists:
+                k = int(track.kmax)
+                outs = [(mine((F, k, 2)), mine(F, np.int32), mine(F), mine(F, np.int32)) for _ in range(K)]
+            pos = [None if o is None else (o if isinstance(o, PitchTrackOutputs) else PitchTrackOutputs(*[_ptr(a) for a in o]))
+                   for o in outs]
+            entries = (ChannelOutputs * max(K, 1))()
+            for i in range(K):
+                entries[i].records, entries[i].status3 = _ptr(recs[i]), _ptr(sts[i])
+                entries[i].outputs = None if pos[i] is None else C.pointer(pos[i])
+            self._check(self.L.vbx_analyze_host_channels(
+                self.ctx, addr, n_sample_frames, C.byref(hf), sel.ctypes.data, K, N, S, C.byref(params), e_ref,
+                None if track is None else C.byref(track), None if seg is None else seg.ctypes.data, 0 if seg is None else seg.size,
+                entries, ld))
+            if out is not None:
+                return None
+            res = []
+            for i in range(K):
+                r = (recs[i].numpy(), sts[i].numpy())
+                if lists:
+                    r = r + tuple(a.numpy() for a in outs[i])
+                res.append(r)
+            return res
+        finally:
+            for d in own:
+                d.free()
 
     # -- spectrum.rs: MFCC ------------------------------------------------------------
     def mfcc(self, x, num_coeffs, freq_bounds, sample_rate, frame_len=None, stride=None, n_frames=None,
