@@ -309,6 +309,28 @@ impl Gpu {
         Ok((Records { data, status3, n_frames, record_ld: ld }, index))
     }
 
+    /// A live session on this context (`vbx_session_open`): ONE channel of a stream of audio that arrives block by block -- a
+    /// microphone, a socket, a decoder.  Every [`Session::push`] delivers the records of the frames its block completes, and all the
+    /// rows pushed equal, bit for bit, what the resident frame loop writes on the concatenated blocks, for every way of cutting the
+    /// stream into blocks of at most `max_block` sample frames.  Everything is allocated and warmed here.
+    #[allow(clippy::too_many_arguments)]
+    pub fn session(&self, format: i32, channels: usize, channel: usize, frame_len: usize, stride: usize, params: &AnalysisParams,
+                   ext: Option<&AnalysisExt>, track: Option<(usize, &PitchPathParams)>, max_block: usize) -> GpuResult<Session<'_>> {
+        let fmt = ffi::VbxHostAudio { format, channels: channels as i32, channel: channel as i32, reserved: 0, chunk_frames: 0 };
+        let p = params.to_ffi();
+        let e = ext.map(|x| x.to_ffi());
+        let e_ptr = e.as_ref().map_or(ptr::null(), |x| x as *const _);
+        let tk = track.map(|(kmax, path)| ffi::VbxPitchTrackParams { kmax, path: path.raw() });
+        let rec = unsafe { ffi::vbx_record_doubles_ex(&p, e_ptr) };
+        let mut raw: *mut ffi::VbxSession = ptr::null_mut();
+        self.check(unsafe {
+            ffi::vbx_session_open(self.raw, &fmt, frame_len, stride, &p, e_ptr, tk.as_ref().map_or(ptr::null(), |t| t as *const _), max_block,
+                                  &mut raw)
+        })?;
+        let sample_frame_bytes = channels * match format { ffi::VBX_SAMPLE_PCM16 => 2, ffi::VBX_SAMPLE_PCM24 => 3, ffi::VBX_SAMPLE_F64 => 8, _ => 4 };
+        Ok(Session { gpu: self, raw, format, sample_frame_bytes, frame_len, stride, record_ld: rec + (rec & 1), kmax: tk.map(|t| t.kmax) })
+    }
+
     /// The selected channels of interleaved sample frames on the device in ONE pass (`vbx_unpack_channels`): plane `k` is channel
     /// `select[k]`, `n_sample_frames` elements from element `k * plane_ld` of `dst`, bit for bit what [`Gpu::unpack_samples`] writes
     /// for that channel.  `select` holds distinct channels in any order, at most `VBX_HOST_MAX_CHANNELS` of them.
@@ -397,6 +419,107 @@ fn last_error(ctx: *const ffi::VbxCtx) -> String {
         String::new()
     } else {
         unsafe { CStr::from_ptr(p) }.to_string_lossy().into_owned()
+    }
+}
+
+/// What one [`Session::push`] delivers: the records and status rows of the `n` frames the block completed and, in the tracked form,
+/// their candidate lists `[n, kmax]`, counts and frame peaks (columns 0-1 of the records are then NOT written: run the pitch path
+/// over an utterance's rows when it ends).
+pub struct SessionRows<'g> {
+    pub records: Records<'g>,
+    pub lists: Option<(DeviceBuf<'g, ffi::VbxPitch>, DeviceBuf<'g, i32>, DeviceBuf<'g, f64>)>,
+}
+
+/// A live session ([`Gpu::session`]); closed on drop.
+pub struct Session<'g> {
+    gpu: &'g Gpu,
+    raw: *mut ffi::VbxSession,
+    format: i32,
+    sample_frame_bytes: usize,
+    frame_len: usize,
+    stride: usize,
+    record_ld: usize,
+    kmax: Option<usize>,
+}
+
+impl<'g> Session<'g> {
+    /// `(sample frames consumed, frames delivered, sample frames carried)` (`vbx_session_info`).
+    pub fn info(&self) -> GpuResult<(usize, usize, usize)> {
+        let (mut a, mut b, mut c) = (0usize, 0usize, 0usize);
+        self.gpu.check(unsafe { ffi::vbx_session_info(self.raw, &mut a, &mut b, &mut c) })?;
+        Ok((a, b, c))
+    }
+
+    fn deliver(&self, block: *const c_void, n_sample_frames: usize, device: bool) -> GpuResult<Option<SessionRows<'g>>> {
+        let consumed = self.info()?.0;
+        let n = unsafe {
+            ffi::vbx_frame_count(consumed + n_sample_frames, self.frame_len, self.stride) - ffi::vbx_frame_count(consumed, self.frame_len, self.stride)
+        };
+        #[allow(clippy::too_many_arguments)]
+        let push = |s: *mut ffi::VbxSession, b: *const c_void, n_sf: usize, rec: *mut f64, ld: usize, st: *mut i32, st_ld: usize,
+                    out: *const ffi::VbxPitchTrackOutputs, got: *mut usize| unsafe {
+            if device {
+                ffi::vbx_session_push_device(s, b, n_sf, rec, ld, st, st_ld, out, got)
+            } else {
+                ffi::vbx_session_push(s, b, n_sf, rec, ld, st, st_ld, out, got)
+            }
+        };
+        if n == 0 {                     // the block only joins the carry: nothing is written
+            self.gpu.check(push(self.raw, block, n_sample_frames, ptr::null_mut(), self.record_ld, ptr::null_mut(), 0, ptr::null(), ptr::null_mut()))?;
+            return Ok(None);
+        }
+        let data = self.gpu.alloc::<f64>(n * self.record_ld)?;
+        let status3 = self.gpu.alloc::<i32>(3 * n)?;
+        let lists = match self.kmax {
+            Some(k) => Some((self.gpu.alloc::<ffi::VbxPitch>(n * k)?, self.gpu.alloc::<i32>(n)?, self.gpu.alloc::<f64>(n)?)),
+            None => None,
+        };
+        let outputs = lists.as_ref().map(|(c, k, p)| ffi::VbxPitchTrackOutputs {
+            cand: c.as_mut_ptr(), count: k.as_mut_ptr(), peak: p.as_mut_ptr(), index: ptr::null_mut(),
+        });
+        let mut got = 0usize;
+        self.gpu.check(push(self.raw, block, n_sample_frames, data.as_mut_ptr(), self.record_ld, status3.as_mut_ptr(), n,
+                            outputs.as_ref().map_or(ptr::null(), |o| o as *const _), &mut got))?;
+        debug_assert_eq!(got, n);
+        Ok(Some(SessionRows { records: Records { data, status3, n_frames: n, record_ld: self.record_ld }, lists }))
+    }
+
+    /// The next block of the stream, from host memory (`vbx_session_push`): interleaved sample frames in the session's format.
+    /// `None` when the block completes no frame.  Returns when the block has been read; the rows are ordered on the context's stream.
+    pub fn push(&self, block: HostSamples) -> GpuResult<Option<SessionRows<'g>>> {
+        let (format, addr, bytes) = match block {
+            HostSamples::Pcm16(a) => (ffi::VBX_SAMPLE_PCM16, a.as_ptr() as *const c_void, a.len() * 2),
+            HostSamples::Pcm24(a) => (ffi::VBX_SAMPLE_PCM24, a.as_ptr() as *const c_void, a.len()),
+            HostSamples::Pcm32(a) => (ffi::VBX_SAMPLE_PCM32, a.as_ptr() as *const c_void, a.len() * 4),
+            HostSamples::F32(a) => (ffi::VBX_SAMPLE_F32, a.as_ptr() as *const c_void, a.len() * 4),
+            HostSamples::F64(a) => (ffi::VBX_SAMPLE_F64, a.as_ptr() as *const c_void, a.len() * 8),
+        };
+        assert!(format == self.format, "the block is not in the session's format");
+        self.deliver(addr, bytes / self.sample_frame_bytes, false)
+    }
+
+    /// The same for a block in device memory (`vbx_session_push_device`), read in stream order with no staging and no host wait.
+    pub fn push_device<S: Copy>(&self, block: &DeviceBuf<S>, n_sample_frames: usize) -> GpuResult<Option<SessionRows<'g>>> {
+        assert!(block.len() * std::mem::size_of::<S>() >= n_sample_frames * self.sample_frame_bytes, "block too small");
+        self.deliver(block.as_ptr() as *const c_void, n_sample_frames, true)
+    }
+
+    /// The next frame delivered starts a new utterance (`vbx_session_mark_utterance`): a `seg_start` entry of the resident call.
+    pub fn mark_utterance(&self) -> GpuResult<()> {
+        self.gpu.check(unsafe { ffi::vbx_session_mark_utterance(self.raw) })
+    }
+
+    /// Drop the carried samples and all state (`vbx_session_reset`): as a freshly opened session.
+    pub fn reset(&self) -> GpuResult<()> {
+        self.gpu.check(unsafe { ffi::vbx_session_reset(self.raw) })
+    }
+}
+
+impl<'g> Drop for Session<'g> {
+    fn drop(&mut self) {
+        unsafe {
+            ffi::vbx_session_close(self.raw);
+        }
     }
 }
 
@@ -1590,6 +1713,17 @@ pub fn host_chunk_plan(n_frames: usize, chunk_frames: usize, c: usize, frame_len
         return Err(GpuError { code: rc, message: last_error(ptr::null()) });
     }
     Ok((plan, s0, s1))
+}
+
+/// What a push of `n_new` sample frames does to a live session that has consumed `consumed` sample frames and whose current
+/// utterance began at frame `utt_frame` (`vbx_session_plan`; host arithmetic only).
+pub fn session_plan(consumed: usize, utt_frame: usize, n_new: usize, frame_len: usize, stride: usize) -> GpuResult<ffi::VbxSessionPlan> {
+    let mut plan = ffi::VbxSessionPlan::default();
+    let rc = unsafe { ffi::vbx_session_plan(consumed, utt_frame, n_new, frame_len, stride, &mut plan) };
+    if rc != ffi::VBX_SUCCESS {
+        return Err(GpuError { code: rc, message: last_error(ptr::null()) });
+    }
+    Ok(plan)
 }
 
 /// Utterance starts of the frames `[lo - warm, hi)` of a plan, re-based to the shard (`vbx_shard_local_segments`): the

@@ -833,6 +833,91 @@ int vbx_analyze_host_channels(vbx_ctx *ctx, const void *h_audio, size_t n_sample
                               const vbx_pitch_track_params *h_track, const int64_t *h_seg_start, size_t n_segments,
                               const vbx_channel_outputs *h_out /* n_sel entries */, size_t record_ld);
 
+/* ------------------------------------------------------------------ live sessions (ABI 5, added) */
+
+/* Audio that ARRIVES -- a microphone, a socket, a decoder, a model emitting a waveform: a session is opened once on a context for
+ * ONE channel of one stream of audio, fed blocks of any size as they come, and every push delivers the records of the frames that
+ * block completes.  (The reference's streaming form is `impl Autocorrelate for VecDeque`, src/periodic.rs:291-304, under a user
+ * loop that consumes a Windower frame by frame.)
+ * Contract: concatenate every block ever pushed, and concatenate every row the pushes wrote: the result equals, bit for bit, what
+ * the resident call writes on the whole recording -- vbx_analyze_frames_ex_pcm16 for PCM16, vbx_analyze_frames_ex_f32in for F32,
+ * vbx_analyze_frames_ex_f64 on the vbx_unpack_samples output for PCM24, PCM32 and F64 -- for EVERY way of cutting the recording
+ * into blocks: blocks of one sample, blocks shorter than a hop that complete no frame, blocks of exactly one hop, blocks of hundreds
+ * of thousands of frames (tests/test_gpu_session.py).
+ * vbx_session_plan is the arithmetic of one push, pure host code: a session that has consumed `consumed` sample frames, whose
+ * current utterance began at frame utt_frame, is pushed n_new more.
+ * vbx_session_open: h_fmt as for vbx_analyze_host (chunk_frames and reserved must be 0); the parameters are copied.  Everything the
+ * session will ever need for blocks of up to max_block_sample_frames is allocated here -- two typed carry buffers of
+ * (VBX_SHARD_WARM_FRAMES + 1) * stride + frame_len + max_block_sample_frames samples each, two raw staging slots, the chunk-local
+ * records, status rows and lists of max_block_sample_frames / stride + 1 + VBX_SHARD_WARM_FRAMES frames, the tracker state -- and
+ * the shape is warmed by one frame-loop call at that frame count on the zeroed carry, which is also where everything only the frame
+ * loop's parts know (orders, the resampled shape, the MFCC geometry) is rejected.  After that no push allocates or drains a stream on
+ * its own account.
+ * vbx_session_push: h_block is HOST memory, n_sample_frames interleaved sample frames in the session's format.  Rows [0, n) of
+ * out_records (device, 16-byte aligned, record_ld as in the resident call) receive frames [lo, hi) of the plan, n = hi - lo; row k
+ * of the three status rows is written at status3 + k * status_ld, n entries (status3 optional; a caller filling one global [3, F]
+ * array passes status3 + lo and status_ld = F); *h_n_frames = n (optional), which vbx_session_plan tells beforehand.  A push that
+ * completes no frame only appends to the carry and writes nothing; n_sample_frames == 0 is a no-op.
+ * How.  The block is uploaded on the context's copy stream into one of the session's two raw slots (ready / freed events as in
+ * vbx_analyze_host: the host runs at most two blocks ahead).  On the context's stream: ONE session_ingest launch writes the carry's
+ * kept tail and the selected channel of the block, as the frame loop's type, into the session's other carry buffer; the frame loop
+ * runs on frames [lo - warm, hi) of it into the chunk-local buffers, with no segment list -- warm never reaches before the
+ * utterance's start, so the analysed range lies in ONE utterance; where the push continues an utterance the tracker is stitched from
+ * the session's state, the formant row of the last frame delivered (vbx_track_stitch_f64's repair; a frame with a bad status passes
+ * the state through, so that row is always the true state); ONE session_deliver launch copies the push's own rows into the caller's
+ * arrays and the last formant row into the state.  A block's device work is its own frames plus at most VBX_SHARD_WARM_FRAMES.
+ * Host timing follows vbx_analyze_host: the push returns when the last byte of h_block has been read; the outputs are ordered on the
+ * context's stream; pinned blocks (vbx_malloc_host) upload beside the previous block's analysis.  Blocks of up to 128 KiB (a hop, a
+ * hundred hops of 16-bit mono) do not take the copy stream: they are copied on the host into one of two session-owned pinned buffers and uploaded from
+ * there on the context's own stream, so that such a push waits for no second stream and for no upload (the host still runs at most
+ * two blocks ahead: a staging buffer is reused when its upload of two pushes ago has left it).  vbx_session_push_device reads
+ * d_block (device memory) in stream order on the context's stream, with no staging and no host wait.
+ * Utterances: vbx_session_mark_utterance makes the next frame delivered -- frame vbx_frame_count(consumed) at the time of the call --
+ * the start of a new utterance.  With marks at frames m1 < m2 < ... the session's output equals the resident call's with
+ * h_seg_start = [0, m1, m2, ...].
+ * The tracked form (h_track non-NULL) runs the fused kernel at kmax and writes the new frames' candidate lists, counts and (where
+ * the path needs them) peaks through h_outputs, n rows each: cand and count are required, peak when silence_threshold != 0, index must
+ * be NULL.  Columns 0-1 of the pushed records are NOT written: the caller runs vbx_pitch_path_f64 over an utterance's rows when it
+ * ends, and because the lists are per frame and equal the resident call's, that contour equals the resident tracked call's columns
+ * 0-1, bit for bit.  (A bounded-delay online path is a different algorithm and not offered.)
+ * The LPC policy is the context's at the time of each push.  Several sessions may live on one context, each owning its carry; any
+ * other entry point may be called on the context between pushes without changing a session's output.  After a push the
+ * vbx_internal_last_* probes describe that push's frame-loop call, and the context holds no state for vbx_track_stitch_f64.  Not
+ * capturable into a graph.  vbx_session_reset drops the carried samples and all state (as a freshly opened session);
+ * vbx_session_info reports the sample frames consumed, the frames delivered and the sample frames carried; vbx_session_close frees
+ * the session (behind the work queued on the context's stream; close every session before its context).
+ * Kernel launches per push and measured round trips: DESIGN.md section 5g.
+ * VBX_E_INVALID, before anything is queued and with session and context left usable: a NULL argument where one is required, an unknown
+ * format, channels < 1, channel outside [0, channels), non-zero reserved or chunk_frames, max_block_sample_frames == 0, a push larger
+ * than max_block_sample_frames, records misaligned, record_ld odd or too small, status_ld < n, the tracked form's missing or
+ * forbidden h_outputs members, everything the resident call rejects from its arguments. */
+typedef struct vbx_session vbx_session;
+
+/* pure host arithmetic, no GPU: what a push of n_new sample frames does to a session that has consumed `consumed` sample
+ * frames and whose current utterance began at frame utt_frame (utt_frame <= vbx_frame_count(consumed); WARM = VBX_SHARD_WARM_FRAMES) */
+typedef struct {
+    size_t lo, hi;        /* frames this push delivers: [vbx_frame_count(consumed), vbx_frame_count(consumed + n_new)) */
+    size_t warm;          /* frames analysed before lo: min(lo - utt_frame, WARM); 0 when hi == lo */
+    int continues_prev;   /* lo > utt_frame and hi > lo: the tracker continues from the last delivered row */
+    size_t read_from;     /* first sample frame the push's analysis reads: (lo - warm) * stride */
+    size_t keep_from;     /* first sample frame still carried afterwards: min(consumed + n_new, (hi - min(hi - utt_frame, WARM)) * stride) */
+} vbx_session_plan_t;
+int vbx_session_plan(size_t consumed, size_t utt_frame, size_t n_new, size_t frame_len, size_t stride, vbx_session_plan_t *h_out);
+
+int vbx_session_open(vbx_ctx *ctx, const vbx_host_audio *h_fmt /* chunk_frames and reserved must be 0 */,
+                     size_t frame_len, size_t stride, const vbx_analysis_params *h_params, const vbx_analysis_ext *h_ext,
+                     const vbx_pitch_track_params *h_track, size_t max_block_sample_frames, vbx_session **out);
+int vbx_session_push(vbx_session *s, const void *h_block, size_t n_sample_frames,
+                     double *out_records /* device */, size_t record_ld, int32_t *status3 /* device, optional */, size_t status_ld,
+                     const vbx_pitch_track_outputs *h_outputs /* device arrays of n rows */, size_t *h_n_frames);
+int vbx_session_push_device(vbx_session *s, const void *d_block, size_t n_sample_frames,
+                            double *out_records, size_t record_ld, int32_t *status3, size_t status_ld,
+                            const vbx_pitch_track_outputs *h_outputs, size_t *h_n_frames);
+int vbx_session_mark_utterance(vbx_session *s);   /* the next frame delivered starts a new utterance (an h_seg_start entry) */
+int vbx_session_reset(vbx_session *s);            /* drop the carried samples and all state: as a freshly opened session */
+int vbx_session_info(const vbx_session *s, size_t *h_consumed, size_t *h_frames, size_t *h_carried);
+void vbx_session_close(vbx_session *s);
+
 /* ------------------------------------------------------------------ multi-GPU: frame-range sharding */
 
 /* The reference has no distribution of any kind; frames are independent (the tracker per utterance), so a long

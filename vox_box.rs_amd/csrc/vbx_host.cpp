@@ -484,5 +484,33 @@ int vbx_host_chunk_plan(size_t n_frames, size_t chunk_frames, size_t c, size_t f
     return vbx_shard_samples(lo - out->warm, hi, frame_len, stride, s0, s1);
 }
 
+// One push of a live session (vbx_session_push): the frames it completes, the warm-up before them, and what the carry must hold.
+// The analysed range [lo - warm, hi) never reaches before utt_frame, so it lies in ONE utterance; keep_from is the earliest sample
+// frame any later push can read (its lo is this hi, its warm-up at most WARM frames and never before utt_frame).
+int vbx_session_plan(size_t consumed, size_t utt_frame, size_t n_new, size_t frame_len, size_t stride, vbx_session_plan_t *out) {
+    if (!out || frame_len < 1 || stride < 1) return fail(nullptr, VBX_E_INVALID, "vbx_session_plan: bad argument");
+    if (consumed + n_new < consumed) return fail(nullptr, VBX_E_INVALID, "vbx_session_plan: consumed + n_new overflows");
+    const size_t W = (size_t)VBX_SHARD_WARM_FRAMES;
+    const size_t lo = vbx_frame_count(consumed, frame_len, stride), hi = vbx_frame_count(consumed + n_new, frame_len, stride);
+    if (utt_frame > lo) return fail(nullptr, VBX_E_INVALID, "vbx_session_plan: utt_frame lies beyond the frames consumed");
+    out->lo = lo; out->hi = hi;
+    out->warm = hi > lo ? (lo - utt_frame < W ? lo - utt_frame : W) : 0;
+    out->continues_prev = (lo > utt_frame && hi > lo) ? 1 : 0;
+    out->read_from = (lo - out->warm) * stride;
+    const size_t back = hi - utt_frame < W ? hi - utt_frame : W;
+    const size_t from = (hi - back) * stride;
+    out->keep_from = from < consumed + n_new ? from : consumed + n_new;
+    return VBX_SUCCESS;
+}
 
 }  // extern "C"
+
+namespace vbx {
+
+size_t session_carry_samples(size_t frame_len, size_t stride, size_t max_block) {
+    return ((size_t)VBX_SHARD_WARM_FRAMES + 1) * stride + frame_len + max_block;
+}
+
+size_t session_max_frames(size_t stride, size_t max_block) { return max_block / stride + 1 + (size_t)VBX_SHARD_WARM_FRAMES; }
+
+}  // namespace vbx

@@ -40,6 +40,12 @@ void slopes_fill(const int32_t *bins, size_t k, double *out);
 // sample 0.10 Converter's linear interpolation: left source index and fraction of each of the m outputs
 void resample_fill(size_t m, double resample_ratio, int32_t *index, double *frac);
 
+// ---- a live session's geometry (vbx_session_plan itself is an entry point: include/voxbox_hip.h, defined in vbx_host.cpp) ----
+// samples a session's carry buffer holds: the kept tail never exceeds WARM hops and a frame, a push adds at most max_block
+size_t session_carry_samples(size_t frame_len, size_t stride, size_t max_block);
+// the most frames one push's frame-loop call covers: the frames max_block samples can complete, and the warm-up
+size_t session_max_frames(size_t stride, size_t max_block);
+
 // table kinds of vbx_internal_host_table (tests, tools/host_property_check.py)
 enum { HOST_TABLE_WINDOW, HOST_TABLE_LAG_F32, HOST_TABLE_GOERTZEL, HOST_TABLE_DFT2, HOST_TABLE_MFMA, HOST_TABLE_DCT,
        HOST_TABLE_SLOPES, HOST_TABLE_RESAMPLE, HOST_TABLE_KINDS };

@@ -341,6 +341,24 @@ void launch_unpack_all(hipStream_t s, int format, const void *src, size_t n, siz
 void launch_host_rows(hipStream_t s, const double *src, size_t src_ld, size_t row0, size_t rows, size_t c0, size_t c1, double *dst,
                       size_t dst_ld, const int32_t *src_st, size_t src_n, int32_t *dst_st, size_t dst_n);
 
+// k_session.hip: the two launches a live session's push puts around the frame loop (vbx_session_push).
+// ingest: out[0, keep) = old[drop, drop + keep) (the format's output type), out[keep, keep + n_new) = what launch_unpack writes for
+// channel `channel` of the n_new interleaved sample frames at raw, bit for bit.  old and out must not overlap.
+void launch_session_ingest(hipStream_t s, int format, const void *old, size_t drop, size_t keep, const void *raw, size_t n_new,
+                           size_t channels, size_t channel, void *out);
+// deliver: rows [row0, row0 + rows) of the chunk-local buffers into the caller's rows [0, rows) -- the records' columns [c0, c1),
+// the [3, src_n] status rows to dst_st + k * dst_st_ld, the tracked form's lists (kmax entries a row), counts and peaks -- and the
+// n_state formant doubles (columns 2 ...) of the last of those rows into state.  Null destinations are skipped; rows >= 1.
+struct session_deliver_t {
+    const double *src; size_t src_ld, row0, rows, c0, c1; double *dst; size_t dst_ld;
+    const int32_t *src_st; size_t src_n; int32_t *dst_st; size_t dst_st_ld;
+    const double *src_cand; double *dst_cand; size_t kmax;
+    const int32_t *src_count; int32_t *dst_count;
+    const double *src_peak; double *dst_peak;
+    double *state; size_t n_state;
+};
+void launch_session_deliver(hipStream_t s, const session_deliver_t &d);
+
 // k_front_ex.hip: RMS::rms of the rectangular frame (launch_rms with a null window, bit for bit) from the f64 view or from 16-bit
 // PCM, written at out_rms + f * rms_ld; out_peak non-null: launch_frame_peak / launch_frame_peak_pcm16 from the same read
 void launch_frame_rms(hipStream_t s, const double *x, const int16_t *pcm, long F, int n, long stride, double *out_rms, long rms_ld,

@@ -430,6 +430,52 @@ inline void analyze_host_channels(Context &c, const void *h_audio, size_t n_samp
 inline void *malloc_host(Context &c, size_t bytes) { void *p = nullptr; c.check(vbx_malloc_host(c.get(), &p, bytes)); return p; }
 inline void free_host(Context &c, void *p) { c.check(vbx_free_host(c.get(), p)); }
 
+// A live session (vbx_session_*): ONE channel of a stream of audio that arrives block by block; every push delivers the records of the
+// frames its block completes, and all the rows pushed equal, bit for bit, what the resident frame loop writes on the concatenated
+// blocks, for every way of cutting the stream into blocks of at most max_block sample frames.  records / status3 / outputs are device
+// memory; push returns the number of rows written (session_plan tells it beforehand).  Tracked form: cand and count (and peak, with a
+// silence threshold) are required, index must be null, columns 0-1 are the caller's path to fill (pitch_path over an utterance's rows).
+using SessionPlan = vbx_session_plan_t;
+inline SessionPlan session_plan(size_t consumed, size_t utt_frame, size_t n_new, size_t frame_len, size_t stride) {
+    SessionPlan p{};
+    if (vbx_session_plan(consumed, utt_frame, n_new, frame_len, stride, &p) != VBX_SUCCESS) throw Error(VBX_E_INVALID, "session_plan: bad argument");
+    return p;
+}
+class session {
+public:
+    session(Context &c, const HostAudio &fmt, size_t frame_len, size_t stride, const AnalysisParams &p, const AnalysisExt *ext,
+            const PitchTrackParams *track, size_t max_block) : c_(c) {
+        c.check(vbx_session_open(c.get(), &fmt, frame_len, stride, &p, ext, track, max_block, &s_));
+    }
+    ~session() { vbx_session_close(s_); }
+    session(const session &) = delete;
+    session &operator=(const session &) = delete;
+    size_t push(const void *h_block, size_t n_sample_frames, double *records, size_t record_ld, int32_t *status3 = nullptr,
+                size_t status_ld = 0, const PitchTrackOutputs *outputs = nullptr) {
+        size_t n = 0;
+        c_.check(vbx_session_push(s_, h_block, n_sample_frames, records, record_ld, status3, status_ld, outputs, &n));
+        return n;
+    }
+    size_t push_device(const void *d_block, size_t n_sample_frames, double *records, size_t record_ld, int32_t *status3 = nullptr,
+                       size_t status_ld = 0, const PitchTrackOutputs *outputs = nullptr) {
+        size_t n = 0;
+        c_.check(vbx_session_push_device(s_, d_block, n_sample_frames, records, record_ld, status3, status_ld, outputs, &n));
+        return n;
+    }
+    void mark_utterance() { c_.check(vbx_session_mark_utterance(s_)); }
+    void reset() { c_.check(vbx_session_reset(s_)); }
+    struct Info { size_t consumed, frames, carried; };
+    Info info() const {
+        Info i{};
+        c_.check(vbx_session_info(s_, &i.consumed, &i.frames, &i.carried));
+        return i;
+    }
+    vbx_session *get() const { return s_; }
+private:
+    Context &c_;
+    vbx_session *s_ = nullptr;
+};
+
 // Frame-range sharding of one recording over the GPUs of a node (no counterpart in the reference) and the gather of the
 // per-frame records to one rank: grouped ncclSend / ncclRecv inside the library, one communicator per process.
 struct Shard { size_t lo, hi, s0, s1; };

@@ -166,6 +166,17 @@ class ChannelOutputs(C.Structure):
     _fields_ = [("records", C.c_void_p), ("status3", C.c_void_p), ("outputs", C.POINTER(PitchTrackOutputs))]
 
 
+class SessionPlan(C.Structure):
+    """vbx_session_plan_t: what one push does to a live session -- the frames [lo, hi) it delivers, the warm frames analysed before
+    them, whether the tracker continues from the last delivered row, the first sample frame the analysis reads and the first one
+    still carried afterwards."""
+    _fields_ = [("lo", C.c_size_t), ("hi", C.c_size_t), ("warm", C.c_size_t), ("continues_prev", C.c_int),
+                ("read_from", C.c_size_t), ("keep_from", C.c_size_t)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -300,6 +311,16 @@ def load_library():
         "vbx_malloc_host": (C.c_int, [vp, C.POINTER(vp), sz]),
         "vbx_free_host": (C.c_int, [vp, vp]),
         "vbx_host_chunk_plan": (C.c_int, [sz, sz, sz, sz, sz, vp, sz, C.POINTER(ShardPlan), C.POINTER(sz), C.POINTER(sz)]),
+        "vbx_session_plan": (C.c_int, [sz, sz, sz, sz, sz, C.POINTER(SessionPlan)]),
+        "vbx_session_open": (C.c_int, [vp, C.POINTER(HostAudio), sz, sz, C.POINTER(AnalysisParams), C.POINTER(AnalysisExt),
+                                       C.POINTER(PitchTrackParams), sz, C.POINTER(vp)]),
+        "vbx_session_push": (C.c_int, [vp, vp, sz, vp, sz, vp, sz, C.POINTER(PitchTrackOutputs), C.POINTER(sz)]),
+        "vbx_session_push_device": (C.c_int, [vp, vp, sz, vp, sz, vp, sz, C.POINTER(PitchTrackOutputs), C.POINTER(sz)]),
+        "vbx_session_mark_utterance": (C.c_int, [vp]),
+        "vbx_session_reset": (C.c_int, [vp]),
+        "vbx_session_info": (C.c_int, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
+        "vbx_session_close": (None, [vp]),
+        "vbx_internal_session_ingest": (C.c_int, [vp, i32, i32, i32, vp, sz, sz, vp, sz, vp]),
         "vbx_find_formants_resampled_f64": (C.c_int, [vp, vp, sz, sz, sz, dbl, dbl, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp]),
         "vbx_shard_range": (C.c_int, [sz, i32, i32, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
         "vbx_shard_samples": (C.c_int, [sz, sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
@@ -425,6 +446,15 @@ def host_chunk_plan(n_frames, chunk_frames, c, frame_len, stride, seg_start=None
     return plan, s0.value, s1.value
 
 
+def session_plan(consumed, utt_frame, n_new, frame_len, stride):
+    """vbx_session_plan: what a push of n_new sample frames does to a live session that has consumed `consumed` sample frames and
+    whose current utterance began at frame utt_frame (host arithmetic only) -- a SessionPlan."""
+    plan = SessionPlan()
+    if load_library().vbx_session_plan(int(consumed), int(utt_frame), int(n_new), int(frame_len), int(stride), C.byref(plan)) != 0:
+        raise VoxBoxError("vbx_session_plan: bad argument")
+    return plan
+
+
 def shard_samples(lo, hi, frame_len, hop):
     s0, s1 = C.c_size_t(), C.c_size_t()
     if load_library().vbx_shard_samples(lo, hi, frame_len, hop, C.byref(s0), C.byref(s1)) != 0:
@@ -534,6 +564,108 @@ def _ptr(a):
     raise TypeError(f"not a device buffer: {type(a)}")
 
 
+class Session:
+    """vbx_session: one channel of one stream of audio analysed block by block (VoxBox.session).  Concatenating what the pushes
+    return gives, bit for bit, what the resident frame loop returns on the concatenated blocks."""
+
+    def __init__(self, vb, params, ext, track, format, channels, channel, frame_len, stride, max_block):
+        self.vb, self.params, self.ext, self.track = vb, params, ext, track
+        self.format, self.channels, self.channel = int(format), int(channels), int(channel)
+        self.frame_len, self.stride, self.max_block = int(frame_len), int(stride), int(max_block)
+        hf = HostAudio.make(self.format, self.channels, self.channel, 0)
+        h = C.c_void_p()
+        vb._check(vb.L.vbx_session_open(vb.ctx, C.byref(hf), self.frame_len, self.stride, C.byref(params),
+                                        None if ext is None else C.byref(ext), None if track is None else C.byref(track),
+                                        self.max_block, C.byref(h)))
+        self.handle = h
+        vb._sessions.add(self)
+        self.rec = int(vb.L.vbx_record_doubles_ex(C.byref(params), None if ext is None else C.byref(ext)))
+
+    def info(self):
+        """(sample frames consumed, frames delivered, sample frames carried)"""
+        a, b, c = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self.vb._check(self.vb.L.vbx_session_info(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def frames_of(self, n_sample_frames):
+        """frames a push of n_sample_frames would deliver now (vbx_session_plan's hi - lo)"""
+        c = self.info()[0]
+        return frame_count(c + int(n_sample_frames), self.frame_len, self.stride) - frame_count(c, self.frame_len, self.stride)
+
+    def _push(self, fn, addr, n_sf, out, status, outputs, record_ld, status_ld):
+        vb = self.vb
+        n = self.frames_of(n_sf)
+        got = C.c_size_t()
+        if out is not None:
+            po = None
+            if outputs is not None:
+                po = outputs if isinstance(outputs, PitchTrackOutputs) else PitchTrackOutputs(*[_ptr(a) for a in outputs])
+            ld = int(record_ld) if record_ld is not None else self.rec + (self.rec & 1)
+            vb._check(fn(self.handle, addr, n_sf, _ptr(out), ld, _ptr(status), int(status_ld) if status_ld is not None else n,
+                         None if po is None else C.byref(po), C.byref(got)))
+            return None
+        assert status is None and outputs is None, "status= and outputs= go with out="
+        ld = int(record_ld) if record_ld is not None else self.rec + (self.rec & 1)
+        own = []
+        try:
+            o, st, lists, po = None, None, (), None
+            if n:
+                o, st = vb.empty((n, ld)), vb.empty((3, n), np.int32)
+                own += [o, st]
+                if self.track is not None:
+                    # columns 0-1 are the caller's path to fill (vbx_pitch_path_f64 over an utterance's rows): NaN until then
+                    vb._check(vb.L.vbx_memset(vb.ctx, o.ptr, 0xFF, o.nbytes))
+                    lists = (vb.empty((n, int(self.track.kmax), 2)), vb.empty(n, np.int32), vb.empty(n))
+                    own += list(lists)
+                    po = PitchTrackOutputs(lists[0].ptr, lists[1].ptr, lists[2].ptr, None)
+            vb._check(fn(self.handle, addr, n_sf, _ptr(o), ld, _ptr(st), n, None if po is None else C.byref(po), C.byref(got)))
+            assert got.value == n
+            if n == 0:
+                res = (np.empty((0, ld)), np.empty((3, 0), np.int32))
+                if self.track is not None:
+                    res = res + (np.empty((0, int(self.track.kmax), 2)), np.empty(0, np.int32), np.empty(0))
+                return res
+            return (o.numpy(), st.numpy()) + tuple(a.numpy() for a in lists)
+        finally:
+            for d in own:
+                d.free()
+
+    def push(self, block, out=None, status=None, outputs=None, record_ld=None, status_ld=None):
+        """vbx_session_push: the next block of the stream, from HOST memory -- a numpy array of the session's sample type shaped
+        [T] or [T, channels], or bytes / a uint8 array of packed 24-bit PCM.  Returns what analyze_frames_ex returns for the frames
+        the block completes: (records [n, ld], status3 [3, n]), in the tracked form also (cand [n, kmax, 2], count, peak) and
+        columns 0-1 of the records left as NaN -- or None when out= (device records; status= and outputs= = (cand, count, peak,
+        None) device buffers, status_ld= the status rows' leading dimension, default n) is given."""
+        keep, fmt, addr, channels, n_sf = VoxBox._host_audio(block, self.format, self.channels, None)
+        assert fmt == self.format and channels == self.channels, "the block is not in the session's format"
+        return self._push(self.vb.L.vbx_session_push, addr, n_sf, out, status, outputs, record_ld, status_ld)
+
+    def push_device(self, block, n_sample_frames, out=None, status=None, outputs=None, record_ld=None, status_ld=None):
+        """vbx_session_push_device: the same for a block in DEVICE memory (a device buffer or a raw address), read in stream order on
+        the context's stream with no staging and no host wait."""
+        return self._push(self.vb.L.vbx_session_push_device, _ptr(block), int(n_sample_frames), out, status, outputs, record_ld, status_ld)
+
+    def mark_utterance(self):
+        """vbx_session_mark_utterance: the next frame delivered starts a new utterance (a seg_start entry of the resident call)."""
+        self.vb._check(self.vb.L.vbx_session_mark_utterance(self.handle))
+
+    def reset(self):
+        """vbx_session_reset: drop the carried samples and all state -- as a freshly opened session."""
+        self.vb._check(self.vb.L.vbx_session_reset(self.handle))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.vb.L.vbx_session_close(self.handle)
+            self.handle = None
+            self.vb._sessions.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class VoxBox:
     """One libvoxbox_hip context = one GPU + one HIP stream."""
 
@@ -541,6 +673,7 @@ class VoxBox:
         self.L = load_library()
         self._allocs = set()
         self._host_allocs = {}                  # pinned host memory of malloc_host: address -> the buffer object numpy views
+        self._sessions = set()                  # live sessions (closed with the context)
         ctx = C.c_void_p()
         rc = self.L.vbx_ctx_create(C.byref(ctx), device, stream)
         if rc != 0:
@@ -589,6 +722,8 @@ class VoxBox:
 
     def close(self):
         if getattr(self, "ctx", None):
+            for sess in list(self._sessions):
+                sess.close()
             for a in list(self._allocs):
                 a.free()
             for addr in list(self._host_allocs):
@@ -1363,6 +1498,15 @@ class VoxBox:
             return self.L.vbx_analyze_host(ctx, ptr, int(n_sample_frames), C.byref(hf), N, S, *rest)
         return self._analyze_tracked(fn, addr, F, int(frame_len), int(stride), params, track, seg_start, out, record_ld, status, lists,
                                      outputs, None, ext=ext)
+
+    def session(self, params, ext=None, track=None, format=SAMPLE_PCM16, channels=1, channel=0, frame_len=None, stride=None,
+                max_block=None):
+        """vbx_session_open: a live session on this context for channel `channel` of a stream of interleaved sample frames in
+        `format` (SAMPLE_*), fed block by block (Session.push; blocks of at most max_block sample frames, default one second's
+        worth of hops: 100 * stride).  Everything is allocated and warmed here; a Session is also a context manager."""
+        assert frame_len and stride
+        return Session(self, params, ext, track, format, channels, channel, frame_len, stride,
+                       int(max_block) if max_block is not None else 100 * int(stride))
 
     @staticmethod
     def _host_audio(audio, format, channels, n_sample_frames):
