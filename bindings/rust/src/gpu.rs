@@ -331,6 +331,17 @@ impl Gpu {
         Ok(Session { gpu: self, raw, format, sample_frame_bytes, frame_len, stride, record_ld: rec + (rec & 1), kmax: tk.map(|t| t.kmax) })
     }
 
+    /// The pitch path committed while the candidate lists arrive (`vbx_path_stream_open`): `vbx_pitch_path_f64`'s contour over lists
+    /// of `kmax` candidates per frame, pushed as they come.  Every row a push commits without a forced flag is the whole utterance's
+    /// path, bit for bit, whatever follows; at most `max_pending` frames are held, and rows that have to leave undecided are flagged.
+    /// `peak_ref` is the P of the silence term (the format's full scale, or a calibrated level).
+    pub fn path_stream(&self, kmax: usize, params: &PitchPathParams, peak_ref: f64, max_pending: usize) -> GpuResult<PathStream<'_>> {
+        let p = params.raw();
+        let mut raw: *mut ffi::VbxPathStream = ptr::null_mut();
+        self.check(unsafe { ffi::vbx_path_stream_open(self.raw, kmax, &p, peak_ref, max_pending, &mut raw) })?;
+        Ok(PathStream { gpu: self, raw, kmax, max_pending })
+    }
+
     /// The selected channels of interleaved sample frames on the device in ONE pass (`vbx_unpack_channels`): plane `k` is channel
     /// `select[k]`, `n_sample_frames` elements from element `k * plane_ld` of `dst`, bit for bit what [`Gpu::unpack_samples`] writes
     /// for that channel.  `select` holds distinct channels in any order, at most `VBX_HOST_MAX_CHANNELS` of them.
@@ -509,9 +520,73 @@ impl<'g> Session<'g> {
         self.gpu.check(unsafe { ffi::vbx_session_mark_utterance(self.raw) })
     }
 
-    /// Drop the carried samples and all state (`vbx_session_reset`): as a freshly opened session.
+    /// Drop the carried samples and all state (`vbx_session_reset`): as a freshly opened session.  A path binding is dropped too.
     pub fn reset(&self) -> GpuResult<()> {
         self.gpu.check(unsafe { ffi::vbx_session_reset(self.raw) })
+    }
+
+    /// The contour from this tracked session (`vbx_session_path_bind`): every push also commits the decided rows of the pitch path
+    /// into `rows` from row 0 (each array holds `max_pending` + the largest push's frames rows) and one `VbxPathCommit` into
+    /// `rows.commit`; [`Session::mark_utterance`] then delivers the rest of the ended utterance at once.  Before the first push or
+    /// after a reset; between pushes only the destinations may change.  The arrays must outlive the session's pushes.
+    pub fn bind_path(&self, peak_ref: f64, max_pending: usize, rows: &PathRows<'g>) -> GpuResult<()> {
+        self.gpu.check(unsafe {
+            ffi::vbx_session_path_bind(self.raw, peak_ref, max_pending, rows.path.as_mut_ptr(), 2, rows.index.as_mut_ptr(),
+                                       rows.forced.as_mut_ptr(), rows.commit.as_mut_ptr())
+        })
+    }
+}
+
+/// Where an online pitch path writes ([`PathStream::push`], [`Session::bind_path`]): `rows` rows of `path` / `index` / `forced`,
+/// written from row 0 by every push, and the push's `VbxPathCommit` (device memory: read it behind a sync).
+pub struct PathRows<'g> {
+    pub path: DeviceBuf<'g, ffi::VbxPitch>,
+    pub index: DeviceBuf<'g, i32>,
+    pub forced: DeviceBuf<'g, u8>,
+    pub commit: DeviceBuf<'g, ffi::VbxPathCommit>,
+}
+
+/// An online pitch path ([`Gpu::path_stream`]); closed on drop.
+pub struct PathStream<'g> {
+    gpu: &'g Gpu,
+    raw: *mut ffi::VbxPathStream,
+    kmax: usize,
+    max_pending: usize,
+}
+
+impl<'g> PathStream<'g> {
+    /// Output arrays for pushes of up to `max_frames` frames: `max_pending + max_frames` rows.
+    pub fn rows(&self, max_frames: usize) -> GpuResult<PathRows<'g>> {
+        let n = self.max_pending + max_frames;
+        Ok(PathRows { path: self.gpu.alloc(n)?, index: self.gpu.alloc(n)?, forced: self.gpu.alloc(n)?, commit: self.gpu.alloc(1)? })
+    }
+
+    /// The lists of the next `n_frames` frames (`vbx_path_stream_push`; device buffers, read in stream order and free to be reused
+    /// behind the call).  Commits every decided frame into `rows` from row 0; `end_utterance` commits everything pending and makes
+    /// the next frame the start of a new utterance (`n_frames == 0` is allowed then).  Asynchronous on the context's stream.
+    #[allow(clippy::too_many_arguments)]
+    pub fn push(&self, cand: &DeviceBuf<ffi::VbxPitch>, count: &DeviceBuf<i32>, status: Option<&DeviceBuf<i32>>,
+                local_peak: Option<&DeviceBuf<f64>>, n_frames: usize, end_utterance: bool, rows: &PathRows<'g>) -> GpuResult<()> {
+        assert!(cand.len() >= n_frames * self.kmax && count.len() >= n_frames, "lists too small");
+        assert!(rows.path.len() >= self.max_pending + n_frames, "output rows too small");
+        self.gpu.check(unsafe {
+            ffi::vbx_path_stream_push(self.raw, cand.as_ptr(), count.as_ptr(), status.map_or(ptr::null(), |b| b.as_ptr()),
+                                      local_peak.map_or(ptr::null(), |b| b.as_ptr()), n_frames, end_utterance as i32,
+                                      rows.path.as_mut_ptr(), 2, rows.index.as_mut_ptr(), rows.forced.as_mut_ptr(), rows.commit.as_mut_ptr())
+        })
+    }
+
+    /// As freshly opened: pending frames are dropped (`vbx_path_stream_reset`).
+    pub fn reset(&self) -> GpuResult<()> {
+        self.gpu.check(unsafe { ffi::vbx_path_stream_reset(self.raw) })
+    }
+}
+
+impl<'g> Drop for PathStream<'g> {
+    fn drop(&mut self) {
+        unsafe {
+            ffi::vbx_path_stream_close(self.raw);
+        }
     }
 }
 

@@ -879,7 +879,8 @@ int vbx_analyze_host_channels(vbx_ctx *ctx, const void *h_audio, size_t n_sample
  * the path needs them) peaks through h_outputs, n rows each: cand and count are required, peak when silence_threshold != 0, index must
  * be NULL.  Columns 0-1 of the pushed records are NOT written: the caller runs vbx_pitch_path_f64 over an utterance's rows when it
  * ends, and because the lists are per frame and equal the resident call's, that contour equals the resident tracked call's columns
- * 0-1, bit for bit.  (A bounded-delay online path is a different algorithm and not offered.)
+ * 0-1, bit for bit.  Or the session is bound to an online path (vbx_session_path_bind, below), and every push also delivers the
+ * rows of the contour that are decided: exact where decided, forced rows only at the cap, P fixed at peak_ref.
  * The LPC policy is the context's at the time of each push.  Several sessions may live on one context, each owning its carry; any
  * other entry point may be called on the context between pushes without changing a session's output.  After a push the
  * vbx_internal_last_* probes describe that push's frame-loop call, and the context holds no state for vbx_track_stitch_f64.  Not
@@ -917,6 +918,72 @@ int vbx_session_mark_utterance(vbx_session *s);   /* the next frame delivered st
 int vbx_session_reset(vbx_session *s);            /* drop the carried samples and all state: as a freshly opened session */
 int vbx_session_info(const vbx_session *s, size_t *h_consumed, size_t *h_frames, size_t *h_carried);
 void vbx_session_close(vbx_session *s);
+
+/* ------------------------------------------------------------------ the pitch path while the lists arrive (ABI 5, added) */
+
+/* vbx_pitch_path_f64's contour, committed while the candidate lists arrive: a path stream is opened once on a context, pushed the
+ * lists of the frames that have come (any number per push), and every push writes the rows of the frames whose state is DECIDED.
+ * Definition.
+ *   Recursion.  lambda, c, D, psi and the leader are vbx_pitch_path_f64's, operation for operation, in IEEE binary64 with no fused
+ *     multiply-add (the same device code computes them).  chunk_frames is ignored: the true D is carried from push to push, so
+ *     nothing is speculated and nothing repaired.
+ *   Silence term.  The resident call divides by P, the utterance's largest local_peak, which is not causal.  Here P = peak_ref, fixed
+ *     at open: the format's full scale, or a level from calibration.  With silence_threshold == 0 or a NULL local_peak
+ *     u_t = voicing_threshold and peak_ref is ignored.
+ *   Decided frames.  When T frames of the current utterance have been scanned, decided(T) is the length of the longest prefix on
+ *     which the psi traces from ALL active states of frame T - 1 agree (T itself when that frame has one state).  Every continuation
+ *     of the utterance passes through one of those states, so the states of that prefix are the whole utterance's path, bit for bit,
+ *     whatever follows.  decided(T) never shrinks.
+ *   Commit.  A push commits every decided frame that is not yet committed.  Rows are written in frame order from row 0 of the output
+ *     arrays: row i at out_path + i * path_ld doubles, with out_index[i] and out_forced[i] (both optional).  The row format is
+ *     vbx_pitch_path_f64's: the chosen list entry, or {0.0, u_t}; the index is the list position, or -1.
+ *   Cap.  At most max_pending frames are ever held.  If, after committing what is decided, max_pending frames are still pending when
+ *     another frame must be scanned, the oldest ceil(max_pending / 2) of them are committed along the trace from the CURRENT leader,
+ *     with out_forced = 1.  A forced row may differ from the whole utterance's path.  Decidedness depends on psi alone, so every row
+ *     that is not forced equals the whole path, forced rows before it or not.
+ *   Utterance end.  end_utterance != 0 commits all pending frames along the trace from the first state with D = 0, as the resident
+ *     path ends (out_forced = 0: these rows are exact); the next frame starts a new utterance with D_0 = e_0 - max e_0.
+ *     n_frames == 0 with the flag set is allowed.
+ *   *d_commit (device memory, written in stream order; read it after a sync or an event).  first: the index of row 0, counted in
+ *     frames pushed since open or reset; n: rows written; n_forced: how many of them were forced; pending: frames still held.
+ *   Output size.  The arrays must hold max_pending + n_frames rows.  Rows beyond n are not touched.
+ *   Schedule independence.  Decisions are evaluated when the ring is full and at the end of a push.  So the states, the forced flags
+ *     and the number of frames committed once frame T has been pushed depend only on the frames pushed so far and on max_pending,
+ *     never on how the frames were cut into pushes (tests/test_gpu_path_stream.py holds one-frame, seven-frame, random and whole
+ *     pushes to the same rows and the same commits).
+ * Everything is asynchronous on the context's stream: the lists are read in stream order and may be reused behind the push (the
+ * stream keeps what a later commit needs in its own ring of max_pending frames, allocated at open); no push allocates, nothing
+ * returns to the host.  A push of any n_frames is accepted; it is ONE launch of one lane group (pitch_path_online in the profile),
+ * sequential by nature: about the resident call's sequential rate on large pushes -- large resident batches
+ * have vbx_pitch_path_f64's chunked form.  Several streams may live on one context.  vbx_path_stream_reset: as freshly opened
+ * (pending frames are dropped).  vbx_path_stream_close frees the stream behind the work queued on the context's stream.
+ * VBX_E_INVALID: kmax 0 or above 63, max_pending 0 (or above 2^24), the parameters vbx_pitch_path_f64 rejects, silence_threshold > 0 with a NULL
+ * local_peak or with peak_ref negative or not finite, a NULL stream, out_path or d_commit, NULL lists with n_frames > 0, path_ld < 2.
+ *
+ * vbx_session_path_bind: the contour from a live session.  Allowed on a session opened with h_track, before the first push or after
+ * a reset (between pushes again, to change the destinations only: peak_ref and max_pending must repeat, the state is kept).  Every
+ * push of a bound session (a push of n_sample_frames == 0 stays a no-op and reports nothing) then runs one more launch behind session_deliver: the online path over the push's own rows of the
+ * session-owned lists, counts, pitch status row and peaks (time_step == 0: stride / sample_rate, as in the tracked call); the
+ * committed rows go to the bound arrays from row 0 (they hold max_pending + the frames of the largest push), the commit to d_commit.
+ * vbx_session_mark_utterance on a bound session ends the path's utterance at once (one launch, n_frames = 0, end_utterance = 1): the
+ * rest of the contour is there when the mark is made.  vbx_session_reset resets the path and drops the binding; vbx_session_close
+ * frees it.  Records, status rows and h_outputs of a bound session's pushes are what they were; an unbound session is unchanged.
+ * Contract: with silence_threshold == 0 and no forced row, the committed rows of all pushes, concatenated, equal columns 0-1 and
+ * `index` of the resident tracked call on the concatenated blocks (marks: h_seg_start), for every way of cutting the audio into
+ * blocks; with silence_threshold > 0 they equal the world-1 shard protocol (vbx_pitch_path_shard_begin_f64 / _enter / _finish)
+ * with every utterance's seg_peak = peak_ref. */
+typedef struct vbx_path_stream vbx_path_stream;
+typedef struct { int64_t first, n, n_forced, pending; } vbx_path_commit;   /* device memory */
+
+int vbx_path_stream_open(vbx_ctx *ctx, size_t kmax, const vbx_pitch_path_params *h_params, double peak_ref, size_t max_pending,
+                         vbx_path_stream **out);
+int vbx_path_stream_push(vbx_path_stream *ps, const vbx_pitch *cand, const int32_t *count, const int32_t *status,
+                         const double *local_peak, size_t n_frames, int end_utterance,
+                         vbx_pitch *out_path, size_t path_ld, int32_t *out_index, uint8_t *out_forced, vbx_path_commit *d_commit);
+int vbx_path_stream_reset(vbx_path_stream *ps);
+void vbx_path_stream_close(vbx_path_stream *ps);
+int vbx_session_path_bind(vbx_session *s, double peak_ref, size_t max_pending,
+                          vbx_pitch *out_path, size_t path_ld, int32_t *out_index, uint8_t *out_forced, vbx_path_commit *d_commit);
 
 /* ------------------------------------------------------------------ multi-GPU: frame-range sharding */
 

@@ -23,6 +23,9 @@
 //   shard   pp_enter_kernel / pp_open_map_kernel / pp_export_kernel / pp_select_kernel   the hand-off across a shard cut
 //                             (vbx_pitch_path_shard_*): the kernels above run unchanged on a rank's frames, these connect them to
 //                             the neighbouring ranks (at the end of the file).
+//   online  pp_online_kernel  vbx_path_stream_push: one group scans the frames a push brings from the true carried state, keeps
+//                             psi and the rows of the pending frames in a device ring, and commits every frame whose state is
+//                             decided (behind the shard kernels).
 #include "vbx_kernels.hpp"
 
 #include <hip/hip_runtime.h>
@@ -427,6 +430,133 @@ __global__ __launch_bounds__(256) void pp_select_kernel(const uint8_t *__restric
     sel[c * G] = map[c * G + e];
 }
 
+// ---- the online path (vbx_path_stream_*): the same recursion while the lists arrive ------------------------------------------
+// One group (block of G lanes, gbase 0) scans the push's frames in order from the TRUE state the last push left in O.st: nothing is
+// speculated, nothing repaired.  Per frame, lane s stores psi and what a commit of state s would write (the output row and index)
+// into slot `frame % cap` of the ring, so the caller's lists are not needed behind the push.  Frame t is DECIDED once the psi traces
+// from all states of the newest frame have met at or after t: every continuation passes through one of those states, so the merged
+// prefix is the whole utterance's path.  Decisions are evaluated when the ring is full and at the end of the push, which commits
+// the same rows as evaluating them after every frame (decided(T) only grows with T); a ring that is still full is relieved of its
+// oldest ceil(cap / 2) frames along the leader's trace, flagged as forced.
+
+// A pending frame is named by its distance d from the newest frame (0 = newest); `head` is the slot the next frame takes, so the
+// frame at distance d lives in slot head - 1 - d (mod cap).  cap <= 2^24: cap * G fits an int.
+__device__ __forceinline__ int pp_ring_slot(int head, int d, int cap) { const int v = head - 1 - d; return (v < 0) ? v + cap : v; }
+
+template <int G>
+__global__ __launch_bounds__(64) void pp_online_kernel(const pp_par_t P_, const pp_online_t O) {
+    __shared__ double2 lds[2][64];
+    __shared__ uint8_t path[PP_TILE];
+    const int s = threadIdx.x;                                 // blockDim.x == G: gbase 0
+    pp_online_state_t *S = O.st;
+    __shared__ double peak;                                    // P = peak_ref: what pp_unvoiced reads as the peak of "segment" 0
+    if (s == 0) peak = O.peak;
+    __syncthreads();
+    pp_par_t P = P_;
+    P.spk = &peak;
+    const int cap = (int)O.cap;
+    double D = S->D[s], lf = S->lf[s];
+    int pn = S->n, buf = 0;
+    unsigned long long pv = S->vmask;
+    int pend = (int)(S->scanned - S->committed), head = (int)(S->scanned % cap);
+    bool fresh = S->utt == 0;                                  // (lane s has a state in the newest frame iff s < pn)
+    int pend0 = pend;                                          // the frame at distance d is output row pend0 + t - 1 - d
+    // what only the row stores use lives in vector registers: the scalar file is full (no spill), and these feed vector addresses
+    double *out_path = reinterpret_cast<double *>(O.out_path);
+    int32_t *out_index = O.out_index;
+    uint8_t *out_forced = O.out_forced;
+    long ld = O.ld;
+    asm volatile("" : "+v"(pend0), "+v"(out_path), "+v"(out_index), "+v"(out_forced), "+v"(ld));
+    long n_forced = 0;
+    lds[buf][s] = make_double2(D, lf);
+    pp_raw_t r, nx;
+    pp_frame_t fr;
+    if (P.F > 0) pp_fetch(P, 0, s, r);
+    for (long t = 0;; t++) {
+        const bool last = t == P.F;
+        if ((last || pend == cap) && pend > 0) {
+            // decisions: when the ring is full, and at the end of the push.  Pass 0 is the merge test: each lane walks its own state's
+            // trace back from the newest frame until a ballot shows one state for all (lanes without a state walk with lane 0, whose
+            // state always exists).  Pass 1 follows the leader's trace: to relieve a ring that is still full of its oldest
+            // ceil(cap / 2) frames (flag 1), or to end the utterance (flag 0).  Either pass commits distances [d_hi, pend).
+            __syncthreads();                                   // the ring stores of the frames scanned, before other lanes read them
+            for (int pass = 0; pass < 2 && pend > 0; pass++) {
+                int d_hi = -1, cur = (s < pn) ? s : 0, flag = 0;
+                if (pass == 0) {
+                    int sl = head;
+                    for (int d = 0; d < pend; d++) {
+                        sl = (sl == 0) ? cap - 1 : sl - 1;
+                        const int ref = __shfl(cur, 0, G);
+                        if ((__ballot(cur != ref) & pp_gmask<G>()) == 0ull) { d_hi = d; break; }
+                        cur = O.psi[sl * G + cur] & (G - 1);
+                    }
+                    if (d_hi < 0) continue;
+                } else {
+                    const bool end = last && O.end != 0;
+                    if (!end && (last || pend < cap)) break;
+                    flag = end ? 0 : 1;
+                    d_hi = end ? 0 : pend - (cap + 1) / 2;
+                    cur = pp_leader<G>(D, s < pn, 0);
+                    int sl = head;
+                    for (int d = 0; d < d_hi; d++) {
+                        sl = (sl == 0) ? cap - 1 : sl - 1;
+                        cur = O.psi[sl * G + cur] & (G - 1);
+                    }
+                }
+                // every lane holds the trace's state at distance d_hi: walk it back tile by tile (lane 0 stages the states in LDS),
+                // then all lanes write the tile's rows
+                for (int d0 = d_hi; d0 < pend; d0 += PP_TILE) {
+                    const int d1 = (d0 + PP_TILE < pend) ? d0 + PP_TILE : pend;
+                    int sl = pp_ring_slot(head, d0, cap);
+                    for (int d = d0; d < d1; d++) {
+                        if (s == 0) path[d - d0] = (uint8_t)cur;
+                        cur = O.psi[sl * G + cur] & (G - 1);
+                        sl = (sl == 0) ? cap - 1 : sl - 1;
+                    }
+                    __syncthreads();
+                    for (int d = d0 + s; d < d1; d += G) {
+                        const int at = pp_ring_slot(head, d, cap) * G + path[d - d0];
+                        const long row = t + (pend0 - 1 - d);
+                        const pitch_t o = O.row[at];
+                        double *dst = out_path + row * ld;                     // (rows of any ld: two 8-byte stores)
+                        dst[0] = o.frequency; dst[1] = o.strength;
+                        if (out_index != nullptr) out_index[row] = (int32_t)O.idx[at];
+                        if (out_forced != nullptr) out_forced[row] = (uint8_t)flag;
+                    }
+                    __syncthreads();                           // the tile, and the slots these rows came from, are free again
+                }
+                if (flag) n_forced += pend - d_hi;
+                pend = d_hi;
+            }
+        }
+        if (last) break;
+        if (t + 1 < P.F) pp_fetch(P, t + 1, s, nx);
+        pp_decode<G>(P, r, 0, s, 0, fr);
+        int arg;
+        D = pp_step<G>(P, fr, fresh, &lds[buf][0], pn, pv, arg);
+        int m = (r.st == 0) ? r.cnt : 0;                       // the listed entries, as pp_decode counts them
+        m = (m < 0) ? 0 : ((m > P.kmax) ? P.kmax : m);
+        const int at = head * G + s;
+        O.psi[at] = (uint8_t)arg;
+        O.row[at] = fr.voiced ? r.e : pitch_t{0.0, fr.lam};    // the chosen list entry, or {0, u_t}
+        O.idx[at] = (int8_t)((s < m) ? s : -1);
+        buf ^= 1;
+        lf = fr.lf;
+        lds[buf][s] = make_double2(D, lf);
+        pn = fr.n; pv = fr.vmask;
+        head = (head + 1 == cap) ? 0 : head + 1;
+        pend++; fresh = false;
+        r = nx;
+    }
+    S->D[s] = D; S->lf[s] = lf;
+    if (s == 0) {
+        const long scanned = S->scanned + P.F, first = S->committed;
+        S->n = pn; S->vmask = pv; S->scanned = scanned; S->committed = scanned - pend;
+        S->utt = (fresh || O.end != 0) ? 0 : 1;
+        *O.commit = pp_commit_t{first, P.F + (pend0 - pend), n_forced, (long)pend};
+    }
+}
+
 // ---- launches ---------------------------------------------------------------------------------------------------------------
 void launch_pitch_path_open_map(hipStream_t s, uint8_t *map, long c, int G) {
     hipLaunchKernelGGL(pp_open_map_kernel, dim3(1), dim3(64), 0, s, map, c, G);
@@ -480,6 +610,9 @@ void launch_pitch_path_write(hipStream_t s, const pp_par_t &P, int G_, const uin
 }
 void launch_pitch_path_enter(hipStream_t s, const pp_par_t &P, int G_, long c0, long c1, const double *state_in, int32_t *changed) {
     VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_enter_kernel<G>, dim3(1), dim3(G), 0, s, P, c0, c1, state_in, changed));
+}
+void launch_pitch_path_online(hipStream_t s, const pp_par_t &P, int G_, const pp_online_t &O) {
+    VBX_PP_DISPATCH(G_, hipLaunchKernelGGL(pp_online_kernel<G>, dim3(1), dim3(G), 0, s, P, O));
 }
 #undef VBX_PP_DISPATCH
 

@@ -2305,6 +2305,118 @@ int vbx_analyze_host_channels(vbx_ctx *ctx, const void *h_audio, size_t n_sample
                              n_segments, chan, record_ld);
 }
 
+// ---- the online pitch path (header: "the pitch path while the lists arrive") --------------------
+
+// One contour that grows while its lists arrive.  The stream owns the carried state and the ring of max_pending frames (one
+// allocation, made at open); a push is one launch of pp_online_kernel on the context's stream and touches nothing of the context's.
+struct vbx_path_stream {
+    vbx_ctx *ctx = nullptr;
+    size_t kmax = 0, max_pending = 0;
+    int G = 4;
+    vbx_pitch_path_params pr{};
+    double peak_ref = 0.0;
+    void *mem = nullptr;                                  // pp_online_state_t, then the ring: row [cap][G], psi [cap][G], idx [cap][G]
+    pp_online_t O{};
+};
+
+static int path_stream_open(vbx_ctx *ctx, const char *fn, size_t kmax, const vbx_pitch_path_params &pr, double peak_ref, size_t max_pending,
+                            vbx_path_stream **out) {
+    int rc = check_pitch_path(ctx, fn, pr, 0, kmax, true, nullptr, 0);
+    if (rc != VBX_SUCCESS) return rc;
+    if (max_pending < 1 || max_pending > ((size_t)1 << 24)) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": max_pending must be in [1, 2^24]");
+    if (pr.silence_threshold > 0.0 && !(std::isfinite(peak_ref) && peak_ref >= 0.0))
+        return fail(ctx, VBX_E_INVALID, std::string(fn) + ": silence_threshold > 0 needs a finite peak_ref >= 0");
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    vbx_path_stream *ps = new vbx_path_stream();
+    ps->ctx = ctx; ps->kmax = kmax; ps->max_pending = max_pending; ps->pr = pr; ps->peak_ref = peak_ref;
+    while (ps->G < (int)kmax + 1) ps->G <<= 1;
+    const size_t G = (size_t)ps->G, b_st = (sizeof(pp_online_state_t) + 255) & ~(size_t)255, b_row = max_pending * G * sizeof(pitch_t),
+                 b_psi = max_pending * G;
+    hipError_t e = hipMalloc(&ps->mem, b_st + b_row + 2 * b_psi);
+    if (e == hipSuccess) e = hipMemsetAsync(ps->mem, 0, b_st, ctx->stream);
+    if (e != hipSuccess) {
+        if (ps->mem) { hipStreamSynchronize(ctx->stream); hipFree(ps->mem); }
+        delete ps;
+        return fail(ctx, VBX_E_RUNTIME, std::string(fn) + ": " + hipGetErrorString(e));
+    }
+    char *p = static_cast<char *>(ps->mem);
+    ps->O.st = reinterpret_cast<pp_online_state_t *>(p); p += b_st;
+    ps->O.row = reinterpret_cast<pitch_t *>(p); p += b_row;
+    ps->O.psi = reinterpret_cast<uint8_t *>(p); p += b_psi;
+    ps->O.idx = reinterpret_cast<int8_t *>(p);
+    ps->O.cap = (long)max_pending;
+    ps->O.peak = peak_ref;
+    *out = ps;
+    return VBX_SUCCESS;
+}
+
+// one launch (arguments checked by the caller): n frames of lists, rows from row 0 of the outputs
+static int path_stream_launch(vbx_path_stream *ps, const char *fn, const vbx_pitch *cand, const int32_t *count, const int32_t *status,
+                              const double *local_peak, size_t n, int end_utterance, vbx_pitch *out_path, size_t path_ld, int32_t *out_index,
+                              uint8_t *out_forced, vbx_path_commit *d_commit) {
+    vbx_ctx *ctx = ps->ctx;
+    const vbx_pitch_path_params &pr = ps->pr;
+    pp_par_t P{};
+    P.cand = reinterpret_cast<const pitch_t *>(cand); P.count = count; P.status = status; P.lpk = local_peak;
+    P.F = (long)n; P.kmax = (int)ps->kmax; P.use_u = (local_peak != nullptr && pr.silence_threshold != 0.0) ? 1 : 0;
+    const double corr = 0.01 / pr.time_step;                   // the host constants of the definition, in its order (pp_setup)
+    P.vt = pr.voicing_threshold; P.oc = pr.octave_cost;
+    P.cvu = pr.voiced_unvoiced_cost * corr; P.cj = pr.octave_jump_cost * corr;
+    P.Lc = std::log2(pr.ceiling_hz); P.q = pr.silence_threshold / (1.0 + pr.voicing_threshold);
+    pp_online_t O = ps->O;
+    O.end = end_utterance ? 1 : 0;
+    O.out_path = reinterpret_cast<pitch_t *>(out_path); O.ld = (long)path_ld; O.out_index = out_index; O.out_forced = out_forced;
+    O.commit = reinterpret_cast<pp_commit_t *>(d_commit);
+    { Prof pf(ctx, "pitch_path_online"); launch_pitch_path_online(ctx->stream, P, ps->G, O); }
+    return check_launch(ctx, fn);
+}
+
+static int path_stream_reset(vbx_path_stream *ps) {
+    VBX_HIP(ps->ctx, hipSetDevice(ps->ctx->device));
+    VBX_HIP(ps->ctx, hipMemsetAsync(ps->mem, 0, sizeof(pp_online_state_t), ps->ctx->stream));
+    return VBX_SUCCESS;
+}
+
+static void path_stream_free(vbx_path_stream *ps) {
+    hipSetDevice(ps->ctx->device);
+    hipStreamSynchronize(ps->ctx->stream);                // queued pushes may still use the ring
+    if (ps->mem) hipFree(ps->mem);
+    delete ps;
+}
+
+int vbx_path_stream_open(vbx_ctx *ctx, size_t kmax, const vbx_pitch_path_params *h_params, double peak_ref, size_t max_pending,
+                         vbx_path_stream **out) {
+    if (!ctx) return fail(nullptr, VBX_E_INVALID, "vbx_path_stream_open: null context");
+    VBX_REQUIRE(ctx, out != nullptr, "null output");
+    *out = nullptr;
+    VBX_REQUIRE(ctx, h_params != nullptr, "null params");
+    return path_stream_open(ctx, __func__, kmax, *h_params, peak_ref, max_pending, out);
+}
+
+int vbx_path_stream_push(vbx_path_stream *ps, const vbx_pitch *cand, const int32_t *count, const int32_t *status, const double *local_peak,
+                         size_t n_frames, int end_utterance, vbx_pitch *out_path, size_t path_ld, int32_t *out_index, uint8_t *out_forced,
+                         vbx_path_commit *d_commit) {
+    if (!ps) return fail(nullptr, VBX_E_INVALID, "vbx_path_stream_push: null stream");
+    vbx_ctx *ctx = ps->ctx;
+    VBX_REQUIRE(ctx, out_path != nullptr && d_commit != nullptr, "null out_path or d_commit");
+    VBX_REQUIRE(ctx, path_ld >= 2, "path_ld must be >= 2");
+    VBX_REQUIRE(ctx, n_frames == 0 || (cand != nullptr && count != nullptr), "null cand or count");
+    VBX_REQUIRE(ctx, !(ps->pr.silence_threshold > 0.0 && n_frames > 0 && local_peak == nullptr), "silence_threshold > 0 needs local_peak");
+    VBX_REQUIRE(ctx, n_frames <= ((size_t)1 << 40), "too many frames for one push");
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    return path_stream_launch(ps, __func__, cand, count, status, local_peak, n_frames, end_utterance, out_path, path_ld, out_index, out_forced,
+                              d_commit);
+}
+
+int vbx_path_stream_reset(vbx_path_stream *ps) {
+    if (!ps) return fail(nullptr, VBX_E_INVALID, "vbx_path_stream_reset: null stream");
+    return path_stream_reset(ps);
+}
+
+void vbx_path_stream_close(vbx_path_stream *ps) {
+    if (ps) path_stream_free(ps);
+}
+
 // ---- live sessions (header: "live sessions") --------------------------------------------------
 
 // blocks of up to this many bytes are staged through the session's pinned buffers and uploaded on the context's own stream: a host
@@ -2343,6 +2455,10 @@ struct vbx_session {
     double *c_rec = nullptr; int32_t *c_st = nullptr;
     vbx_pitch *c_cand = nullptr; int32_t *c_count = nullptr; double *c_peak = nullptr;
     double *state = nullptr;                              // 2 * n_est doubles: the formant row of the last frame delivered
+    // vbx_session_path_bind: the online path over the session-owned lists, and where its rows go
+    vbx_path_stream *path = nullptr;
+    bool bound = false;
+    vbx_pitch *p_out = nullptr; size_t p_ld = 0; int32_t *p_index = nullptr; uint8_t *p_forced = nullptr; vbx_path_commit *p_commit = nullptr;
 };
 
 static void session_free(vbx_session *s) {
@@ -2360,6 +2476,7 @@ static void session_free(vbx_session *s) {
     if (s->c_count) hipFree(s->c_count);
     if (s->c_peak) hipFree(s->c_peak);
     if (s->state) hipFree(s->state);
+    if (s->path) path_stream_free(s->path);
     delete s;
 }
 
@@ -2532,6 +2649,14 @@ static int session_push_impl(vbx_session *s, const char *fn, const void *block, 
         ctx->last_track.n_est = 0;
         s->frames += nf;
     }
+    if (s->bound) {
+        // the contour: the online path over the push's own rows of the session-owned lists, behind session_deliver (a push that
+        // completes no frame still reports: n = 0 and what is pending)
+        const size_t w = nf ? pl.warm : 0;
+        int rc = path_stream_launch(s->path, fn, s->c_cand + w * s->track.kmax, s->c_count + w, s->c_st + w, want_peak ? s->c_peak + w : nullptr,
+                                    nf, 0, s->p_out, s->p_ld, s->p_index, s->p_forced, s->p_commit);
+        if (rc != VBX_SUCCESS) return bail(rc);
+    }
     int rc = check_launch(ctx, fn);
     if (rc != VBX_SUCCESS) return bail(rc);
     if (h_n) *h_n = nf;
@@ -2552,6 +2677,40 @@ int vbx_session_push_device(vbx_session *s, const void *d_block, size_t n_sample
 int vbx_session_mark_utterance(vbx_session *s) {
     if (!s) return fail(nullptr, VBX_E_INVALID, "vbx_session_mark_utterance: null session");
     s->utt_frame = vbx_frame_count(s->consumed, s->frame_len, s->stride);
+    if (s->bound) {                                       // the rest of the contour now, not when the next frame arrives
+        VBX_HIP(s->ctx, hipSetDevice(s->ctx->device));
+        return path_stream_launch(s->path, __func__, nullptr, nullptr, nullptr, nullptr, 0, 1, s->p_out, s->p_ld, s->p_index, s->p_forced,
+                                  s->p_commit);
+    }
+    return VBX_SUCCESS;
+}
+
+int vbx_session_path_bind(vbx_session *s, double peak_ref, size_t max_pending, vbx_pitch *out_path, size_t path_ld, int32_t *out_index,
+                          uint8_t *out_forced, vbx_path_commit *d_commit) {
+    if (!s) return fail(nullptr, VBX_E_INVALID, "vbx_session_path_bind: null session");
+    vbx_ctx *ctx = s->ctx;
+    VBX_REQUIRE(ctx, s->have_track, "the session was opened without h_track: it has no candidate lists");
+    VBX_REQUIRE(ctx, out_path != nullptr && d_commit != nullptr, "null out_path or d_commit");
+    VBX_REQUIRE(ctx, path_ld >= 2, "path_ld must be >= 2");
+    if (s->bound) {                                       // between pushes: other destinations, the same path
+        VBX_REQUIRE(ctx, max_pending == s->path->max_pending && std::memcmp(&peak_ref, &s->path->peak_ref, sizeof(double)) == 0,
+                    "a bound session keeps its peak_ref and max_pending (vbx_session_reset drops the binding)");
+    } else {
+        VBX_REQUIRE(ctx, s->consumed == 0, "bind before the first push or after vbx_session_reset");
+        vbx_pitch_path_params path = s->track.path;
+        if (path.time_step == 0.0) path.time_step = (double)s->stride / s->p.sample_rate;
+        // the path of before a reset (its state was reset with the session) serves again when nothing about it changes
+        const bool same = s->path != nullptr && s->path->max_pending == max_pending && std::memcmp(&peak_ref, &s->path->peak_ref, sizeof(double)) == 0;
+        if (!same) {
+            vbx_path_stream *ps = nullptr;
+            int rc = path_stream_open(ctx, __func__, s->track.kmax, path, peak_ref, max_pending, &ps);
+            if (rc != VBX_SUCCESS) return rc;
+            if (s->path) path_stream_free(s->path);
+            s->path = ps;
+        }
+        s->bound = true;
+    }
+    s->p_out = out_path; s->p_ld = path_ld; s->p_index = out_index; s->p_forced = out_forced; s->p_commit = d_commit;
     return VBX_SUCCESS;
 }
 
@@ -2559,6 +2718,10 @@ int vbx_session_reset(vbx_session *s) {
     if (!s) return fail(nullptr, VBX_E_INVALID, "vbx_session_reset: null session");
     // (nothing is queued: the next ingest keeps nothing of the carry, and a first push of an utterance stitches from no state)
     s->consumed = 0; s->utt_frame = 0; s->frames = 0; s->base = 0; s->keep_from = 0;
+    if (s->path) {                                        // the path's state goes, and the binding with it
+        s->bound = false;
+        return path_stream_reset(s->path);
+    }
     return VBX_SUCCESS;
 }
 

@@ -451,4 +451,26 @@ void launch_pitch_path_export(hipStream_t s, const double *src /* ns or NULL */,
                               double *state_out /* 64 or NULL */, int32_t *back_map /* 64 or NULL */);
 void launch_pitch_path_select(hipStream_t s, const uint8_t *map, long c0, long nch, int G, const int32_t *end_state, uint8_t *sel);
 
+// the online path (vbx_path_stream_*): what one stream carries from push to push, and its ring of max_pending frames.  Frame g
+// (counted since open / reset) lives in slot g % cap while it is pending; a slot holds, per state, psi and the row and index a
+// commit of that state writes -- the caller's lists are not read again behind the push that scanned them.
+struct pp_online_state_t {
+    double D[64], lf[64];                                         // {D, log2 f} of the last frame scanned
+    unsigned long long vmask;                                     // ... its voiced states
+    int32_t n, pad;                                               // ... and how many states it has
+    int64_t scanned, committed, utt;                              // frames since open / reset: scanned, committed; utt: 0 = the next frame starts an utterance
+};
+struct pp_commit_t { int64_t first, n, n_forced, pending; };      // vbx_path_commit
+struct pp_online_t {
+    pp_online_state_t *st;
+    uint8_t *psi; pitch_t *row; int8_t *idx;                      // the ring: [cap][G] each
+    long cap;                                                     // max_pending (<= 2^24)
+    int end;                                                      // end_utterance
+    double peak;                                                  // P = peak_ref of the silence term
+    pitch_t *out_path; long ld; int32_t *out_index; uint8_t *out_forced;
+    pp_commit_t *commit;
+};
+// P: cand / count / status / lpk of the push's F frames, kmax, use_u and the constants; nothing else is read (spk: O.peak)
+void launch_pitch_path_online(hipStream_t s, const pp_par_t &P, int G, const pp_online_t &O);
+
 }  // namespace vbx

@@ -464,6 +464,12 @@ public:
     }
     void mark_utterance() { c_.check(vbx_session_mark_utterance(s_)); }
     void reset() { c_.check(vbx_session_reset(s_)); }
+    // the contour from a tracked session (vbx_session_path_bind): every push also commits the decided rows of the pitch path into the
+    // bound device arrays from row 0 (max_pending + the largest push's frames rows each) and one PathCommit into d_commit
+    void bind_path(double peak_ref, size_t max_pending, vbx_pitch *out_path, size_t path_ld, int32_t *out_index, uint8_t *out_forced,
+                   vbx_path_commit *d_commit) {
+        c_.check(vbx_session_path_bind(s_, peak_ref, max_pending, out_path, path_ld, out_index, out_forced, d_commit));
+    }
     struct Info { size_t consumed, frames, carried; };
     Info info() const {
         Info i{};
@@ -474,6 +480,31 @@ public:
 private:
     Context &c_;
     vbx_session *s_ = nullptr;
+};
+
+// The pitch path committed while the candidate lists arrive (vbx_path_stream_*): pitch_path's contour over lists pushed as they come.
+// Every row a push commits without a forced flag is the whole utterance's path, bit for bit, whatever follows; at most max_pending
+// frames are held.  All pointers are device memory; a push is one launch on the context's stream and d_commit is written in stream
+// order (read it behind a sync).  The output arrays hold max_pending + n_frames rows and are written from row 0.
+using PathCommit = vbx_path_commit;
+class path_stream {
+public:
+    path_stream(Context &c, size_t kmax, const vbx_pitch_path_params &params, double peak_ref, size_t max_pending) : c_(c) {
+        c.check(vbx_path_stream_open(c.get(), kmax, &params, peak_ref, max_pending, &s_));
+    }
+    ~path_stream() { vbx_path_stream_close(s_); }
+    path_stream(const path_stream &) = delete;
+    path_stream &operator=(const path_stream &) = delete;
+    void push(const vbx_pitch *cand, const int32_t *count, const int32_t *status, const double *local_peak, size_t n_frames,
+              bool end_utterance, vbx_pitch *out_path, size_t path_ld, int32_t *out_index, uint8_t *out_forced, PathCommit *d_commit) {
+        c_.check(vbx_path_stream_push(s_, cand, count, status, local_peak, n_frames, end_utterance ? 1 : 0, out_path, path_ld, out_index,
+                                      out_forced, d_commit));
+    }
+    void reset() { c_.check(vbx_path_stream_reset(s_)); }
+    vbx_path_stream *get() const { return s_; }
+private:
+    Context &c_;
+    vbx_path_stream *s_ = nullptr;
 };
 
 // Frame-range sharding of one recording over the GPUs of a node (no counterpart in the reference) and the gather of the

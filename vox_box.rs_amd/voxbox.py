@@ -177,6 +177,15 @@ class SessionPlan(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class PathCommit(C.Structure):
+    """vbx_path_commit (device memory): what one push of the online pitch path committed -- `first`: the frame (counted since
+    open / reset) of output row 0; `n`: rows written; `n_forced`: how many of them were forced at the cap; `pending`: frames held."""
+    _fields_ = [("first", C.c_int64), ("n", C.c_int64), ("n_forced", C.c_int64), ("pending", C.c_int64)]
+
+    def as_tuple(self):
+        return int(self.first), int(self.n), int(self.n_forced), int(self.pending)
+
+
 _lib = None
 
 
@@ -320,6 +329,11 @@ def load_library():
         "vbx_session_reset": (C.c_int, [vp]),
         "vbx_session_info": (C.c_int, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
         "vbx_session_close": (None, [vp]),
+        "vbx_path_stream_open": (C.c_int, [vp, sz, C.POINTER(PitchPathParams), dbl, sz, C.POINTER(vp)]),
+        "vbx_path_stream_push": (C.c_int, [vp, vp, vp, vp, vp, sz, i32, vp, sz, vp, vp, vp]),
+        "vbx_path_stream_reset": (C.c_int, [vp]),
+        "vbx_path_stream_close": (None, [vp]),
+        "vbx_session_path_bind": (C.c_int, [vp, dbl, sz, vp, sz, vp, vp, vp]),
         "vbx_internal_session_ingest": (C.c_int, [vp, i32, i32, i32, vp, sz, sz, vp, sz, vp]),
         "vbx_find_formants_resampled_f64": (C.c_int, [vp, vp, sz, sz, sz, dbl, dbl, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp]),
         "vbx_shard_range": (C.c_int, [sz, i32, i32, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
@@ -646,8 +660,18 @@ class Session:
         return self._push(self.vb.L.vbx_session_push_device, _ptr(block), int(n_sample_frames), out, status, outputs, record_ld, status_ld)
 
     def mark_utterance(self):
-        """vbx_session_mark_utterance: the next frame delivered starts a new utterance (a seg_start entry of the resident call)."""
+        """vbx_session_mark_utterance: the next frame delivered starts a new utterance (a seg_start entry of the resident call).
+        On a bound session (bind_path) the rest of the ended utterance's contour is committed by this call."""
         self.vb._check(self.vb.L.vbx_session_mark_utterance(self.handle))
+
+    def bind_path(self, out_path, commit, peak_ref=1.0, max_pending=64, path_ld=2, out_index=None, out_forced=None):
+        """vbx_session_path_bind: every push of this tracked session also commits the decided rows of the pitch contour (the
+        online path, PathStream) into device buffers -- out_path (rows path_ld doubles apart), out_index (int32) and out_forced
+        (uint8), both optional, each of max_pending + the largest push's frames rows, written from row 0 by every push -- and one
+        PathCommit into `commit` (device, 32 bytes; read it behind a sync: commit_of).  Before the first push or after reset();
+        between pushes only the destinations may change."""
+        self.vb._check(self.vb.L.vbx_session_path_bind(self.handle, float(peak_ref), int(max_pending), _ptr(out_path), int(path_ld),
+                                                       _ptr(out_index), _ptr(out_forced), _ptr(commit)))
 
     def reset(self):
         """vbx_session_reset: drop the carried samples and all state -- as a freshly opened session."""
@@ -656,6 +680,82 @@ class Session:
     def close(self):
         if getattr(self, "handle", None):
             self.vb.L.vbx_session_close(self.handle)
+            self.handle = None
+            self.vb._sessions.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def commit_of(vb, commit):
+    """The PathCommit in a device buffer, as (first, n, n_forced, pending): a blocking download behind the context's stream."""
+    pc = PathCommit()
+    vb._check(vb.L.vbx_memcpy_d2h(vb.ctx, C.addressof(pc), _ptr(commit), C.sizeof(pc)))
+    return pc.as_tuple()
+
+
+class PathStream:
+    """vbx_path_stream: vbx_pitch_path_f64's contour committed while the candidate lists arrive (VoxBox.path_stream).  Every row
+    that is not flagged as forced is the whole utterance's path, bit for bit, whatever follows."""
+
+    def __init__(self, vb, kmax, params, peak_ref, max_pending):
+        self.vb, self.kmax, self.max_pending = vb, int(kmax), int(max_pending)
+        self.params = params if params is not None else PitchPathParams.make()
+        h = C.c_void_p()
+        vb._check(vb.L.vbx_path_stream_open(vb.ctx, self.kmax, C.byref(self.params), float(peak_ref), self.max_pending, C.byref(h)))
+        self.handle = h
+        vb._sessions.add(self)
+
+    def push(self, cand, count, status=None, local_peak=None, n_frames=None, end_utterance=False, out=None, path_ld=2):
+        """vbx_path_stream_push.  cand [n, kmax, 2] / count / status / local_peak: host arrays (uploaded) or device buffers (then
+        n_frames is needed).  Returns (path [n_rows, 2], index, forced, (first, n, n_forced, pending)) as numpy -- or, with
+        out = (path, index, forced, commit) device buffers of max_pending + n_frames rows (index / forced may be None; commit: 32
+        bytes), queues the push and returns None (read the commit behind a sync: commit_of)."""
+        vb = self.vb
+        own = []
+
+        def dev(a, dtype):
+            if a is None or not isinstance(a, np.ndarray):
+                return a
+            if a.size == 0:
+                return None
+            d = vb.to_device(np.ascontiguousarray(a, dtype=dtype))
+            own.append(d)
+            return d
+        if isinstance(cand, np.ndarray):
+            n_frames = cand.shape[0]
+        n = int(n_frames or 0)
+        try:
+            dc, dn, ds, dl = dev(cand, np.float64), dev(count, np.int32), dev(status, np.int32), dev(local_peak, np.float64)
+            if out is not None:
+                path, idx, forced, commit = out
+            else:
+                rows = self.max_pending + n
+                path, idx, forced, commit = vb.empty((rows, 2)), vb.empty(rows, np.int32), vb.empty(rows, np.uint8), vb.empty(4, np.int64)
+                own += [path, idx, forced, commit]
+            vb._check(vb.L.vbx_path_stream_push(self.handle, _ptr(dc), _ptr(dn), _ptr(ds), _ptr(dl), n, int(bool(end_utterance)),
+                                                _ptr(path), int(path_ld), _ptr(idx), _ptr(forced), _ptr(commit)))
+            if out is not None:
+                if own:
+                    vb.sync()                       # the uploaded lists are freed below
+                return None
+            c = commit_of(vb, commit)
+            k = c[1]
+            return path.numpy()[:k], idx.numpy()[:k], forced.numpy()[:k], c
+        finally:
+            for d in own:
+                d.free()
+
+    def reset(self):
+        """vbx_path_stream_reset: as freshly opened (pending frames are dropped)."""
+        self.vb._check(self.vb.L.vbx_path_stream_reset(self.handle))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.vb.L.vbx_path_stream_close(self.handle)
             self.handle = None
             self.vb._sessions.discard(self)
 
@@ -1507,6 +1607,12 @@ class VoxBox:
         assert frame_len and stride
         return Session(self, params, ext, track, format, channels, channel, frame_len, stride,
                        int(max_block) if max_block is not None else 100 * int(stride))
+
+    def path_stream(self, kmax, params=None, peak_ref=1.0, max_pending=64):
+        """vbx_path_stream_open: an online pitch path on this context over lists of kmax candidates per frame (PathStream.push).
+        peak_ref: the P of the silence term (the format's full scale, or a calibrated level); max_pending: the frames held at
+        most -- rows that have to leave undecided are flagged as forced.  A PathStream is also a context manager."""
+        return PathStream(self, kmax, params, peak_ref, max_pending)
 
     @staticmethod
     def _host_audio(audio, format, channels, n_sample_frames):
