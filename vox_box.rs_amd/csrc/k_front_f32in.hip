@@ -89,4 +89,17 @@ void launch_frame_rms_f32in(hipStream_t s, const float *x, long F, int n, long s
     else hipLaunchKernelGGL((frame_rms_f32in_kernel<false>), g, b, 0, s, x, F, n, stride, out_rms, rms_ld, out_peak);
 }
 
+// ---- frames of any sample type: the form of x.kind ----------------------------------------------------------------------------
+void launch_frame_peak(hipStream_t s, frames_t x, long F, long n, long stride, double *out) {
+    switch (x.kind) {
+        case SAMPLE_F64: launch_frame_peak(s, x.f64(), F, n, stride, out); break;
+        case SAMPLE_PCM16: launch_frame_peak_pcm16(s, x.pcm16(), F, n, stride, out); break;
+        case SAMPLE_F32: launch_frame_peak_f32in(s, x.f32in(), F, n, stride, out); break;
+    }
+}
+void launch_frame_rms(hipStream_t s, frames_t x, long F, int n, long stride, double *out_rms, long rms_ld, double *out_peak) {
+    if (x.kind == SAMPLE_F32) launch_frame_rms_f32in(s, x.f32in(), F, n, stride, out_rms, rms_ld, out_peak);
+    else launch_frame_rms(s, x.f64(), x.pcm16(), F, n, stride, out_rms, rms_ld, out_peak);
+}
+
 }  // namespace vbx

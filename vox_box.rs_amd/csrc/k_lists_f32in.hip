@@ -59,4 +59,27 @@ void launch_lpc_ref_f32in(hipStream_t s, const float *x, long F, int n, long str
     else hipLaunchKernelGGL((lpc_ref_kernel<false, 0, true>), dim3(grid), dim3(64), lds, s, x, F, n, stride, window, n_lags, p, normalize, out_r, r_ld, out_lpc, lpc_ld);
 }
 
+// ---- frames of any sample type: the form of x.kind (the f64 kernels take PCM through their f64 argument, behind a flag) ----------
+void launch_pitch_list(hipStream_t s, const int32_t *frame_list, const int32_t *list_count, int grid, frames_t x, int n, long stride,
+                       const double *window, const double *lag_window, double sample_rate, double threshold, double fmin, double fmax,
+                       int kmax, pitch_t *out_cand, long cand_ld, int32_t *out_count, int32_t *status, unsigned long long *work) {
+    if (x.kind == SAMPLE_F32)
+        launch_pitch_list_f32in(s, frame_list, list_count, grid, x.f32in(), n, stride, window, lag_window, sample_rate, threshold, fmin,
+                                fmax, kmax, out_cand, cand_ld, out_count, status, work);
+    else
+        launch_pitch_list(s, frame_list, list_count, grid, static_cast<const double *>(x.p), n, stride, window, lag_window, sample_rate,
+                          threshold, fmin, fmax, kmax, out_cand, cand_ld, out_count, status, work, x.kind == SAMPLE_PCM16);
+}
+void launch_lpc_exact_list(hipStream_t s, const int32_t *frame_list, const int32_t *list_count, int cus, frames_t x, int n, long stride,
+                           const double *window, int p, double *out_lpc, long lpc_ld) {
+    if (x.kind == SAMPLE_F32) launch_lpc_exact_list_f32in(s, frame_list, list_count, cus, x.f32in(), n, stride, window, p, out_lpc, lpc_ld);
+    else launch_lpc_exact_list(s, frame_list, list_count, cus, static_cast<const double *>(x.p), n, stride, window, x.kind == SAMPLE_PCM16, p,
+                               out_lpc, lpc_ld);
+}
+void launch_lpc_ref(hipStream_t s, frames_t x, long F, int n, long stride, const double *window, int n_lags, int p, int normalize,
+                    double *out_r, long r_ld, double *out_lpc, long lpc_ld) {
+    if (x.kind == SAMPLE_F32) launch_lpc_ref_f32in(s, x.f32in(), F, n, stride, window, n_lags, p, normalize, out_r, r_ld, out_lpc, lpc_ld);
+    else launch_lpc_ref(s, x.p, x.kind == SAMPLE_PCM16, F, n, stride, window, n_lags, p, normalize, out_r, r_ld, out_lpc, lpc_ld);
+}
+
 }  // namespace vbx

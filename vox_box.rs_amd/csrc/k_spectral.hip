@@ -202,8 +202,11 @@ bool spectral_list_parked(const spectral_launch_t &L) {
 }
 
 int launch_analyze(hipStream_t s, const spectral_launch_t &L) {
+    // (PCM / float32: full 1200-sample frames only -- the host side asks for nothing else)
+    if (L.x.kind != SAMPLE_F64 && (L.plan != SPECTRAL_PLAN_1200 || L.n != SP_N)) return -1;
     spectral_args_t a;
-    a.frames = L.x; a.n_frames = L.F; a.stride = L.stride; a.window = L.window; a.lag_window = L.lag_window;
+    a.frames = static_cast<const double *>(L.x.p);           // (the kernels take PCM / float32 through the f64 argument: a.pcm says PCM, k_spectral_f32in.hip is compiled for float32)
+    a.n_frames = L.F; a.stride = L.stride; a.window = L.window; a.lag_window = L.lag_window;
     a.tab = reinterpret_cast<const double2 *>(L.tab);
     a.n = L.n;
     a.pp.sample_rate = L.sample_rate; a.pp.threshold = L.threshold; a.pp.fmin = L.fmin; a.pp.fmax = L.fmax; a.pp.kmax = L.kmax; a.pp.f32 = 0;
@@ -214,7 +217,7 @@ int launch_analyze(hipStream_t s, const spectral_launch_t &L) {
     a.bins = L.bins; a.slopes = L.slopes; a.dct = L.dct; a.num_coeffs = L.num_coeffs; a.nb = L.nb;
     a.unsure_list = L.unsure_list; a.unsure_count = L.unsure_count;
     a.out_r = L.out_r; a.n_lags = L.n_lags;
-    a.pcm = ((L.pcm && L.n == SP_N) ? SP_FLAG_PCM : 0) | (L.lag_rcp ? SP_FLAG_LAG_RCP : 0) | ((L.mfcc_defer && L.num_coeffs <= 16) ? SP_FLAG_MFCC_DEFER : 0);      // (PCM: the host side only asks for it on full 1200-sample frames)
+    a.pcm = (L.x.kind == SAMPLE_PCM16 ? SP_FLAG_PCM : 0) | (L.lag_rcp ? SP_FLAG_LAG_RCP : 0) | ((L.mfcc_defer && L.num_coeffs <= 16) ? SP_FLAG_MFCC_DEFER : 0);
     a.mfcc_q = (L.plan != SPECTRAL_PLAN_NONE && L.n > 0) ? (2 * spectral_plan_nc(L.plan)) / L.n : 2;
     a.ip = mfcc_interp_t{};
     if (L.plan != SPECTRAL_PLAN_1200) return launch_analyze_pow2(s, L, a);
@@ -249,8 +252,7 @@ int launch_analyze(hipStream_t s, const spectral_launch_t &L) {
     // 33.7 -> 37.8 M frames/s, the fused loop (the headline) 30.0 -> 33.5 M.  VBX_SPECTRAL_W3=0: two wavefronts as before (A/B).
     static const bool want3 = [] { const char *e = getenv("VBX_SPECTRAL_W3"); return e == nullptr || atoi(e) != 0; }();
     const bool w3 = want3 && extra == 0 && 12 * lds <= 160 * 1024;
-    if (L.f32in) {                                           // float32 samples (full frames only: analyze_frames_impl asks for nothing else)
-        if (L.n != SP_N) return -1;
+    if (L.x.kind == SAMPLE_F32) {
         launch_analyze_f32in(s, a, (unsigned)L.F, lds, lpc, mf, w3);
         return 0;
     }

@@ -542,7 +542,7 @@ int vbx_autocorrelate_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t
     if (ctx->lpc_policy == VBX_LPC_POLICY_REFERENCE) {
         // every lag the crate's sequential fold (k_lpc_ref.hip) instead of the FFT / matrix-core / register forms
         VBX_REQUIRE(ctx, frame_len <= 0x7fffffffull, "frame_len too large");
-        { Prof p(ctx, "autocorr_ref"); launch_lpc_ref(ctx->stream, x, false, (long)n_frames, (int)frame_len, (long)stride, window, (int)n_lags, 0, 0,
+        { Prof p(ctx, "autocorr_ref"); launch_lpc_ref(ctx->stream, x, (long)n_frames, (int)frame_len, (long)stride, window, (int)n_lags, 0, 0,
                                                       out, (long)n_lags, nullptr, 0); }
         return check_launch(ctx, __func__);
     }
@@ -641,12 +641,9 @@ static int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, c
         // 4 ms to come and go with nothing to do, beside 13.5 ms of the analysis itself.  One per CU where the state is large.
         const int cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
         const int grid = pitch_lds_bytes(L.n) > 24 * 1024 ? cus : cus * 4;
-        if (L.f32in) launch_pitch_list_f32in(st, L.unsure_list, L.unsure_count, grid, reinterpret_cast<const float *>(L.x), L.n, L.stride, L.window,
-                                             L.lag_window, L.sample_rate, L.threshold, L.fmin, L.fmax, L.kmax, L.out_cand, L.cand_ld, L.out_count,
-                                             L.pitch_status, L.work);
-        else launch_pitch_list(st, L.unsure_list, L.unsure_count, grid, L.x, L.n, L.stride, L.window, L.lag_window,
+        launch_pitch_list(st, L.unsure_list, L.unsure_count, grid, L.x, L.n, L.stride, L.window, L.lag_window,
                           L.sample_rate, L.threshold, L.fmin, L.fmax, L.kmax, L.out_cand, L.cand_ld, L.out_count,
-                          L.pitch_status, L.work, L.pcm);
+                          L.pitch_status, L.work);
     }
     if (L.out_lpc != nullptr) {
         // the fused kernel left r[0..12] in every frame's LPC row: LPC::lpc(12) in place, one row per lane (+ the conditioning probe), then
@@ -657,19 +654,14 @@ static int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, c
         if (L.lpc_list != nullptr) {
             Prof p(ctx, "lpc_exact_list", st);
             const int cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
-            if (L.f32in) launch_lpc_exact_list_f32in(st, L.lpc_list, L.lpc_count, cus, reinterpret_cast<const float *>(L.x), L.n, L.stride, L.window,
-                                                     SPECTRAL_LPC_ORDER, L.out_lpc, L.lpc_ld);
-            else launch_lpc_exact_list(st, L.lpc_list, L.lpc_count, cus, L.x, L.n, L.stride, L.window, L.pcm, SPECTRAL_LPC_ORDER, L.out_lpc, L.lpc_ld);
+            launch_lpc_exact_list(st, L.lpc_list, L.lpc_count, cus, L.x, L.n, L.stride, L.window, SPECTRAL_LPC_ORDER, L.out_lpc, L.lpc_ld);
         }
         if (ctx->lpc_policy == VBX_LPC_POLICY_REFERENCE) {
             // the crate's rows (k_lpc_ref.hip) over the column, after the kernels above on the same stream: the fused kernel and the
             // Levinson pass run as under every policy (their instantiations, and so every other column, unchanged), only the LPC
             // row is replaced
             Prof p(ctx, "lpc_ref", st);
-            if (L.f32in) launch_lpc_ref_f32in(st, reinterpret_cast<const float *>(L.x), L.F, L.n, L.stride, L.window, SPECTRAL_LPC_ORDER + 1,
-                                              SPECTRAL_LPC_ORDER, 0, nullptr, 0, L.out_lpc, L.lpc_ld);
-            else launch_lpc_ref(st, L.x, L.pcm != 0, L.F, L.n, L.stride, L.window, SPECTRAL_LPC_ORDER + 1, SPECTRAL_LPC_ORDER, 0, nullptr, 0,
-                           L.out_lpc, L.lpc_ld);
+            launch_lpc_ref(st, L.x, L.F, L.n, L.stride, L.window, SPECTRAL_LPC_ORDER + 1, SPECTRAL_LPC_ORDER, 0, nullptr, 0, L.out_lpc, L.lpc_ld);
         }
     }
     return check_launch(ctx, "launch_spectral");
@@ -799,7 +791,7 @@ static int run_autocorr_lpc(vbx_ctx *ctx, hipStream_t st, const double *x, size_
         // the crate's own arithmetic (k_lpc_ref.hip): fold, [normalize,] recursion, bit for bit; no probe, no redo
         VBX_REQUIRE(ctx, frame_len <= 0x7fffffffull, "frame_len too large");
         { Prof p(ctx, "lpc_ref", st);
-          launch_lpc_ref(st, x, false, (long)n_frames, (int)frame_len, (long)stride, window, n_lags, (int)n_coeffs, normalize, out_r, n_lags,
+          launch_lpc_ref(st, x, (long)n_frames, (int)frame_len, (long)stride, window, n_lags, (int)n_coeffs, normalize, out_r, n_lags,
                          out_lpc, (long)lpc_ld); }
         return check_launch(ctx, "vbx_autocorr_lpc_f64");
     }
@@ -818,7 +810,7 @@ static int run_autocorr_lpc(vbx_ctx *ctx, hipStream_t st, const double *x, size_
         if (lpc_list == nullptr) return;
         Prof p(ctx, "lpc_exact_list", st);
         const int cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
-        launch_lpc_exact_list(st, lpc_list, lpc_count, cus, x, (int)frame_len, (long)stride, window, false, (int)n_coeffs, out_lpc, (long)lpc_ld);
+        launch_lpc_exact_list(st, lpc_list, lpc_count, cus, x, (int)frame_len, (long)stride, window, (int)n_coeffs, out_lpc, (long)lpc_ld);
     };
     if (fewlags_supported((int)frame_len, n_lags, out_lpc != nullptr)) {
         { Prof p(ctx, "autocorr_lpc", st);
@@ -862,18 +854,19 @@ static bool burg_order_ok(size_t frame_len, size_t n_coeffs) {
 
 // Burg on a batch: the one-pass form (k_burg_fast.hip) where it exists, the frames its guard turns away and every other
 // shape through the direct recursion (k_burg.hip)
-// rp (vbx_find_formants_resampled_f64, vbx_analyze_frames_ex_*): x / pcm hold the caller's frames of rp->n_src samples and Burg runs on
+// rp (vbx_find_formants_resampled_f64, vbx_analyze_frames_ex_*): x holds the caller's frames of rp->n_src samples and Burg runs on
 // their RESAMPLED view -- n is then the resampled length m and window its periodic Hanning window.  The shapes the resampled
 // loaders take (k_burg_resampled.hip) never exist as a batch; the others are resampled into a context-owned dense batch, a
 // chunk of frames at a time, and take this function's plain form -- the same kernels at the same parameters either way.
 struct resample_plan_t { resample_src_t rs; size_t n_src, m; bool direct; };
 constexpr size_t EX_DENSE_BYTES = size_t(256) << 20;          // the dense fallback's batch: at most this, or one resampled frame
+static const char *const k_kind_names[3] = {"f64", "pcm16", "float32"};      // by sample_kind_t, for messages
 
-static int run_burg(vbx_ctx *ctx, hipStream_t stm, const double *x, const int16_t *pcm, long F, int n, long stride,
-                    const double *window, int p, double *coeffs, int32_t *st, frame_map_t map = frame_map_t{0, 0, 0},
-                    const resample_plan_t *rp = nullptr, const float *f32 = nullptr /* the frames as float32 samples instead of x / pcm */) {
+static int run_burg(vbx_ctx *ctx, hipStream_t stm, frames_t x, long F, int n, long stride, const double *window, int p, double *coeffs,
+                    int32_t *st, frame_map_t map = frame_map_t{0, 0, 0}, const resample_plan_t *rp = nullptr) {
     if (rp && !rp->direct) {
-        // the dense fallback (f64 frames only: the callers widen PCM first; no time slices: run_find_formants)
+        // the dense fallback (the callers widen PCM / float32 first; no time slices: run_find_formants)
+        if (x.kind != SAMPLE_F64) return fail(ctx, VBX_E_RUNTIME, "run_burg: the dense resampled batch is made from f64 frames");
         long per = (long)(EX_DENSE_BYTES / ((size_t)n * sizeof(double)));
         if (per < 1) per = 1;
         if (per > F) per = F;
@@ -885,46 +878,18 @@ static int run_burg(vbx_ctx *ctx, hipStream_t stm, const double *x, const int16_
         bool counted = false;
         for (long f0 = 0; f0 < F; f0 += per) {
             const long nf = (F - f0 < per) ? F - f0 : per;
-            { Prof pr(ctx, "resample", stm); launch_resample(stm, x + f0 * stride, nf, (int)rp->n_src, stride, rp->rs.li, rp->rs.frac, n, dense); }
-            rc = run_burg(ctx, stm, dense, nullptr, nf, n, (long)n, window, p, coeffs + f0 * (long)p, st + f0);
+            { Prof pr(ctx, "resample", stm); launch_resample(stm, x.f64() + f0 * stride, nf, (int)rp->n_src, stride, rp->rs.li, rp->rs.frac, n, dense); }
+            rc = run_burg(ctx, stm, dense, nf, n, (long)n, window, p, coeffs + f0 * (long)p, st + f0);
             if (rc != VBX_SUCCESS) return rc;
             if (ctx->burg_list_count) { launch_count_accumulate(stm, ctx->burg_list_count + 1, total + 1, f0 == 0); counted = true; }
         }
         if (counted) ctx->burg_list_count = total;
         return VBX_SUCCESS;
     }
-    if (rp) {
-        if (burg_fast_supported(n, p)) {
-            void *w = nullptr;
-            int rc = ws_get(ctx, vbx_ctx::WS_BURG_LIST, burg_fast_scratch_bytes(F, p), &w);
-            if (rc != VBX_SUCCESS) return rc;
-            int32_t *list = burg_fast_list(w, F, p);
-            ctx->burg_list_count = list;
-            VBX_HIP(ctx, hipMemsetAsync(list, 0, sizeof(int32_t), stm));
-            const long items = frame_map_items(map, F), chunk = burg_fast_chunk(F);
-            for (long i0 = 0; i0 < items; i0 += chunk) {
-                const long m = (items - i0 < chunk) ? items - i0 : chunk;
-                { Prof pr(ctx, "burg_lags_resampled", stm);
-                  if (f32) { if (!launch_burg_lags_resampled_f32in(stm, f32, F, n, stride, window, rp->rs, p, map, i0, m, w))
-                                 return fail(ctx, VBX_E_RUNTIME, "burg_lags_resampled: no float32 lag kernel at order " + std::to_string(p)); }
-                  else launch_burg_lags_resampled(stm, x, pcm, F, n, stride, window, rp->rs, p, map, i0, m, w); }
-                { Prof pr(ctx, "burg_recursion", stm); launch_burg_recursion(stm, F, p, map, i0, m, coeffs, st, w); }
-            }
-            { Prof pr(ctx, "burg_direct_list_resampled", stm);
-              if (f32) launch_burg_resampled_f32in_list(stm, f32, F, n, stride, window, rp->rs, p, coeffs, st, list + 2, list);
-              else launch_burg_resampled_list(stm, x, pcm, F, n, stride, window, rp->rs, p, coeffs, st, list + 2, list); }
-            launch_count_accumulate(stm, list, list + 1, map.seg_len == 0 || map.t0 == 0);
-            return VBX_SUCCESS;
-        }
-        Prof pr(ctx, "burg_resampled", stm);
-        ctx->burg_list_count = nullptr;
-        if (f32) launch_burg_resampled_f32in(stm, f32, F, n, stride, window, rp->rs, p, coeffs, st, map);
-        else launch_burg_resampled(stm, x, pcm, F, n, stride, window, rp->rs, p, coeffs, st, map);
-        return VBX_SUCCESS;
-    }
-    if (n > VBX_MAX_FRAME_LEN) {
+    if (!rp && n > VBX_MAX_FRAME_LEN) {
         // a frame longer than a wavefront's registers hold (tests/lib.rs:27-41 passes a whole file as one): one workgroup per
         // frame, the error arrays in an L2-resident scratch (k_long.hip); batches of frames so that the scratch stays <= 1 GiB
+        if (x.kind != SAMPLE_F64) return fail(ctx, VBX_E_RUNTIME, "run_burg: the long-frame kernel reads f64 frames");
         ctx->burg_list_count = nullptr;
         long per = (long)((size_t(1) << 30) / burg_long_scratch_bytes(1, n));
         if (per < 1) per = 1;
@@ -934,10 +899,11 @@ static int run_burg(vbx_ctx *ctx, hipStream_t stm, const double *x, const int16_
         if (rc != VBX_SUCCESS) return rc;
         Prof pr(ctx, "burg_long", stm);
         for (long f0 = 0; f0 < F; f0 += per)
-            launch_burg_long(stm, x, f0, (f0 + per < F) ? f0 + per : F, F, n, stride, window, p, coeffs, st, (double *)w);
+            launch_burg_long(stm, x.f64(), f0, (f0 + per < F) ? f0 + per : F, F, n, stride, window, p, coeffs, st, (double *)w);
         return VBX_SUCCESS;
     }
     if (burg_fast_supported(n, p)) {
+        const char *const lags_name = rp ? "burg_lags_resampled" : "burg_lags", *const list_name = rp ? "burg_direct_list_resampled" : "burg_direct_list";
         void *w = nullptr;
         int rc = ws_get(ctx, vbx_ctx::WS_BURG_LIST, burg_fast_scratch_bytes(F, p), &w);
         if (rc != VBX_SUCCESS) return rc;
@@ -947,26 +913,23 @@ static int run_burg(vbx_ctx *ctx, hipStream_t stm, const double *x, const int16_
         const long items = frame_map_items(map, F), chunk = burg_fast_chunk(F);
         for (long i0 = 0; i0 < items; i0 += chunk) {
             const long m = (items - i0 < chunk) ? items - i0 : chunk;
-            { Prof pr(ctx, "burg_lags", stm);
-              if (f32) { if (!launch_burg_lags_f32in(stm, f32, F, n, stride, window, p, map, i0, m, w))
-                             return fail(ctx, VBX_E_RUNTIME, "burg_lags: no float32 lag kernel at order " + std::to_string(p)); }
-              else if (pcm) launch_burg_lags_pcm16(stm, pcm, F, n, stride, window, p, map, i0, m, w);
-              else launch_burg_lags(stm, x, F, n, stride, window, p, map, i0, m, w); }
+            { Prof pr(ctx, lags_name, stm);
+              const bool ok = rp ? launch_burg_lags_resampled(stm, x, F, n, stride, window, rp->rs, p, map, i0, m, w)
+                                 : launch_burg_lags(stm, x, F, n, stride, window, p, map, i0, m, w);
+              if (!ok) return fail(ctx, VBX_E_RUNTIME, std::string(lags_name) + ": no " + k_kind_names[x.kind] + " lag kernel at order " + std::to_string(p)); }
             { Prof pr(ctx, "burg_recursion", stm); launch_burg_recursion(stm, F, p, map, i0, m, coeffs, st, w); }
         }
-        { Prof pr(ctx, "burg_direct_list", stm);
-          if (f32) launch_burg_f32in_list(stm, f32, F, n, stride, window, p, coeffs, st, list + 2, list);
-          else if (pcm) launch_burg_pcm16_list(stm, pcm, F, n, stride, window, p, coeffs, st, list + 2, list);
+        { Prof pr(ctx, list_name, stm);
+          if (rp) launch_burg_resampled_list(stm, x, F, n, stride, window, rp->rs, p, coeffs, st, list + 2, list);
           else launch_burg_list(stm, x, F, n, stride, window, p, coeffs, st, list + 2, list); }
         // the probe (vbx_internal_last_burg_direct_count) reports the whole CALL: list[0] restarts with every time slice of
         // find_formants, list[1] adds the slices up (reset with the call's first slice)
         launch_count_accumulate(stm, list, list + 1, map.seg_len == 0 || map.t0 == 0);
         return VBX_SUCCESS;
     }
-    Prof pr(ctx, "burg", stm);
+    Prof pr(ctx, rp ? "burg_resampled" : "burg", stm);
     ctx->burg_list_count = nullptr;
-    if (f32) launch_burg_f32in(stm, f32, F, n, stride, window, p, coeffs, st, map);
-    else if (pcm) launch_burg_pcm16(stm, pcm, F, n, stride, window, p, coeffs, st, map);
+    if (rp) launch_burg_resampled(stm, x, F, n, stride, window, rp->rs, p, coeffs, st, map);
     else launch_burg(stm, x, F, n, stride, window, p, coeffs, st, map);
     return VBX_SUCCESS;
 }
@@ -978,7 +941,7 @@ int vbx_lpc_burg_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t fram
     VBX_REQUIRE(ctx, out != nullptr, "null output");
     VBX_REQUIRE(ctx, burg_order_ok(frame_len, n_coeffs), "frame_len must be >= 2, order in [1, 62]");
     VBX_HIP(ctx, hipSetDevice(ctx->device));
-    rc = run_burg(ctx, ctx->stream, x, nullptr, (long)n_frames, (int)frame_len, (long)stride, window, (int)n_coeffs, out, status);
+    rc = run_burg(ctx, ctx->stream, x, (long)n_frames, (int)frame_len, (long)stride, window, (int)n_coeffs, out, status);
     if (rc != VBX_SUCCESS) return rc;
     return check_launch(ctx, __func__);
 }
@@ -1160,14 +1123,13 @@ static int run_formant_resonances(vbx_ctx *ctx, hipStream_t stm, const double *c
     return VBX_SUCCESS;
 }
 
-static int run_find_formants(vbx_ctx *ctx, hipStream_t stm, const double *x, size_t n_frames, size_t frame_len,
+static int run_find_formants(vbx_ctx *ctx, hipStream_t stm, frames_t x, size_t n_frames, size_t frame_len,
                              size_t stride, double sample_rate, size_t n_coeffs,
                              const int64_t *h_seg_start, size_t n_segments,
                              const vbx_resonance *h_est_init, size_t n_est,
                              vbx_resonance *out_formants, size_t formants_ld, vbx_resonance *out_res, int32_t *out_res_count,
-                             double *out_coeffs, int32_t *status, const int16_t *pcm = nullptr /* the frames as 16-bit PCM instead of x */,
-                             const resample_plan_t *rp = nullptr /* find_formants on the frames' resampled view (run_burg) */,
-                             const float *f32 = nullptr /* the frames as float32 samples instead of x / pcm */) {
+                             double *out_coeffs, int32_t *status,
+                             const resample_plan_t *rp = nullptr /* find_formants on the frames' resampled view (run_burg) */) {
     VBX_REQUIRE(ctx, h_est_init && out_formants, "null argument");
     if (rp) frame_len = rp->m;                                   // what Burg sees
     VBX_REQUIRE(ctx, burg_order_ok(frame_len, n_coeffs), "frame_len must be >= 2, order in [1, 62]");
@@ -1217,7 +1179,7 @@ static int run_find_formants(vbx_ctx *ctx, hipStream_t stm, const double *x, siz
     ctx->last_track.res = res; ctx->last_track.cnt = cnt; ctx->last_track.st = st; ctx->last_track.F = F;
     ctx->last_track.n_est = (int)n_est; ctx->last_track.out = (res_t *)out_formants; ctx->last_track.out_ld = (long)formants_ld;
     if (n_slices == 1) {
-        rc = run_burg(ctx, stm, x, pcm, F, (int)frame_len, (long)stride, hann, p, coeffs, st, frame_map_t{0, 0, 0}, rp, f32);      // :75
+        rc = run_burg(ctx, stm, x, F, (int)frame_len, (long)stride, hann, p, coeffs, st, frame_map_t{0, 0, 0}, rp);                // :75
         if (rc != VBX_SUCCESS) return rc;
         rc = run_formant_resonances(ctx, stm, coeffs, F, p, sample_rate, res, cnt, st);                                            // :80-110
         if (rc != VBX_SUCCESS) return rc;
@@ -1233,7 +1195,7 @@ static int run_find_formants(vbx_ctx *ctx, hipStream_t stm, const double *x, siz
     }
     for (int j = 0; j < n_slices && j * tc < seg_len; j++) {
         const frame_map_t map{seg_len, j * tc, (seg_len - j * tc < tc) ? seg_len - j * tc : tc};   // the last slice may be shorter
-        rc = run_burg(ctx, stm, x, pcm, F, (int)frame_len, (long)stride, hann, p, coeffs, st, map, rp, f32);
+        rc = run_burg(ctx, stm, x, F, (int)frame_len, (long)stride, hann, p, coeffs, st, map, rp);
         if (rc != VBX_SUCCESS) return rc;
         rc = run_formant_resonances(ctx, stm, coeffs, F, p, sample_rate, res, cnt, st, map);
         if (rc != VBX_SUCCESS) return rc;
@@ -1620,15 +1582,14 @@ struct track_req_t { size_t kmax; vbx_pitch_path_params path; vbx_pitch_track_ou
 // vbx_analyze_frames_ex_*: find_formants on the frames' resampled view (rp non-null) at formant_rate, and the RMS column
 struct ex_req_t { const resample_plan_t *rp; double formant_rate; bool rms; };
 
-// x: the frames as f64 samples, or -- pcm16 non-null -- as 16-bit PCM (the kernels that have a PCM form read it directly:
-// 1200-sample frames through the fused spectral kernel, Burg at every length; every other shape is widened into a
-// context-owned f64 copy of the view first and takes the f64 path), or -- f32 non-null -- as float32 samples, by the same rule (the
-// kernels that have a float form read them directly, every other shape takes one widening pass into that copy first)
-static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, const int16_t *pcm16, size_t n_frames, size_t frame_len,
+// own: the caller's frames, as f64, 16-bit PCM or float32 samples.  PCM and float32 are read directly where EVERY kernel that goes over
+// the samples has a form for them (full 1200-sample frames through the fused spectral kernel with nothing beside it but Burg, which
+// has one at every length); every other shape takes one widening pass into a context-owned f64 copy of the view and the f64 path.
+static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, frames_t own, size_t n_frames, size_t frame_len,
                                size_t stride, const vbx_analysis_params *h_p, const int64_t *h_seg_start, size_t n_segments,
                                double *out_records, size_t record_ld, int32_t *status3, const track_req_t *tk = nullptr,
-                               const ex_req_t *ex = nullptr, const float *f32 = nullptr) {
-    int rc = check_frames(ctx, fn, f32 ? (const void *)f32 : pcm16 ? (const void *)pcm16 : (const void *)x, n_frames, frame_len, stride, VBX_MAX_LONG_FRAME_LEN);
+                               const ex_req_t *ex = nullptr) {
+    int rc = check_frames(ctx, fn, own.p, n_frames, frame_len, stride, VBX_MAX_LONG_FRAME_LEN);
     if (rc == 1 && tk) { ctx->path_redone = nullptr; ctx->path_last = true; }      // an empty batch: an empty path
     if (rc != VBX_SUCCESS) return rc < 0 ? rc : VBX_SUCCESS;
     VBX_REQUIRE(ctx, h_p && out_records, "null argument");
@@ -1678,35 +1639,19 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
         VBX_HIP(ctx, ctx->tables.interp(plan, (int)frame_len, hb.front(), nb, &ip, &interp_mfcc));
         fused_mfcc = interp_mfcc;
     }
-    // 16-bit PCM frames: the fused kernel of full 1200-sample frames, the pitch fallback and Burg read them directly;
-    // anything that would send another kernel over the samples takes one widening pass into a context-owned f64 copy
-    const int16_t *const pcm_in = pcm16;                                   // (the peak kernel reads the caller's PCM whichever form the rest takes)
-    const bool pcm_native = pcm16 != nullptr && fused && frame_len == (size_t)SPECTRAL_N &&
-                            (!h_p->lpc_order || fused_lpc) && (!h_p->mfcc_coeffs || fused_mfcc) &&
-                            !(ex && ex->rp && !ex->rp->direct);            // (the dense fallback resamples f64 frames)
-    if (pcm16 != nullptr && !pcm_native) {
+    // x: what the kernels read -- the caller's own samples, or their widened copy (the RMS and peak kernels read `own` either way)
+    frames_t x = own;
+    const bool native = fused && frame_len == (size_t)SPECTRAL_N && (!h_p->lpc_order || fused_lpc) && (!h_p->mfcc_coeffs || fused_mfcc) &&
+                        !(ex && ex->rp && !ex->rp->direct);                // (the dense fallback resamples f64 frames)
+    if (own.kind != SAMPLE_F64 && !native) {
         const size_t ns = (n_frames - 1) * stride + frame_len;
         void *w = nullptr;
         rc = ws_get(ctx, vbx_ctx::WS_F32_IN, ns * sizeof(double), &w);
         if (rc != VBX_SUCCESS) return rc;
-        { Prof p(ctx, "pcm16"); launch_pcm16(ctx->stream, pcm16, ns, 32767.0, (double *)w); }
-        x = (const double *)w; pcm16 = nullptr;
+        if (own.kind == SAMPLE_PCM16) { Prof p(ctx, "pcm16"); launch_pcm16(ctx->stream, own.pcm16(), ns, 32767.0, (double *)w); }
+        else { Prof p(ctx, "f32_to_f64"); launch_f32_to_f64(ctx->stream, own.f32in(), ns, (double *)w); }
+        x = (const double *)w;
     }
-    if (pcm_native) x = reinterpret_cast<const double *>(pcm16);          // the PCM kernels take the pointer through the f64 slot
-    // float32 frames, by the same rule: the shapes whose every kernel over the samples has a float form read the caller's floats
-    const float *const f32_in = f32;                                       // (the RMS / peak kernel reads them whichever form the rest takes)
-    const bool f32_native = f32 != nullptr && fused && frame_len == (size_t)SPECTRAL_N &&
-                            (!h_p->lpc_order || fused_lpc) && (!h_p->mfcc_coeffs || fused_mfcc) &&
-                            !(ex && ex->rp && !ex->rp->direct);
-    if (f32 != nullptr && !f32_native) {
-        const size_t ns = (n_frames - 1) * stride + frame_len;
-        void *w = nullptr;
-        rc = ws_get(ctx, vbx_ctx::WS_F32_IN, ns * sizeof(double), &w);
-        if (rc != VBX_SUCCESS) return rc;
-        { Prof p(ctx, "f32_to_f64"); launch_f32_to_f64(ctx->stream, f32, ns, (double *)w); }
-        x = (const double *)w; f32 = nullptr;
-    }
-    if (f32_native) x = reinterpret_cast<const double *>(f32);            // the float kernels take the pointer through the f64 slot
     const double *hann = nullptr;
     VBX_HIP(ctx, ctx->tables.window(VBX_WINDOW_HANNING, frame_len, &hann));        // Windower::hanning frames (examples/pitch_detection.rs:23)
     // record columns
@@ -1741,7 +1686,7 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
     VBX_HIP(ctx, hipStreamWaitEvent(side, ctx->ev_fork, 0));
     const bool mfcc_beside = h_p->mfcc_coeffs && !fused_mfcc;              // MFCC from its own kernel on the side stream
     if (tk && mfcc_beside) {                                               // (tracked: first, see above; its columns are nobody else's)
-        rc = run_mfcc(ctx, side, x, n_frames, frame_len, stride, hann, h_p->mfcc_coeffs, h_p->mfcc_lo_hz, h_p->mfcc_hi_hz,
+        rc = run_mfcc(ctx, side, x.f64(), n_frames, frame_len, stride, hann, h_p->mfcc_coeffs, h_p->mfcc_lo_hz, h_p->mfcc_hi_hz,
                       h_p->sample_rate, out_records + c_mfcc, record_ld, st_mfcc);
         if (rc != VBX_SUCCESS) return rc;
     }
@@ -1751,14 +1696,12 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
     const bool want_rms = ex && ex->rms;
     if (tk_peak && want_rms) {
         { Prof p(ctx, "frame_rms_peak", side);
-          if (f32_in) launch_frame_rms_f32in(side, f32_in, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, tk_peak);
-          else launch_frame_rms(side, pcm_in ? nullptr : x, pcm_in, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, tk_peak); }
+          launch_frame_rms(side, own, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, tk_peak); }
         VBX_HIP(ctx, hipEventRecord(ctx->ev_peak, side));
     } else if (tk_peak) {
         // max |x| per frame, first on the side stream: HBM-bound, beside the FP64-bound kernel; the path waits for ev_peak
-        if (f32_in) { Prof p(ctx, "frame_peak_f32in", side); launch_frame_peak_f32in(side, f32_in, (long)n_frames, (long)frame_len, (long)stride, tk_peak); }
-        else if (pcm_in) { Prof p(ctx, "frame_peak_pcm16", side); launch_frame_peak_pcm16(side, pcm_in, (long)n_frames, (long)frame_len, (long)stride, tk_peak); }
-        else { Prof p(ctx, "frame_peak", side); launch_frame_peak(side, x, (long)n_frames, (long)frame_len, (long)stride, tk_peak); }
+        static const char *const k_peak_names[3] = {"frame_peak", "frame_peak_pcm16", "frame_peak_f32in"};      // by sample_kind_t
+        { Prof p(ctx, k_peak_names[own.kind], side); launch_frame_peak(side, own, (long)n_frames, (long)frame_len, (long)stride, tk_peak); }
         VBX_HIP(ctx, hipEventRecord(ctx->ev_peak, side));
     }
     if (h_p->formant_order) {
@@ -1766,40 +1709,28 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
         for (size_t e = 0; e < h_p->n_est; e++) est[e] = h_p->est_init[e];
         rc = run_find_formants(ctx, side, x, n_frames, frame_len, stride, ex ? ex->formant_rate : h_p->sample_rate, h_p->formant_order,
                                h_seg_start, n_segments, est, h_p->n_est, (vbx_resonance *)(out_records + c_form), record_ld,
-                               nullptr, nullptr, nullptr, st_form, pcm_native ? pcm16 : nullptr, ex ? ex->rp : nullptr, f32_native ? f32 : nullptr);
+                               nullptr, nullptr, nullptr, st_form, ex ? ex->rp : nullptr);
         if (rc != VBX_SUCCESS) return rc;
     } else {
         ctx->last_track.res = nullptr;                        // no tracks in these records: nothing for vbx_track_stitch_f64 to continue
         ctx->last_track.n_est = 0;                            // ... and no row for a communicator to send on
         if (st_form) VBX_HIP(ctx, hipMemsetAsync(st_form, 0, n_frames * sizeof(int32_t), side));
     }
-    if (fused && h_p->lpc_order && !fused_lpc) {
-        rc = run_autocorr_lpc(ctx, side, x, n_frames, frame_len, stride, hann, h_p->lpc_order, 0, nullptr,
+    // (what runs beside the spectral kernel reads f64: `native` is false wherever one of these runs)
+    if (h_p->lpc_order && !fused_lpc) {
+        rc = run_autocorr_lpc(ctx, side, x.f64(), n_frames, frame_len, stride, hann, h_p->lpc_order, 0, nullptr,
                               out_records + c_lpc, record_ld);
         if (rc != VBX_SUCCESS) return rc;
     }
-    if (fused && mfcc_beside && !tk) {
-        rc = run_mfcc(ctx, side, x, n_frames, frame_len, stride, hann, h_p->mfcc_coeffs, h_p->mfcc_lo_hz, h_p->mfcc_hi_hz,
+    if (mfcc_beside && !tk) {
+        rc = run_mfcc(ctx, side, x.f64(), n_frames, frame_len, stride, hann, h_p->mfcc_coeffs, h_p->mfcc_lo_hz, h_p->mfcc_hi_hz,
                       h_p->sample_rate, out_records + c_mfcc, record_ld, st_mfcc);
         if (rc != VBX_SUCCESS) return rc;
-    }
-    if (!fused) {
-        if (h_p->lpc_order) {
-            rc = run_autocorr_lpc(ctx, side, x, n_frames, frame_len, stride, hann, h_p->lpc_order, 0, nullptr,
-                                  out_records + c_lpc, record_ld);
-            if (rc != VBX_SUCCESS) return rc;
-        }
-        if (mfcc_beside && !tk) {
-            rc = run_mfcc(ctx, side, x, n_frames, frame_len, stride, hann, h_p->mfcc_coeffs, h_p->mfcc_lo_hz, h_p->mfcc_hi_hz,
-                          h_p->sample_rate, out_records + c_mfcc, record_ld, st_mfcc);
-            if (rc != VBX_SUCCESS) return rc;
-        }
     }
     if (!h_p->mfcc_coeffs && st_mfcc) VBX_HIP(ctx, hipMemsetAsync(st_mfcc, 0, n_frames * sizeof(int32_t), side));
     if (want_rms && !tk_peak) {
         Prof p(ctx, "frame_rms", side);
-        if (f32_in) launch_frame_rms_f32in(side, f32_in, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, nullptr);
-        else launch_frame_rms(side, pcm_in ? nullptr : x, pcm_in, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, nullptr);
+        launch_frame_rms(side, own, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, nullptr);
     }
     VBX_HIP(ctx, hipEventRecord(ctx->ev_join, side));
     if (fused) {
@@ -1821,8 +1752,6 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
         L.lag_rcp = lag_rcp;
         L.sample_rate = h_p->sample_rate; L.threshold = h_p->pitch_threshold; L.fmin = h_p->pitch_fmin; L.fmax = h_p->pitch_fmax;
         L.kmax = 1;
-        L.pcm = pcm_native;
-        L.f32in = f32_native;
         L.whole_curve = ctx->pitch_whole_curve;
         L.out_cand = (pitch_t *)out_records; L.cand_ld = (long)record_ld; L.out_count = nullptr; L.pitch_status = st_pitch;
         if (tk) { L.kmax = (int)tk->kmax; L.out_cand = (pitch_t *)tk_cand; L.cand_ld = 2 * (long)tk->kmax; L.out_count = tk_count; }
@@ -1835,10 +1764,10 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
         }
         rc = launch_spectral(ctx, ctx->stream, L, "analyze");
     } else if (tk) {
-        rc = run_pitch(ctx, ctx->stream, x, n_frames, frame_len, stride, hann, h_p->sample_rate, h_p->pitch_threshold,
+        rc = run_pitch(ctx, ctx->stream, x.f64(), n_frames, frame_len, stride, hann, h_p->sample_rate, h_p->pitch_threshold,
                        h_p->pitch_fmin, h_p->pitch_fmax, tk->kmax, tk_cand, 2 * tk->kmax, tk_count, st_pitch);
     } else {
-        rc = run_pitch(ctx, ctx->stream, x, n_frames, frame_len, stride, hann, h_p->sample_rate, h_p->pitch_threshold,
+        rc = run_pitch(ctx, ctx->stream, x.f64(), n_frames, frame_len, stride, hann, h_p->sample_rate, h_p->pitch_threshold,
                        h_p->pitch_fmin, h_p->pitch_fmax, 1, (vbx_pitch *)out_records, record_ld, nullptr, st_pitch);
     }
     if (rc != VBX_SUCCESS) return rc;
@@ -1856,50 +1785,14 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, const double *x, co
 int vbx_analyze_frames_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
                            const vbx_analysis_params *h_p, const int64_t *h_seg_start, size_t n_segments,
                            double *out_records, size_t record_ld, int32_t *status3) {
-    return analyze_frames_impl(ctx, __func__, x, nullptr, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records,
-                               record_ld, status3);
+    return analyze_frames_impl(ctx, __func__, x, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records, record_ld, status3);
 }
 
 int vbx_analyze_frames_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
                              const vbx_analysis_params *h_p, const int64_t *h_seg_start, size_t n_segments,
                              double *out_records, size_t record_ld, int32_t *status3) {
     if (n_frames != 0 && ctx && !pcm) return fail(ctx, VBX_E_INVALID, "vbx_analyze_frames_pcm16: null frame pointer");
-    return analyze_frames_impl(ctx, __func__, nullptr, pcm, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records,
-                               record_ld, status3);
-}
-
-// The frame loop with the TRACKED contour in columns 0-1: the fused kernel at the caller's kmax into list buffers, the frame peaks
-// beside it, the pitch path behind it.  Everything is checked before anything is launched.
-static int analyze_tracked(vbx_ctx *ctx, const char *fn, const double *x, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
-                           const vbx_analysis_params *h_p, const vbx_pitch_track_params *h_track, const int64_t *h_seg_start,
-                           size_t n_segments, double *out_records, size_t record_ld, int32_t *status3, const vbx_pitch_track_outputs *h_out) {
-    if (!ctx) return fail(nullptr, VBX_E_INVALID, std::string(fn) + ": null context");
-    if (!h_track) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": null track parameters");
-    if (!h_p) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": null argument");
-    track_req_t tk{};
-    tk.kmax = h_track->kmax; tk.path = h_track->path;
-    if (h_out) tk.out = *h_out;
-    if (tk.path.time_step == 0.0) tk.path.time_step = (double)stride / h_p->sample_rate;      // the batch's own hop
-    int rc = check_pitch_path(ctx, fn, tk.path, n_frames, tk.kmax, true, h_seg_start, n_segments);
-    if (rc != VBX_SUCCESS) return rc;
-    return analyze_frames_impl(ctx, fn, x, pcm, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records, record_ld, status3, &tk);
-}
-
-int vbx_analyze_frames_tracked_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
-                                   const vbx_analysis_params *h_p, const vbx_pitch_track_params *h_track,
-                                   const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld,
-                                   int32_t *status3, const vbx_pitch_track_outputs *h_outputs) {
-    return analyze_tracked(ctx, __func__, x, nullptr, n_frames, frame_len, stride, h_p, h_track, h_seg_start, n_segments, out_records,
-                           record_ld, status3, h_outputs);
-}
-
-int vbx_analyze_frames_tracked_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
-                                     const vbx_analysis_params *h_p, const vbx_pitch_track_params *h_track,
-                                     const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld,
-                                     int32_t *status3, const vbx_pitch_track_outputs *h_outputs) {
-    if (n_frames != 0 && ctx && !pcm) return fail(ctx, VBX_E_INVALID, "vbx_analyze_frames_tracked_pcm16: null frame pointer");
-    return analyze_tracked(ctx, __func__, nullptr, pcm, n_frames, frame_len, stride, h_p, h_track, h_seg_start, n_segments, out_records,
-                           record_ld, status3, h_outputs);
+    return analyze_frames_impl(ctx, __func__, pcm, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records, record_ld, status3);
 }
 
 // find_formants' resample_ratio (src/lib.rs:40-64) as a plan: the checks every entry point that takes a ratio shares, the
@@ -1925,11 +1818,10 @@ static int make_resample_plan(vbx_ctx *ctx, const char *fn, double ratio, size_t
 // The frame loop of examples/formant_extraction/src/main.rs:72-88: find_formants at a resample_ratio, the frame's RMS as the
 // record's last column.  Everything is checked before anything is launched; an h_ext that asks for nothing is the plain /
 // tracked call itself.
-static int analyze_ex(vbx_ctx *ctx, const char *fn, const double *x, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
+static int analyze_ex(vbx_ctx *ctx, const char *fn, frames_t x, size_t n_frames, size_t frame_len, size_t stride,
                       const vbx_analysis_params *h_p, const vbx_analysis_ext *h_ext, const vbx_pitch_track_params *h_track,
                       const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld, int32_t *status3,
-                      const vbx_pitch_track_outputs *h_out, const float *f32 = nullptr /* the frames as float32 samples instead of x / pcm */,
-                      bool defer_path = false /* vbx_analyze_host's chunks: track_req_t */) {
+                      const vbx_pitch_track_outputs *h_out, bool defer_path = false /* vbx_analyze_host's chunks: track_req_t */) {
     if (!ctx) return fail(nullptr, VBX_E_INVALID, std::string(fn) + ": null context");
     if (!h_p) return fail(ctx, VBX_E_INVALID, std::string(fn) + ": null argument");
     resample_plan_t rp{}; ex_req_t ex{nullptr, h_p->sample_rate, false};
@@ -1947,8 +1839,8 @@ static int analyze_ex(vbx_ctx *ctx, const char *fn, const double *x, const int16
         ex.rms = h_ext->rms != 0;
         if (have || ex.rms || rate != 0.0) exp = &ex;
     }
-    if (!h_track) return analyze_frames_impl(ctx, fn, x, pcm, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records, record_ld,
-                                             status3, nullptr, exp, f32);
+    if (!h_track) return analyze_frames_impl(ctx, fn, x, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records, record_ld,
+                                             status3, nullptr, exp);
     track_req_t tk{};
     tk.kmax = h_track->kmax; tk.path = h_track->path;
     if (h_out) tk.out = *h_out;
@@ -1956,14 +1848,37 @@ static int analyze_ex(vbx_ctx *ctx, const char *fn, const double *x, const int16
     if (tk.path.time_step == 0.0) tk.path.time_step = (double)stride / h_p->sample_rate;      // the batch's own hop
     int rc = check_pitch_path(ctx, fn, tk.path, n_frames, tk.kmax, true, h_seg_start, n_segments);
     if (rc != VBX_SUCCESS) return rc;
-    return analyze_frames_impl(ctx, fn, x, pcm, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records, record_ld, status3, &tk, exp, f32);
+    return analyze_frames_impl(ctx, fn, x, n_frames, frame_len, stride, h_p, h_seg_start, n_segments, out_records, record_ld, status3, &tk, exp);
+}
+
+// The frame loop with the TRACKED contour in columns 0-1 (the fused kernel at the caller's kmax into list buffers, the frame peaks
+// beside it, the pitch path behind it): analyze_ex with no extension, behind the two checks that come first here.
+int vbx_analyze_frames_tracked_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
+                                   const vbx_analysis_params *h_p, const vbx_pitch_track_params *h_track,
+                                   const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld,
+                                   int32_t *status3, const vbx_pitch_track_outputs *h_outputs) {
+    if (!ctx) return fail(nullptr, VBX_E_INVALID, std::string(__func__) + ": null context");
+    if (!h_track) return fail(ctx, VBX_E_INVALID, std::string(__func__) + ": null track parameters");
+    return analyze_ex(ctx, __func__, x, n_frames, frame_len, stride, h_p, nullptr, h_track, h_seg_start, n_segments, out_records,
+                      record_ld, status3, h_outputs);
+}
+
+int vbx_analyze_frames_tracked_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_frames, size_t frame_len, size_t stride,
+                                     const vbx_analysis_params *h_p, const vbx_pitch_track_params *h_track,
+                                     const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld,
+                                     int32_t *status3, const vbx_pitch_track_outputs *h_outputs) {
+    if (n_frames != 0 && ctx && !pcm) return fail(ctx, VBX_E_INVALID, "vbx_analyze_frames_tracked_pcm16: null frame pointer");
+    if (!ctx) return fail(nullptr, VBX_E_INVALID, std::string(__func__) + ": null context");
+    if (!h_track) return fail(ctx, VBX_E_INVALID, std::string(__func__) + ": null track parameters");
+    return analyze_ex(ctx, __func__, pcm, n_frames, frame_len, stride, h_p, nullptr, h_track, h_seg_start, n_segments, out_records,
+                      record_ld, status3, h_outputs);
 }
 
 int vbx_analyze_frames_ex_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
                               const vbx_analysis_params *h_p, const vbx_analysis_ext *h_ext, const vbx_pitch_track_params *h_track,
                               const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld,
                               int32_t *status3, const vbx_pitch_track_outputs *h_outputs) {
-    return analyze_ex(ctx, __func__, x, nullptr, n_frames, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, out_records,
+    return analyze_ex(ctx, __func__, x, n_frames, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, out_records,
                       record_ld, status3, h_outputs);
 }
 
@@ -1972,7 +1887,7 @@ int vbx_analyze_frames_ex_pcm16(vbx_ctx *ctx, const int16_t *pcm, size_t n_frame
                                 const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld,
                                 int32_t *status3, const vbx_pitch_track_outputs *h_outputs) {
     if (n_frames != 0 && ctx && !pcm) return fail(ctx, VBX_E_INVALID, "vbx_analyze_frames_ex_pcm16: null frame pointer");
-    return analyze_ex(ctx, __func__, nullptr, pcm, n_frames, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, out_records,
+    return analyze_ex(ctx, __func__, pcm, n_frames, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, out_records,
                       record_ld, status3, h_outputs);
 }
 
@@ -1981,8 +1896,8 @@ int vbx_analyze_frames_ex_f32in(vbx_ctx *ctx, const float *x, size_t n_frames, s
                                 const int64_t *h_seg_start, size_t n_segments, double *out_records, size_t record_ld,
                                 int32_t *status3, const vbx_pitch_track_outputs *h_outputs) {
     if (n_frames != 0 && ctx && !x) return fail(ctx, VBX_E_INVALID, "vbx_analyze_frames_ex_f32in: null frame pointer");
-    return analyze_ex(ctx, __func__, nullptr, nullptr, n_frames, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, out_records,
-                      record_ld, status3, h_outputs, x);
+    return analyze_ex(ctx, __func__, x, n_frames, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, out_records,
+                      record_ld, status3, h_outputs);
 }
 
 // ---- host-resident recordings (header: "host-resident recordings") ---------------------------
@@ -1990,7 +1905,9 @@ int vbx_analyze_frames_ex_f32in(vbx_ctx *ctx, const float *x, size_t n_frames, s
 static const char *const k_unpack_names[6] = {"", "unpack_pcm16", "unpack_pcm24", "unpack_pcm32", "unpack_f32", "unpack_f64"};
 static bool sample_format_ok(int f) { return f >= VBX_SAMPLE_PCM16 && f <= VBX_SAMPLE_F64; }
 static size_t sample_src_bytes(int f) { return f == VBX_SAMPLE_PCM16 ? 2 : f == VBX_SAMPLE_PCM24 ? 3 : f == VBX_SAMPLE_F64 ? 8 : 4; }
-static size_t sample_out_bytes(int f) { return f == VBX_SAMPLE_PCM16 ? 2 : f == VBX_SAMPLE_F32 ? 4 : 8; }
+// the typed plane the frame loop reads for a VBX_SAMPLE_* format (what launch_unpack writes): PCM24 / PCM32 / F64 unpack to f64
+static sample_kind_t sample_plane_kind(int f) { return f == VBX_SAMPLE_PCM16 ? SAMPLE_PCM16 : f == VBX_SAMPLE_F32 ? SAMPLE_F32 : SAMPLE_F64; }
+static size_t sample_out_bytes(int f) { static const size_t bytes[3] = {8, 2, 4}; return bytes[sample_plane_kind(f)]; }
 
 int vbx_unpack_samples(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames, int format, int channels, int channel, void *d_out) {
     VBX_REQUIRE(ctx, ctx != nullptr, "null context");
@@ -2098,7 +2015,7 @@ static int analyze_host_impl(vbx_ctx *ctx, const char *fn, const void *h_audio, 
     const size_t F = vbx_frame_count(n_sample_frames, frame_len, stride);
     if (F == 0) {                                         // the resident call's empty batch: its checks, its state
         for (size_t k = 0; k < n_sel; k++) {
-            int rc0 = analyze_ex(ctx, fn, nullptr, nullptr, 0, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, chan[k].rec,
+            int rc0 = analyze_ex(ctx, fn, frames_t(), 0, frame_len, stride, h_p, h_ext, h_track, h_seg_start, n_segments, chan[k].rec,
                                  record_ld, chan[k].st, chan[k].out);
             if (rc0 != VBX_SUCCESS) return rc0;
         }
@@ -2239,10 +2156,8 @@ static int analyze_host_impl(vbx_ctx *ctx, const char *fn, const void *h_audio, 
             const void *xs = unpack ? static_cast<const void *>(typed + k * plane_bytes) : ctx->host_raw[slot];
             vbx_pitch_track_outputs to{};
             if (h_track) { to.cand = h.g_cand + first * kmax; to.count = h.g_count + first; to.peak = h.g_peak ? h.g_peak + first : nullptr; }
-            const bool as_pcm = fmt == VBX_SAMPLE_PCM16, as_f32 = fmt == VBX_SAMPLE_F32;
-            rc = analyze_ex(ctx, fn, (as_pcm || as_f32) ? nullptr : static_cast<const double *>(xs), as_pcm ? static_cast<const int16_t *>(xs) : nullptr,
-                            n, frame_len, stride, h_p, h_ext, h_track, seg_c, nseg_c, c_rec, ld_c, c_st, h_track ? &to : nullptr,
-                            as_f32 ? static_cast<const float *>(xs) : nullptr, true);
+            rc = analyze_ex(ctx, fn, frames_t(xs, sample_plane_kind(fmt)), n, frame_len, stride, h_p, h_ext, h_track, seg_c, nseg_c, c_rec, ld_c, c_st,
+                            h_track ? &to : nullptr, true);
             if (rc != VBX_SUCCESS) return bail(rc);
             if (!unpack) VBX_HIP(ctx, hipEventRecord(ctx->host_freed[slot], ctx->stream));      // (mono: the one channel read the slot itself)
             // a cut inside an utterance: the tracker continues from the true state, the row before the cut (already in place)
@@ -2482,13 +2397,11 @@ static void session_free(vbx_session *s) {
 
 // the frame loop on frames [0, n) of the session's current carry buffer into the chunk-local buffers
 static int session_analyze(vbx_session *s, const char *fn, size_t n, bool want_peak) {
-    const void *xs = s->carry[s->cur];
-    const bool as_pcm = s->fmt == VBX_SAMPLE_PCM16, as_f32 = s->fmt == VBX_SAMPLE_F32;
     vbx_pitch_track_outputs to{};
     to.cand = s->c_cand; to.count = s->c_count; to.peak = want_peak ? s->c_peak : nullptr;
-    return analyze_ex(s->ctx, fn, (as_pcm || as_f32) ? nullptr : static_cast<const double *>(xs), as_pcm ? static_cast<const int16_t *>(xs) : nullptr,
-                      n, s->frame_len, s->stride, &s->p, s->have_ext ? &s->ext : nullptr, s->have_track ? &s->track : nullptr, nullptr, 0,
-                      s->c_rec, s->ld_c, s->c_st, s->have_track ? &to : nullptr, as_f32 ? static_cast<const float *>(xs) : nullptr, true);
+    return analyze_ex(s->ctx, fn, frames_t(s->carry[s->cur], sample_plane_kind(s->fmt)), n, s->frame_len, s->stride, &s->p,
+                      s->have_ext ? &s->ext : nullptr, s->have_track ? &s->track : nullptr, nullptr, 0, s->c_rec, s->ld_c, s->c_st,
+                      s->have_track ? &to : nullptr, true);
 }
 
 int vbx_session_open(vbx_ctx *ctx, const vbx_host_audio *h_fmt, size_t frame_len, size_t stride, const vbx_analysis_params *h_p,
@@ -2773,7 +2686,7 @@ int vbx_find_formants_resampled_f64(vbx_ctx *ctx, const double *x, size_t n_fram
     if (rc != VBX_SUCCESS) return rc;
     VBX_HIP(ctx, hipSetDevice(ctx->device));
     return run_find_formants(ctx, ctx->stream, x, n_frames, frame_len, stride, sample_rate, n_coeffs, h_seg_start, n_segments,
-                             h_est_init, n_est, out_formants, 2 * n_est, out_res, out_res_count, out_coeffs, status, nullptr,
+                             h_est_init, n_est, out_formants, 2 * n_est, out_res, out_res_count, out_coeffs, status,
                              have ? &rp : nullptr);
 }
 

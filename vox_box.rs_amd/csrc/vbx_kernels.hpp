@@ -30,6 +30,22 @@ struct pitch_t { double frequency, strength; };
 struct cplx_t { double re, im; };
 struct cplx32_t { float re, im; };
 
+// The frames a launcher reads, with the type of their samples: f64, 16-bit PCM (a kernel widens a sample in registers: s / 32767) or
+// float32 (widened exactly where it is loaded).  A typed pointer converts to the view of its own kind, so pointer and kind cannot
+// disagree; the kind is that of the typed plane a kernel reads, not a VBX_SAMPLE_* format (PCM24 / PCM32 / F64 all unpack to f64).
+enum sample_kind_t { SAMPLE_F64, SAMPLE_PCM16, SAMPLE_F32 };
+struct frames_t {
+    const void *p; sample_kind_t kind;
+    frames_t(const double *x = nullptr) : p(x), kind(SAMPLE_F64) {}
+    frames_t(const int16_t *x) : p(x), kind(SAMPLE_PCM16) {}
+    frames_t(const float *x) : p(x), kind(SAMPLE_F32) {}
+    frames_t(const void *x, sample_kind_t k) : p(x), kind(k) {}
+    // the samples at their own type; null through an accessor of another kind
+    const double *f64() const { return kind == SAMPLE_F64 ? static_cast<const double *>(p) : nullptr; }
+    const int16_t *pcm16() const { return kind == SAMPLE_PCM16 ? static_cast<const int16_t *>(p) : nullptr; }
+    const float *f32in() const { return kind == SAMPLE_F32 ? static_cast<const float *>(p) : nullptr; }
+};
+
 // k_lpc.hip
 bool fewlags_supported(int n, int n_lags, bool want_lpc);
 void launch_autocorr_fewlags(hipStream_t s, const double *x, long F, int n, long stride, const double *window,
@@ -54,44 +70,40 @@ void launch_levinson_rows_probe(hipStream_t s, const double *r, long rows, long 
 
 // k_burg.hip
 bool burg_supported(int n, int p);
-void launch_burg(hipStream_t s, const double *x, long F, int n, long stride, const double *window,
-                 int p, double *out, int32_t *status, frame_map_t map = frame_map_t{0, 0, 0});
-// the same on 16-bit PCM frames (samples widened in registers: s / 32767), f64 coefficients
-void launch_burg_pcm16(hipStream_t s, const int16_t *x, long F, int n, long stride, const double *window,
-                       int p, double *out, int32_t *status, frame_map_t map = frame_map_t{0, 0, 0});
-void launch_burg_list(hipStream_t s, const double *x, long F, int n, long stride, const double *window,
-                      int p, double *out, int32_t *status, const int32_t *list, const int32_t *count);
-void launch_burg_pcm16_list(hipStream_t s, const int16_t *x, long F, int n, long stride, const double *window,
-                            int p, double *out, int32_t *status, const int32_t *list, const int32_t *count);
+// (f64 coefficients whatever the samples' type; PCM samples are widened in registers: s / 32767)
+void launch_burg(hipStream_t s, frames_t x, long F, int n, long stride, const double *window, int p, double *out, int32_t *status,
+                 frame_map_t map);
+void launch_burg_list(hipStream_t s, frames_t x, long F, int n, long stride, const double *window, int p, double *out, int32_t *status,
+                      const int32_t *list, const int32_t *count);
 
 // k_burg_fast.hip: the same coefficients from the frame's lag sums and edge samples (one pass over the frame), in chunks
 // of burg_fast_chunk(F) items: launch_burg_lags, then launch_burg_recursion, per chunk; the frames its guard turns away
-// are appended to burg_fast_list(ws, F, p) ([0] = count, indices from [2]) for launch_burg_list / launch_burg_pcm16_list.
+// are appended to burg_fast_list(ws, F, p) ([0] = count, indices from [2]) for launch_burg_list.
 // ws: burg_fast_scratch_bytes(F, p) bytes; the caller zeroes the list's count before the first chunk.
 bool burg_fast_supported(int n, int p);
 long burg_fast_chunk(long F);
 size_t burg_fast_scratch_bytes(long F, int p);
 int32_t *burg_fast_list(void *ws, long F, int p);
-void launch_burg_lags(hipStream_t s, const double *x, long F, int n, long stride, const double *window, int p,
-                      frame_map_t map, long i0, long m, void *ws);
-void launch_burg_lags_pcm16(hipStream_t s, const int16_t *x, long F, int n, long stride, const double *window, int p,
-                            frame_map_t map, long i0, long m, void *ws);
+// false: the order has no lag kernel -- NOTHING was launched, and the recursion behind would read scratch that no kernel wrote (the
+// caller fails the call)
+bool launch_burg_lags(hipStream_t s, frames_t x, long F, int n, long stride, const double *window, int p, frame_map_t map, long i0,
+                      long m, void *ws);
 void launch_burg_recursion(hipStream_t s, long F, int p, frame_map_t map, long i0, long m, double *out, int32_t *status, void *ws);
 
 void launch_count_accumulate(hipStream_t s, const int32_t *count, int32_t *total, bool reset);   // total = (reset ? 0 : total) + count
 
 // k_burg_resampled.hip: launch_burg / launch_burg_list / launch_burg_lags on the RESAMPLED view of the frames (find_formants with a
-// resample_ratio): x (or pcm, if non-null) holds the caller's frames of rs.n_src samples; m: the resampled length; window: the
+// resample_ratio): x holds the caller's frames of rs.n_src samples; m: the resampled length; window: the
 // periodic Hanning window of length m; rs: the (li, frac) table of vbx_resample_linear_f64.  Bit for bit the dense launchers on
 // the [F, m] batch that entry point writes.  launch_burg_recursion runs behind launch_burg_lags_resampled unchanged.
 struct resample_src_t { const int32_t *li; const double *frac; int n_src; };
 bool burg_resampled_supported(int n_src, int m, int p);
-void launch_burg_resampled(hipStream_t s, const double *x, const int16_t *pcm, long F, int m, long stride, const double *window,
-                           resample_src_t rs, int p, double *out, int32_t *status, frame_map_t map);
-void launch_burg_resampled_list(hipStream_t s, const double *x, const int16_t *pcm, long F, int m, long stride, const double *window,
-                                resample_src_t rs, int p, double *out, int32_t *status, const int32_t *list, const int32_t *count);
-void launch_burg_lags_resampled(hipStream_t s, const double *x, const int16_t *pcm, long F, int m, long stride, const double *window,
-                                resample_src_t rs, int p, frame_map_t map, long i0, long n_items, void *ws);
+void launch_burg_resampled(hipStream_t s, frames_t x, long F, int m, long stride, const double *window, resample_src_t rs, int p,
+                           double *out, int32_t *status, frame_map_t map);
+void launch_burg_resampled_list(hipStream_t s, frames_t x, long F, int m, long stride, const double *window, resample_src_t rs, int p,
+                                double *out, int32_t *status, const int32_t *list, const int32_t *count);
+bool launch_burg_lags_resampled(hipStream_t s, frames_t x, long F, int m, long stride, const double *window, resample_src_t rs, int p,
+                                frame_map_t map, long i0, long n_items, void *ws);      // false: as launch_burg_lags
 
 // k_roots.hip
 void launch_find_roots(hipStream_t s, cplx_t *polys, long F, int len, int32_t *status);
@@ -161,11 +173,9 @@ void launch_pitch(hipStream_t s, const double *x, long F, int n, long stride, co
                   int kmax, pitch_t *out_cand, long cand_ld /* doubles per output row, >= 2*kmax, even */,
                   int32_t *out_count, int32_t *status, unsigned long long *work);
 // the same kernel over a device-resident list of frame indices (fallback of k_spectral.hip), fixed grid
-void launch_pitch_list(hipStream_t s, const int32_t *frame_list, const int32_t *list_count, int grid,
-                       const double *x, int n, long stride, const double *window,
-                       const double *lag_window, double sample_rate, double threshold, double fmin, double fmax,
-                       int kmax, pitch_t *out_cand, long cand_ld, int32_t *out_count, int32_t *status,
-                       unsigned long long *work, bool pcm = false /* x points to int16 PCM samples */);
+void launch_pitch_list(hipStream_t s, const int32_t *frame_list, const int32_t *list_count, int grid, frames_t x, int n, long stride,
+                       const double *window, const double *lag_window, double sample_rate, double threshold, double fmin, double fmax,
+                       int kmax, pitch_t *out_cand, long cand_ld, int32_t *out_count, int32_t *status, unsigned long long *work);
 void launch_sinc_points(hipStream_t s, const double *y, int ylen, long offset, long nx, const double *xs, long m,
                         long depth, double *out, int32_t *status);
 void launch_extremum_points(hipStream_t s, const double *y, int ylen, long offset, long nx, const double *ix, long m,
@@ -221,7 +231,8 @@ bool mfcc_interp_fill(int plan, int n, int b_lo, int nb, void *h_table, mfcc_int
 
 struct spectral_launch_t {
     int plan; int n;                                             // spectral_plan(n), frame length
-    const double *x; long F; long stride; const double *window; const double *lag_window; const double *tab;
+    frames_t x;                                                  // PCM / float32 samples: full 1200-sample frames only (k_spectral.hip, k_spectral_f32in.hip)
+    long F; long stride; const double *window; const double *lag_window; const double *tab;
     bool mfcc_defer;                                             // the MFCC rows leave the kernel as filter sums; launch_mfcc_rows finishes them (num_coeffs <= 16)
     bool lag_rcp;                                                // lag_window[((n + 1) & ~1) + i] = RN(1 / lag_window[i]) (quotient_by_table, vbx_spectral.hpp)
     double sample_rate, threshold, fmin, fmax; int kmax;
@@ -233,8 +244,6 @@ struct spectral_launch_t {
     int32_t *lpc_list; int32_t *lpc_count;                       // frames handed to launch_lpc_exact_list (ill-conditioned LPC rows); NULL: no probe
     bool mfcc_only;                                              // MFCC::mfcc alone (n == the plan's Nc): no pitch, no LPC
     double *out_r; int n_lags;                                   // non-NULL: Autocorrelate::autocorrelate(n_lags) alone, [F, n_lags]
-    bool pcm;                                                    // x points to int16 PCM samples (n == 1200 only)
-    bool f32in;                                                  // x points to float32 samples (n == 1200 only; k_spectral_f32in.hip)
     bool whole_curve;                                            // keep every lag of the curve in LDS (VBX_PITCH_CURVE_CUT=0; tests)
     bool interp; mfcc_interp_t ip;                               // MFCC by interpolation of the transform's bins (device pointers)
     double *curve_ws; size_t curve_ws_bytes;                     // scratch for the split form of the 4096-point plan (lag curves between its two kernels); NULL: fused
@@ -248,14 +257,14 @@ int launch_analyze(hipStream_t s, const spectral_launch_t &L);       // 1: the c
 // k_mfcc.hip: log10 (clamped at 1e-10) + DCT of rows of mel filter sums, in place, a lane per row (the deferred tail of MFCC::mfcc, vbx_mfcc_tail.hpp)
 void launch_mfcc_rows(hipStream_t s, double *rows, long F, long ld, int num_coeffs, const double *dct);
 bool lpc_exact_supported(int n, int p);                               // frames of 2..4096 samples, orders 1..31
-void launch_lpc_exact_list(hipStream_t s, const int32_t *frame_list, const int32_t *list_count, int cus, const double *x, int n,
-                           long stride, const double *window, bool pcm, int p, double *out_lpc, long lpc_ld);
+void launch_lpc_exact_list(hipStream_t s, const int32_t *frame_list, const int32_t *list_count, int cus, frames_t x, int n, long stride,
+                           const double *window, int p, double *out_lpc, long lpc_ld);
 
 // k_lpc_ref.hip (VBX_LPC_POLICY_REFERENCE): the crate's own f64 arithmetic, bit for bit -- lag sums as the sequential fold of
 // src/periodic.rs:276-289, [normalize,] the recursion of src/spectrum.rs:63-84, no contraction.  p == 0: lag sums only
-// (n_lags <= n, out_r: [F, r_ld]); p >= 1: n_lags = p + 1, out_r (optional) and out_lpc [F, lpc_ld].  pcm: x is 16-bit PCM.
-void launch_lpc_ref(hipStream_t s, const void *x, bool pcm, long F, int n, long stride, const double *window, int n_lags, int p,
-                    int normalize, double *out_r, long r_ld, double *out_lpc, long lpc_ld);
+// (n_lags <= n, out_r: [F, r_ld]); p >= 1: n_lags = p + 1, out_r (optional) and out_lpc [F, lpc_ld].
+void launch_lpc_ref(hipStream_t s, frames_t x, long F, int n, long stride, const double *window, int n_lags, int p, int normalize,
+                    double *out_r, long r_ld, double *out_lpc, long lpc_ld);
 void launch_levinson_ref_rows(hipStream_t s, const double *r, long rows, long r_stride, int p, double *out, long out_ld, double *out_kc);
 
 // the f32 instantiation (Sample = f32): the same kernels with float frames and float outputs
@@ -319,8 +328,9 @@ void launch_resample(hipStream_t s, const double *x, long F, int n, long stride,
                      const double *tab_frac, int m, double *out);
 void launch_ring_frames(hipStream_t s, const double *ring, long capacity, long head, long F, int n, long stride, double *out);
 void launch_pcm16(hipStream_t s, const int16_t *pcm, size_t n, double denom, double *out);
-// max |s| / 32767 per frame of 16-bit PCM: launch_frame_peak (k_pitch_path.hip) on the widened samples, bit for bit
-void launch_frame_peak_pcm16(hipStream_t s, const int16_t *pcm, long F, long n, long stride, double *out);
+// max |x| per frame of any sample type: the f64 launch_frame_peak (k_pitch_path.hip) on the widened samples, bit for bit (PCM: an
+// integer max widened once by s / 32767; float32: taken in float and widened once, NaNs ignored as there)
+void launch_frame_peak(hipStream_t s, frames_t x, long F, long n, long stride, double *out);
 void launch_rms(hipStream_t s, const double *x, long F, int n, long stride, const double *window, double *out);
 void launch_preemphasis(hipStream_t s, const double *x, long F, int n, long stride, double c, double *out);
 
@@ -359,16 +369,53 @@ struct session_deliver_t {
 };
 void launch_session_deliver(hipStream_t s, const session_deliver_t &d);
 
-// k_front_ex.hip: RMS::rms of the rectangular frame (launch_rms with a null window, bit for bit) from the f64 view or from 16-bit
-// PCM, written at out_rms + f * rms_ld; out_peak non-null: launch_frame_peak / launch_frame_peak_pcm16 from the same read
-void launch_frame_rms(hipStream_t s, const double *x, const int16_t *pcm, long F, int n, long stride, double *out_rms, long rms_ld,
-                      double *out_peak);
+// k_front_ex.hip: RMS::rms of the rectangular frame (launch_rms with a null window, bit for bit) of any sample type, written at
+// out_rms + f * rms_ld; out_peak non-null: launch_frame_peak from the same read
+void launch_frame_rms(hipStream_t s, frames_t x, long F, int n, long stride, double *out_rms, long rms_ld, double *out_peak);
 
+// k_front_f32in.hip: the widening pass of float32 samples (launch_pcm16's counterpart)
+void launch_f32_to_f64(hipStream_t s, const float *x, size_t n, double *out);
+
+// ---- the seam between translation units: the forms of ONE sample type of the launchers above that take a frames_t --------------
+// ONLY those launchers call these.  Each frames_t launcher switches on x.kind -- nobody else does -- and is defined beside the float32
+// instantiations (k_burg_f32in.hip, k_burg_lags_f32in.hip, k_front_f32in.hip, k_lists_f32in.hip); every instantiation stays in the
+// unit of its kernel.  (launch_frame_peak on const double *, k_pitch_path.hip, is also vbx_frame_peak_f64 itself.)
+// k_burg.hip, k_burg_fast.hip, k_burg_resampled.hip, k_front.hip, k_front_ex.hip, k_pitch.hip, k_lpc_exact.hip, k_lpc_ref.hip: the f64 and PCM forms
+void launch_burg(hipStream_t s, const double *x, long F, int n, long stride, const double *window,
+                 int p, double *out, int32_t *status, frame_map_t map = frame_map_t{0, 0, 0});
+void launch_burg_pcm16(hipStream_t s, const int16_t *x, long F, int n, long stride, const double *window,
+                       int p, double *out, int32_t *status, frame_map_t map = frame_map_t{0, 0, 0});
+void launch_burg_list(hipStream_t s, const double *x, long F, int n, long stride, const double *window,
+                      int p, double *out, int32_t *status, const int32_t *list, const int32_t *count);
+void launch_burg_pcm16_list(hipStream_t s, const int16_t *x, long F, int n, long stride, const double *window,
+                            int p, double *out, int32_t *status, const int32_t *list, const int32_t *count);
+void launch_burg_lags(hipStream_t s, const double *x, long F, int n, long stride, const double *window, int p,
+                      frame_map_t map, long i0, long m, void *ws);
+void launch_burg_lags_pcm16(hipStream_t s, const int16_t *x, long F, int n, long stride, const double *window, int p,
+                            frame_map_t map, long i0, long m, void *ws);
+// (x, or pcm if non-null)
+void launch_burg_resampled(hipStream_t s, const double *x, const int16_t *pcm, long F, int m, long stride, const double *window,
+                           resample_src_t rs, int p, double *out, int32_t *status, frame_map_t map);
+void launch_burg_resampled_list(hipStream_t s, const double *x, const int16_t *pcm, long F, int m, long stride, const double *window,
+                                resample_src_t rs, int p, double *out, int32_t *status, const int32_t *list, const int32_t *count);
+void launch_burg_lags_resampled(hipStream_t s, const double *x, const int16_t *pcm, long F, int m, long stride, const double *window,
+                                resample_src_t rs, int p, frame_map_t map, long i0, long n_items, void *ws);
+void launch_pitch_list(hipStream_t s, const int32_t *frame_list, const int32_t *list_count, int grid,
+                       const double *x, int n, long stride, const double *window,
+                       const double *lag_window, double sample_rate, double threshold, double fmin, double fmax,
+                       int kmax, pitch_t *out_cand, long cand_ld, int32_t *out_count, int32_t *status,
+                       unsigned long long *work, bool pcm /* x points to int16 PCM samples */);
+void launch_lpc_exact_list(hipStream_t s, const int32_t *frame_list, const int32_t *list_count, int cus, const double *x, int n,
+                           long stride, const double *window, bool pcm /* x points to int16 PCM samples */, int p, double *out_lpc, long lpc_ld);
+void launch_lpc_ref(hipStream_t s, const void *x, bool pcm /* x is 16-bit PCM */, long F, int n, long stride, const double *window, int n_lags,
+                    int p, int normalize, double *out_r, long r_ld, double *out_lpc, long lpc_ld);
+void launch_frame_peak_pcm16(hipStream_t s, const int16_t *pcm, long F, long n, long stride, double *out);
+void launch_frame_rms(hipStream_t s, const double *x, const int16_t *pcm /* instead of x, if non-null */, long F, int n, long stride,
+                      double *out_rms, long rms_ld, double *out_peak);
 // k_front_f32in.hip, k_burg_f32in.hip, k_burg_lags_f32in*.hip, k_lists_f32in.hip (and k_spectral_f32in.hip, declared in vbx_spectral.hpp):
 // the kernels above that read a frame's samples, on FLOAT32 samples (vbx_analyze_frames_ex_f32in).  Each widens a sample in registers
 // before its first use -- every float is a double, so the frame is the one launch_f32_to_f64 would have written and every result
 // is the f64 launcher's on that copy, bit for bit; windows, tables and results stay f64.
-void launch_f32_to_f64(hipStream_t s, const float *x, size_t n, double *out);
 // max |x| per frame taken in float and widened once: launch_frame_peak on the widened samples (NaNs ignored, as there)
 void launch_frame_peak_f32in(hipStream_t s, const float *x, long F, long n, long stride, double *out);
 void launch_frame_rms_f32in(hipStream_t s, const float *x, long F, int n, long stride, double *out_rms, long rms_ld, double *out_peak);
