@@ -100,6 +100,6 @@ def test_the_kernel_lives_beside_the_reader():
     reader = read("k_reader.hip")
     assert "unpack_all_tiled_kernel" in reader and "unpack_all_elem_kernel" in reader and "__shared__" in reader
     assert "void launch_unpack_all(" in read("vbx_kernels.hpp")
-    api = read("vbx_api.hip")
+    api = read("vbx_api_host.hip")
     for name in ("unpack_all_pcm16", "unpack_all_pcm24", "unpack_all_pcm32", "unpack_all_f32", "unpack_all_f64"):
         assert '"' + name + '"' in api, name

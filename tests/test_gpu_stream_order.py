@@ -7,7 +7,7 @@ next call while the side stream still reads it would pass all of them.
   A  the late producer (tests/stream_harness.py late_producer): behind a delay of milliseconds, the input is copied into place ON
      the stream, the call follows, a device copy of every output follows the call; the host has run ahead (hipStreamQuery), and
      after one synchronisation the copies equal the call bracketed by vbx_sync, bit for bit.  One case per ordering mechanism of
-     vbx_api.hip; which mechanism ran is asserted from the profile of the synchronised pass.  One case makes the side stream LATE
+     the vbx_api_*.hip units; which mechanism ran is asserted from the profile of the synchronised pass.  One case makes the side stream LATE
      (a sequential tracker scan several times longer than the fused kernel), so that a missing join shows.
   B  a fixed list of calls queued behind a delay with ONE synchronisation at the end, forward and reversed: neighbours share
      workspace slots at different sizes, alternate between two segment lists and two estimate sets (re-upload and skip-upload of the

@@ -135,7 +135,7 @@ def test_the_kernel_lives_beside_the_helpers_it_shares():
         assert n in body, n
     assert "fma(" not in body and "#pragma clang fp contract(off)" in k
     assert "void launch_pitch_path_online(" in read("vbx_kernels.hpp")
-    assert '"pitch_path_online"' in read("vbx_api.hip")
+    assert '"pitch_path_online"' in read("vbx_api_path.hip")
 
 
 def test_the_built_kernel_has_no_scratch_and_no_spills():

@@ -147,7 +147,7 @@ def test_the_kernels_live_in_their_own_unit():
     hpp = read("vbx_kernels.hpp")
     assert "void launch_session_ingest(" in hpp and "void launch_session_deliver(" in hpp
     assert "session_carry_samples" in read("vbx_host.hpp") and "int vbx_session_plan(" in read("vbx_host.cpp")
-    api = read("vbx_api.hip")
+    api = read("vbx_api_session.hip")
     for name in ("session_ingest_pcm16", "session_ingest_pcm24", "session_ingest_pcm32", "session_ingest_f32", "session_ingest_f64", "session_deliver"):
         assert '"' + name + '"' in api, name
     usage = open(os.path.join(ROOT, "profiles", "session", "resource_usage.txt")).read()

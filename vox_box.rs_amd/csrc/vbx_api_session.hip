@@ -1,0 +1,350 @@
+// vbx_api_session.hip -- live sessions: one channel of one stream of audio, analysed block by block.
+#include "vbx_ctx.hpp"
+
+#include <cstring>
+#include <string>
+
+using namespace vbx;
+
+// ---- live sessions (header: "live sessions") --------------------------------------------------
+
+extern "C" {
+
+// blocks of up to this many bytes are staged through the session's pinned buffers and uploaded on the context's own stream: a host
+// copy of about 10 us at this size, which is what the copy stream's event round trip was measured to add to a push (DESIGN.md
+// section 5g); larger blocks take the copy stream, where their upload runs beside the previous block's analysis
+#define VBX_SESSION_STAGE_BYTES 131072
+static const char *const k_ingest_names[6] = {"", "session_ingest_pcm16", "session_ingest_pcm24", "session_ingest_pcm32", "session_ingest_f32",
+                                              "session_ingest_f64"};
+
+// One channel of one stream of audio, analysed block by block.  The session owns what lives between pushes and everything a push
+// writes before the caller's arrays: the two carry buffers (ping-pong: a push's ingest writes the other one), the two raw staging
+// slots with their events, the chunk-local records / status rows / lists and the tracker state.  The frame loop's own workspaces are
+// the context's, grown once by the warm-up call of vbx_session_open.
+struct vbx_session {
+    vbx_ctx *ctx = nullptr;
+    int fmt = 0; size_t channels = 1, channel = 0;
+    size_t frame_len = 0, stride = 0, max_block = 0;
+    vbx_analysis_params p{}; vbx_analysis_ext ext{}; vbx_pitch_track_params track{};
+    bool have_ext = false, have_track = false;
+    size_t rec = 0, ld_c = 0, nmax = 0;
+    // the stream so far
+    size_t consumed = 0, utt_frame = 0, frames = 0;
+    size_t base = 0;                                      // the sample frame element 0 of carry[cur] holds
+    size_t keep_from = 0;                                 // the first sample frame a later push may still read (vbx_session_plan)
+    int cur = 0;
+    size_t uploads = 0;                                   // host pushes so far: push k stages through raw slot k & 1
+    // device memory
+    void *carry[2] = {nullptr, nullptr};
+    void *raw[2] = {nullptr, nullptr};
+    hipEvent_t ready[2] = {nullptr, nullptr}, freed[2] = {nullptr, nullptr};
+    // small blocks (a hop, a few hops): two pinned staging buffers the block is copied into on the host, uploaded from on the context's
+    // own stream -- no second stream to wait for, no host wait for the upload; staged[i]: slot i's last upload has left it
+    void *stage[2] = {nullptr, nullptr};
+    size_t stage_bytes = 0;
+    hipEvent_t staged[2] = {nullptr, nullptr};
+    double *c_rec = nullptr; int32_t *c_st = nullptr;
+    vbx_pitch *c_cand = nullptr; int32_t *c_count = nullptr; double *c_peak = nullptr;
+    double *state = nullptr;                              // 2 * n_est doubles: the formant row of the last frame delivered
+    // vbx_session_path_bind: the online path over the session-owned lists, and where its rows go
+    vbx_path_stream *path = nullptr;
+    bool bound = false;
+    vbx_pitch *p_out = nullptr; size_t p_ld = 0; int32_t *p_index = nullptr; uint8_t *p_forced = nullptr; vbx_path_commit *p_commit = nullptr;
+};
+
+static void session_free(vbx_session *s) {
+    for (int i = 0; i < 2; i++) {
+        if (s->carry[i]) hipFree(s->carry[i]);
+        if (s->raw[i]) hipFree(s->raw[i]);
+        if (s->ready[i]) hipEventDestroy(s->ready[i]);
+        if (s->freed[i]) hipEventDestroy(s->freed[i]);
+        if (s->stage[i]) hipHostFree(s->stage[i]);
+        if (s->staged[i]) hipEventDestroy(s->staged[i]);
+    }
+    if (s->c_rec) hipFree(s->c_rec);
+    if (s->c_st) hipFree(s->c_st);
+    if (s->c_cand) hipFree(s->c_cand);
+    if (s->c_count) hipFree(s->c_count);
+    if (s->c_peak) hipFree(s->c_peak);
+    if (s->state) hipFree(s->state);
+    if (s->path) path_stream_free(s->path);
+    delete s;
+}
+
+// the frame loop on frames [0, n) of the session's current carry buffer into the chunk-local buffers
+static int session_analyze(vbx_session *s, const char *fn, size_t n, bool want_peak) {
+    vbx_pitch_track_outputs to{};
+    to.cand = s->c_cand; to.count = s->c_count; to.peak = want_peak ? s->c_peak : nullptr;
+    return analyze_ex(s->ctx, fn, frames_t(s->carry[s->cur], sample_plane_kind(s->fmt)), n, s->frame_len, s->stride, &s->p,
+                      s->have_ext ? &s->ext : nullptr, s->have_track ? &s->track : nullptr, nullptr, 0, s->c_rec, s->ld_c, s->c_st,
+                      s->have_track ? &to : nullptr, true);
+}
+
+int vbx_session_open(vbx_ctx *ctx, const vbx_host_audio *h_fmt, size_t frame_len, size_t stride, const vbx_analysis_params *h_p,
+                     const vbx_analysis_ext *h_ext, const vbx_pitch_track_params *h_track, size_t max_block, vbx_session **out) {
+    if (!ctx) return fail(nullptr, VBX_E_INVALID, "vbx_session_open: null context");
+    VBX_REQUIRE(ctx, out != nullptr, "null output");
+    *out = nullptr;
+    VBX_REQUIRE(ctx, h_fmt != nullptr && h_p != nullptr, "null argument");
+    VBX_REQUIRE(ctx, sample_format_ok(h_fmt->format), "unknown sample format");
+    VBX_REQUIRE(ctx, h_fmt->channels >= 1 && h_fmt->channel >= 0 && h_fmt->channel < h_fmt->channels, "need channels >= 1 and 0 <= channel < channels");
+    VBX_REQUIRE(ctx, h_fmt->reserved == 0 && h_fmt->chunk_frames == 0, "reserved and chunk_frames must be 0");
+    VBX_REQUIRE(ctx, max_block >= 1, "max_block_sample_frames must be >= 1");
+    VBX_REQUIRE(ctx, frame_len >= 1 && frame_len <= VBX_MAX_LONG_FRAME_LEN, "frame_len must be in [1, 67108864]");
+    VBX_REQUIRE(ctx, stride >= 1, "stride must be >= 1");
+    VBX_REQUIRE(ctx, max_block <= ((size_t)1 << 40) && stride <= ((size_t)1 << 40), "max_block_sample_frames or stride too large");
+    VBX_REQUIRE(ctx, !h_p->formant_order || (h_p->n_est >= 1 && h_p->n_est <= VBX_FORMANT_SLOTS), "n_est must be in [1, 6]");
+    const size_t nmax = session_max_frames(stride, max_block);
+    VBX_REQUIRE(ctx, nmax <= 0x7fffffffull, "too many frames for one launch");
+    if (h_track) {
+        vbx_pitch_path_params path = h_track->path;
+        if (path.time_step == 0.0) path.time_step = (double)stride / h_p->sample_rate;
+        int rc = check_pitch_path(ctx, __func__, path, nmax, h_track->kmax, true, nullptr, 0);
+        if (rc != VBX_SUCCESS) return rc;
+    }
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_host_slots(ctx, 0);                   // (the copy stream; the context's own raw slots stay as they are)
+    if (rc != VBX_SUCCESS) return rc;
+    vbx_session *s = new vbx_session();
+    s->ctx = ctx; s->fmt = h_fmt->format; s->channels = (size_t)h_fmt->channels; s->channel = (size_t)h_fmt->channel;
+    s->frame_len = frame_len; s->stride = stride; s->max_block = max_block;
+    s->p = *h_p;
+    if (h_ext) { s->ext = *h_ext; s->have_ext = true; }
+    if (h_track) { s->track = *h_track; s->have_track = true; }
+    s->rec = vbx_record_doubles_ex(h_p, h_ext);
+    s->ld_c = s->rec + (s->rec & 1);
+    s->nmax = nmax;
+    const size_t cap = session_carry_samples(frame_len, stride, max_block), ob = sample_out_bytes(s->fmt);
+    const size_t kmax = h_track ? h_track->kmax : 0;
+    const size_t raw_bytes = max_block * s->channels * sample_src_bytes(s->fmt);
+    const size_t stage_bytes = raw_bytes < (size_t)VBX_SESSION_STAGE_BYTES ? raw_bytes : (size_t)VBX_SESSION_STAGE_BYTES;
+#define SESSION_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { hipStreamSynchronize(ctx->stream); session_free(s); \
+        return fail(ctx, VBX_E_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
+    for (int i = 0; i < 2; i++) {
+        SESSION_HIP(hipMalloc(&s->carry[i], cap * ob));                     // (hipMalloc: 256-byte aligned bases)
+        SESSION_HIP(hipMemsetAsync(s->carry[i], 0, cap * ob, ctx->stream));
+        SESSION_HIP(hipMalloc(&s->raw[i], raw_bytes));
+        SESSION_HIP(hipEventCreateWithFlags(&s->ready[i], hipEventDisableTiming));
+        SESSION_HIP(hipEventCreateWithFlags(&s->freed[i], hipEventDisableTiming));
+        SESSION_HIP(hipHostMalloc(&s->stage[i], stage_bytes, hipHostMallocDefault));
+        SESSION_HIP(hipEventCreateWithFlags(&s->staged[i], hipEventDisableTiming));
+    }
+    s->stage_bytes = stage_bytes;
+    SESSION_HIP(hipMalloc((void **)&s->c_rec, nmax * s->ld_c * sizeof(double)));
+    SESSION_HIP(hipMalloc((void **)&s->c_st, 3 * nmax * sizeof(int32_t)));
+    if (h_track) {
+        SESSION_HIP(hipMalloc((void **)&s->c_cand, nmax * kmax * sizeof(vbx_pitch)));
+        SESSION_HIP(hipMalloc((void **)&s->c_count, nmax * sizeof(int32_t)));
+        SESSION_HIP(hipMalloc((void **)&s->c_peak, nmax * sizeof(double)));
+    }
+    SESSION_HIP(hipMalloc((void **)&s->state, 2 * VBX_FORMANT_SLOTS * sizeof(double)));
+    SESSION_HIP(hipMemsetAsync(s->state, 0, 2 * VBX_FORMANT_SLOTS * sizeof(double), ctx->stream));
+#undef SESSION_HIP
+    // the largest shape a push can ask for, on the zeroed carry: the context's workspaces and tables are as large as they will ever
+    // have to be, and what only the frame loop's parts know is rejected here
+    rc = session_analyze(s, __func__, nmax, true);
+    if (rc == VBX_SUCCESS) rc = check_launch(ctx, __func__);
+    ctx->last_track.res = nullptr;                        // the chunk-local rows are no track of the caller's
+    ctx->last_track.n_est = 0;
+    if (rc != VBX_SUCCESS) { const std::string why = ctx->last_error; hipStreamSynchronize(ctx->stream); vbx_sync(ctx); session_free(s); return fail(ctx, rc, why); }
+    *out = s;
+    return VBX_SUCCESS;
+}
+
+static int session_push_impl(vbx_session *s, const char *fn, const void *block, bool on_device, size_t n, double *out_records,
+                             size_t record_ld, int32_t *status3, size_t status_ld, const vbx_pitch_track_outputs *h_out, size_t *h_n) {
+    if (!s) return fail(nullptr, VBX_E_INVALID, std::string(fn) + ": null session");
+    vbx_ctx *ctx = s->ctx;
+    if (h_n) *h_n = 0;
+    if (n == 0) return VBX_SUCCESS;
+    VBX_REQUIRE_FN(ctx, fn, block != nullptr, "null block");
+    VBX_REQUIRE_FN(ctx, fn, n <= s->max_block, "the block is larger than the session's max_block_sample_frames");
+    VBX_REQUIRE_FN(ctx, fn, !on_device || s->fmt == VBX_SAMPLE_PCM24 || (uintptr_t)block % sample_src_bytes(s->fmt) == 0, "the block needs its type's alignment");
+    vbx_session_plan_t pl{};
+    if (vbx_session_plan(s->consumed, s->utt_frame, n, s->frame_len, s->stride, &pl) != VBX_SUCCESS)
+        return fail(ctx, VBX_E_INVALID, std::string(fn) + ": bad session plan");
+    const size_t nf = pl.hi - pl.lo;
+    bool want_peak = false;
+    if (nf) {
+        VBX_REQUIRE_FN(ctx, fn, out_records != nullptr, "null argument");
+        VBX_REQUIRE_FN(ctx, fn, ((uintptr_t)out_records & 15) == 0, "records must be 16-byte aligned");
+        VBX_REQUIRE_FN(ctx, fn, record_ld >= s->rec && record_ld % 2 == 0, "record_ld must be even and >= vbx_record_doubles(params)");
+        VBX_REQUIRE_FN(ctx, fn, status3 == nullptr || status_ld >= nf, "status_ld must be >= the frames the push delivers");
+        if (s->have_track) {
+            VBX_REQUIRE_FN(ctx, fn, h_out != nullptr && h_out->cand != nullptr && h_out->count != nullptr, "the tracked form needs h_outputs->cand and ->count");
+            VBX_REQUIRE_FN(ctx, fn, s->track.path.silence_threshold == 0.0 || h_out->peak != nullptr, "a silence_threshold needs h_outputs->peak");
+            VBX_REQUIRE_FN(ctx, fn, h_out->index == nullptr, "h_outputs->index must be NULL: the caller runs the path (vbx_pitch_path_f64)");
+            want_peak = h_out->peak != nullptr;
+        }
+    }
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t sf_bytes = s->channels * sample_src_bytes(s->fmt);
+    const void *raw = block;
+    int slot = -1;
+    bool wait_ready = false;
+    if (!on_device) {                                     // the block into raw slot `slot`
+        slot = (int)(s->uploads & 1);
+        const size_t bytes = n * sf_bytes;
+        if (bytes <= s->stage_bytes) {
+            // through pinned staging, on the context's stream: behind the slot's last reader by stream order; the caller's block has
+            // been read when the host copy returns (the staging buffer's previous upload, two pushes ago, has long left it)
+            VBX_HIP(ctx, hipEventSynchronize(s->staged[slot]));
+            std::memcpy(s->stage[slot], block, bytes);
+            VBX_HIP(ctx, hipMemcpyAsync(s->raw[slot], s->stage[slot], bytes, hipMemcpyHostToDevice, ctx->stream));
+            VBX_HIP(ctx, hipEventRecord(s->staged[slot], ctx->stream));
+        } else {                                          // on the copy stream, behind the slot's last reader
+            VBX_HIP(ctx, hipStreamWaitEvent(ctx->copy, s->freed[slot], 0));
+            VBX_HIP(ctx, hipMemcpyAsync(s->raw[slot], block, bytes, hipMemcpyHostToDevice, ctx->copy));
+            VBX_HIP(ctx, hipEventRecord(s->ready[slot], ctx->copy));
+            VBX_HIP(ctx, hipStreamWaitEvent(ctx->stream, s->ready[slot], 0));
+            wait_ready = true;
+        }
+        raw = s->raw[slot];
+        s->uploads++;
+    }
+    // the other carry buffer: from sample frame nb on -- what this push's analysis reads first, or, when it completes no frame, what
+    // a later one may.  (stride > frame_len: nb may lie beyond the carried samples, inside the block; the gap's samples are dropped)
+    const size_t c = s->consumed, nb = nf ? pl.read_from : pl.keep_from;
+    const size_t from_old = nb < c ? nb : c, skip = nb > c ? nb - c : 0;
+    { Prof p(ctx, k_ingest_names[s->fmt]);
+      launch_session_ingest(ctx->stream, s->fmt, s->carry[s->cur], from_old - s->base, c - from_old,
+                            static_cast<const char *>(raw) + skip * sf_bytes, n - skip, s->channels, s->channel, s->carry[s->cur ^ 1]); }
+    if (slot >= 0) VBX_HIP(ctx, hipEventRecord(s->freed[slot], ctx->stream));
+    s->cur ^= 1; s->base = nb; s->consumed = c + n; s->keep_from = pl.keep_from;
+    auto bail = [&](int code) { if (wait_ready) hipEventSynchronize(s->ready[slot]); return code; };      // the block is not read after the call returns
+    if (nf) {
+        const size_t n_an = pl.warm + nf;
+        int rc = session_analyze(s, fn, n_an, want_peak);
+        if (rc != VBX_SUCCESS) return bail(rc);
+        // the push continues an utterance: the tracker goes on from the true state, the formant row of the last frame delivered
+        if (pl.continues_prev && s->p.formant_order) {
+            rc = vbx_internal_track_stitch(ctx, nullptr, reinterpret_cast<vbx_resonance *>(s->c_rec + 2), n_an, s->ld_c, pl.warm, n_an, s->state, nullptr);
+            if (rc != VBX_SUCCESS) return bail(rc);
+        }
+        session_deliver_t d{};
+        d.src = s->c_rec; d.src_ld = s->ld_c; d.row0 = pl.warm; d.rows = nf; d.c0 = s->have_track ? 2 : 0; d.c1 = s->rec;
+        d.dst = out_records; d.dst_ld = record_ld;
+        d.src_st = s->c_st; d.src_n = n_an; d.dst_st = status3; d.dst_st_ld = status_ld;
+        if (s->have_track) {
+            d.src_cand = reinterpret_cast<const double *>(s->c_cand); d.dst_cand = reinterpret_cast<double *>(h_out->cand); d.kmax = s->track.kmax;
+            d.src_count = s->c_count; d.dst_count = h_out->count;
+            if (want_peak) { d.src_peak = s->c_peak; d.dst_peak = h_out->peak; }
+        }
+        if (s->p.formant_order) { d.state = s->state; d.n_state = 2 * s->p.n_est; }
+        { Prof p(ctx, "session_deliver"); launch_session_deliver(ctx->stream, d); }
+        ctx->last_track.res = nullptr;                    // the chunk-local rows are no track of the caller's: nothing to stitch
+        ctx->last_track.n_est = 0;
+        s->frames += nf;
+    }
+    if (s->bound) {
+        // the contour: the online path over the push's own rows of the session-owned lists, behind session_deliver (a push that
+        // completes no frame still reports: n = 0 and what is pending)
+        const size_t w = nf ? pl.warm : 0;
+        int rc = path_stream_launch(s->path, fn, s->c_cand + w * s->track.kmax, s->c_count + w, s->c_st + w, want_peak ? s->c_peak + w : nullptr,
+                                    nf, 0, s->p_out, s->p_ld, s->p_index, s->p_forced, s->p_commit);
+        if (rc != VBX_SUCCESS) return bail(rc);
+    }
+    int rc = check_launch(ctx, fn);
+    if (rc != VBX_SUCCESS) return bail(rc);
+    if (h_n) *h_n = nf;
+    if (wait_ready) VBX_HIP(ctx, hipEventSynchronize(s->ready[slot]));     // the last byte of h_block has been read
+    return VBX_SUCCESS;
+}
+
+int vbx_session_push(vbx_session *s, const void *h_block, size_t n_sample_frames, double *out_records, size_t record_ld, int32_t *status3,
+                     size_t status_ld, const vbx_pitch_track_outputs *h_outputs, size_t *h_n_frames) {
+    return session_push_impl(s, __func__, h_block, false, n_sample_frames, out_records, record_ld, status3, status_ld, h_outputs, h_n_frames);
+}
+
+int vbx_session_push_device(vbx_session *s, const void *d_block, size_t n_sample_frames, double *out_records, size_t record_ld,
+                            int32_t *status3, size_t status_ld, const vbx_pitch_track_outputs *h_outputs, size_t *h_n_frames) {
+    return session_push_impl(s, __func__, d_block, true, n_sample_frames, out_records, record_ld, status3, status_ld, h_outputs, h_n_frames);
+}
+
+int vbx_session_mark_utterance(vbx_session *s) {
+    if (!s) return fail(nullptr, VBX_E_INVALID, "vbx_session_mark_utterance: null session");
+    s->utt_frame = vbx_frame_count(s->consumed, s->frame_len, s->stride);
+    if (s->bound) {                                       // the rest of the contour now, not when the next frame arrives
+        VBX_HIP(s->ctx, hipSetDevice(s->ctx->device));
+        return path_stream_launch(s->path, __func__, nullptr, nullptr, nullptr, nullptr, 0, 1, s->p_out, s->p_ld, s->p_index, s->p_forced,
+                                  s->p_commit);
+    }
+    return VBX_SUCCESS;
+}
+
+int vbx_session_path_bind(vbx_session *s, double peak_ref, size_t max_pending, vbx_pitch *out_path, size_t path_ld, int32_t *out_index,
+                          uint8_t *out_forced, vbx_path_commit *d_commit) {
+    if (!s) return fail(nullptr, VBX_E_INVALID, "vbx_session_path_bind: null session");
+    vbx_ctx *ctx = s->ctx;
+    VBX_REQUIRE(ctx, s->have_track, "the session was opened without h_track: it has no candidate lists");
+    VBX_REQUIRE(ctx, out_path != nullptr && d_commit != nullptr, "null out_path or d_commit");
+    VBX_REQUIRE(ctx, path_ld >= 2, "path_ld must be >= 2");
+    if (s->bound) {                                       // between pushes: other destinations, the same path
+        VBX_REQUIRE(ctx, max_pending == s->path->max_pending && std::memcmp(&peak_ref, &s->path->peak_ref, sizeof(double)) == 0,
+                    "a bound session keeps its peak_ref and max_pending (vbx_session_reset drops the binding)");
+    } else {
+        VBX_REQUIRE(ctx, s->consumed == 0, "bind before the first push or after vbx_session_reset");
+        vbx_pitch_path_params path = s->track.path;
+        if (path.time_step == 0.0) path.time_step = (double)s->stride / s->p.sample_rate;
+        // the path of before a reset (its state was reset with the session) serves again when nothing about it changes
+        const bool same = s->path != nullptr && s->path->max_pending == max_pending && std::memcmp(&peak_ref, &s->path->peak_ref, sizeof(double)) == 0;
+        if (!same) {
+            vbx_path_stream *ps = nullptr;
+            int rc = path_stream_open(ctx, __func__, s->track.kmax, path, peak_ref, max_pending, &ps);
+            if (rc != VBX_SUCCESS) return rc;
+            if (s->path) path_stream_free(s->path);
+            s->path = ps;
+        }
+        s->bound = true;
+    }
+    s->p_out = out_path; s->p_ld = path_ld; s->p_index = out_index; s->p_forced = out_forced; s->p_commit = d_commit;
+    return VBX_SUCCESS;
+}
+
+int vbx_session_reset(vbx_session *s) {
+    if (!s) return fail(nullptr, VBX_E_INVALID, "vbx_session_reset: null session");
+    // (nothing is queued: the next ingest keeps nothing of the carry, and a first push of an utterance stitches from no state)
+    s->consumed = 0; s->utt_frame = 0; s->frames = 0; s->base = 0; s->keep_from = 0;
+    if (s->path) {                                        // the path's state goes, and the binding with it
+        s->bound = false;
+        return path_stream_reset(s->path);
+    }
+    return VBX_SUCCESS;
+}
+
+int vbx_session_info(const vbx_session *s, size_t *h_consumed, size_t *h_frames, size_t *h_carried) {
+    if (!s) return fail(nullptr, VBX_E_INVALID, "vbx_session_info: null session");
+    if (h_consumed) *h_consumed = s->consumed;
+    if (h_frames) *h_frames = s->frames;
+    if (h_carried) *h_carried = s->consumed - s->keep_from;
+    return VBX_SUCCESS;
+}
+
+void vbx_session_close(vbx_session *s) {
+    if (!s) return;
+    hipSetDevice(s->ctx->device);
+    hipStreamSynchronize(s->ctx->stream);                 // the session's buffers may still be read by queued work
+    if (s->ctx->side) hipStreamSynchronize(s->ctx->side);
+    if (s->ctx->trk) hipStreamSynchronize(s->ctx->trk);
+    if (s->ctx->copy) hipStreamSynchronize(s->ctx->copy);
+    session_free(s);
+}
+
+// test hook (tests/test_gpu_session_ingest.py): the ingest kernel on its own, on the context's stream
+int vbx_internal_session_ingest(vbx_ctx *ctx, int format, int channels, int channel, const void *d_old, size_t drop, size_t keep,
+                                const void *d_raw, size_t n_new, void *d_out) {
+    VBX_REQUIRE(ctx, ctx != nullptr, "null context");
+    VBX_REQUIRE(ctx, sample_format_ok(format), "unknown sample format");
+    VBX_REQUIRE(ctx, channels >= 1 && channel >= 0 && channel < channels, "need channels >= 1 and 0 <= channel < channels");
+    if (keep + n_new == 0) return VBX_SUCCESS;
+    VBX_REQUIRE(ctx, d_out && (keep == 0 || d_old) && (n_new == 0 || d_raw), "null argument");
+    VBX_REQUIRE(ctx, format == VBX_SAMPLE_PCM24 || (uintptr_t)d_raw % sample_src_bytes(format) == 0, "the source needs its type's alignment");
+    VBX_REQUIRE(ctx, (uintptr_t)d_out % sample_out_bytes(format) == 0 && (uintptr_t)d_old % sample_out_bytes(format) == 0,
+                "the carry buffers need their type's alignment");
+    VBX_HIP(ctx, hipSetDevice(ctx->device));
+    { Prof p(ctx, k_ingest_names[format]);
+      launch_session_ingest(ctx->stream, format, d_old, drop, keep, d_raw, n_new, (size_t)channels, (size_t)channel, d_out); }
+    return check_launch(ctx, __func__);
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// vbx_table_cache.hpp -- every host-built device table of a context (vbx_api.hip) in one cache.  A key is the table's kind and its
+// vbx_table_cache.hpp -- every host-built device table of a context (vbx_ctx.hpp) in one cache.  A key is the table's kind and its
 // parameters; an entry is ONE device allocation with the byte offsets of its sub-tables; one miss path sizes, builds on the host,
 // allocates, uploads and inserts, and leaves nothing behind when a step fails.  The builders are plain host functions: vbx_host.cpp,
 // or beside their kernels (spectral_fill_tab, mfcc_interp_fill, mfcc_czt_fill_tabs).
