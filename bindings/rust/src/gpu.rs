@@ -331,6 +331,31 @@ impl Gpu {
         Ok(Session { gpu: self, raw, format, sample_frame_bytes, frame_len, stride, record_ld: rec + (rec & 1), kmax: tk.map(|t| t.kmax) })
     }
 
+    /// ONE live session for several channels of a stream (`vbx_session_open_channels`): a stereo interface, a microphone array.
+    /// `select` holds distinct channels in any order (at most `VBX_HOST_MAX_CHANNELS`); every [`SessionChannels::push`] uploads the
+    /// block once and runs one frame-loop call over all of them, and entry `k` of what it returns is, bit for bit, what a
+    /// one-channel [`Session`] on channel `select[k]` returns for the same block.  One parameter set and one list of marks for all.
+    #[allow(clippy::too_many_arguments)]
+    pub fn session_channels(&self, format: i32, channels: usize, select: &[i32], frame_len: usize, stride: usize, params: &AnalysisParams,
+                            ext: Option<&AnalysisExt>, track: Option<(usize, &PitchPathParams)>, max_block: usize)
+                            -> GpuResult<SessionChannels<'_>> {
+        assert!(channels >= 1 && !select.is_empty() && select.len() <= channels.min(ffi::VBX_HOST_MAX_CHANNELS), "bad selection");
+        let fmt = ffi::VbxHostAudio { format, channels: channels as i32, channel: 0, reserved: 0, chunk_frames: 0 };
+        let p = params.to_ffi();
+        let e = ext.map(|x| x.to_ffi());
+        let e_ptr = e.as_ref().map_or(ptr::null(), |x| x as *const _);
+        let tk = track.map(|(kmax, path)| ffi::VbxPitchTrackParams { kmax, path: path.raw() });
+        let rec = unsafe { ffi::vbx_record_doubles_ex(&p, e_ptr) };
+        let mut raw: *mut ffi::VbxSession = ptr::null_mut();
+        self.check(unsafe {
+            ffi::vbx_session_open_channels(self.raw, &fmt, select.as_ptr(), select.len(), frame_len, stride, &p, e_ptr,
+                                           tk.as_ref().map_or(ptr::null(), |t| t as *const _), max_block, &mut raw)
+        })?;
+        let sample_frame_bytes = channels * match format { ffi::VBX_SAMPLE_PCM16 => 2, ffi::VBX_SAMPLE_PCM24 => 3, ffi::VBX_SAMPLE_F64 => 8, _ => 4 };
+        let one = Session { gpu: self, raw, format, sample_frame_bytes, frame_len, stride, record_ld: rec + (rec & 1), kmax: tk.map(|t| t.kmax) };
+        Ok(SessionChannels { one, n_sel: select.len() })
+    }
+
     /// The pitch path committed while the candidate lists arrive (`vbx_path_stream_open`): `vbx_pitch_path_f64`'s contour over lists
     /// of `kmax` candidates per frame, pushed as they come.  Every row a push commits without a forced flag is the whole utterance's
     /// path, bit for bit, whatever follows; at most `max_pending` frames are held, and rows that have to leave undecided are flagged.
@@ -534,6 +559,95 @@ impl<'g> Session<'g> {
             ffi::vbx_session_path_bind(self.raw, peak_ref, max_pending, rows.path.as_mut_ptr(), 2, rows.index.as_mut_ptr(),
                                        rows.forced.as_mut_ptr(), rows.commit.as_mut_ptr())
         })
+    }
+}
+
+/// A live session over several channels ([`Gpu::session_channels`]); closed on drop.  `info`, `mark_utterance` (a mark applies to
+/// every channel) and `reset` are those of [`Session`], reached through [`SessionChannels::session`].
+pub struct SessionChannels<'g> {
+    one: Session<'g>,
+    n_sel: usize,
+}
+
+impl<'g> SessionChannels<'g> {
+    /// The session's handle as a [`Session`]: `info`, `mark_utterance` and `reset` work on it unchanged (its `push` does not: the
+    /// one-channel and the multi-channel calls do not mix).
+    pub fn session(&self) -> &Session<'g> {
+        &self.one
+    }
+
+    fn deliver(&self, block: *const c_void, n_sample_frames: usize, device: bool) -> GpuResult<Option<Vec<SessionRows<'g>>>> {
+        let s = &self.one;
+        let consumed = s.info()?.0;
+        let n = unsafe {
+            ffi::vbx_frame_count(consumed + n_sample_frames, s.frame_len, s.stride) - ffi::vbx_frame_count(consumed, s.frame_len, s.stride)
+        };
+        let mut rows = Vec::with_capacity(self.n_sel);
+        let mut outputs = Vec::with_capacity(self.n_sel);
+        for _ in 0..self.n_sel {
+            // (a push that completes no frame writes nothing: one element each keeps the entries valid)
+            let data = s.gpu.alloc::<f64>(n.max(1) * s.record_ld)?;
+            let status3 = s.gpu.alloc::<i32>(3 * n.max(1))?;
+            let lists = match s.kmax {
+                Some(k) => Some((s.gpu.alloc::<ffi::VbxPitch>(n.max(1) * k)?, s.gpu.alloc::<i32>(n.max(1))?, s.gpu.alloc::<f64>(n.max(1))?)),
+                None => None,
+            };
+            outputs.push(lists.as_ref().map(|(c, k, p)| ffi::VbxPitchTrackOutputs {
+                cand: c.as_mut_ptr(), count: k.as_mut_ptr(), peak: p.as_mut_ptr(), index: ptr::null_mut(),
+            }));
+            rows.push(SessionRows { records: Records { data, status3, n_frames: n, record_ld: s.record_ld }, lists });
+        }
+        // (`outputs` is complete before its entries' addresses are taken: it does not move again)
+        let entries: Vec<ffi::VbxChannelOutputs> = rows.iter().zip(outputs.iter())
+            .map(|(r, o)| ffi::VbxChannelOutputs {
+                records: r.records.data.as_mut_ptr(), status3: r.records.status3.as_mut_ptr(),
+                outputs: o.as_ref().map_or(ptr::null(), |x| x as *const _),
+            })
+            .collect();
+        let mut got = 0usize;
+        s.gpu.check(unsafe {
+            if device {
+                ffi::vbx_session_push_channels_device(s.raw, block, n_sample_frames, entries.as_ptr(), s.record_ld, n.max(1), &mut got)
+            } else {
+                ffi::vbx_session_push_channels(s.raw, block, n_sample_frames, entries.as_ptr(), s.record_ld, n.max(1), &mut got)
+            }
+        })?;
+        debug_assert_eq!(got, n);
+        Ok(if n == 0 { None } else { Some(rows) })
+    }
+
+    /// The next block of the stream, from host memory (`vbx_session_push_channels`): interleaved sample frames of ALL the stream's
+    /// channels in the session's format, uploaded once.  One [`SessionRows`] per selected channel; `None` when the block completes
+    /// no frame.  Returns when the block has been read; the rows are ordered on the context's stream.
+    pub fn push(&self, block: HostSamples) -> GpuResult<Option<Vec<SessionRows<'g>>>> {
+        let (format, addr, bytes) = match block {
+            HostSamples::Pcm16(a) => (ffi::VBX_SAMPLE_PCM16, a.as_ptr() as *const c_void, a.len() * 2),
+            HostSamples::Pcm24(a) => (ffi::VBX_SAMPLE_PCM24, a.as_ptr() as *const c_void, a.len()),
+            HostSamples::Pcm32(a) => (ffi::VBX_SAMPLE_PCM32, a.as_ptr() as *const c_void, a.len() * 4),
+            HostSamples::F32(a) => (ffi::VBX_SAMPLE_F32, a.as_ptr() as *const c_void, a.len() * 4),
+            HostSamples::F64(a) => (ffi::VBX_SAMPLE_F64, a.as_ptr() as *const c_void, a.len() * 8),
+        };
+        assert!(format == self.one.format, "the block is not in the session's format");
+        self.deliver(addr, bytes / self.one.sample_frame_bytes, false)
+    }
+
+    /// Every channel's contour from this tracked session (`vbx_session_path_bind_channels`): each push also commits the decided
+    /// rows of channel `select[k]`'s pitch path into `rows[k]` from row 0, all channels in one launch; `mark_utterance` then delivers
+    /// the rest of every channel's utterance at once.  One [`PathRows`] per selected channel; they must outlive the pushes.
+    pub fn bind_path(&self, peak_ref: f64, max_pending: usize, rows: &[PathRows<'g>]) -> GpuResult<()> {
+        assert!(rows.len() == self.n_sel, "one PathRows per selected channel");
+        let entries: Vec<ffi::VbxChannelPathOutputs> = rows.iter()
+            .map(|r| ffi::VbxChannelPathOutputs {
+                out_path: r.path.as_mut_ptr(), out_index: r.index.as_mut_ptr(), out_forced: r.forced.as_mut_ptr(), d_commit: r.commit.as_mut_ptr(),
+            })
+            .collect();
+        self.one.gpu.check(unsafe { ffi::vbx_session_path_bind_channels(self.one.raw, peak_ref, max_pending, entries.as_ptr(), 2) })
+    }
+
+    /// The same for a block in device memory (`vbx_session_push_channels_device`), read in stream order with no staging.
+    pub fn push_device<S: Copy>(&self, block: &DeviceBuf<S>, n_sample_frames: usize) -> GpuResult<Option<Vec<SessionRows<'g>>>> {
+        assert!(block.len() * std::mem::size_of::<S>() >= n_sample_frames * self.one.sample_frame_bytes, "block too small");
+        self.deliver(block.as_ptr() as *const c_void, n_sample_frames, true)
     }
 }
 
@@ -1788,6 +1902,21 @@ pub fn host_chunk_plan(n_frames: usize, chunk_frames: usize, c: usize, frame_len
         return Err(GpuError { code: rc, message: last_error(ptr::null()) });
     }
     Ok((plan, s0, s1))
+}
+
+/// [`session_plan`] for one push of a multi-channel session plus the layout of the planes its one frame-loop call runs over, and
+/// that call's segment list `[0, Q, 2Q, ...]` (`vbx_session_channels_plan`; host arithmetic only).  `elem_bytes`: 2 for PCM16, 4
+/// for F32, 8 for PCM24 / PCM32 / F64.
+#[allow(clippy::too_many_arguments)]
+pub fn session_channels_plan(consumed: usize, utt_frame: usize, n_new: usize, frame_len: usize, stride: usize, elem_bytes: usize,
+                             n_sel: usize) -> GpuResult<(ffi::VbxSessionChannelsPlan, Vec<i64>)> {
+    let mut plan = ffi::VbxSessionChannelsPlan::default();
+    let mut seg = vec![0i64; n_sel.clamp(1, ffi::VBX_HOST_MAX_CHANNELS)];
+    let rc = unsafe { ffi::vbx_session_channels_plan(consumed, utt_frame, n_new, frame_len, stride, elem_bytes, n_sel, &mut plan, seg.as_mut_ptr()) };
+    if rc != ffi::VBX_SUCCESS {
+        return Err(GpuError { code: rc, message: last_error(ptr::null()) });
+    }
+    Ok((plan, seg))
 }
 
 /// What a push of `n_new` sample frames does to a live session that has consumed `consumed` sample frames and whose current

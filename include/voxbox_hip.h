@@ -985,6 +985,91 @@ void vbx_path_stream_close(vbx_path_stream *ps);
 int vbx_session_path_bind(vbx_session *s, double peak_ref, size_t max_pending,
                           vbx_pitch *out_path, size_t path_ld, int32_t *out_index, uint8_t *out_forced, vbx_path_commit *d_commit);
 
+/* ------------------------------------------------------------------ live sessions over several channels (ABI 5, added) */
+
+/* Every selected channel of live audio -- a stereo interface, a microphone array, the channels of one decoder -- from ONE session and
+ * ONE frame-loop call per push.  vbx_session_open_channels opens a session for n_sel channels of one stream of interleaved sample
+ * frames: h_fmt as for vbx_session_open with h_fmt->channel == 0 (chunk_frames and reserved must be 0); h_channels / n_sel follow
+ * vbx_unpack_channels (HOST memory, distinct values in [0, channels), any order, 1 <= n_sel <= min(channels, VBX_HOST_MAX_CHANNELS)).
+ * All channels share one parameter set, one cut into blocks and one list of utterance marks.  Open allocates and warms the largest
+ * shape, as vbx_session_open does; no push allocates or drains a stream.
+ * vbx_session_push_channels (h_block in HOST memory) / vbx_session_push_channels_device (d_block in device memory, read in stream
+ * order): h_out holds n_sel entries (a HOST array, read before the call returns); entry k receives rows [0, n) of this push for
+ * channel h_channels[k], n = hi - lo of vbx_session_plan: records (device, 16-byte aligned, rows record_ld doubles apart), status3
+ * (optional; row j of the three status rows at status3 + j * status_ld) and, in the tracked form, outputs with cand and count, peak
+ * when silence_threshold != 0, index NULL.  *h_n_frames = n (optional).  Stricter than vbx_session_push in one point: h_out itself
+ * must be non-NULL for every push of n_sample_frames > 0, also for one that completes no frame (its entries are then not read).
+ * Contract: for every k, the rows all pushes wrote through h_out[k], concatenated, equal bit for bit what a one-channel session
+ * opened with h_fmt->channel = h_channels[k] writes when it is pushed the same blocks -- by that session's contract the resident call
+ * on the whole channel (vbx_analyze_frames_ex_pcm16 / _f32in / _f64 on the vbx_unpack_samples output, marks as h_seg_start) -- for
+ * every way of cutting the stream into blocks, every format, the plain, tracked and ext forms, every LPC policy, pinned and pageable
+ * blocks and the device form (tests/test_gpu_session_channels.py).  A NaN or Inf in one channel touches no other channel's rows.
+ * How.  The block is uploaded ONCE (the two routes of vbx_session_push: pinned staging on the context's stream up to 128 KiB, the
+ * copy stream with ready / freed events above).  Then, whatever n_sel: ONE session_ingest_all_<fmt> launch writes the other carry
+ * buffer -- n_sel planes, plane k = the kept tail of the old plane k and channel h_channels[k] of the block as the frame loop's type
+ * (the block is read from memory once: tiles of whole sample frames through LDS, 16-byte stores into every plane; per-element code with
+ * the same bits for a source off a dword boundary, sample frames too wide for a tile, the group where tail and block meet and the
+ * ragged end); ONE frame-loop call over all planes as one recording with the segment list [0, Q, 2Q, ...] (vbx_session_channels_plan:
+ * plane k starts at element k * Q * stride, Q rounded up so that every plane base is a multiple of 256 bytes; channel k's frames are
+ * [kQ, kQ + m), m = warm + n; the frames [kQ + m, (k + 1)Q) read stale or zeroed samples -- the carry is zeroed at open -- lie
+ * BEHIND channel k's own frames in channel k's segment, so the causal tracker cannot let them reach a delivered row, and are never
+ * delivered); ONE batched tracker stitch (a block per channel, each from its own state row: vbx_track_stitch_f64's repair); ONE
+ * session_deliver_all launch that copies every channel's own rows to its destinations (kernel arguments) and its last formant row
+ * into its state.  Launches per push do not depend on n_sel.
+ * vbx_session_mark_utterance (a mark applies to every channel), vbx_session_reset, vbx_session_info and vbx_session_close work on
+ * such a session unchanged.  The one-channel and the multi-channel calls do not mix: vbx_session_push, vbx_session_push_device and
+ * vbx_session_path_bind on a session opened here, and the _channels calls (vbx_session_path_bind_channels included) on a
+ * one-channel session, return VBX_E_INVALID with nothing queued.  n_sel == 1 is allowed and equals the one-channel session.  Device memory: n_sel carry planes (twice) and n_sel
+ * times the chunk-local buffers of vbx_session_open.
+ * VBX_E_INVALID, before anything is queued and with the session left usable: everything the one-channel calls reject; a bad selection;
+ * h_fmt->channel != 0; a NULL h_out; an entry with NULL or misaligned records; two entries whose [n, record_ld] ranges overlap; more
+ * than 0x7fffffff frames in the largest frame-loop call.
+ * vbx_session_channels_plan: pure host arithmetic, no GPU -- vbx_session_plan for the push (every channel shares it) and the plane
+ * layout for samples of elem_bytes bytes (2: PCM16, 4: F32, 8: PCM24 / PCM32 / F64); h_seg_start (optional, n_sel entries) receives
+ * the segment list. */
+typedef struct {
+    vbx_session_plan_t push;  /* what vbx_session_plan gives for (consumed, utt_frame, n_new) */
+    size_t frames;            /* m: frames analysed per channel, warm + (hi - lo); 0 when the push completes no frame */
+    size_t base;              /* first sample frame a plane holds after the push: read_from, or keep_from when hi == lo */
+    size_t keep;              /* elements of a plane that come from the old plane: consumed - base, or 0 */
+    size_t len;               /* elements of a plane the ingest writes: consumed + n_new - base */
+    size_t plane_frames;      /* Q: the plane pitch in frames */
+    size_t plane_ld;          /* Q * stride: plane k starts at element k * plane_ld (a multiple of 256 bytes) */
+    size_t call_frames;       /* frames of the one frame-loop call: (n_sel - 1) * Q + m; 0 when m == 0 */
+    size_t capacity;          /* elements of a plane the call may read: nothing is read beyond n_sel * capacity */
+} vbx_session_channels_plan_t;
+int vbx_session_channels_plan(size_t consumed, size_t utt_frame, size_t n_new, size_t frame_len, size_t stride, size_t elem_bytes,
+                              size_t n_sel, vbx_session_channels_plan_t *h_out, int64_t *h_seg_start);
+
+int vbx_session_open_channels(vbx_ctx *ctx, const vbx_host_audio *h_fmt /* channel, chunk_frames and reserved must be 0 */,
+                              const int32_t *h_channels, size_t n_sel, size_t frame_len, size_t stride,
+                              const vbx_analysis_params *h_params, const vbx_analysis_ext *h_ext, const vbx_pitch_track_params *h_track,
+                              size_t max_block_sample_frames, vbx_session **out);
+int vbx_session_push_channels(vbx_session *s, const void *h_block, size_t n_sample_frames,
+                              const vbx_channel_outputs *h_out /* n_sel entries */, size_t record_ld, size_t status_ld,
+                              size_t *h_n_frames);
+int vbx_session_push_channels_device(vbx_session *s, const void *d_block, size_t n_sample_frames,
+                                     const vbx_channel_outputs *h_out /* n_sel entries */, size_t record_ld, size_t status_ld,
+                                     size_t *h_n_frames);
+/* vbx_session_path_bind for a multi-channel session: every channel gets its own online path (its own state and ring of max_pending
+ * frames, one peak_ref and max_pending for all), and every push of the bound session runs ONE more launch behind session_deliver_all
+ * -- pitch_path_online_all, a lane group per channel, each over its own channel's rows of the session-owned lists -- that commits
+ * channel h_channels[k]'s decided rows through h_out[k] (n_sel entries, a HOST array of device pointers: out_path and d_commit
+ * required, out_index and out_forced optional; each array holds max_pending + the frames of the largest push rows, rows path_ld
+ * doubles apart).  The rules are vbx_session_path_bind's: a session opened with h_track, before the first push or after a reset;
+ * between pushes again to change the destinations only.  vbx_session_mark_utterance on a bound session ends EVERY channel's path
+ * utterance in one launch; vbx_session_reset resets the paths and drops the binding.
+ * Contract: per channel the committed rows, indices, forced flags and commit records of every push equal those of a bound one-channel
+ * session on that channel pushed the same blocks (tests/test_gpu_session_channels_path.py). */
+typedef struct {
+    vbx_pitch *out_path;       /* device, rows path_ld doubles apart */
+    int32_t *out_index;        /* device, optional */
+    uint8_t *out_forced;       /* device, optional */
+    vbx_path_commit *d_commit; /* device */
+} vbx_channel_path_outputs;
+int vbx_session_path_bind_channels(vbx_session *s, double peak_ref, size_t max_pending,
+                                   const vbx_channel_path_outputs *h_out /* n_sel entries */, size_t path_ld);
+
 /* ------------------------------------------------------------------ multi-GPU: frame-range sharding */
 
 /* The reference has no distribution of any kind; frames are independent (the tracker per utterance), so a long

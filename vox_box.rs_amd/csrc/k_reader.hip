@@ -83,21 +83,6 @@ __global__ __launch_bounds__(256) void unpack_pcm24_tiled_kernel(const uint32_t 
 // eight puts all 32 lanes on one bank (32 dwords apart).  The bits are the same, and the measured rates do not show the difference: one
 // channel of two or of eight runs at 0.62-0.66 of the HBM roof in every format.
 // 8 KiB tiles: eight blocks per CU keep 64 KiB of loads in flight and use 8 x (8208 + 256) B = 66 of the 160 KiB of LDS.
-#define UNPACK_ALL_TILE_BYTES 8192
-static_assert(UNPACK_ALL_TILE_BYTES / 16 <= 2 * 256, "the staging loop is two 16-byte loads per lane");
-
-// the sample at byte b of the tile (b is a multiple of B: the tile starts on a sample frame)
-template <int FMT>
-__device__ __forceinline__ typename reader_t<FMT>::out_t lds_one(const uint32_t *tile, unsigned b) {
-    if constexpr (FMT == UNPACK_PCM16) return (uint16_t)(tile[b >> 2] >> ((b & 2) * 8));      // (a dword read: lanes on the two halves of one dword broadcast)
-    else if constexpr (FMT == UNPACK_PCM24) {                // three bytes at any byte offset: out of the two dwords that hold them
-        const uint64_t w = (uint64_t)tile[b >> 2] | ((uint64_t)tile[(b >> 2) + 1] << 32);
-        return pcm24_value(sext24((uint32_t)(w >> ((b & 3) * 8))));
-    } else if constexpr (FMT == UNPACK_PCM32) return pcm32_value((int)tile[b >> 2]);
-    else if constexpr (FMT == UNPACK_F32) return tile[b >> 2];
-    else return reinterpret_cast<const uint64_t *>(tile)[b >> 3];
-}
-
 // n_tiles whole tiles of T sample frames; src on a dword boundary at least, out 16-byte aligned, plane_ld a multiple of G
 template <int FMT>
 __global__ __launch_bounds__(256) void unpack_all_tiled_kernel(const unsigned char *__restrict__ src, size_t n_tiles, unsigned T, unsigned channels,
@@ -113,17 +98,7 @@ __global__ __launch_bounds__(256) void unpack_all_tiled_kernel(const unsigned ch
     const bool wide = (reinterpret_cast<uintptr_t>(src) & 15) == 0;             // kernel-uniform; tile_bytes is a multiple of 16
     for (size_t k = blockIdx.x; k < n_tiles; k += gridDim.x) {                  // (block-uniform trip count: the barriers are safe)
         const unsigned char *w = src + k * tile_bytes;
-        if (wide) {                                                             // at most 512 words of 16 bytes: both loads of a lane in flight
-            const uint4 *w4 = reinterpret_cast<const uint4 *>(w);
-            uint4 *tile4 = reinterpret_cast<uint4 *>(tile);
-            const unsigned n16 = tile_bytes / 16;
-            const bool two = t + 256 < n16;
-            uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0;
-            if (t < n16) q0 = w4[t];
-            if (two) q1 = w4[t + 256];
-            if (t < n16) tile4[t] = q0;
-            if (two) tile4[t + 256] = q1;
-        } else for (unsigned i = t; i < tile_bytes / 4; i += 256) tile[i] = reinterpret_cast<const uint32_t *>(w)[i];
+        lds_stage_tile(tile, w, tile_bytes, wide, t);
         __syncthreads();
         for (unsigned it = t; it < items; it += 256) {
             const unsigned gl = it / n_sel, p = it - gl * n_sel;                // lane group gl of plane p

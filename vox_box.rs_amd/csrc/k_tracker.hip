@@ -628,6 +628,28 @@ __global__ __launch_bounds__(64) void tracker_stitch_kernel(const trk_in_t in, l
     if (changed != nullptr) *changed = n;
 }
 
+// tracker_stitch_kernel for every channel of a multi-channel session in ONE launch: block k repairs rows
+// [k * plane_frames + first, k * plane_frames + stop) of channel k's own segment from its own state row (first >= 1: the push
+// continues an utterance, so at least one warm-up frame precedes it inside the plane).  One lane per block, as there.
+template <int NE>
+__global__ __launch_bounds__(64) void tracker_stitch_all_kernel(const trk_in_t in, long plane_frames, long first, long stop,
+                                                                const double *__restrict__ state) {
+    if (threadIdx.x != 0) return;
+    const long base = (long)blockIdx.x * plane_frames;
+    const double *state_in = state + (long)blockIdx.x * 2 * NS;
+    double ef[NS], eb[NS];
+#pragma unroll
+    for (int e = 0; e < NS; e++) { ef[e] = 0.0; eb[e] = 0.0; }
+#pragma unroll
+    for (int e = 0; e < NE; e++) { ef[e] = state_in[2 * e]; eb[e] = state_in[2 * e + 1]; }
+    if (first > 0 && trk_row_is<NE>(in, base + first - 1, ef, eb)) return;
+    for (long f = base + first; f < base + stop; f++) {
+        trk_frame<NE>(in, f, ef, eb);
+        if (trk_row_is<NE>(in, f, ef, eb)) break;              // met the rows already there: the rest follows from them
+        trk_store_row<NE>(in, f, ef, eb);
+    }
+}
+
 // VBX_TRACKER_GENERAL=1 (read per launch): the general step on every frame instead of the index form
 static int tracker_general() { const char *e = getenv("VBX_TRACKER_GENERAL"); return (e && atoi(e) != 0) ? 1 : 0; }
 
@@ -679,6 +701,22 @@ void launch_tracker_stitch(hipStream_t s, const res_t *res, long F, int n_res, c
                            const double *state_in, int32_t *changed) {
     trk_in_t in{res, F, n_res, res_count, nullptr, 1, nullptr, frame_status, reinterpret_cast<double *>(out), out_ld, tracker_general()};
 #define VBX_TRK_ST(NE) hipLaunchKernelGGL(tracker_stitch_kernel<NE>, dim3(1), dim3(64), 0, s, in, first, stop, state_in, changed)
+    switch (n_est) {
+        case 1: VBX_TRK_ST(1); break;
+        case 2: VBX_TRK_ST(2); break;
+        case 3: VBX_TRK_ST(3); break;
+        case 4: VBX_TRK_ST(4); break;
+        case 5: VBX_TRK_ST(5); break;
+        default: VBX_TRK_ST(6); break;
+    }
+#undef VBX_TRK_ST
+}
+
+void launch_tracker_stitch_all(hipStream_t s, const res_t *res, long F, int n_res, const int32_t *res_count, int n_est,
+                               const int32_t *frame_status, res_t *out, long out_ld, long plane_frames, long first, long stop,
+                               const double *state, long n_sel) {
+    trk_in_t in{res, F, n_res, res_count, nullptr, 1, nullptr, frame_status, reinterpret_cast<double *>(out), out_ld, tracker_general()};
+#define VBX_TRK_ST(NE) hipLaunchKernelGGL(tracker_stitch_all_kernel<NE>, dim3((unsigned)n_sel), dim3(64), 0, s, in, plane_frames, first, stop, state)
     switch (n_est) {
         case 1: VBX_TRK_ST(1); break;
         case 2: VBX_TRK_ST(2); break;

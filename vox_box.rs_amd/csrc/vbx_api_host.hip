@@ -36,6 +36,17 @@ int ensure_host_slots(vbx_ctx *ctx, size_t bytes) {
     return VBX_SUCCESS;
 }
 
+// a selection of channels: 1 <= n_sel <= min(channels, VBX_HOST_MAX_CHANNELS) distinct values in [0, channels)
+bool channel_selection_ok(const int32_t *h_channels, size_t n_sel, int channels, unpack_sel_t *sel) {
+    if (!h_channels || channels < 1 || n_sel < 1 || n_sel > (size_t)channels || n_sel > (size_t)VBX_HOST_MAX_CHANNELS) return false;
+    for (size_t k = 0; k < n_sel; k++) {
+        if (h_channels[k] < 0 || h_channels[k] >= channels) return false;
+        for (size_t j = 0; j < k; j++) if (h_channels[j] == h_channels[k]) return false;
+        sel->ch[k] = h_channels[k];
+    }
+    return true;
+}
+
 }  // namespace vbx
 
 extern "C" {
@@ -57,17 +68,6 @@ int vbx_unpack_samples(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames, 
 
 static const char *const k_unpack_all_names[6] = {"", "unpack_all_pcm16", "unpack_all_pcm24", "unpack_all_pcm32", "unpack_all_f32", "unpack_all_f64"};
 static_assert(UNPACK_MAX_SEL == VBX_HOST_MAX_CHANNELS, "the selection is a kernel argument of VBX_HOST_MAX_CHANNELS entries");
-
-// a selection of channels: 1 <= n_sel <= min(channels, VBX_HOST_MAX_CHANNELS) distinct values in [0, channels)
-static bool channel_selection_ok(const int32_t *h_channels, size_t n_sel, int channels, unpack_sel_t *sel) {
-    if (!h_channels || channels < 1 || n_sel < 1 || n_sel > (size_t)channels || n_sel > (size_t)VBX_HOST_MAX_CHANNELS) return false;
-    for (size_t k = 0; k < n_sel; k++) {
-        if (h_channels[k] < 0 || h_channels[k] >= channels) return false;
-        for (size_t j = 0; j < k; j++) if (h_channels[j] == h_channels[k]) return false;
-        sel->ch[k] = h_channels[k];
-    }
-    return true;
-}
 
 int vbx_unpack_channels(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames, int format, int channels, const int32_t *h_channels,
                         size_t n_sel, void *d_out, size_t plane_ld) {

@@ -393,6 +393,38 @@ int path_stream_launch(vbx_path_stream *ps, const char *fn, const vbx_pitch *can
     return check_launch(ctx, fn);
 }
 
+// the same launch for the n_sel streams of a bound multi-channel session (they share kmax, the parameters, peak_ref and max_pending):
+// ONE launch, block k scans rows [k * plane_frames, k * plane_frames + n) of the lists from ps[k]'s state into out[k]
+int path_stream_launch_all(vbx_path_stream *const *ps, size_t n_sel, const char *fn, const vbx_pitch *cand, const int32_t *count,
+                           const int32_t *status, const double *local_peak, size_t plane_frames, size_t n, int end_utterance,
+                           const vbx_channel_path_outputs *out, size_t path_ld) {
+    vbx_ctx *ctx = ps[0]->ctx;
+    const vbx_pitch_path_params &pr = ps[0]->pr;
+    pp_par_t P{};
+    P.cand = reinterpret_cast<const pitch_t *>(cand); P.count = count; P.status = status; P.lpk = local_peak;
+    P.F = (long)n; P.kmax = (int)ps[0]->kmax; P.use_u = (local_peak != nullptr && pr.silence_threshold != 0.0) ? 1 : 0;
+    const double corr = 0.01 / pr.time_step;                   // the host constants of the definition, in its order (pp_setup)
+    P.vt = pr.voicing_threshold; P.oc = pr.octave_cost;
+    P.cvu = pr.voiced_unvoiced_cost * corr; P.cj = pr.octave_jump_cost * corr;
+    P.Lc = std::log2(pr.ceiling_hz); P.q = pr.silence_threshold / (1.0 + pr.voicing_threshold);
+    pp_online_t O = ps[0]->O;                                  // cap and peak; the pointers are each block's own
+    O.end = end_utterance ? 1 : 0;
+    O.ld = (long)path_ld;
+    pp_online_all_t A{};
+    A.plane_frames = (long)plane_frames;
+    const char *mem0 = static_cast<const char *>(ps[0]->mem);
+    A.off_row = (size_t)(reinterpret_cast<const char *>(ps[0]->O.row) - mem0);
+    A.off_psi = (size_t)(reinterpret_cast<const char *>(ps[0]->O.psi) - mem0);
+    A.off_idx = (size_t)(reinterpret_cast<const char *>(ps[0]->O.idx) - mem0);
+    for (size_t k = 0; k < n_sel; k++) {
+        A.ch[k].mem = ps[k]->mem;
+        A.ch[k].out_path = reinterpret_cast<pitch_t *>(out[k].out_path); A.ch[k].out_index = out[k].out_index;
+        A.ch[k].out_forced = out[k].out_forced; A.ch[k].commit = reinterpret_cast<pp_commit_t *>(out[k].d_commit);
+    }
+    { Prof pf(ctx, "pitch_path_online_all"); launch_pitch_path_online_all(ctx->stream, P, ps[0]->G, O, A, (int)n_sel); }
+    return check_launch(ctx, fn);
+}
+
 int path_stream_reset(vbx_path_stream *ps) {
     VBX_HIP(ps->ctx, hipSetDevice(ps->ctx->device));
     VBX_HIP(ps->ctx, hipMemsetAsync(ps->mem, 0, sizeof(pp_online_state_t), ps->ctx->stream));

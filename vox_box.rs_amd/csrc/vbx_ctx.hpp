@@ -207,6 +207,8 @@ size_t sample_src_bytes(int f);
 sample_kind_t sample_plane_kind(int f);
 size_t sample_out_bytes(int f);
 int ensure_host_slots(vbx_ctx *ctx, size_t bytes);
+// a selection of channels (vbx_unpack_channels' rules), copied into *sel
+bool channel_selection_ok(const int32_t *h_channels, size_t n_sel, int channels, unpack_sel_t *sel);
 
 // ---- the pitch path (vbx_api_path.hip) ---------------------------------------------------------
 
@@ -220,6 +222,9 @@ int path_stream_open(vbx_ctx *ctx, const char *fn, size_t kmax, const vbx_pitch_
 int path_stream_launch(vbx_path_stream *ps, const char *fn, const vbx_pitch *cand, const int32_t *count, const int32_t *status,
                        const double *local_peak, size_t n, int end_utterance, vbx_pitch *out_path, size_t path_ld, int32_t *out_index,
                        uint8_t *out_forced, vbx_path_commit *d_commit);
+int path_stream_launch_all(vbx_path_stream *const *ps, size_t n_sel, const char *fn, const vbx_pitch *cand, const int32_t *count,
+                           const int32_t *status, const double *local_peak, size_t plane_frames, size_t n, int end_utterance,
+                           const vbx_channel_path_outputs *out, size_t path_ld);
 int path_stream_reset(vbx_path_stream *ps);
 void path_stream_free(vbx_path_stream *ps);
 

@@ -503,6 +503,40 @@ int vbx_session_plan(size_t consumed, size_t utt_frame, size_t n_new, size_t fra
     return VBX_SUCCESS;
 }
 
+// One push of a multi-channel session (vbx_session_push_channels): vbx_session_plan's arithmetic -- every channel shares it -- and
+// the layout of the n_sel planes the one frame-loop call runs over.  A plane holds what the one-channel session's carry holds after
+// the push: `len` elements from sample frame `base`.  Its pitch is a whole number of hops, plane_frames, so that frame
+// k * plane_frames + j of the call is frame j of plane k; it covers the plane's elements and is rounded up until every plane base is a
+// multiple of 256 bytes.
+int vbx_session_channels_plan(size_t consumed, size_t utt_frame, size_t n_new, size_t frame_len, size_t stride, size_t elem_bytes,
+                              size_t n_sel, vbx_session_channels_plan_t *out, int64_t *h_seg_start) {
+    if (!out) return fail(nullptr, VBX_E_INVALID, "vbx_session_channels_plan: bad argument");
+    if (!(elem_bytes == 2 || elem_bytes == 4 || elem_bytes == 8) || n_sel < 1 || n_sel > (size_t)VBX_HOST_MAX_CHANNELS)
+        return fail(nullptr, VBX_E_INVALID, "vbx_session_channels_plan: elem_bytes must be 2, 4 or 8 and n_sel in [1, 64]");
+    int rc = vbx_session_plan(consumed, utt_frame, n_new, frame_len, stride, &out->push);
+    if (rc != VBX_SUCCESS) return fail(nullptr, rc, "vbx_session_channels_plan: bad argument");
+    if (stride > ((size_t)1 << 40) || n_new > ((size_t)1 << 48) || frame_len > ((size_t)1 << 40))
+        return fail(nullptr, VBX_E_INVALID, "vbx_session_channels_plan: n_new, frame_len or stride too large");
+    const vbx_session_plan_t &p = out->push;
+    const size_t nf = p.hi - p.lo, end = consumed + n_new;
+    out->frames = nf ? p.warm + nf : 0;
+    out->base = nf ? p.read_from : p.keep_from;           // (<= end: the last frame delivered ends inside the block)
+    out->keep = out->base < consumed ? consumed - out->base : 0;
+    out->len = end - out->base;
+    size_t align = 256;                                   // plane_frames * stride * elem_bytes must be a multiple of 256
+    const size_t hop_bytes = ((stride % 256) * elem_bytes) % 256;
+    for (size_t g = 256; g >= 1; g /= 2) if (hop_bytes % g == 0) { align = 256 / g; break; }
+    size_t q = out->len / stride + (out->len % stride != 0);
+    if (q < 1) q = 1;
+    q = (q + align - 1) / align * align;
+    out->plane_frames = q;
+    out->plane_ld = q * stride;
+    out->call_frames = out->frames ? (n_sel - 1) * q + out->frames : 0;
+    out->capacity = out->plane_ld;
+    if (h_seg_start) for (size_t k = 0; k < n_sel; k++) h_seg_start[k] = (int64_t)(k * q);
+    return VBX_SUCCESS;
+}
+
 }  // extern "C"
 
 namespace vbx {

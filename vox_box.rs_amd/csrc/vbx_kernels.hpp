@@ -369,6 +369,30 @@ struct session_deliver_t {
 };
 void launch_session_deliver(hipStream_t s, const session_deliver_t &d);
 
+// k_session_channels.hip: the same two launches for EVERY selected channel of a multi-channel session (vbx_session_push_channels).
+// ingest_all: plane p of out (out_ld elements apart) = old plane p (old_ld apart) from element drop, keep elements, then channel
+// sel.ch[p] of the n_new interleaved sample frames at raw -- per plane, bit for bit, what launch_session_ingest writes.  The block is
+// read from memory once (tiles of whole sample frames through LDS); keep + n_new <= out_ld; old and out must not overlap.
+void launch_session_ingest_all(hipStream_t s, int format, const void *old, size_t old_ld, size_t drop, size_t keep, const void *raw,
+                               size_t n_new, size_t channels, const unpack_sel_t &sel, size_t n_sel, void *out, size_t out_ld);
+// deliver_all: channel k's rows [k * plane_frames + row0, ... + rows) of the chunk-local buffers into ch[k]'s arrays, and the formant
+// columns of its last row into state + k * 2 * VBX_FORMANT_SLOTS_K.  The destinations travel as kernel arguments.
+struct session_deliver_all_t {
+    const double *src; size_t src_ld, plane_frames, row0, rows, c0, c1, dst_ld;
+    const int32_t *src_st; size_t src_n, dst_st_ld;
+    const double *src_cand; size_t kmax;
+    const int32_t *src_count;
+    const double *src_peak;
+    double *state; size_t n_state;
+    struct { double *rec; int32_t *st; double *cand; int32_t *count; double *peak; } ch[UNPACK_MAX_SEL];
+};
+void launch_session_deliver_all(hipStream_t s, const session_deliver_all_t &d, size_t n_sel);
+// k_tracker.hip: launch_tracker_stitch for n_sel channels in ONE launch (a block per channel): channel k's rows
+// [k * plane_frames + first, k * plane_frames + stop) continued from state + k * 2 * VBX_FORMANT_SLOTS_K
+void launch_tracker_stitch_all(hipStream_t s, const res_t *res, long F, int n_res, const int32_t *res_count, int n_est,
+                               const int32_t *frame_status, res_t *out, long out_ld, long plane_frames, long first, long stop,
+                               const double *state, long n_sel);
+
 // k_front_ex.hip: RMS::rms of the rectangular frame (launch_rms with a null window, bit for bit) of any sample type, written at
 // out_rms + f * rms_ld; out_peak non-null: launch_frame_peak from the same read
 void launch_frame_rms(hipStream_t s, frames_t x, long F, int n, long stride, double *out_rms, long rms_ld, double *out_peak);
@@ -519,5 +543,12 @@ struct pp_online_t {
 };
 // P: cand / count / status / lpk of the push's F frames, kmax, use_u and the constants; nothing else is read (spk: O.peak)
 void launch_pitch_path_online(hipStream_t s, const pp_par_t &P, int G, const pp_online_t &O);
+// k_pitch_path_channels.hip: the same scan for the n_sel channels of a bound multi-channel session in ONE launch, a block per
+// channel.  P: the lists of channel 0's first frame (channel k's rows lie k * plane_frames rows further on), F frames per channel;
+// O: cap, end, peak and ld (its pointers are not read); ch[k]: channel k's stream allocation (pp_online_state_t, then the ring at
+// off_row / off_psi / off_idx bytes) and where its rows and its commit go.  (64 channels: UNPACK_MAX_SEL, defined above.)
+struct pp_online_ch_t { void *mem; pitch_t *out_path; int32_t *out_index; uint8_t *out_forced; pp_commit_t *commit; };
+struct pp_online_all_t { long plane_frames; size_t off_row, off_psi, off_idx; pp_online_ch_t ch[64]; };
+void launch_pitch_path_online_all(hipStream_t s, const pp_par_t &P, int G, const pp_online_t &O, const pp_online_all_t &A, int n_sel);
 
 }  // namespace vbx

@@ -43,4 +43,36 @@ __device__ __forceinline__ void read_group_wide(const unsigned char *__restrict_
     }
 }
 
+// ---- tiles of whole sample frames through LDS (k_reader.hip: unpack_all_tiled_kernel; k_session_channels.hip: the ingest) ----
+#define UNPACK_ALL_TILE_BYTES 8192
+static_assert(UNPACK_ALL_TILE_BYTES / 16 <= 2 * 256, "the staging loop is two 16-byte loads per lane");
+
+// the sample at byte b of the tile (b is a multiple of B: the tile starts on a sample frame)
+template <int FMT>
+__device__ __forceinline__ typename reader_t<FMT>::out_t lds_one(const uint32_t *tile, unsigned b) {
+    if constexpr (FMT == UNPACK_PCM16) return (uint16_t)(tile[b >> 2] >> ((b & 2) * 8));      // (a dword read: lanes on the two halves of one dword broadcast)
+    else if constexpr (FMT == UNPACK_PCM24) {                // three bytes at any byte offset: out of the two dwords that hold them
+        const uint64_t w = (uint64_t)tile[b >> 2] | ((uint64_t)tile[(b >> 2) + 1] << 32);
+        return pcm24_value(sext24((uint32_t)(w >> ((b & 3) * 8))));
+    } else if constexpr (FMT == UNPACK_PCM32) return pcm32_value((int)tile[b >> 2]);
+    else if constexpr (FMT == UNPACK_F32) return tile[b >> 2];
+    else return reinterpret_cast<const uint64_t *>(tile)[b >> 3];
+}
+
+// a block of 256 lanes (lane t) stages tile_bytes (a multiple of 16, <= UNPACK_ALL_TILE_BYTES) from w into the 16-byte aligned tile:
+// 16-byte loads where w sits on a 16-byte boundary (wide), dword loads otherwise (w on a dword boundary)
+__device__ __forceinline__ void lds_stage_tile(uint32_t *tile, const unsigned char *__restrict__ w, unsigned tile_bytes, bool wide, unsigned t) {
+    if (wide) {                                                             // at most 512 words of 16 bytes: both loads of a lane in flight
+        const uint4 *w4 = reinterpret_cast<const uint4 *>(w);
+        uint4 *tile4 = reinterpret_cast<uint4 *>(tile);
+        const unsigned n16 = tile_bytes / 16;
+        const bool two = t + 256 < n16;
+        uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0;
+        if (t < n16) q0 = w4[t];
+        if (two) q1 = w4[t + 256];
+        if (t < n16) tile4[t] = q0;
+        if (two) tile4[t + 256] = q1;
+    } else for (unsigned i = t; i < tile_bytes / 4; i += 256) tile[i] = reinterpret_cast<const uint32_t *>(w)[i];
+}
+
 }  // namespace vbx

@@ -482,6 +482,54 @@ private:
     vbx_session *s_ = nullptr;
 };
 
+// A live session over several channels (vbx_session_open_channels / vbx_session_push_channels): ONE session, one upload and one
+// frame-loop call per push for every selected channel of a stream -- a stereo interface, a microphone array.  select: n_sel distinct
+// channels in any order; out: n_sel entries (a host array), entry k the device outputs of channel select[k] for this push's rows.
+// Per channel the rows equal, bit for bit, a one-channel session's on that channel.  One parameter set and one list of marks for all.
+using SessionChannelsPlan = vbx_session_channels_plan_t;
+inline SessionChannelsPlan session_channels_plan(size_t consumed, size_t utt_frame, size_t n_new, size_t frame_len, size_t stride,
+                                                 size_t elem_bytes, size_t n_sel, int64_t *h_seg_start = nullptr) {
+    SessionChannelsPlan p{};
+    if (vbx_session_channels_plan(consumed, utt_frame, n_new, frame_len, stride, elem_bytes, n_sel, &p, h_seg_start) != VBX_SUCCESS)
+        throw Error(VBX_E_INVALID, "session_channels_plan: bad argument");
+    return p;
+}
+class session_channels {
+public:
+    session_channels(Context &c, const HostAudio &fmt /* channel 0 */, const int32_t *select, size_t n_sel, size_t frame_len, size_t stride,
+                     const AnalysisParams &p, const AnalysisExt *ext, const PitchTrackParams *track, size_t max_block) : c_(c) {
+        c.check(vbx_session_open_channels(c.get(), &fmt, select, n_sel, frame_len, stride, &p, ext, track, max_block, &s_));
+    }
+    ~session_channels() { vbx_session_close(s_); }
+    session_channels(const session_channels &) = delete;
+    session_channels &operator=(const session_channels &) = delete;
+    size_t push(const void *h_block, size_t n_sample_frames, const ChannelOutputs *out, size_t record_ld, size_t status_ld = 0) {
+        size_t n = 0;
+        c_.check(vbx_session_push_channels(s_, h_block, n_sample_frames, out, record_ld, status_ld, &n));
+        return n;
+    }
+    size_t push_device(const void *d_block, size_t n_sample_frames, const ChannelOutputs *out, size_t record_ld, size_t status_ld = 0) {
+        size_t n = 0;
+        c_.check(vbx_session_push_channels_device(s_, d_block, n_sample_frames, out, record_ld, status_ld, &n));
+        return n;
+    }
+    // every channel's contour from a tracked session (vbx_session_path_bind_channels): out holds n_sel entries of device pointers
+    void bind_path(double peak_ref, size_t max_pending, const vbx_channel_path_outputs *out, size_t path_ld = 2) {
+        c_.check(vbx_session_path_bind_channels(s_, peak_ref, max_pending, out, path_ld));
+    }
+    void mark_utterance() { c_.check(vbx_session_mark_utterance(s_)); }      // (a mark applies to every channel)
+    void reset() { c_.check(vbx_session_reset(s_)); }
+    session::Info info() const {
+        session::Info i{};
+        c_.check(vbx_session_info(s_, &i.consumed, &i.frames, &i.carried));
+        return i;
+    }
+    vbx_session *get() const { return s_; }
+private:
+    Context &c_;
+    vbx_session *s_ = nullptr;
+};
+
 // The pitch path committed while the candidate lists arrive (vbx_path_stream_*): pitch_path's contour over lists pushed as they come.
 // Every row a push commits without a forced flag is the whole utterance's path, bit for bit, whatever follows; at most max_pending
 // frames are held.  All pointers are device memory; a push is one launch on the context's stream and d_commit is written in stream

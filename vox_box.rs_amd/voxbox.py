@@ -166,6 +166,12 @@ class ChannelOutputs(C.Structure):
     _fields_ = [("records", C.c_void_p), ("status3", C.c_void_p), ("outputs", C.POINTER(PitchTrackOutputs))]
 
 
+class ChannelPathOutputs(C.Structure):
+    """vbx_channel_path_outputs: where one channel's online pitch path of a bound multi-channel session writes (device pointers):
+    the committed rows, their list indices and forced flags (both optional) and the push's PathCommit."""
+    _fields_ = [("out_path", C.c_void_p), ("out_index", C.c_void_p), ("out_forced", C.c_void_p), ("d_commit", C.c_void_p)]
+
+
 class SessionPlan(C.Structure):
     """vbx_session_plan_t: what one push does to a live session -- the frames [lo, hi) it delivers, the warm frames analysed before
     them, whether the tracker continues from the last delivered row, the first sample frame the analysis reads and the first one
@@ -175,6 +181,20 @@ class SessionPlan(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class SessionChannelsPlan(C.Structure):
+    """vbx_session_channels_plan_t: one push of a multi-channel session -- vbx_session_plan's fields (`push`, every channel shares
+    them) and the layout of the planes the one frame-loop call runs over: m = `frames` analysed per channel, a plane holds `len`
+    elements from sample frame `base` (`keep` of them from the old plane), planes are `plane_frames` = Q frames = `plane_ld`
+    elements apart, the call covers `call_frames` frames and reads nothing beyond n_sel * `capacity` elements."""
+    _fields_ = [("push", SessionPlan), ("frames", C.c_size_t), ("base", C.c_size_t), ("keep", C.c_size_t), ("len", C.c_size_t),
+                ("plane_frames", C.c_size_t), ("plane_ld", C.c_size_t), ("call_frames", C.c_size_t), ("capacity", C.c_size_t)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "push"}
+        d["push"] = self.push.as_dict()
+        return d
 
 
 class PathCommit(C.Structure):
@@ -329,12 +349,19 @@ def load_library():
         "vbx_session_reset": (C.c_int, [vp]),
         "vbx_session_info": (C.c_int, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
         "vbx_session_close": (None, [vp]),
+        "vbx_session_channels_plan": (C.c_int, [sz, sz, sz, sz, sz, sz, sz, C.POINTER(SessionChannelsPlan), C.POINTER(C.c_int64)]),
+        "vbx_session_open_channels": (C.c_int, [vp, C.POINTER(HostAudio), vp, sz, sz, sz, C.POINTER(AnalysisParams), C.POINTER(AnalysisExt),
+                                                C.POINTER(PitchTrackParams), sz, C.POINTER(vp)]),
+        "vbx_session_push_channels": (C.c_int, [vp, vp, sz, C.POINTER(ChannelOutputs), sz, sz, C.POINTER(sz)]),
+        "vbx_session_push_channels_device": (C.c_int, [vp, vp, sz, C.POINTER(ChannelOutputs), sz, sz, C.POINTER(sz)]),
         "vbx_path_stream_open": (C.c_int, [vp, sz, C.POINTER(PitchPathParams), dbl, sz, C.POINTER(vp)]),
         "vbx_path_stream_push": (C.c_int, [vp, vp, vp, vp, vp, sz, i32, vp, sz, vp, vp, vp]),
         "vbx_path_stream_reset": (C.c_int, [vp]),
         "vbx_path_stream_close": (None, [vp]),
         "vbx_session_path_bind": (C.c_int, [vp, dbl, sz, vp, sz, vp, vp, vp]),
         "vbx_internal_session_ingest": (C.c_int, [vp, i32, i32, i32, vp, sz, sz, vp, sz, vp]),
+        "vbx_session_path_bind_channels": (C.c_int, [vp, dbl, sz, C.POINTER(ChannelPathOutputs), sz]),
+        "vbx_internal_session_ingest_channels": (C.c_int, [vp, i32, i32, vp, sz, vp, sz, sz, sz, vp, sz, vp, sz]),
         "vbx_find_formants_resampled_f64": (C.c_int, [vp, vp, sz, sz, sz, dbl, dbl, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp]),
         "vbx_shard_range": (C.c_int, [sz, i32, i32, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
         "vbx_shard_samples": (C.c_int, [sz, sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
@@ -458,6 +485,19 @@ def host_chunk_plan(n_frames, chunk_frames, c, frame_len, stride, seg_start=None
     if rc != 0:
         raise VoxBoxError("vbx_host_chunk_plan: bad argument")
     return plan, s0.value, s1.value
+
+
+def session_channels_plan(consumed, utt_frame, n_new, frame_len, stride, elem_bytes, n_sel):
+    """vbx_session_channels_plan: session_plan for one push of a multi-channel session plus the plane layout of its one frame-loop
+    call, for samples of elem_bytes bytes (2: PCM16, 4: F32, 8: PCM24 / PCM32 / F64) and n_sel selected channels.  Returns
+    (SessionChannelsPlan, the segment list [0, Q, 2Q, ...] as an int64 array).  Host arithmetic only."""
+    plan = SessionChannelsPlan()
+    seg = np.zeros(max(int(n_sel), 1), np.int64)
+    ok = 1 <= int(n_sel) <= HOST_MAX_CHANNELS
+    if load_library().vbx_session_channels_plan(int(consumed), int(utt_frame), int(n_new), int(frame_len), int(stride), int(elem_bytes),
+                                                int(n_sel), C.byref(plan), seg.ctypes.data_as(C.POINTER(C.c_int64)) if ok else None) != 0:
+        raise VoxBoxError("vbx_session_channels_plan: bad argument")
+    return plan, seg
 
 
 def session_plan(consumed, utt_frame, n_new, frame_len, stride):
@@ -688,6 +728,117 @@ class Session:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class SessionChannels:
+    """vbx_session opened with vbx_session_open_channels: every selected channel of one stream of interleaved audio analysed block
+    by block from ONE session -- one upload and one frame-loop call per push whatever the number of channels
+    (VoxBox.session_channels).  Per channel, concatenating what the pushes return gives, bit for bit, what a one-channel Session
+    on that channel returns for the same blocks."""
+
+    def __init__(self, vb, params, ext, track, format, channels, select, frame_len, stride, max_block):
+        self.vb, self.params, self.ext, self.track = vb, params, ext, track
+        self.format, self.channels = int(format), int(channels)
+        self.select = np.ascontiguousarray(np.arange(self.channels) if select is None else select, dtype=np.int32)
+        self.n_sel = int(self.select.size)
+        self.frame_len, self.stride, self.max_block = int(frame_len), int(stride), int(max_block)
+        hf = HostAudio.make(self.format, self.channels, 0, 0)
+        h = C.c_void_p()
+        vb._check(vb.L.vbx_session_open_channels(vb.ctx, C.byref(hf), self.select.ctypes.data, self.n_sel, self.frame_len, self.stride,
+                                                 C.byref(params), None if ext is None else C.byref(ext),
+                                                 None if track is None else C.byref(track), self.max_block, C.byref(h)))
+        self.handle = h
+        vb._sessions.add(self)
+        self.rec = int(vb.L.vbx_record_doubles_ex(C.byref(params), None if ext is None else C.byref(ext)))
+
+    info = Session.info
+    frames_of = Session.frames_of
+    mark_utterance = Session.mark_utterance
+    reset = Session.reset
+    close = Session.close
+    __enter__ = Session.__enter__
+    __exit__ = Session.__exit__
+
+    def _push(self, fn, addr, n_sf, out, status, outputs, record_ld, status_ld):
+        vb, K = self.vb, self.n_sel
+        n = self.frames_of(n_sf)
+        got = C.c_size_t()
+        ld = int(record_ld) if record_ld is not None else self.rec + (self.rec & 1)
+        entries = (ChannelOutputs * max(K, 1))()
+        if out is not None:
+            for per_channel in (out, status, outputs):
+                assert per_channel is None or len(per_channel) == K, "out / status / outputs take one entry per selected channel"
+            pos = [None] * K
+            for i in range(K):
+                entries[i].records = _ptr(out[i])
+                entries[i].status3 = None if status is None else _ptr(status[i])
+                o = None if outputs is None else outputs[i]
+                if o is not None:
+                    pos[i] = o if isinstance(o, PitchTrackOutputs) else PitchTrackOutputs(*[_ptr(a) for a in o])
+                    entries[i].outputs = C.pointer(pos[i])
+            vb._check(fn(self.handle, addr, n_sf, entries, ld, int(status_ld) if status_ld is not None else n, C.byref(got)))
+            return None
+        assert status is None and outputs is None, "status= and outputs= go with out="
+        own, res, pos = [], [], []
+        try:
+            per = []
+            for i in range(K if n else 0):
+                o, st = vb.empty((n, ld)), vb.empty((3, n), np.int32)
+                own += [o, st]
+                lists = ()
+                entries[i].records, entries[i].status3 = o.ptr, st.ptr
+                if self.track is not None:
+                    # columns 0-1 are the caller's path to fill (vbx_pitch_path_f64 over an utterance's rows): NaN until then
+                    vb._check(vb.L.vbx_memset(vb.ctx, o.ptr, 0xFF, o.nbytes))
+                    lists = (vb.empty((n, int(self.track.kmax), 2)), vb.empty(n, np.int32), vb.empty(n))
+                    own += list(lists)
+                    pos.append(PitchTrackOutputs(lists[0].ptr, lists[1].ptr, lists[2].ptr, None))
+                    entries[i].outputs = C.pointer(pos[-1])
+                per.append((o, st) + lists)
+            vb._check(fn(self.handle, addr, n_sf, entries, ld, n, C.byref(got)))
+            assert got.value == n
+            for i in range(K):
+                if n == 0:
+                    r = (np.empty((0, ld)), np.empty((3, 0), np.int32))
+                    if self.track is not None:
+                        r = r + (np.empty((0, int(self.track.kmax), 2)), np.empty(0, np.int32), np.empty(0))
+                else:
+                    r = tuple(a.numpy() for a in per[i])
+                res.append(r)
+            return res
+        finally:
+            for d in own:
+                d.free()
+
+    def push(self, block, out=None, status=None, outputs=None, record_ld=None, status_ld=None):
+        """vbx_session_push_channels: the next block of the stream, from HOST memory -- what Session.push takes ([T, channels]
+        arrays, packed 24-bit bytes).  Returns a list with one entry per selected channel, each what Session.push returns for that
+        channel -- or None when out= (one device record buffer per selected channel; status= and outputs= likewise, entries as in
+        Session.push) is given."""
+        keep, fmt, addr, channels, n_sf = VoxBox._host_audio(block, self.format, self.channels, None)
+        assert fmt == self.format and channels == self.channels, "the block is not in the session's format"
+        return self._push(self.vb.L.vbx_session_push_channels, addr, n_sf, out, status, outputs, record_ld, status_ld)
+
+    def bind_path(self, out_path, commit, peak_ref=1.0, max_pending=64, path_ld=2, out_index=None, out_forced=None):
+        """vbx_session_path_bind_channels: every push of this tracked session also commits the decided rows of EVERY channel's
+        pitch contour, in one launch.  out_path / commit (and out_index / out_forced, optional): one device buffer per selected
+        channel, as Session.bind_path takes for its one channel.  Before the first push or after reset(); between pushes only the
+        destinations may change."""
+        K = self.n_sel
+        for per_channel in (out_path, commit, out_index, out_forced):
+            assert per_channel is None or len(per_channel) == K, "one entry per selected channel"
+        ent = (ChannelPathOutputs * max(K, 1))()
+        for i in range(K):
+            ent[i].out_path, ent[i].d_commit = _ptr(out_path[i]), _ptr(commit[i])
+            ent[i].out_index = None if out_index is None else _ptr(out_index[i])
+            ent[i].out_forced = None if out_forced is None else _ptr(out_forced[i])
+        self.vb._check(self.vb.L.vbx_session_path_bind_channels(self.handle, float(peak_ref), int(max_pending), ent, int(path_ld)))
+
+    def push_device(self, block, n_sample_frames, out=None, status=None, outputs=None, record_ld=None, status_ld=None):
+        """vbx_session_push_channels_device: the same for a block in DEVICE memory, read in stream order on the context's stream
+        with no staging and no host wait."""
+        return self._push(self.vb.L.vbx_session_push_channels_device, _ptr(block), int(n_sample_frames), out, status, outputs, record_ld,
+                          status_ld)
 
 
 def commit_of(vb, commit):
@@ -1607,6 +1758,16 @@ class VoxBox:
         assert frame_len and stride
         return Session(self, params, ext, track, format, channels, channel, frame_len, stride,
                        int(max_block) if max_block is not None else 100 * int(stride))
+
+    def session_channels(self, params, ext=None, track=None, format=SAMPLE_PCM16, channels=1, select=None, frame_len=None, stride=None,
+                         max_block=None):
+        """vbx_session_open_channels: ONE live session on this context for the selected channels (select: distinct channel
+        numbers in any order; None = every channel) of a stream of interleaved sample frames in `format`, fed block by block
+        (SessionChannels.push): one upload, one frame-loop call and a fixed number of launches per push whatever the number of
+        channels.  All channels share the parameters, the cut into blocks and the utterance marks."""
+        assert frame_len and stride
+        return SessionChannels(self, params, ext, track, format, channels, select, frame_len, stride,
+                               int(max_block) if max_block is not None else 100 * int(stride))
 
     def path_stream(self, kmax, params=None, peak_ref=1.0, max_pending=64):
         """vbx_path_stream_open: an online pitch path on this context over lists of kmax candidates per frame (PathStream.push).
