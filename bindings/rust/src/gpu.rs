@@ -309,6 +309,39 @@ impl Gpu {
         Ok((Records { data, status3, n_frames, record_ld: ld }, index))
     }
 
+    /// The frame loop on a batch of variable-length clips in separate device buffers, from ONE call (`vbx_analyze_clips`): a speech
+    /// dataset, a padded batch with lengths, the utterances a VAD cut out.  `clips` holds each clip's device address and its length
+    /// in samples of `format` (`VBX_SAMPLE_*`; mono, contiguous); `group_frames` 0 takes the library's default.  Clip `b`'s rows are
+    /// rows `[row_start, row_start + n_rows)` of the records ([`clips_plan`] gives them), bit for bit what the resident call writes
+    /// on that clip alone; a clip shorter than one frame has no rows and is not read.
+    #[allow(clippy::too_many_arguments)]
+    pub fn analyze_clips(&self, clips: &[(*const c_void, usize)], format: i32, group_frames: usize, frame_len: usize, stride: usize,
+                         params: &AnalysisParams, ext: Option<&AnalysisExt>, track: Option<(usize, &PitchPathParams)>)
+                         -> GpuResult<(Records, Option<DeviceBuf<i32>>, Vec<ffi::VbxClipRow>)> {
+        let ptrs: Vec<*const c_void> = clips.iter().map(|c| c.0).collect();
+        let lens: Vec<usize> = clips.iter().map(|c| c.1).collect();
+        let (rows, n_frames, _) = clips_plan(&lens, frame_len, stride, group_frames)?;
+        let fmt = ffi::VbxClipFormat { format, reserved: 0, group_frames };
+        let p = params.to_ffi();
+        let e = ext.map(|x| x.to_ffi());
+        let e_ptr = e.as_ref().map_or(ptr::null(), |x| x as *const _);
+        let rec = unsafe { ffi::vbx_record_doubles_ex(&p, e_ptr) };
+        let ld = rec + (rec & 1);
+        let data = self.alloc::<f64>(n_frames * ld)?;
+        let status3 = self.alloc::<i32>(3 * n_frames)?;
+        let tk = track.map(|(kmax, path)| ffi::VbxPitchTrackParams { kmax, path: path.raw() });
+        let index = if tk.is_some() { Some(self.alloc::<i32>(n_frames)?) } else { None };
+        let outputs = ffi::VbxPitchTrackOutputs {
+            cand: ptr::null_mut(), count: ptr::null_mut(), peak: ptr::null_mut(),
+            index: index.as_ref().map_or(ptr::null_mut(), |b| b.as_mut_ptr()),
+        };
+        self.check(unsafe {
+            ffi::vbx_analyze_clips(self.raw, ptrs.as_ptr(), lens.as_ptr(), clips.len(), &fmt, frame_len, stride, &p, e_ptr,
+                                   tk.as_ref().map_or(ptr::null(), |t| t as *const _), data.as_mut_ptr(), ld, status3.as_mut_ptr(), &outputs)
+        })?;
+        Ok((Records { data, status3, n_frames, record_ld: ld }, index, rows))
+    }
+
     /// A live session on this context (`vbx_session_open`): ONE channel of a stream of audio that arrives block by block -- a
     /// microphone, a socket, a decoder.  Every [`Session::push`] delivers the records of the frames its block completes, and all the
     /// rows pushed equal, bit for bit, what the resident frame loop writes on the concatenated blocks, for every way of cutting the
@@ -1917,6 +1950,19 @@ pub fn session_channels_plan(consumed: usize, utt_frame: usize, n_new: usize, fr
         return Err(GpuError { code: rc, message: last_error(ptr::null()) });
     }
     Ok((plan, seg))
+}
+
+/// Where [`Gpu::analyze_clips`] puts clips of `lengths` samples (`vbx_clips_plan`; host arithmetic only): per clip its rows in the
+/// outputs, the internal group that analyses it (-1: no frame) and its first frame inside that group's packed plane; then the total
+/// rows and the number of groups.
+pub fn clips_plan(lengths: &[usize], frame_len: usize, stride: usize, group_frames: usize) -> GpuResult<(Vec<ffi::VbxClipRow>, usize, usize)> {
+    let mut rows = vec![ffi::VbxClipRow::default(); lengths.len()];
+    let (mut total, mut groups) = (0usize, 0usize);
+    let rc = unsafe { ffi::vbx_clips_plan(lengths.as_ptr(), lengths.len(), frame_len, stride, group_frames, rows.as_mut_ptr(), &mut total, &mut groups) };
+    if rc != ffi::VBX_SUCCESS {
+        return Err(GpuError { code: rc, message: last_error(ptr::null()) });
+    }
+    Ok((rows, total, groups))
 }
 
 /// What a push of `n_new` sample frames does to a live session that has consumed `consumed` sample frames and whose current

@@ -1070,6 +1070,72 @@ typedef struct {
 int vbx_session_path_bind_channels(vbx_session *s, double peak_ref, size_t max_pending,
                                    const vbx_channel_path_outputs *h_out /* n_sel entries */, size_t path_ld);
 
+/* ------------------------------------------------------------------ a batch of variable-length clips (ABI 5, added) */
+
+/* A corpus -- a speech dataset, a padded [B, Tmax] batch with lengths[B], the utterances a VAD cut out of a day of audio -- is many
+ * short clips in separate device buffers, of ragged lengths, each with its first frame at its own sample 0.  vbx_analyze_clips
+ * analyses all of them from ONE call: h_clip holds n_clips DEVICE pointers (the array itself in HOST memory), h_len their lengths in
+ * samples; the clips are mono, contiguous, of h_fmt->format (h_fmt->reserved must be 0).  Clip b gives n_rows_b =
+ * vbx_frame_count(h_len[b], frame_len, stride) rows; the outputs hold total_rows = sum n_rows_b rows, clip after clip: out_records
+ * [total_rows, record_ld] (16-byte aligned), status3 [3, total_rows] (optional) and the arrays of h_outputs (tracked form; each
+ * optional, as in the resident call) with total_rows rows.
+ * Contract: for every clip b, rows [row_start_b, row_start_b + n_rows_b) of every output -- the records, the three status rows, cand /
+ * count / peak / index -- are bit for bit what the resident call writes when it analyses clip b alone: vbx_analyze_frames_ex_pcm16 /
+ * _f32in / _f64 on the clip's own samples (PCM24 / PCM32: _f64 on vbx_unpack_samples' doubles), one segment, the same other
+ * arguments -- for every list of lengths, every group_frames, the plain, tracked and ext forms, every LPC policy and every frame
+ * shape the resident call accepts (frames beyond 4096 samples and stride > frame_len included; tests/test_gpu_clips.py).  A clip
+ * shorter than one frame has no rows and is not read (its pointer may be NULL); clips may overlap or repeat in memory; samples past
+ * h_len[b] are never read; a NaN or Inf in one clip touches no other clip's rows.  The host arrays may be reused as soon as the call
+ * returns.
+ * How.  vbx_clips_plan cuts the clips, in order, into groups of whole clips of about group_frames analysed
+ * frames.  Per group: ONE clips_pack_<fmt> launch gathers the group's clips through a device table into one plane of the type the
+ * frame loop reads natively (int16 / float / double; PCM24 / PCM32 through vbx_unpack_samples' arithmetic), clip b's sample 0 at
+ * element plane_frame_b * stride, the gap of fewer than `stride` elements behind a clip zero-filled; ONE frame-loop call over the
+ * plane with the segment list [plane_frame_b] (every clip a segment of its own: the causal tracker never carries one clip's state
+ * into the next, and the few frames that straddle two clips lie BEHIND the first one's own frames in its segment); ONE clips_deliver
+ * launch copies each clip's own rows to rows [row_start_b, ...) of the caller's arrays.  The straddling rows are computed and never
+ * delivered.  The tracked form then runs the pitch path over the COMPACTED lists with the segment list [row_start_b], straight into
+ * columns 0-1 of out_records.
+ * The call is asynchronous on the context's stream.  It may WAIT ON THE HOST for a previous upload of its tables (the staged uploads
+ * of the segment lists and of the clip table: a buffer is reused once its last copy has left it), and it is NOT capturable into a
+ * graph.  Device memory: context-owned workspaces for one group's plane and staging rows, about VBX_CLIPS_PLANE_BYTES at the default
+ * group size.  Afterwards there is no state for vbx_track_stitch_f64, and the vbx_internal_last_* probes describe the last group only.
+ * VBX_E_INVALID, before anything is written and with the context left usable: a NULL array with n_clips > 0; a NULL clip pointer
+ * with a length that gives a frame; a clip pointer not aligned to its element type (PCM24: any address); an unknown format or a
+ * non-zero reserved; 0 < group_frames < VBX_CLIPS_MIN_GROUP_FRAMES; more than 0x7fffffff total rows; anything
+ * vbx_analyze_frames_ex_f64 rejects.  n_clips == 0, or no clip with a frame, succeeds and writes nothing.
+ * vbx_clips_plan: pure host arithmetic, no GPU.  Groups are greedy runs of whole clips in order: a group closes when the next clip
+ * with frames would take it past group_frames analysed frames; a clip that is larger on its own is a group by itself.  group_frames
+ * == 0: the default -- the largest count whose f64 plane (stride * 8 bytes a frame) stays within VBX_CLIPS_PLANE_BYTES, at least
+ * VBX_CLIPS_MIN_GROUP_FRAMES and at most VBX_HOST_DEFAULT_CHUNK_FRAMES.  Inside a group the first clip with frames has plane_frame
+ * 0 and the next one starts ceil(len / stride) frames behind it; the group analyses frames [0, plane_frame_last + n_rows_last), and
+ * its plane ends where that last frame ends.  One exception: with frame_len > VBX_MAX_FRAME_LEN every clip is a group by itself,
+ * whatever group_frames -- the long-frame kernels choose how they split a frame's sums from the frame count of the call, so only a
+ * call of the clip's own frame count gives the resident call's bits (launches then grow with the clip count).  h_total_rows and
+ * h_n_groups are optional. */
+#define VBX_CLIPS_MIN_GROUP_FRAMES 64
+#define VBX_CLIPS_PLANE_BYTES 268435456
+typedef struct {
+    int32_t format;        /* VBX_SAMPLE_* : PCM16, PCM24, PCM32, F32, F64 -- mono, contiguous samples */
+    int32_t reserved;      /* must be 0 */
+    size_t group_frames;   /* analysis frames per internal group; 0: the library's default */
+} vbx_clip_format;
+typedef struct {
+    int64_t row_start;     /* first output row of the clip (prefix sum of the frame counts) */
+    int64_t n_rows;        /* vbx_frame_count(len, frame_len, stride) */
+    int64_t group;         /* which internal group analyses it; -1: no frame */
+    int64_t plane_frame;   /* its first frame inside that group's packed plane */
+} vbx_clip_row;
+int vbx_clips_plan(const size_t *h_len, size_t n_clips, size_t frame_len, size_t stride, size_t group_frames,
+                   vbx_clip_row *h_rows /* [n_clips] */, size_t *h_total_rows, size_t *h_n_groups);
+int vbx_analyze_clips(vbx_ctx *ctx, const void *const *h_clip /* [n_clips] DEVICE pointers, in HOST memory */,
+                      const size_t *h_len /* [n_clips] samples */, size_t n_clips, const vbx_clip_format *h_fmt,
+                      size_t frame_len, size_t stride,
+                      const vbx_analysis_params *h_params, const vbx_analysis_ext *h_ext,
+                      const vbx_pitch_track_params *h_track,
+                      double *out_records, size_t record_ld, int32_t *status3 /* [3, total_rows] */,
+                      const vbx_pitch_track_outputs *h_outputs /* arrays of total_rows rows */);
+
 /* ------------------------------------------------------------------ multi-GPU: frame-range sharding */
 
 /* The reference has no distribution of any kind; frames are independent (the tracker per utterance), so a long

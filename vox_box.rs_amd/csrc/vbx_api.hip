@@ -227,7 +227,7 @@ void vbx_ctx_destroy(vbx_ctx *ctx) {
         if (ctx->host_ready[i]) hipEventDestroy(ctx->host_ready[i]);
         if (ctx->host_freed[i]) hipEventDestroy(ctx->host_freed[i]);
     }
-    for (int i = 0; i < 3; i++) { if (ctx->stage[i]) hipHostFree(ctx->stage[i]); if (ctx->stage_ev[i]) hipEventDestroy(ctx->stage_ev[i]); }
+    for (int i = 0; i < vbx_ctx::N_STAGE; i++) { if (ctx->stage[i]) hipHostFree(ctx->stage[i]); if (ctx->stage_ev[i]) hipEventDestroy(ctx->stage_ev[i]); }
     if (ctx->t0) hipEventDestroy(ctx->t0);
     if (ctx->t1) hipEventDestroy(ctx->t1);
     if (ctx->owns_stream) hipStreamDestroy(ctx->stream);

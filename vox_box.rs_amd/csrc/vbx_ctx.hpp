@@ -41,7 +41,7 @@ struct vbx_ctx {
     std::string arch;
     int cu_count = 0;
     // workspaces (grown on demand, never shrunk)
-    enum { WS_COEFFS, WS_RES, WS_COUNT, WS_STATUS, WS_MISC, WS_SEG, WS_EST, WS_UNSURE, WS_F32_IN, WS_F32_OUT, WS_TRK, WS_BURG_LIST, WS_ROOTS_LIST, WS_LONG, WS_LONG2, WS_CZT, WS_CURVE, WS_LPC_LIST, WS_PATH, WS_PATH_TAB, WS_TRACK, WS_EX, WS_HOST, WS_HOST_TYPED, WS_N };
+    enum { WS_COEFFS, WS_RES, WS_COUNT, WS_STATUS, WS_MISC, WS_SEG, WS_EST, WS_UNSURE, WS_F32_IN, WS_F32_OUT, WS_TRK, WS_BURG_LIST, WS_ROOTS_LIST, WS_LONG, WS_LONG2, WS_CZT, WS_CURVE, WS_LPC_LIST, WS_PATH, WS_PATH_TAB, WS_TRACK, WS_EX, WS_HOST, WS_HOST_TYPED, WS_CLIPS_TAB, WS_CLIPS_PLANE, WS_CLIPS_ROWS, WS_CLIPS_LISTS, WS_N };
     void *ws[WS_N] = {nullptr};
     const int32_t *burg_list_count = nullptr;             // device counter of the last one-pass Burg call (tests)
     const int32_t *roots_list_count = nullptr;            // the same for the resonance kernel of find_formants
@@ -83,10 +83,11 @@ struct vbx_ctx {
     hipEvent_t ev_slice[8] = {nullptr}, ev_trk = nullptr;
     // pinned staging of the small host arrays (segment starts, initial estimates): the caller's arrays may be
     // freed on return, and an upload whose content has not changed since the last call is skipped
-    void *stage[3] = {nullptr, nullptr, nullptr};         // 0: segment starts, 1: initial estimates, 2: the pitch path's chunk table
-    size_t stage_cap[3] = {0, 0, 0};
-    std::vector<char> staged[3];                          // content now on the device
-    hipEvent_t stage_ev[3] = {nullptr, nullptr, nullptr}; // completion of the last staged copy
+    enum { N_STAGE = 4 };
+    void *stage[N_STAGE] = {nullptr};                     // 0: segment starts, 1: initial estimates, 2: the pitch path's chunk table, 3: vbx_analyze_clips' clip table
+    size_t stage_cap[N_STAGE] = {0};
+    std::vector<char> staged[N_STAGE];                    // content now on the device
+    hipEvent_t stage_ev[N_STAGE] = {nullptr};             // completion of the last staged copy
     // what the tracker of the last find_formants / analyze_frames call ran on (vbx_track_stitch_f64 continues that track)
     struct { const vbx::res_t *res = nullptr; const int32_t *cnt = nullptr, *st = nullptr; long F = 0; int n_est = 0;
              vbx::res_t *out = nullptr; long out_ld = 0; } last_track;

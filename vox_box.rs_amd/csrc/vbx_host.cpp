@@ -537,6 +537,50 @@ int vbx_session_channels_plan(size_t consumed, size_t utt_frame, size_t n_new, s
     return VBX_SUCCESS;
 }
 
+// A batch of clips (vbx_analyze_clips): each clip's rows in the outputs, the group that analyses it and where it lies in that
+// group's packed plane.  Groups are greedy runs of whole clips in order.  Inside a group clip b's sample 0 lies at element
+// plane_frame_b * stride; the next clip with frames starts ceil(len_b / stride) frames behind it, so the gap between them is shorter
+// than one hop and every frame of [plane_frame_b, plane_frame_b + n_rows_b) reads clip b's own samples only.  Frames longer than
+// VBX_MAX_FRAME_LEN: every clip is a group by itself -- the long-frame kernels (k_long.hip) choose how they split a frame's sums
+// from the frame count of the call, so only a call of the clip's own frame count gives the resident call's bits.
+int vbx_clips_plan(const size_t *h_len, size_t n_clips, size_t frame_len, size_t stride, size_t group_frames, vbx_clip_row *h_rows,
+                   size_t *h_total_rows, size_t *h_n_groups) {
+    if (h_total_rows) *h_total_rows = 0;
+    if (h_n_groups) *h_n_groups = 0;
+    if (frame_len < 1 || stride < 1) return fail(nullptr, VBX_E_INVALID, "vbx_clips_plan: frame_len and stride must be >= 1");
+    if (n_clips > 0 && (!h_len || !h_rows)) return fail(nullptr, VBX_E_INVALID, "vbx_clips_plan: null array");
+    if (group_frames != 0 && group_frames < (size_t)VBX_CLIPS_MIN_GROUP_FRAMES)
+        return fail(nullptr, VBX_E_INVALID, "vbx_clips_plan: group_frames must be 0 or >= VBX_CLIPS_MIN_GROUP_FRAMES");
+    size_t gf = group_frames;
+    if (gf == 0) {                                        // the default: an f64 plane of at most VBX_CLIPS_PLANE_BYTES
+        gf = (size_t)VBX_CLIPS_PLANE_BYTES / sizeof(double) / stride;
+        if (gf > (size_t)VBX_HOST_DEFAULT_CHUNK_FRAMES) gf = (size_t)VBX_HOST_DEFAULT_CHUNK_FRAMES;
+        if (gf < (size_t)VBX_CLIPS_MIN_GROUP_FRAMES) gf = (size_t)VBX_CLIPS_MIN_GROUP_FRAMES;
+    }
+    if (gf > 0x7fffffffull) gf = 0x7fffffffull;           // (a group is one frame-loop call)
+    size_t total = 0;
+    for (size_t b = 0; b < n_clips; b++) {                // first: nothing is written for a batch that is refused
+        const size_t n = vbx_frame_count(h_len[b], frame_len, stride);
+        if (n > 0x7fffffffull - total) return fail(nullptr, VBX_E_INVALID, "vbx_clips_plan: more than 0x7fffffff rows");
+        total += n;
+    }
+    const bool alone = frame_len > (size_t)VBX_MAX_FRAME_LEN;
+    size_t row = 0, groups = 0, next = 0;                 // next: the plane frame the next clip of the open group would start at
+    for (size_t b = 0; b < n_clips; b++) {
+        const size_t n = vbx_frame_count(h_len[b], frame_len, stride);
+        vbx_clip_row &r = h_rows[b];
+        r.row_start = (int64_t)row; r.n_rows = (int64_t)n; r.group = -1; r.plane_frame = 0;
+        if (n == 0) continue;
+        if (groups == 0 || alone || next + n > gf) { groups++; next = 0; }      // (a clip larger than gf on its own: a group by itself)
+        r.group = (int64_t)(groups - 1); r.plane_frame = (int64_t)next;
+        next += h_len[b] / stride + (h_len[b] % stride != 0);
+        row += n;
+    }
+    if (h_total_rows) *h_total_rows = total;
+    if (h_n_groups) *h_n_groups = groups;
+    return VBX_SUCCESS;
+}
+
 }  // extern "C"
 
 namespace vbx {

@@ -387,6 +387,30 @@ struct session_deliver_all_t {
     struct { double *rec; int32_t *st; double *cand; int32_t *count; double *peak; } ch[UNPACK_MAX_SEL];
 };
 void launch_session_deliver_all(hipStream_t s, const session_deliver_all_t &d, size_t n_sel);
+// k_clips.hip: the two launches vbx_analyze_clips puts around a group's frame-loop call.  One table entry per clip WITH frames, in
+// order: off (= plane_frame * stride) and row_start ascend.
+struct clip_entry_t {
+    const void *src;                                      // the clip's samples (device), its format's alignment
+    uint64_t len, off;                                    // samples; the plane element its sample 0 goes to
+    int64_t plane_frame, row_start, n_rows;               // its first frame in the plane; its rows in the caller's arrays
+};
+// pack: plane[0, total) (the format's output type, launch_unpack's bits) = every clip's samples at its off, zeros between a clip's
+// end and the next clip's off; tab[0].off == 0, total > tab[n - 1].off, and the last clip has at least total - off samples.  Every
+// element is written once; no sample past a clip's len is read.
+void launch_clips_pack(hipStream_t s, int format, const clip_entry_t *tab, size_t n, size_t total, void *plane);
+// deliver: rows [plane_frame_b, + n_rows_b) of the group's staging into rows [row_start_b, ...) of the destinations (which point at
+// row 0 of the caller's arrays): the records' columns [c0, c1), the three status rows (src: [3, src_n]; dst_st[q] may be null), the
+// lists (kmax entries a row), counts and peaks where the destination is non-null.  rows = the group's delivered rows, from row0 on.
+struct clips_deliver_t {
+    const clip_entry_t *tab; size_t n, row0, rows;
+    const double *src; size_t src_ld, c0, c1; double *dst; size_t dst_ld;
+    const int32_t *src_st; size_t src_n; int32_t *dst_st[3];
+    const double *src_cand; double *dst_cand; size_t kmax;
+    const int32_t *src_count; int32_t *dst_count;
+    const double *src_peak; double *dst_peak;
+};
+void launch_clips_deliver(hipStream_t s, const clips_deliver_t &d);
+
 // k_tracker.hip: launch_tracker_stitch for n_sel channels in ONE launch (a block per channel): channel k's rows
 // [k * plane_frames + first, k * plane_frames + stop) continued from state + k * 2 * VBX_FORMANT_SLOTS_K
 void launch_tracker_stitch_all(hipStream_t s, const res_t *res, long F, int n_res, const int32_t *res_count, int n_est,

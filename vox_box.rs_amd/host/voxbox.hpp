@@ -426,6 +426,29 @@ inline void analyze_host_channels(Context &c, const void *h_audio, size_t n_samp
     c.check(vbx_analyze_host_channels(c.get(), h_audio, n_sample_frames, &fmt, h_channels, n_sel, frame_len, stride, &p, ext, track,
                                       seg.h_seg_start, seg.n, out, record_ld));
 }
+// A batch of variable-length clips in separate device buffers from ONE call (vbx_analyze_clips): h_clip holds n_clips device
+// pointers (a host array), h_len their lengths in samples; clip b's rows are rows [row_start_b, row_start_b + n_rows_b) of every
+// output (clips_plan gives them), bit for bit what the resident call writes on that clip alone.  clip_format(): the default groups.
+using ClipFormat = vbx_clip_format;
+using ClipRow = vbx_clip_row;
+inline ClipFormat clip_format(int format, size_t group_frames = 0) {
+    ClipFormat f{};
+    f.format = format; f.group_frames = group_frames;
+    return f;
+}
+struct ClipsPlan { std::vector<ClipRow> rows; size_t total_rows = 0, n_groups = 0; };
+inline ClipsPlan clips_plan(const size_t *h_len, size_t n_clips, size_t frame_len, size_t stride, size_t group_frames = 0) {
+    ClipsPlan p;
+    p.rows.resize(n_clips);
+    if (vbx_clips_plan(h_len, n_clips, frame_len, stride, group_frames, p.rows.data(), &p.total_rows, &p.n_groups) != VBX_SUCCESS)
+        throw Error(VBX_E_INVALID, "clips_plan: bad argument");
+    return p;
+}
+inline void analyze_clips(Context &c, const void *const *h_clip, const size_t *h_len, size_t n_clips, const ClipFormat &fmt, size_t frame_len,
+                          size_t stride, const AnalysisParams &p, const AnalysisExt *ext, const PitchTrackParams *track, double *records,
+                          size_t record_ld, int32_t *status3 = nullptr, const PitchTrackOutputs *outputs = nullptr) {
+    c.check(vbx_analyze_clips(c.get(), h_clip, h_len, n_clips, &fmt, frame_len, stride, &p, ext, track, records, record_ld, status3, outputs));
+}
 // pinned host memory for analyze_host's h_audio (vbx_malloc_host / vbx_free_host)
 inline void *malloc_host(Context &c, size_t bytes) { void *p = nullptr; c.check(vbx_malloc_host(c.get(), &p, bytes)); return p; }
 inline void free_host(Context &c, void *p) { c.check(vbx_free_host(c.get(), p)); }

@@ -160,6 +160,29 @@ class HostAudio(C.Structure):
 HOST_MAX_CHANNELS = 64
 
 
+CLIPS_MIN_GROUP_FRAMES = 64
+CLIPS_PLANE_BYTES = 1 << 28
+
+
+class ClipFormat(C.Structure):
+    """vbx_clip_format: what vbx_analyze_clips is handed about its clips -- their sample format (SAMPLE_*; mono, contiguous) and
+    the analysis frames per internal group (0: the library's default, an f64 plane of at most CLIPS_PLANE_BYTES)."""
+    _fields_ = [("format", C.c_int32), ("reserved", C.c_int32), ("group_frames", C.c_size_t)]
+
+    @classmethod
+    def make(cls, format, group_frames=0):
+        return cls(int(format), 0, int(group_frames))
+
+
+class ClipRow(C.Structure):
+    """vbx_clip_row: where vbx_clips_plan puts one clip -- its rows [row_start, row_start + n_rows) in the outputs, the internal
+    group that analyses it (-1: the clip has no frame) and its first frame inside that group's packed plane."""
+    _fields_ = [("row_start", C.c_int64), ("n_rows", C.c_int64), ("group", C.c_int64), ("plane_frame", C.c_int64)]
+
+    def as_tuple(self):
+        return int(self.row_start), int(self.n_rows), int(self.group), int(self.plane_frame)
+
+
 class ChannelOutputs(C.Structure):
     """vbx_channel_outputs: one selected channel's device outputs of vbx_analyze_host_channels -- records [F, record_ld], status3
     [3, F] (optional) and the tracked form's optional arrays (a pointer to a PitchTrackOutputs, or NULL)."""
@@ -362,6 +385,10 @@ def load_library():
         "vbx_internal_session_ingest": (C.c_int, [vp, i32, i32, i32, vp, sz, sz, vp, sz, vp]),
         "vbx_session_path_bind_channels": (C.c_int, [vp, dbl, sz, C.POINTER(ChannelPathOutputs), sz]),
         "vbx_internal_session_ingest_channels": (C.c_int, [vp, i32, i32, vp, sz, vp, sz, sz, sz, vp, sz, vp, sz]),
+        "vbx_clips_plan": (C.c_int, [C.POINTER(sz), sz, sz, sz, sz, C.POINTER(ClipRow), C.POINTER(sz), C.POINTER(sz)]),
+        "vbx_analyze_clips": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), sz, C.POINTER(ClipFormat), sz, sz, C.POINTER(AnalysisParams),
+                                        C.POINTER(AnalysisExt), C.POINTER(PitchTrackParams), vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
+        "vbx_internal_clips_pack": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(sz), sz, sz, vp, C.POINTER(sz)]),
         "vbx_find_formants_resampled_f64": (C.c_int, [vp, vp, sz, sz, sz, dbl, dbl, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp]),
         "vbx_shard_range": (C.c_int, [sz, i32, i32, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
         "vbx_shard_samples": (C.c_int, [sz, sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
@@ -498,6 +525,19 @@ def session_channels_plan(consumed, utt_frame, n_new, frame_len, stride, elem_by
                                                 int(n_sel), C.byref(plan), seg.ctypes.data_as(C.POINTER(C.c_int64)) if ok else None) != 0:
         raise VoxBoxError("vbx_session_channels_plan: bad argument")
     return plan, seg
+
+
+def clips_plan(lengths, frame_len, stride, group_frames=0):
+    """vbx_clips_plan: where vbx_analyze_clips puts clips of `lengths` samples -- returns (rows, total_rows, n_groups), rows an
+    int64 array [n_clips, 4] of (row_start, n_rows, group, plane_frame) per clip (group -1: no frame).  Host arithmetic only."""
+    ln = np.ascontiguousarray(lengths, dtype=np.uint64).reshape(-1)
+    rows = (ClipRow * max(ln.size, 1))()
+    total, groups = C.c_size_t(), C.c_size_t()
+    if load_library().vbx_clips_plan(ln.ctypes.data_as(C.POINTER(C.c_size_t)), ln.size, int(frame_len), int(stride), int(group_frames), rows,
+                                     C.byref(total), C.byref(groups)) != 0:
+        raise VoxBoxError("vbx_clips_plan: bad argument")
+    out = np.array([rows[i].as_tuple() for i in range(ln.size)], dtype=np.int64).reshape(ln.size, 4)
+    return out, int(total.value), int(groups.value)
 
 
 def session_plan(consumed, utt_frame, n_new, frame_len, stride):
@@ -1748,6 +1788,43 @@ class VoxBox:
         def fn(ctx, ptr, F_, N, S, *rest):
             return self.L.vbx_analyze_host(ctx, ptr, int(n_sample_frames), C.byref(hf), N, S, *rest)
         return self._analyze_tracked(fn, addr, F, int(frame_len), int(stride), params, track, seg_start, out, record_ld, status, lists,
+                                     outputs, None, ext=ext)
+
+    def analyze_clips(self, clips, lengths=None, params=None, ext=None, track=None, format=None, group_frames=0, frame_len=None,
+                      stride=None, out=None, record_ld=None, status=None, lists=False, outputs=None):
+        """vbx_analyze_clips: the frame loop on a batch of variable-length clips in device memory, from one call.  clips: a list of
+        1-D device buffers (DeviceArrays -- format and lengths follow from them -- or raw addresses with format= and lengths=), or
+        ONE 2-D padded DeviceArray [B, Tmax] with lengths[B] (row b's first lengths[b] samples are clip b).  PCM24 clips are uint8
+        DeviceArrays / addresses with format=SAMPLE_PCM24 and lengths= in samples.  Clip b's rows are rows [row_start_b, +n_rows_b)
+        of everything returned (clips_plan gives them), bit for bit the resident call's on that clip alone.  Returns what
+        analyze_frames_ex returns."""
+        assert frame_len and stride and params is not None
+        if isinstance(clips, DeviceArray) and len(clips.shape) == 2:
+            assert lengths is not None and len(lengths) == clips.shape[0]
+            assert all(0 <= int(n) <= clips.shape[1] for n in lengths)
+            pitch = clips.shape[1] * clips.dtype.itemsize
+            ptrs, dt = [clips.ptr + b * pitch for b in range(clips.shape[0])], clips.dtype
+        else:
+            ptrs = [_ptr(c) for c in clips]
+            dts = {c.dtype for c in clips if isinstance(c, DeviceArray)}
+            assert len(dts) <= 1, "the clips share one sample type"
+            dt = dts.pop() if dts else None
+            if lengths is None:
+                assert all(isinstance(c, DeviceArray) and len(c.shape) == 1 for c in clips), "lengths= is needed for raw addresses"
+                lengths = [c.shape[0] for c in clips]
+        if format is None:
+            format = {np.dtype(np.int16): SAMPLE_PCM16, np.dtype(np.int32): SAMPLE_PCM32, np.dtype(np.float32): SAMPLE_F32,
+                      np.dtype(np.float64): SAMPLE_F64}[np.dtype(dt)]
+        n = len(ptrs)
+        assert len(lengths) == n
+        h_clip = (C.c_void_p * max(n, 1))(*ptrs)
+        h_len = (C.c_size_t * max(n, 1))(*[int(v) for v in lengths])
+        cf = ClipFormat.make(format, group_frames)
+        _, total, _ = clips_plan(list(lengths), frame_len, stride, group_frames)
+
+        def fn(ctx, ptr, F_, N, S, p, e, t, seg, nseg, *rest):
+            return self.L.vbx_analyze_clips(ctx, h_clip, h_len, n, C.byref(cf), N, S, p, e, t, *rest)
+        return self._analyze_tracked(fn, None, total, int(frame_len), int(stride), params, track, None, out, record_ld, status, lists,
                                      outputs, None, ext=ext)
 
     def session(self, params, ext=None, track=None, format=SAMPLE_PCM16, channels=1, channel=0, frame_len=None, stride=None,
