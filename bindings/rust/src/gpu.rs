@@ -254,12 +254,13 @@ impl Gpu {
     }
 
     /// One channel of interleaved sample frames on the device, as the type the frame loop reads natively (`vbx_unpack_samples`):
-    /// `format` is a `VBX_SAMPLE_*`; `dst` holds `n_sample_frames` elements of i16 (PCM16), f32 (F32) or f64 (PCM24 / PCM32 / F64).
+    /// `format` is a `VBX_SAMPLE_*`; `dst` holds `n_sample_frames` elements of i16 (PCM16 / ULAW / ALAW), f32 (F32) or f64 (PCM24 / PCM32 /
+    /// F64 / U8).
     /// 24- and 32-bit PCM become `s / 8388607` and `s / 2147483647`, correctly rounded.
     pub fn unpack_samples<S: Copy, D: Copy>(&self, src: &DeviceBuf<S>, n_sample_frames: usize, format: i32, channels: i32, channel: i32,
                                             dst: &DeviceBuf<D>) -> GpuResult<()> {
-        let src_bytes = match format { ffi::VBX_SAMPLE_PCM16 => 2, ffi::VBX_SAMPLE_PCM24 => 3, ffi::VBX_SAMPLE_F64 => 8, _ => 4 };
-        let dst_bytes = match format { ffi::VBX_SAMPLE_PCM16 => 2, ffi::VBX_SAMPLE_F32 => 4, _ => 8 };
+        let src_bytes = sample_src_bytes(format);
+        let dst_bytes = sample_out_bytes(format);
         assert!(channels >= 1 && src.len() * std::mem::size_of::<S>() >= n_sample_frames * channels as usize * src_bytes, "source too small");
         assert!(dst.len() * std::mem::size_of::<D>() >= n_sample_frames * dst_bytes, "destination too small");
         self.check(unsafe {
@@ -360,7 +361,7 @@ impl Gpu {
             ffi::vbx_session_open(self.raw, &fmt, frame_len, stride, &p, e_ptr, tk.as_ref().map_or(ptr::null(), |t| t as *const _), max_block,
                                   &mut raw)
         })?;
-        let sample_frame_bytes = channels * match format { ffi::VBX_SAMPLE_PCM16 => 2, ffi::VBX_SAMPLE_PCM24 => 3, ffi::VBX_SAMPLE_F64 => 8, _ => 4 };
+        let sample_frame_bytes = channels * sample_src_bytes(format);
         Ok(Session { gpu: self, raw, format, sample_frame_bytes, frame_len, stride, record_ld: rec + (rec & 1), kmax: tk.map(|t| t.kmax) })
     }
 
@@ -384,7 +385,7 @@ impl Gpu {
             ffi::vbx_session_open_channels(self.raw, &fmt, select.as_ptr(), select.len(), frame_len, stride, &p, e_ptr,
                                            tk.as_ref().map_or(ptr::null(), |t| t as *const _), max_block, &mut raw)
         })?;
-        let sample_frame_bytes = channels * match format { ffi::VBX_SAMPLE_PCM16 => 2, ffi::VBX_SAMPLE_PCM24 => 3, ffi::VBX_SAMPLE_F64 => 8, _ => 4 };
+        let sample_frame_bytes = channels * sample_src_bytes(format);
         let one = Session { gpu: self, raw, format, sample_frame_bytes, frame_len, stride, record_ld: rec + (rec & 1), kmax: tk.map(|t| t.kmax) };
         Ok(SessionChannels { one, n_sel: select.len() })
     }
@@ -406,8 +407,8 @@ impl Gpu {
     #[allow(clippy::too_many_arguments)]
     pub fn unpack_channels<S: Copy, D: Copy>(&self, src: &DeviceBuf<S>, n_sample_frames: usize, format: i32, channels: i32, select: &[i32],
                                              dst: &DeviceBuf<D>, plane_ld: usize) -> GpuResult<()> {
-        let src_bytes = match format { ffi::VBX_SAMPLE_PCM16 => 2, ffi::VBX_SAMPLE_PCM24 => 3, ffi::VBX_SAMPLE_F64 => 8, _ => 4 };
-        let dst_bytes = match format { ffi::VBX_SAMPLE_PCM16 => 2, ffi::VBX_SAMPLE_F32 => 4, _ => 8 };
+        let src_bytes = sample_src_bytes(format);
+        let dst_bytes = sample_out_bytes(format);
         assert!(channels >= 1 && src.len() * std::mem::size_of::<S>() >= n_sample_frames * channels as usize * src_bytes, "source too small");
         assert!(!select.is_empty() && select.len() <= ffi::VBX_HOST_MAX_CHANNELS && plane_ld >= n_sample_frames, "bad selection or plane_ld");
         assert!(dst.len() * std::mem::size_of::<D>() >= ((select.len() - 1) * plane_ld + n_sample_frames) * dst_bytes, "destination too small");
@@ -1963,6 +1964,37 @@ pub fn clips_plan(lengths: &[usize], frame_len: usize, stride: usize, group_fram
         return Err(GpuError { code: rc, message: last_error(ptr::null()) });
     }
     Ok((rows, total, groups))
+}
+
+/// The 256 16-bit linear values of a G.711 law (`format`: `VBX_SAMPLE_ULAW` or `VBX_SAMPLE_ALAW`; `vbx_g711_table`, host arithmetic
+/// only), by the function the reader kernels run: `table[code as usize]` decodes one byte.
+pub fn g711_table(format: c_int) -> GpuResult<[i16; 256]> {
+    let mut table = [0i16; 256];
+    let rc = unsafe { ffi::vbx_g711_table(format, table.as_mut_ptr()) };
+    if rc != ffi::VBX_SUCCESS {
+        return Err(GpuError { code: rc, message: last_error(ptr::null()) });
+    }
+    Ok(table)
+}
+
+/// Bytes of one source sample of a `VBX_SAMPLE_*` format (the 8-bit formats -- U8, ULAW, ALAW -- are one byte).
+pub fn sample_src_bytes(format: c_int) -> usize {
+    match format {
+        ffi::VBX_SAMPLE_U8 | ffi::VBX_SAMPLE_ULAW | ffi::VBX_SAMPLE_ALAW => 1,
+        ffi::VBX_SAMPLE_PCM16 => 2,
+        ffi::VBX_SAMPLE_PCM24 => 3,
+        ffi::VBX_SAMPLE_F64 => 8,
+        _ => 4,
+    }
+}
+
+/// Bytes of one element of the typed plane a `VBX_SAMPLE_*` format unpacks to (i16 for PCM16 / ULAW / ALAW, f32 for F32, else f64).
+pub fn sample_out_bytes(format: c_int) -> usize {
+    match format {
+        ffi::VBX_SAMPLE_PCM16 | ffi::VBX_SAMPLE_ULAW | ffi::VBX_SAMPLE_ALAW => 2,
+        ffi::VBX_SAMPLE_F32 => 4,
+        _ => 8,
+    }
 }
 
 /// What a push of `n_new` sample frames does to a live session that has consumed `consumed` sample frames and whose current

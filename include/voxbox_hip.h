@@ -705,7 +705,23 @@ int vbx_find_formants_resampled_f64(vbx_ctx *ctx, const double *x, size_t n_fram
  *   VBX_SAMPLE_PCM32  int32                           -> double, s / 2147483647
  *   VBX_SAMPLE_F32    float                           -> float, as it is (bit patterns are copied: NaN payloads, -0.0, subnormals survive)
  *   VBX_SAMPLE_F64    double                          -> double, as it is
+ *   VBX_SAMPLE_U8     unsigned 8-bit PCM (WAV, 8 bits per sample) -> double, (b - 128) / 127   (tests/lib.rs:17-19 at bits_per_sample = 8)
+ *   VBX_SAMPLE_ULAW   G.711 mu-law, one byte          -> int16, the 16-bit linear value below
+ *   VBX_SAMPLE_ALAW   G.711 A-law, one byte           -> int16, the 16-bit linear value below
  * PCM24 and PCM32 results are the correctly rounded quotient (IEEE division), bit for bit numpy.float64(s) / denom.
+ * 8-bit telephone audio (ABI 5, added).  U8 is the same kind of quotient, bit for bit numpy.float64(b - 128) / 127,
+ * from -128/127 to 1.  ULAW and ALAW are the ITU-T G.711 expansions that ffmpeg, sox and CPython's audioop implement:
+ *   mu-law: u = ~b & 0xff, e = (u >> 4) & 7, m = u & 15, mag = (((m << 3) + 0x84) << e) - 0x84; the value is -mag if u & 0x80, else mag
+ *           (+-32124 at most; 0x7f and 0xff both give 0);
+ *   A-law:  a = b ^ 0x55, e = (a >> 4) & 7, m = a & 15, mag = e == 0 ? (m << 4) + 8 : ((m << 4) + 0x108) << (e - 1); the value is mag if
+ *           a & 0x80, else -mag (+-32256 at most; there is no zero code).
+ * The decoded int16 means what every PCM16 sample means to this library, s / 32767, and is handed to the PCM16 kernels as it is.  The
+ * decode is integer arithmetic in registers inside the reader kernels (no table); vbx_g711_table runs the same function on the host.
+ * Contract: every byte a call writes for a ULAW or ALAW source equals, bit for bit, what the same call writes for PCM16 on the decoded
+ * int16 samples, and every byte it writes for U8 equals what it writes for F64 on (b - 128) / 127 (tests/test_gpu_unpack8.py,
+ * tests/test_gpu_analyze_sample8.py).  An 8-bit source has no alignment requirement.  Profiled as unpack_u8 / unpack_ulaw / unpack_alaw.
+ * The values 6 and 7 -- the WAV format tags of A-law and mu-law -- are NOT formats of this library: 0, 6 to 15 and 19 and above are
+ * rejected.  Container parsing stays with the caller (which WAV tag maps to which constant).
  * Alignment: a PCM24 source may sit at any byte address; every other source and every destination needs its type's natural
  * alignment.  A 16-byte aligned destination is written by 16-byte stores, a mono source of matching alignment read by the widest
  * loads; the results are the same bits either way.  channels == 1 with PCM16, F32 or F64 is a plain copy.  One pass, asynchronous
@@ -717,7 +733,15 @@ int vbx_find_formants_resampled_f64(vbx_ctx *ctx, const double *x, size_t n_fram
 #define VBX_SAMPLE_PCM32 3
 #define VBX_SAMPLE_F32 4
 #define VBX_SAMPLE_F64 5
+#define VBX_SAMPLE_U8 16     /* unsigned 8-bit PCM (WAV, 8 bits per sample): (b - 128) / 127      -> double */
+#define VBX_SAMPLE_ULAW 17   /* G.711 mu-law: the 16-bit linear value above                        -> int16  */
+#define VBX_SAMPLE_ALAW 18   /* G.711 A-law:  the 16-bit linear value above                        -> int16  */
 int vbx_unpack_samples(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames, int format, int channels, int channel, void *d_out);
+
+/* The 256 values of a G.711 law: h_out[b] = the 16-bit linear value of code b, by the same function the reader kernels run.  Host
+ * arithmetic only: no context, no GPU (a caller can decode a header's worth of samples with it).  VBX_E_INVALID: a format other
+ * than VBX_SAMPLE_ULAW or VBX_SAMPLE_ALAW, a NULL h_out. */
+int vbx_g711_table(int format, int16_t *h_out /* [256] */);
 
 /* The frame loop on a recording that lives in HOST memory, of any length, from one call: vbx_analyze_frames_ex_* fed chunk by chunk.
  * h_audio holds n_sample_frames interleaved sample frames in h_fmt->format; channel h_fmt->channel is analysed;
@@ -752,6 +776,9 @@ int vbx_unpack_samples(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames, 
  * Afterwards the vbx_internal_last_* probes describe the LAST chunk's call only (not part of the contract), and the context holds
  * no state for vbx_track_stitch_f64, which returns VBX_E_INVALID.  Not capturable into a graph.
  * h_fmt->chunk_frames: analysis frames per chunk; 0 = the library's default, 250,000 frames (120 M samples at a 480-sample hop).
+ * 8-bit sources (VBX_SAMPLE_U8 / ULAW / ALAW, one byte per sample, any byte address): every byte written for a ULAW or ALAW source
+ * equals, bit for bit, what the same call writes for PCM16 on the decoded int16 samples (vbx_g711_table), and every byte written for
+ * U8 equals what it writes for F64 on (b - 128) / 127 -- the bytes are decoded inside this call's own reader kernel, never in a pass before it.
  * VBX_E_INVALID, before anything is written and with the context left usable: a NULL h_fmt, an unknown format, channels < 1,
  * channel outside [0, channels), reserved != 0, a NULL h_audio with F > 0, 0 < chunk_frames < VBX_SHARD_WARM_FRAMES, anything the
  * resident call rejects.  F == 0 succeeds. */
@@ -789,6 +816,9 @@ int vbx_free_host(vbx_ctx *ctx, void *p);
  * aligned and choose plane_ld as a multiple of 8 elements (n_sample_frames rounded up), which keeps every plane on the tiled form.
  * Measured rates, subsets included: DESIGN.md section 5f.  Asynchronous on the context's stream; profiled as unpack_all_pcm16 / unpack_all_pcm24 /
  * unpack_all_pcm32 / unpack_all_f32 / unpack_all_f64.
+ * 8-bit sources (VBX_SAMPLE_U8 / ULAW / ALAW, one byte per sample, any byte address): every byte written for a ULAW or ALAW source
+ * equals, bit for bit, what the same call writes for PCM16 on the decoded int16 samples (vbx_g711_table), and every byte written for
+ * U8 equals what it writes for F64 on (b - 128) / 127 -- the bytes are decoded inside this call's own reader kernel, never in a pass before it.
  * VBX_E_INVALID, with nothing written: an unknown format, channels < 1, n_sel outside [1, min(channels, VBX_HOST_MAX_CHANNELS)], a
  * NULL h_channels, a repeated or out-of-range channel, plane_ld < n_sample_frames, a NULL pointer with n_sample_frames > 0, a pointer
  * that breaks its type's natural alignment (a PCM24 source has none).  n_sample_frames == 0 succeeds. */
@@ -819,6 +849,9 @@ int vbx_unpack_channels(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames,
  * chunk-sized workspaces, the tracked form's per-channel lists, the caller's outputs.
  * Host timing, vbx_sync, calls that follow one another with no wait between them, "not capturable into a graph" and the state left
  * behind (the probes describe the last chunk's last channel; none for vbx_track_stitch_f64) are as for vbx_analyze_host.
+ * 8-bit sources (VBX_SAMPLE_U8 / ULAW / ALAW, one byte per sample, any byte address): every byte written for a ULAW or ALAW source
+ * equals, bit for bit, what the same call writes for PCM16 on the decoded int16 samples (vbx_g711_table), and every byte written for
+ * U8 equals what it writes for F64 on (b - 128) / 127 -- the bytes are decoded inside this call's own reader kernel, never in a pass before it.
  * VBX_E_INVALID, before anything is written and with the context left usable: everything vbx_analyze_host rejects; a bad selection
  * (as vbx_unpack_channels); h_fmt->channel != 0; a NULL h_out; an entry whose records are NULL or not 16-byte aligned; two entries
  * whose [F, record_ld] record ranges overlap.  F == 0 succeeds. */
@@ -888,6 +921,9 @@ int vbx_analyze_host_channels(vbx_ctx *ctx, const void *h_audio, size_t n_sample
  * vbx_session_info reports the sample frames consumed, the frames delivered and the sample frames carried; vbx_session_close frees
  * the session (behind the work queued on the context's stream; close every session before its context).
  * Kernel launches per push and measured round trips: DESIGN.md section 5g.
+ * 8-bit sources (VBX_SAMPLE_U8 / ULAW / ALAW, one byte per sample, any byte address): every byte written for a ULAW or ALAW source
+ * equals, bit for bit, what the same call writes for PCM16 on the decoded int16 samples (vbx_g711_table), and every byte written for
+ * U8 equals what it writes for F64 on (b - 128) / 127 -- the bytes are decoded inside this call's own reader kernel, never in a pass before it.
  * VBX_E_INVALID, before anything is queued and with session and context left usable: a NULL argument where one is required, an unknown
  * format, channels < 1, channel outside [0, channels), non-zero reserved or chunk_frames, max_block_sample_frames == 0, a push larger
  * than max_block_sample_frames, records misaligned, record_ld odd or too small, status_ld < n, the tracked form's missing or
@@ -1021,6 +1057,9 @@ int vbx_session_path_bind(vbx_session *s, double peak_ref, size_t max_pending,
  * vbx_session_path_bind on a session opened here, and the _channels calls (vbx_session_path_bind_channels included) on a
  * one-channel session, return VBX_E_INVALID with nothing queued.  n_sel == 1 is allowed and equals the one-channel session.  Device memory: n_sel carry planes (twice) and n_sel
  * times the chunk-local buffers of vbx_session_open.
+ * 8-bit sources (VBX_SAMPLE_U8 / ULAW / ALAW, one byte per sample, any byte address): every byte written for a ULAW or ALAW source
+ * equals, bit for bit, what the same call writes for PCM16 on the decoded int16 samples (vbx_g711_table), and every byte written for
+ * U8 equals what it writes for F64 on (b - 128) / 127 -- the bytes are decoded inside this call's own reader kernel, never in a pass before it.
  * VBX_E_INVALID, before anything is queued and with the session left usable: everything the one-channel calls reject; a bad selection;
  * h_fmt->channel != 0; a NULL h_out; an entry with NULL or misaligned records; two entries whose [n, record_ld] ranges overlap; more
  * than 0x7fffffff frames in the largest frame-loop call.
@@ -1100,6 +1139,9 @@ int vbx_session_path_bind_channels(vbx_session *s, double peak_ref, size_t max_p
  * of the segment lists and of the clip table: a buffer is reused once its last copy has left it), and it is NOT capturable into a
  * graph.  Device memory: context-owned workspaces for one group's plane and staging rows, about VBX_CLIPS_PLANE_BYTES at the default
  * group size.  Afterwards there is no state for vbx_track_stitch_f64, and the vbx_internal_last_* probes describe the last group only.
+ * 8-bit sources (VBX_SAMPLE_U8 / ULAW / ALAW, one byte per sample, any byte address): every byte written for a ULAW or ALAW source
+ * equals, bit for bit, what the same call writes for PCM16 on the decoded int16 samples (vbx_g711_table), and every byte written for
+ * U8 equals what it writes for F64 on (b - 128) / 127 -- the bytes are decoded inside this call's own reader kernel, never in a pass before it.
  * VBX_E_INVALID, before anything is written and with the context left usable: a NULL array with n_clips > 0; a NULL clip pointer
  * with a length that gives a frame; a clip pointer not aligned to its element type (PCM24: any address); an unknown format or a
  * non-zero reserved; 0 < group_frames < VBX_CLIPS_MIN_GROUP_FRAMES; more than 0x7fffffff total rows; anything
@@ -1116,7 +1158,7 @@ int vbx_session_path_bind_channels(vbx_session *s, double peak_ref, size_t max_p
 #define VBX_CLIPS_MIN_GROUP_FRAMES 64
 #define VBX_CLIPS_PLANE_BYTES 268435456
 typedef struct {
-    int32_t format;        /* VBX_SAMPLE_* : PCM16, PCM24, PCM32, F32, F64 -- mono, contiguous samples */
+    int32_t format;        /* VBX_SAMPLE_* : PCM16, PCM24, PCM32, F32, F64, U8, ULAW, ALAW -- mono, contiguous samples */
     int32_t reserved;      /* must be 0 */
     size_t group_frames;   /* analysis frames per internal group; 0: the library's default */
 } vbx_clip_format;

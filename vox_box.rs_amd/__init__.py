@@ -21,7 +21,7 @@ from .voxbox import (  # noqa: F401
     Session, SessionPlan, session_plan, SessionChannels, SessionChannelsPlan, ChannelPathOutputs, session_channels_plan, PathStream, PathCommit, commit_of,
     ClipFormat, ClipRow, clips_plan, CLIPS_MIN_GROUP_FRAMES, CLIPS_PLANE_BYTES,
     HostAudio, host_chunk_plan, HOST_DEFAULT_CHUNK_FRAMES, ChannelOutputs, HOST_MAX_CHANNELS,
-    SAMPLE_PCM16, SAMPLE_PCM24, SAMPLE_PCM32, SAMPLE_F32, SAMPLE_F64,
+    SAMPLE_PCM16, SAMPLE_PCM24, SAMPLE_PCM32, SAMPLE_F32, SAMPLE_F64, SAMPLE_U8, SAMPLE_ULAW, SAMPLE_ALAW, g711_table,
     GATHER_NONE, GATHER_RECV, GATHER_SEND, GATHER_COPY,
     MAX_PITCH_CANDIDATES, pitch_max_candidates,
     LPC_POLICY_EXACT, LPC_POLICY_PLAIN, LPC_POLICY_REFERENCE,

@@ -1,7 +1,10 @@
 // k_reader.hip -- what a WAV reader hands over, turned into the type the frame loop reads natively (vbx_unpack_samples, and the
 // per-chunk step of vbx_analyze_host): ONE channel of interleaved sample frames,
 //   16-bit PCM -> int16 (the PCM kernels' input), 24-bit packed / 32-bit PCM -> f64 = s / (i32::MAX >> (32 - bits)), correctly
-//   rounded (tests/lib.rs:17-19), float / double -> as they are (copied as bit patterns: NaN payloads survive).
+//   rounded (tests/lib.rs:17-19), float / double -> as they are (copied as bit patterns: NaN payloads survive);
+//   one byte per sample: G.711 mu-law / A-law -> int16 (the ITU expansion, integer arithmetic in registers: vbx_sample8.hpp),
+//   unsigned 8-bit PCM -> f64 = (b - 128) / 127.  A lane's 16 output bytes are 8 source bytes of G.711 (one 8-byte load from a mono
+//   source on an 8-byte boundary) or 2 of unsigned PCM (one 2-byte load); such a source may sit at any byte address.
 // HBM-bound byte work: one pass, grid-stride over groups of consecutive OUTPUT elements, capped grid, size_t indices.  A lane
 // owns 16 consecutive output bytes per step, so every wave instruction touches ONE contiguous span: with a 16-byte aligned
 // destination a wave's store is 1 KiB, and a mono source of matching alignment arrives by one load per lane of the same shape
@@ -28,7 +31,7 @@ __global__ __launch_bounds__(256) void unpack_kernel(const unsigned char *__rest
     const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t step = (size_t)gridDim.x * blockDim.x;
     const bool vec_out = (reinterpret_cast<uintptr_t>(out) & 15) == 0;                        // kernel-uniform
-    const bool wide_in = FMT != UNPACK_PCM24 && channels == 1 && (reinterpret_cast<uintptr_t>(src) & (FMT == UNPACK_PCM32 ? 7 : 15)) == 0;
+    const bool wide_in = FMT != UNPACK_PCM24 && channels == 1 && (reinterpret_cast<uintptr_t>(src) & (R::W - 1)) == 0;
     const size_t ng = vec_out ? n / R::G : 0;
     for (size_t g = t0; g < ng; g += step) {
         alignas(16) out_t v[R::G];
@@ -202,6 +205,9 @@ void launch_unpack(hipStream_t s, int format, const void *src, size_t n, size_t 
         case UNPACK_PCM32: launch_unpack_as<UNPACK_PCM32>(s, src, n, channels, channel, out); break;
         case UNPACK_F32: launch_unpack_as<UNPACK_F32>(s, src, n, channels, channel, out); break;
         case UNPACK_F64: launch_unpack_as<UNPACK_F64>(s, src, n, channels, channel, out); break;
+        case UNPACK_U8: launch_unpack_as<UNPACK_U8>(s, src, n, channels, channel, out); break;
+        case UNPACK_ULAW: launch_unpack_as<UNPACK_ULAW>(s, src, n, channels, channel, out); break;
+        case UNPACK_ALAW: launch_unpack_as<UNPACK_ALAW>(s, src, n, channels, channel, out); break;
     }
 }
 
@@ -215,6 +221,9 @@ void launch_unpack_all(hipStream_t s, int format, const void *src, size_t n, siz
         case UNPACK_PCM32: launch_unpack_all_as<UNPACK_PCM32>(s, src, n, channels, sel, n_sel, out, plane_ld); break;
         case UNPACK_F32: launch_unpack_all_as<UNPACK_F32>(s, src, n, channels, sel, n_sel, out, plane_ld); break;
         case UNPACK_F64: launch_unpack_all_as<UNPACK_F64>(s, src, n, channels, sel, n_sel, out, plane_ld); break;
+        case UNPACK_U8: launch_unpack_all_as<UNPACK_U8>(s, src, n, channels, sel, n_sel, out, plane_ld); break;
+        case UNPACK_ULAW: launch_unpack_all_as<UNPACK_ULAW>(s, src, n, channels, sel, n_sel, out, plane_ld); break;
+        case UNPACK_ALAW: launch_unpack_all_as<UNPACK_ALAW>(s, src, n, channels, sel, n_sel, out, plane_ld); break;
     }
 }
 

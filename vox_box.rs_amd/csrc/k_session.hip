@@ -1,7 +1,8 @@
 // k_session.hip -- the two kernels a live session (vbx_session_push) puts around the frame loop.
 // session_ingest_<fmt>: ONE launch builds a push's input in the session's other carry buffer: elements [0, keep) are the kept tail of
 //   the old buffer (from element `drop`), behind them the selected channel of the new block, turned into the type the frame loop
-//   reads by the readers' own arithmetic (vbx_reader.hpp: correctly rounded PCM24 / PCM32 quotients, floats as bit patterns).  The
+//   reads by the readers' own arithmetic (vbx_reader.hpp: correctly rounded PCM24 / PCM32 / U8 quotients, floats as bit patterns,
+//   G.711 decoded to int16 -- the kept tail is carried DECODED, in the plane's type, for every format).  The
 //   two buffers ping-pong, so the move never overlaps itself.  As in k_reader.hip a lane owns 16 consecutive output bytes and stores
 //   them at once (the carry's base is 256-byte aligned); a group that lies wholly in the kept tail or wholly in a mono block is loaded
 //   by one load per lane where that source's address allows it, element by element otherwise -- the same bits either way.  The
@@ -36,7 +37,7 @@ __global__ __launch_bounds__(256) void session_ingest_kernel(const typename read
     const bool wide_old = (reinterpret_cast<uintptr_t>(old) & 15) == 0;
     const size_t lead = (R::G - keep % R::G) % R::G;                            // new elements that complete the group the tail ends in
     const bool wide_new = FMT != UNPACK_PCM24 && channels == 1 &&
-                          ((reinterpret_cast<uintptr_t>(raw) + lead * R::B) & (FMT == UNPACK_PCM32 ? 7 : 15)) == 0;
+                          ((reinterpret_cast<uintptr_t>(raw) + lead * R::B) & (R::W - 1)) == 0;
     auto one = [&](size_t i) -> out_t { return i < keep ? old[i] : read_one<FMT>(raw, (i - keep) * channels + channel); };
     const size_t ng = vec_out ? total / R::G : 0;
     for (size_t g = t0; g < ng; g += step) {
@@ -105,6 +106,9 @@ void launch_session_ingest(hipStream_t s, int format, const void *old, size_t dr
         case UNPACK_PCM32: launch_ingest_as<UNPACK_PCM32>(s, old, drop, keep, raw, n_new, channels, channel, out); break;
         case UNPACK_F32: launch_ingest_as<UNPACK_F32>(s, old, drop, keep, raw, n_new, channels, channel, out); break;
         case UNPACK_F64: launch_ingest_as<UNPACK_F64>(s, old, drop, keep, raw, n_new, channels, channel, out); break;
+        case UNPACK_U8: launch_ingest_as<UNPACK_U8>(s, old, drop, keep, raw, n_new, channels, channel, out); break;
+        case UNPACK_ULAW: launch_ingest_as<UNPACK_ULAW>(s, old, drop, keep, raw, n_new, channels, channel, out); break;
+        case UNPACK_ALAW: launch_ingest_as<UNPACK_ALAW>(s, old, drop, keep, raw, n_new, channels, channel, out); break;
     }
 }
 

@@ -10,8 +10,10 @@ using namespace vbx;
 
 extern "C" {
 
-static const char *const k_pack_names[6] = {"", "clips_pack_pcm16", "clips_pack_pcm24", "clips_pack_pcm32", "clips_pack_f32", "clips_pack_f64"};
-static_assert(UNPACK_PCM16 == VBX_SAMPLE_PCM16 && UNPACK_F64 == VBX_SAMPLE_F64, "the pack kernels take the header's formats");
+static const char *const k_pack_names[9] = {"", "clips_pack_pcm16", "clips_pack_pcm24", "clips_pack_pcm32", "clips_pack_f32", "clips_pack_f64",
+                                            "clips_pack_u8", "clips_pack_ulaw", "clips_pack_alaw"};      // by sample_name_slot
+static_assert(UNPACK_PCM16 == VBX_SAMPLE_PCM16 && UNPACK_F64 == VBX_SAMPLE_F64 && UNPACK_U8 == VBX_SAMPLE_U8 && UNPACK_ULAW == VBX_SAMPLE_ULAW &&
+              UNPACK_ALAW == VBX_SAMPLE_ALAW, "the pack kernels take the header's formats");
 
 // a * b + c in size_t, false on overflow
 static bool mul_add(size_t a, size_t b, size_t c, size_t *out) {
@@ -131,7 +133,7 @@ int vbx_analyze_clips(vbx_ctx *ctx, const void *const *h_clip, const size_t *h_l
     std::vector<int64_t> seg;
     for (const group_t &g : groups) {
         const size_t cnt = g.e1 - g.e0;
-        { Prof p(ctx, k_pack_names[fmt]); launch_clips_pack(ctx->stream, fmt, d_tab + g.e0, cnt, g.elems, plane); }
+        { Prof p(ctx, k_pack_names[sample_name_slot(fmt)]); launch_clips_pack(ctx->stream, fmt, d_tab + g.e0, cnt, g.elems, plane); }
         // every clip a segment of its own: the rows between two clips lie behind the first one's own rows in its segment
         seg.resize(cnt);
         for (size_t i = 0; i < cnt; i++) seg[i] = tab[g.e0 + i].plane_frame;
@@ -190,7 +192,7 @@ int vbx_internal_clips_pack(vbx_ctx *ctx, int format, const void *const *h_clip,
     void *d = nullptr;
     int rc = stage_upload(ctx, 3, vbx_ctx::WS_CLIPS_TAB, tab.data(), tab.size() * sizeof(clip_entry_t), ctx->stream, &d);
     if (rc != VBX_SUCCESS) return rc;
-    { Prof p(ctx, k_pack_names[format]); launch_clips_pack(ctx->stream, format, static_cast<const clip_entry_t *>(d), n_clips, total, d_out); }
+    { Prof p(ctx, k_pack_names[sample_name_slot(format)]); launch_clips_pack(ctx->stream, format, static_cast<const clip_entry_t *>(d), n_clips, total, d_out); }
     return check_launch(ctx, __func__);
 }
 

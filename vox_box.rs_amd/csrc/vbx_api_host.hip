@@ -10,10 +10,13 @@ using namespace vbx;
 
 namespace vbx {
 
-bool sample_format_ok(int f) { return f >= VBX_SAMPLE_PCM16 && f <= VBX_SAMPLE_F64; }
-size_t sample_src_bytes(int f) { return f == VBX_SAMPLE_PCM16 ? 2 : f == VBX_SAMPLE_PCM24 ? 3 : f == VBX_SAMPLE_F64 ? 8 : 4; }
-// the typed plane the frame loop reads for a VBX_SAMPLE_* format (what launch_unpack writes): PCM24 / PCM32 / F64 unpack to f64
-sample_kind_t sample_plane_kind(int f) { return f == VBX_SAMPLE_PCM16 ? SAMPLE_PCM16 : f == VBX_SAMPLE_F32 ? SAMPLE_F32 : SAMPLE_F64; }
+// the accepted set: 1..5 and the three 8-bit formats (6 and 7 are the WAV tags of A-law and mu-law, NOT formats of this library)
+bool sample_format_ok(int f) { return (f >= VBX_SAMPLE_PCM16 && f <= VBX_SAMPLE_F64) || f == VBX_SAMPLE_U8 || f == VBX_SAMPLE_ULAW || f == VBX_SAMPLE_ALAW; }
+static bool sample_is_8bit(int f) { return f == VBX_SAMPLE_U8 || f == VBX_SAMPLE_ULAW || f == VBX_SAMPLE_ALAW; }
+size_t sample_src_bytes(int f) { return sample_is_8bit(f) ? 1 : f == VBX_SAMPLE_PCM16 ? 2 : f == VBX_SAMPLE_PCM24 ? 3 : f == VBX_SAMPLE_F64 ? 8 : 4; }
+// the typed plane the frame loop reads for a VBX_SAMPLE_* format (what launch_unpack writes): PCM24 / PCM32 / F64 / U8 unpack to f64,
+// G.711 to the int16 plane of PCM16 (from there on it IS a PCM16 recording: the same kernels, the same dispatch)
+sample_kind_t sample_plane_kind(int f) { return (f == VBX_SAMPLE_PCM16 || f == VBX_SAMPLE_ULAW || f == VBX_SAMPLE_ALAW) ? SAMPLE_PCM16 : f == VBX_SAMPLE_F32 ? SAMPLE_F32 : SAMPLE_F64; }
 size_t sample_out_bytes(int f) { static const size_t bytes[3] = {8, 2, 4}; return bytes[sample_plane_kind(f)]; }
 
 // the copy stream, the slots' events and the two raw slots of `bytes` each (grown on demand: both streams are drained first)
@@ -51,7 +54,8 @@ bool channel_selection_ok(const int32_t *h_channels, size_t n_sel, int channels,
 
 extern "C" {
 
-static const char *const k_unpack_names[6] = {"", "unpack_pcm16", "unpack_pcm24", "unpack_pcm32", "unpack_f32", "unpack_f64"};
+static const char *const k_unpack_names[9] = {"", "unpack_pcm16", "unpack_pcm24", "unpack_pcm32", "unpack_f32", "unpack_f64",
+                                              "unpack_u8", "unpack_ulaw", "unpack_alaw"};      // by sample_name_slot
 
 int vbx_unpack_samples(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames, int format, int channels, int channel, void *d_out) {
     VBX_REQUIRE(ctx, ctx != nullptr, "null context");
@@ -62,11 +66,12 @@ int vbx_unpack_samples(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames, 
     VBX_REQUIRE(ctx, format == VBX_SAMPLE_PCM24 || (uintptr_t)d_src % sample_src_bytes(format) == 0, "the source needs its type's alignment");
     VBX_REQUIRE(ctx, (uintptr_t)d_out % sample_out_bytes(format) == 0, "the destination needs its type's alignment");
     VBX_HIP(ctx, hipSetDevice(ctx->device));
-    { Prof p(ctx, k_unpack_names[format]); launch_unpack(ctx->stream, format, d_src, n_sample_frames, (size_t)channels, (size_t)channel, d_out); }
+    { Prof p(ctx, k_unpack_names[sample_name_slot(format)]); launch_unpack(ctx->stream, format, d_src, n_sample_frames, (size_t)channels, (size_t)channel, d_out); }
     return check_launch(ctx, __func__);
 }
 
-static const char *const k_unpack_all_names[6] = {"", "unpack_all_pcm16", "unpack_all_pcm24", "unpack_all_pcm32", "unpack_all_f32", "unpack_all_f64"};
+static const char *const k_unpack_all_names[9] = {"", "unpack_all_pcm16", "unpack_all_pcm24", "unpack_all_pcm32", "unpack_all_f32", "unpack_all_f64",
+                                                  "unpack_all_u8", "unpack_all_ulaw", "unpack_all_alaw"};
 static_assert(UNPACK_MAX_SEL == VBX_HOST_MAX_CHANNELS, "the selection is a kernel argument of VBX_HOST_MAX_CHANNELS entries");
 
 int vbx_unpack_channels(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames, int format, int channels, const int32_t *h_channels,
@@ -83,7 +88,7 @@ int vbx_unpack_channels(vbx_ctx *ctx, const void *d_src, size_t n_sample_frames,
     VBX_REQUIRE(ctx, format == VBX_SAMPLE_PCM24 || (uintptr_t)d_src % sample_src_bytes(format) == 0, "the source needs its type's alignment");
     VBX_REQUIRE(ctx, (uintptr_t)d_out % sample_out_bytes(format) == 0, "the destination needs its type's alignment");
     VBX_HIP(ctx, hipSetDevice(ctx->device));
-    { Prof p(ctx, k_unpack_all_names[format]);
+    { Prof p(ctx, k_unpack_all_names[sample_name_slot(format)]);
       launch_unpack_all(ctx->stream, format, d_src, n_sample_frames, (size_t)channels, sel, n_sel, d_out, plane_ld); }
     return check_launch(ctx, __func__);
 }
@@ -175,7 +180,7 @@ static int analyze_host_impl(vbx_ctx *ctx, const char *fn, const void *h_audio, 
     const size_t nmax = (nc == 1) ? F : (cf + VBX_SHARD_WARM_FRAMES < F ? cf + VBX_SHARD_WARM_FRAMES : F);
     const size_t ns_max = (nmax - 1) * stride + frame_len;                    // sample frames of the largest chunk
     const size_t sf_bytes = C * sample_src_bytes(fmt);                        // one interleaved sample frame
-    // mono PCM16 / F32 / F64: the slot holds the frame loop's type already
+    // mono PCM16 / F32 / F64: the slot holds the frame loop's type already (an 8-bit slot never does: its bytes are always unpacked)
     const bool unpack = !(C == 1 && (fmt == VBX_SAMPLE_PCM16 || fmt == VBX_SAMPLE_F32 || fmt == VBX_SAMPLE_F64));
     int rc = ensure_host_slots(ctx, ns_max * sf_bytes);
     if (rc != VBX_SUCCESS) return rc;
@@ -246,9 +251,9 @@ static int analyze_host_impl(vbx_ctx *ctx, const char *fn, const void *h_audio, 
         const size_t first = pl.lo - pl.warm, n = pl.hi - first, own = pl.hi - pl.lo;
         VBX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->host_ready[slot], 0));
         if (unpack) {
-            if (sel) { Prof p(ctx, k_unpack_all_names[fmt]);
+            if (sel) { Prof p(ctx, k_unpack_all_names[sample_name_slot(fmt)]);
                        launch_unpack_all(ctx->stream, fmt, ctx->host_raw[slot], s1 - s0, C, *sel, n_sel, typed, plane_bytes / sample_out_bytes(fmt)); }
-            else { Prof p(ctx, k_unpack_names[fmt]); launch_unpack(ctx->stream, fmt, ctx->host_raw[slot], s1 - s0, C, ch, typed); }
+            else { Prof p(ctx, k_unpack_names[sample_name_slot(fmt)]); launch_unpack(ctx->stream, fmt, ctx->host_raw[slot], s1 - s0, C, ch, typed); }
             VBX_HIP(ctx, hipEventRecord(ctx->host_freed[slot], ctx->stream));
         }
         const int64_t *seg_c = nullptr; size_t nseg_c = 0;

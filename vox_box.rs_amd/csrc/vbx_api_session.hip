@@ -15,10 +15,11 @@ extern "C" {
 // copy of about 10 us at this size, which is what the copy stream's event round trip was measured to add to a push (DESIGN.md
 // section 5g); larger blocks take the copy stream, where their upload runs beside the previous block's analysis
 #define VBX_SESSION_STAGE_BYTES 131072
-static const char *const k_ingest_names[6] = {"", "session_ingest_pcm16", "session_ingest_pcm24", "session_ingest_pcm32", "session_ingest_f32",
-                                              "session_ingest_f64"};
-static const char *const k_ingest_all_names[6] = {"", "session_ingest_all_pcm16", "session_ingest_all_pcm24", "session_ingest_all_pcm32",
-                                                  "session_ingest_all_f32", "session_ingest_all_f64"};
+static const char *const k_ingest_names[9] = {"", "session_ingest_pcm16", "session_ingest_pcm24", "session_ingest_pcm32", "session_ingest_f32",
+                                              "session_ingest_f64", "session_ingest_u8", "session_ingest_ulaw", "session_ingest_alaw"};      // by sample_name_slot
+static const char *const k_ingest_all_names[9] = {"", "session_ingest_all_pcm16", "session_ingest_all_pcm24", "session_ingest_all_pcm32",
+                                                  "session_ingest_all_f32", "session_ingest_all_f64", "session_ingest_all_u8",
+                                                  "session_ingest_all_ulaw", "session_ingest_all_alaw"};
 
 // One channel of one stream of audio, analysed block by block.  The session owns what lives between pushes and everything a push
 // writes before the caller's arrays: the two carry buffers (ping-pong: a push's ingest writes the other one), the two raw staging
@@ -269,7 +270,7 @@ static int session_push_impl(vbx_session *s, const char *fn, const void *block, 
     // a later one may.  (stride > frame_len: nb may lie beyond the carried samples, inside the block; the gap's samples are dropped)
     const size_t c = s->consumed, nb = nf ? pl.read_from : pl.keep_from;
     const size_t from_old = nb < c ? nb : c, skip = nb > c ? nb - c : 0;
-    { Prof p(ctx, k_ingest_names[s->fmt]);
+    { Prof p(ctx, k_ingest_names[sample_name_slot(s->fmt)]);
       launch_session_ingest(ctx->stream, s->fmt, s->carry[s->cur], from_old - s->base, c - from_old,
                             static_cast<const char *>(raw) + skip * sf_bytes, n - skip, s->channels, s->channel, s->carry[s->cur ^ 1]); }
     if (slot >= 0) VBX_HIP(ctx, hipEventRecord(s->freed[slot], ctx->stream));
@@ -448,7 +449,7 @@ int vbx_internal_session_ingest(vbx_ctx *ctx, int format, int channels, int chan
     VBX_REQUIRE(ctx, (uintptr_t)d_out % sample_out_bytes(format) == 0 && (uintptr_t)d_old % sample_out_bytes(format) == 0,
                 "the carry buffers need their type's alignment");
     VBX_HIP(ctx, hipSetDevice(ctx->device));
-    { Prof p(ctx, k_ingest_names[format]);
+    { Prof p(ctx, k_ingest_names[sample_name_slot(format)]);
       launch_session_ingest(ctx->stream, format, d_old, drop, keep, d_raw, n_new, (size_t)channels, (size_t)channel, d_out); }
     return check_launch(ctx, __func__);
 }
@@ -503,7 +504,7 @@ static int session_push_channels_impl(vbx_session *s, const char *fn, const void
     }
     // the other carry buffer, every plane from sample frame cp.base on (session_push_impl's rule, per plane)
     const size_t c = s->consumed, from_old = c - cp.keep, skip = cp.base > c ? cp.base - c : 0;
-    { Prof p(ctx, k_ingest_all_names[s->fmt]);
+    { Prof p(ctx, k_ingest_all_names[sample_name_slot(s->fmt)]);
       launch_session_ingest_all(ctx->stream, s->fmt, s->carry[s->cur], s->plane_ld, from_old - s->base, cp.keep,
                                 static_cast<const char *>(raw) + skip * sf_bytes, n - skip, s->channels, s->sel, K, s->carry[s->cur ^ 1], cp.plane_ld); }
     if (slot >= 0) VBX_HIP(ctx, hipEventRecord(s->freed[slot], ctx->stream));
@@ -584,7 +585,7 @@ int vbx_internal_session_ingest_channels(vbx_ctx *ctx, int format, int channels,
     VBX_REQUIRE(ctx, (uintptr_t)d_out % sample_out_bytes(format) == 0 && (uintptr_t)d_old % sample_out_bytes(format) == 0,
                 "the carry buffers need their type's alignment");
     VBX_HIP(ctx, hipSetDevice(ctx->device));
-    { Prof p(ctx, k_ingest_all_names[format]);
+    { Prof p(ctx, k_ingest_all_names[sample_name_slot(format)]);
       launch_session_ingest_all(ctx->stream, format, d_old, old_ld, drop, keep, d_raw, n_new, (size_t)channels, sel, n_sel, d_out, out_ld); }
     return check_launch(ctx, __func__);
 }

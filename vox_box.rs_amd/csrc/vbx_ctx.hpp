@@ -204,6 +204,8 @@ int analyze_ex(vbx_ctx *ctx, const char *fn, frames_t x, size_t n_frames, size_t
 // ---- host-resident recordings (vbx_api_host.hip) -----------------------------------------------
 
 bool sample_format_ok(int f);
+// where the per-format tables of profile names keep a format's entry: 1..5 as they are, the 8-bit formats (16, 17, 18) at 6, 7, 8
+inline int sample_name_slot(int f) { return f >= VBX_SAMPLE_U8 ? f - VBX_SAMPLE_U8 + 6 : f; }
 size_t sample_src_bytes(int f);
 sample_kind_t sample_plane_kind(int f);
 size_t sample_out_bytes(int f);

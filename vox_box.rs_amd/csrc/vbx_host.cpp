@@ -5,6 +5,7 @@
 // (tools/host_asan/Makefile).
 #include "../../include/voxbox_hip.h"
 #include "vbx_host.hpp"
+#include "vbx_sample8.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -543,6 +544,14 @@ int vbx_session_channels_plan(size_t consumed, size_t utt_frame, size_t n_new, s
 // than one hop and every frame of [plane_frame_b, plane_frame_b + n_rows_b) reads clip b's own samples only.  Frames longer than
 // VBX_MAX_FRAME_LEN: every clip is a group by itself -- the long-frame kernels (k_long.hip) choose how they split a frame's sums
 // from the frame count of the call, so only a call of the clip's own frame count gives the resident call's bits.
+// the 256 values of a G.711 law, by the function the reader kernels run (vbx_sample8.hpp)
+int vbx_g711_table(int format, int16_t *h_out) {
+    if (format != VBX_SAMPLE_ULAW && format != VBX_SAMPLE_ALAW) return fail(nullptr, VBX_E_INVALID, "vbx_g711_table: format must be VBX_SAMPLE_ULAW or VBX_SAMPLE_ALAW");
+    if (!h_out) return fail(nullptr, VBX_E_INVALID, "vbx_g711_table: null output");
+    for (uint32_t b = 0; b < 256; b++) h_out[b] = format == VBX_SAMPLE_ULAW ? vbx::ulaw_value(b) : vbx::alaw_value(b);
+    return VBX_SUCCESS;
+}
+
 int vbx_clips_plan(const size_t *h_len, size_t n_clips, size_t frame_len, size_t stride, size_t group_frames, vbx_clip_row *h_rows,
                    size_t *h_total_rows, size_t *h_n_groups) {
     if (h_total_rows) *h_total_rows = 0;

@@ -337,7 +337,9 @@ void launch_preemphasis(hipStream_t s, const double *x, long F, int n, long stri
 // k_reader.hip: channel `channel` of n interleaved sample frames of `channels` samples each, as the type the frame loop reads natively
 // (format = VBX_SAMPLE_* of the C header: out is int16 for PCM16, float for F32, double for PCM24 / PCM32 / F64; PCM24 / PCM32 are
 // divided by 8388607 / 2147483647 with IEEE division).  A PCM24 source may sit at any byte address, the others need their type's.
-enum { UNPACK_PCM16 = 1, UNPACK_PCM24 = 2, UNPACK_PCM32 = 3, UNPACK_F32 = 4, UNPACK_F64 = 5 };
+// One byte per sample (any byte address): U8 -> double, (b - 128) / 127 with IEEE division; ULAW / ALAW -> int16, the G.711 expansion
+// (vbx_sample8.hpp), which the PCM16 kernels then read as any 16-bit sample.
+enum { UNPACK_PCM16 = 1, UNPACK_PCM24 = 2, UNPACK_PCM32 = 3, UNPACK_F32 = 4, UNPACK_F64 = 5, UNPACK_U8 = 16, UNPACK_ULAW = 17, UNPACK_ALAW = 18 };
 void launch_unpack(hipStream_t s, int format, const void *src, size_t n, size_t channels, size_t channel, void *out);
 // the same for n_sel selected channels in ONE pass over the interleaved frames (vbx_unpack_channels): plane k = channel sel.ch[k], n
 // elements from element k * plane_ld of out, bit for bit what launch_unpack writes for that channel.  The selection travels as a
@@ -398,6 +400,12 @@ struct clip_entry_t {
 // end and the next clip's off; tab[0].off == 0, total > tab[n - 1].off, and the last clip has at least total - off samples.  Every
 // element is written once; no sample past a clip's len is read.
 void launch_clips_pack(hipStream_t s, int format, const clip_entry_t *tab, size_t n, size_t total, void *plane);
+// k_sample8.hip: the 8-bit formats (U8 / ULAW / ALAW) of the two kernel templates that k_session_channels.hip and k_clips.hip
+// instantiate for the other five (vbx_session_ingest_all.hpp, vbx_clips_pack.hpp); launch_session_ingest_all and launch_clips_pack
+// hand these formats on to them, so callers see one launcher each.
+void launch_session_ingest_all8(hipStream_t s, int format, const void *old, size_t old_ld, size_t drop, size_t keep, const void *raw,
+                                size_t n_new, size_t channels, const unpack_sel_t &sel, size_t n_sel, void *out, size_t out_ld);
+void launch_clips_pack8(hipStream_t s, int format, const clip_entry_t *tab, size_t n, size_t total, void *plane);
 // deliver: rows [plane_frame_b, + n_rows_b) of the group's staging into rows [row_start_b, ...) of the destinations (which point at
 // row 0 of the caller's arrays): the records' columns [c0, c1), the three status rows (src: [3, src_n]; dst_st[q] may be null), the
 // lists (kmax entries a row), counts and peaks where the destination is non-null.  rows = the group's delivered rows, from row0 on.

@@ -1,18 +1,34 @@
 // vbx_reader.hpp -- the per-sample arithmetic of the readers (k_reader.hip: vbx_unpack_samples; k_session.hip: a live session's
-// ingest): what one source sample becomes, and the widest load a lane's 16 output bytes can come from.  Device code only.
+// ingest; vbx_session_ingest_all.hpp, vbx_clips_pack.hpp: the multi-channel ingest and the clip pack): what one source sample becomes,
+// and the widest load a lane's 16 output bytes can come from.  Device code only.
 #pragma once
 #include "vbx_device.hpp"
 #include "vbx_kernels.hpp"
+#include "vbx_sample8.hpp"
 
 namespace vbx {
 
 template <int FMT> struct reader_t;
-// out_t: what is written; G: elements in a lane's 16 output bytes; B: bytes of a source sample
-template <> struct reader_t<UNPACK_PCM16> { using out_t = uint16_t; static constexpr int G = 8; static constexpr int B = 2; };
-template <> struct reader_t<UNPACK_PCM24> { using out_t = double;   static constexpr int G = 2; static constexpr int B = 3; };
-template <> struct reader_t<UNPACK_PCM32> { using out_t = double;   static constexpr int G = 2; static constexpr int B = 4; };
-template <> struct reader_t<UNPACK_F32>   { using out_t = uint32_t; static constexpr int G = 4; static constexpr int B = 4; };
-template <> struct reader_t<UNPACK_F64>   { using out_t = uint64_t; static constexpr int G = 2; static constexpr int B = 8; };
+// out_t: what is written; G: elements in a lane's 16 output bytes; B: bytes of a source sample; W = G * B: the bytes of the one
+// load a lane's group comes from (read_group_wide), which is also the alignment that load needs (0: there is no such load)
+template <> struct reader_t<UNPACK_PCM16> { using out_t = uint16_t; static constexpr int G = 8; static constexpr int B = 2; static constexpr int W = 16; };
+template <> struct reader_t<UNPACK_PCM24> { using out_t = double;   static constexpr int G = 2; static constexpr int B = 3; static constexpr int W = 0; };
+template <> struct reader_t<UNPACK_PCM32> { using out_t = double;   static constexpr int G = 2; static constexpr int B = 4; static constexpr int W = 8; };
+template <> struct reader_t<UNPACK_F32>   { using out_t = uint32_t; static constexpr int G = 4; static constexpr int B = 4; static constexpr int W = 16; };
+template <> struct reader_t<UNPACK_F64>   { using out_t = uint64_t; static constexpr int G = 2; static constexpr int B = 8; static constexpr int W = 16; };
+// one byte per sample: G.711 decodes to the int16 the PCM16 kernels read, unsigned 8-bit PCM to a quotient in double
+template <> struct reader_t<UNPACK_U8>    { using out_t = double;   static constexpr int G = 2; static constexpr int B = 1; static constexpr int W = 2; };
+template <> struct reader_t<UNPACK_ULAW>  { using out_t = uint16_t; static constexpr int G = 8; static constexpr int B = 1; static constexpr int W = 8; };
+template <> struct reader_t<UNPACK_ALAW>  { using out_t = uint16_t; static constexpr int G = 8; static constexpr int B = 1; static constexpr int W = 8; };
+
+// one byte of an 8-bit format, decoded (vbx_sample8.hpp)
+template <int FMT>
+__device__ __forceinline__ typename reader_t<FMT>::out_t byte_value(uint32_t b) {
+    static_assert(reader_t<FMT>::B == 1, "the 8-bit formats");
+    if constexpr (FMT == UNPACK_U8) return u8_value(b);
+    else if constexpr (FMT == UNPACK_ULAW) return (uint16_t)ulaw_value(b);
+    else return (uint16_t)alaw_value(b);
+}
 
 __device__ __forceinline__ int sext24(uint32_t v) { return (int)(v << 8) >> 8; }
 __device__ __forceinline__ double pcm24_value(int s) { return (double)s / 8388607.0; }
@@ -27,7 +43,8 @@ __device__ __forceinline__ typename reader_t<FMT>::out_t read_one(const unsigned
         return pcm24_value(sext24((uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16)));
     } else if constexpr (FMT == UNPACK_PCM32) return pcm32_value(reinterpret_cast<const int *>(src)[e]);
     else if constexpr (FMT == UNPACK_F32) return reinterpret_cast<const uint32_t *>(src)[e];
-    else return reinterpret_cast<const uint64_t *>(src)[e];
+    else if constexpr (FMT == UNPACK_F64) return reinterpret_cast<const uint64_t *>(src)[e];
+    else return byte_value<FMT>(src[e]);
 }
 
 // G consecutive mono samples from group g of a source aligned for it (wide_in below): one load per lane
@@ -37,6 +54,13 @@ __device__ __forceinline__ void read_group_wide(const unsigned char *__restrict_
     if constexpr (FMT == UNPACK_PCM32) {
         const int2 q = reinterpret_cast<const int2 *>(src)[g];
         v[0] = pcm32_value(q.x); v[1] = pcm32_value(q.y);
+    } else if constexpr (FMT == UNPACK_U8) {                   // two bytes in
+        const uint32_t h = reinterpret_cast<const uint16_t *>(src)[g];
+        v[0] = byte_value<FMT>(h & 0xffu); v[1] = byte_value<FMT>(h >> 8);
+    } else if constexpr (FMT == UNPACK_ULAW || FMT == UNPACK_ALAW) {      // eight bytes in, decoded in registers
+        const uint2 q = reinterpret_cast<const uint2 *>(src)[g];
+#pragma unroll
+        for (int j = 0; j < 4; j++) { v[j] = byte_value<FMT>((q.x >> (8 * j)) & 0xffu); v[4 + j] = byte_value<FMT>((q.y >> (8 * j)) & 0xffu); }
     } else {                                                   // the plain copies: 16 bytes in, 16 bytes out
         const uint4 q = reinterpret_cast<const uint4 *>(src)[g];
         __builtin_memcpy(v, &q, 16);
@@ -56,7 +80,8 @@ __device__ __forceinline__ typename reader_t<FMT>::out_t lds_one(const uint32_t 
         return pcm24_value(sext24((uint32_t)(w >> ((b & 3) * 8))));
     } else if constexpr (FMT == UNPACK_PCM32) return pcm32_value((int)tile[b >> 2]);
     else if constexpr (FMT == UNPACK_F32) return tile[b >> 2];
-    else return reinterpret_cast<const uint64_t *>(tile)[b >> 3];
+    else if constexpr (FMT == UNPACK_F64) return reinterpret_cast<const uint64_t *>(tile)[b >> 3];
+    else return byte_value<FMT>((tile[b >> 2] >> ((b & 3) * 8)) & 0xffu);      // a byte at any byte offset of the tile's dwords
 }
 
 // a block of 256 lanes (lane t) stages tile_bytes (a multiple of 16, <= UNPACK_ALL_TILE_BYTES) from w into the 16-byte aligned tile:

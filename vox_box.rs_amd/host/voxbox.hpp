@@ -21,6 +21,7 @@
 // runtime failures throw voxbox::Error.  There is no CPU fallback.
 #pragma once
 
+#include <array>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
@@ -429,12 +430,19 @@ inline void analyze_host_channels(Context &c, const void *h_audio, size_t n_samp
 // A batch of variable-length clips in separate device buffers from ONE call (vbx_analyze_clips): h_clip holds n_clips device
 // pointers (a host array), h_len their lengths in samples; clip b's rows are rows [row_start_b, row_start_b + n_rows_b) of every
 // output (clips_plan gives them), bit for bit what the resident call writes on that clip alone.  clip_format(): the default groups.
+// (8-bit clips -- VBX_SAMPLE_U8 / VBX_SAMPLE_ULAW / VBX_SAMPLE_ALAW, one byte per sample -- are named in clip_format like any other.)
 using ClipFormat = vbx_clip_format;
 using ClipRow = vbx_clip_row;
 inline ClipFormat clip_format(int format, size_t group_frames = 0) {
     ClipFormat f{};
     f.format = format; f.group_frames = group_frames;
     return f;
+}
+// The 256 16-bit linear values of a G.711 law (VBX_SAMPLE_ULAW or VBX_SAMPLE_ALAW), by the function the reader kernels run; host only.
+inline std::array<int16_t, 256> g711_table(int format) {
+    std::array<int16_t, 256> t{};
+    if (vbx_g711_table(format, t.data()) != VBX_SUCCESS) throw Error(VBX_E_INVALID, "g711_table: format must be VBX_SAMPLE_ULAW or VBX_SAMPLE_ALAW");
+    return t;
 }
 struct ClipsPlan { std::vector<ClipRow> rows; size_t total_rows = 0, n_groups = 0; };
 inline ClipsPlan clips_plan(const size_t *h_len, size_t n_clips, size_t frame_len, size_t stride, size_t group_frames = 0) {

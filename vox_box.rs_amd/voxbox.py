@@ -138,11 +138,17 @@ class AnalysisExt(C.Structure):
 
 
 SAMPLE_PCM16, SAMPLE_PCM24, SAMPLE_PCM32, SAMPLE_F32, SAMPLE_F64 = 1, 2, 3, 4, 5
+# one byte per sample: unsigned 8-bit PCM, (b - 128) / 127 as a double; G.711 mu-law / A-law, decoded to the int16 of PCM16 (g711_table).
+# Never inferred from a dtype -- a uint8 array is also how packed PCM24 is handed over -- the caller names them.  (6 and 7, the WAV
+# tags of A-law and mu-law, are not formats.)
+SAMPLE_U8, SAMPLE_ULAW, SAMPLE_ALAW = 16, 17, 18
+_SAMPLE_8BIT = (SAMPLE_U8, SAMPLE_ULAW, SAMPLE_ALAW)
 _SAMPLE_OF_DTYPE = {np.dtype(np.int16): SAMPLE_PCM16, np.dtype(np.int32): SAMPLE_PCM32, np.dtype(np.float32): SAMPLE_F32,
                     np.dtype(np.float64): SAMPLE_F64}
-_SAMPLE_SRC_BYTES = {SAMPLE_PCM16: 2, SAMPLE_PCM24: 3, SAMPLE_PCM32: 4, SAMPLE_F32: 4, SAMPLE_F64: 8}
+_SAMPLE_SRC_BYTES = {SAMPLE_PCM16: 2, SAMPLE_PCM24: 3, SAMPLE_PCM32: 4, SAMPLE_F32: 4, SAMPLE_F64: 8, SAMPLE_U8: 1, SAMPLE_ULAW: 1,
+                     SAMPLE_ALAW: 1}
 _SAMPLE_OUT_DTYPE = {SAMPLE_PCM16: np.int16, SAMPLE_PCM24: np.float64, SAMPLE_PCM32: np.float64, SAMPLE_F32: np.float32,
-                     SAMPLE_F64: np.float64}
+                     SAMPLE_F64: np.float64, SAMPLE_U8: np.float64, SAMPLE_ULAW: np.int16, SAMPLE_ALAW: np.int16}
 HOST_DEFAULT_CHUNK_FRAMES = 250000
 
 
@@ -385,6 +391,7 @@ def load_library():
         "vbx_internal_session_ingest": (C.c_int, [vp, i32, i32, i32, vp, sz, sz, vp, sz, vp]),
         "vbx_session_path_bind_channels": (C.c_int, [vp, dbl, sz, C.POINTER(ChannelPathOutputs), sz]),
         "vbx_internal_session_ingest_channels": (C.c_int, [vp, i32, i32, vp, sz, vp, sz, sz, sz, vp, sz, vp, sz]),
+        "vbx_g711_table": (C.c_int, [i32, C.POINTER(C.c_int16)]),
         "vbx_clips_plan": (C.c_int, [C.POINTER(sz), sz, sz, sz, sz, C.POINTER(ClipRow), C.POINTER(sz), C.POINTER(sz)]),
         "vbx_analyze_clips": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), sz, C.POINTER(ClipFormat), sz, sz, C.POINTER(AnalysisParams),
                                         C.POINTER(AnalysisExt), C.POINTER(PitchTrackParams), vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
@@ -525,6 +532,15 @@ def session_channels_plan(consumed, utt_frame, n_new, frame_len, stride, elem_by
                                                 int(n_sel), C.byref(plan), seg.ctypes.data_as(C.POINTER(C.c_int64)) if ok else None) != 0:
         raise VoxBoxError("vbx_session_channels_plan: bad argument")
     return plan, seg
+
+
+def g711_table(format):
+    """vbx_g711_table: the 256 16-bit linear values of a G.711 law (SAMPLE_ULAW or SAMPLE_ALAW) as an int16 array, by the function
+    the reader kernels run.  Host arithmetic only: table[codes] decodes a uint8 array."""
+    out = np.empty(256, np.int16)
+    if load_library().vbx_g711_table(int(format), out.ctypes.data_as(C.POINTER(C.c_int16))) != 0:
+        raise VoxBoxError("vbx_g711_table: format must be SAMPLE_ULAW or SAMPLE_ALAW")
+    return out
 
 
 def clips_plan(lengths, frame_len, stride, group_frames=0):
@@ -726,7 +742,7 @@ class Session:
 
     def push(self, block, out=None, status=None, outputs=None, record_ld=None, status_ld=None):
         """vbx_session_push: the next block of the stream, from HOST memory -- a numpy array of the session's sample type shaped
-        [T] or [T, channels], or bytes / a uint8 array of packed 24-bit PCM.  Returns what analyze_frames_ex returns for the frames
+        [T] or [T, channels], or bytes / a uint8 array of packed 24-bit PCM or of the session's 8-bit format.  Returns what analyze_frames_ex returns for the frames
         the block completes: (records [n, ld], status3 [3, n]), in the tracked form also (cand [n, kmax, 2], count, peak) and
         columns 0-1 of the records left as NaN -- or None when out= (device records; status= and outputs= = (cand, count, peak,
         None) device buffers, status_ld= the status rows' leading dimension, default n) is given."""
@@ -1767,7 +1783,8 @@ class VoxBox:
 
     def unpack_samples(self, src, n_sample_frames, format, channels=1, channel=0, out=None):
         """vbx_unpack_samples: channel `channel` of n interleaved sample frames on the device, as the type the frame loop reads
-        (int16 for PCM16, float32 for F32, float64 for PCM24 / PCM32 / F64).  src / out: device buffers or raw addresses."""
+        (int16 for PCM16 / ULAW / ALAW, float32 for F32, float64 for PCM24 / PCM32 / F64 / U8).  src / out: device buffers or raw
+        addresses."""
         n = int(n_sample_frames)
         o = out if out is not None else self.empty(n, _SAMPLE_OUT_DTYPE[format])
         self._check(self.L.vbx_unpack_samples(self.ctx, _ptr(src), n, int(format), int(channels), int(channel), _ptr(o)))
@@ -1779,6 +1796,7 @@ class VoxBox:
         """vbx_analyze_host: the frame loop on a recording in HOST memory, chunk by chunk with the uploads overlapped; the recording
         is never resident on the device, the records are.  audio: a numpy array of int16 / int32 / float32 / float64 shaped [T] or
         [T, C] (format and channels follow from it); bytes / bytearray / a uint8 array of packed 24-bit PCM (format=SAMPLE_PCM24,
+        channels=) or of an 8-bit format (format=SAMPLE_U8 / SAMPLE_ULAW / SAMPLE_ALAW, always named; [T], [T, C] or flat with
         channels=); or a raw host address with format=, channels= and n_sample_frames=.  Returns what analyze_frames_ex returns."""
         assert frame_len and stride
         keep, fmt, addr, channels, n_sample_frames = self._host_audio(audio, format, channels, n_sample_frames)
@@ -1795,7 +1813,8 @@ class VoxBox:
         """vbx_analyze_clips: the frame loop on a batch of variable-length clips in device memory, from one call.  clips: a list of
         1-D device buffers (DeviceArrays -- format and lengths follow from them -- or raw addresses with format= and lengths=), or
         ONE 2-D padded DeviceArray [B, Tmax] with lengths[B] (row b's first lengths[b] samples are clip b).  PCM24 clips are uint8
-        DeviceArrays / addresses with format=SAMPLE_PCM24 and lengths= in samples.  Clip b's rows are rows [row_start_b, +n_rows_b)
+        DeviceArrays / addresses with format=SAMPLE_PCM24 and lengths= in samples; 8-bit clips (SAMPLE_U8 / ULAW / ALAW) are uint8
+        DeviceArrays / addresses with the format named.  Clip b's rows are rows [row_start_b, +n_rows_b)
         of everything returned (clips_plan gives them), bit for bit the resident call's on that clip alone.  Returns what
         analyze_frames_ex returns."""
         assert frame_len and stride and params is not None
@@ -1812,6 +1831,7 @@ class VoxBox:
             if lengths is None:
                 assert all(isinstance(c, DeviceArray) and len(c.shape) == 1 for c in clips), "lengths= is needed for raw addresses"
                 lengths = [c.shape[0] for c in clips]
+        assert format not in _SAMPLE_8BIT or dt is None or np.dtype(dt) == np.uint8, "an 8-bit format takes uint8 clips"
         if format is None:
             format = {np.dtype(np.int16): SAMPLE_PCM16, np.dtype(np.int32): SAMPLE_PCM32, np.dtype(np.float32): SAMPLE_F32,
                       np.dtype(np.float64): SAMPLE_F64}[np.dtype(dt)]
@@ -1862,12 +1882,16 @@ class VoxBox:
         if isinstance(keep, np.ndarray):
             if keep.dtype == np.uint8:
                 fmt = SAMPLE_PCM24 if format is None else int(format)
-                assert fmt == SAMPLE_PCM24 and keep.ndim == 1
+                assert fmt == SAMPLE_PCM24 or fmt in _SAMPLE_8BIT, "a uint8 array is packed PCM24 or a named 8-bit format"
+                if fmt in _SAMPLE_8BIT and keep.ndim == 2:
+                    channels = keep.shape[1]
+                else:
+                    assert keep.ndim == 1
                 keep = np.ascontiguousarray(keep)
-                T = keep.size // (3 * int(channels))
+                T = keep.size // (_SAMPLE_SRC_BYTES[fmt] * int(channels))
             else:
                 fmt = _SAMPLE_OF_DTYPE[keep.dtype]
-                assert format is None or int(format) == fmt
+                assert format is None or int(format) == fmt, "the format does not go with the array's dtype (an 8-bit format takes uint8)"
                 assert keep.ndim in (1, 2)
                 if keep.ndim == 2:
                     channels = keep.shape[1]
