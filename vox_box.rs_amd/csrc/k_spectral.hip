@@ -201,7 +201,24 @@ bool spectral_list_parked(const spectral_launch_t &L) {
            L.out_r == nullptr && !L.mfcc_only && rows16;
 }
 
-int launch_analyze(hipStream_t s, const spectral_launch_t &L) {
+// The launch-specialised instance (SP_SPEC_*, vbx_spectral.hpp) serves the three-wavefront launch of full f64 / PCM frames with
+// everything it was compiled for in place; every other launch -- and every launch of an experiment build that reads the work
+// pointer or the count early (VBX_EXP_PHASES, VBX_EXP_STOP) -- takes the generic one.  L.allow_spec: the context's
+// VBX_SPECTRAL_SPEC switch (0: the generic one; A/B, tests).  w3, extra: launch_analyze's own three-wavefront decision and LDS list.
+static int spectral_spec(const spectral_launch_t &L, bool w3, size_t extra) {
+#if defined(VBX_EXP_PHASES) || VBX_EXP_STOP != 0
+    return SP_SPEC_NONE;
+#else
+    if (!L.allow_spec || !w3 || extra != 0 || L.plan != SPECTRAL_PLAN_1200 || L.n != SP_N || L.mfcc_only || L.out_r != nullptr) return SP_SPEC_NONE;
+    if (L.x.kind != SAMPLE_F64 && L.x.kind != SAMPLE_PCM16) return SP_SPEC_NONE;
+    if (!L.lag_rcp || pitch_full_list_bytes(L.n, L.kmax) != 0) return SP_SPEC_NONE;
+    if (L.out_mfcc != nullptr && !(L.mfcc_defer && L.num_coeffs <= 16)) return SP_SPEC_NONE;
+    return L.x.kind == SAMPLE_PCM16 ? SP_SPEC_PCM16 : SP_SPEC_F64;
+#endif
+}
+
+int launch_analyze(hipStream_t s, const spectral_launch_t &L, int *launched_spec) {
+    if (launched_spec) *launched_spec = SP_SPEC_NONE;
     // (PCM / float32: full 1200-sample frames only -- the host side asks for nothing else)
     if (L.x.kind != SAMPLE_F64 && (L.plan != SPECTRAL_PLAN_1200 || L.n != SP_N)) return -1;
     spectral_args_t a;
@@ -231,12 +248,13 @@ int launch_analyze(hipStream_t s, const spectral_launch_t &L) {
     if (spectral_list_parked(L)) { a.pp.full_off = -1; extra = 0; }
     const size_t lds = base + extra;
     const bool lpc = L.out_lpc != nullptr, mf = L.out_mfcc != nullptr;
+    const spectral_args_1200_t a12(a);                       // the block without the other plans' fields (the interpolated and autocorrelation-only forms take `a`)
     if (L.mfcc_only) {                                       // n == SP_N, or a padded frame with interpolated bins
         if (L.interp && L.n != SP_N) {
             a.ip = L.ip;
             const size_t li = spectral_lds_bytes(0) > (size_t)L.ip.lds_bytes ? spectral_lds_bytes(0) : (((size_t)L.ip.lds_bytes + 15) & ~(size_t)15);
             hipLaunchKernelGGL((analyze_kernel<false, true, false, SP_MFCC_ONLY_INTERP>), grid, block, li, s, a);
-        } else hipLaunchKernelGGL((analyze_kernel<false, true, true, SP_MFCC_ONLY>), grid, block, spectral_lds_bytes(0), s, a);
+        } else hipLaunchKernelGGL((analyze_kernel<false, true, true, SP_MFCC_ONLY>), grid, block, spectral_lds_bytes(0), s, a12);
         return 0;
     }
     if (L.out_r != nullptr) {                                // autocorrelate(n_lags) alone
@@ -253,14 +271,28 @@ int launch_analyze(hipStream_t s, const spectral_launch_t &L) {
     static const bool want3 = [] { const char *e = getenv("VBX_SPECTRAL_W3"); return e == nullptr || atoi(e) != 0; }();
     const bool w3 = want3 && extra == 0 && 12 * lds <= 160 * 1024;
     if (L.x.kind == SAMPLE_F32) {
-        launch_analyze_f32in(s, a, (unsigned)L.F, lds, lpc, mf, w3);
+        launch_analyze_f32in(s, a12, (unsigned)L.F, lds, lpc, mf, w3);
         return 0;
     }
 #define VBX_SP_LAUNCH(LPC_, MF_, FULL_)                                                                              \
     do {                                                                                                              \
-        if (w3) hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, FULL_, SP_ANALYZE, 3>), grid, block, lds, s, a);        \
-        else hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, FULL_>), grid, block, lds, s, a);                          \
+        if (w3) hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, FULL_, SP_ANALYZE, 3>), grid, block, lds, s, a12);      \
+        else hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, FULL_>), grid, block, lds, s, a12);                        \
     } while (0)
+#define VBX_SP_LAUNCH_SPEC(LPC_, MF_)                                                                                                          \
+    do {                                                                                                                                        \
+        if (spec == SP_SPEC_PCM16) hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, true, SP_ANALYZE, 3, sp_launch_pcm16_t>), grid, block, lds, s, a12);   \
+        else hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, true, SP_ANALYZE, 3, sp_launch_f64_t>), grid, block, lds, s, a12);          \
+    } while (0)
+    const int spec = spectral_spec(L, w3, extra);
+    if (spec != SP_SPEC_NONE) {
+        if (launched_spec) *launched_spec = spec;            // (set here, at the branch that launches it)
+        if (lpc && mf) VBX_SP_LAUNCH_SPEC(true, true);
+        else if (lpc) VBX_SP_LAUNCH_SPEC(true, false);
+        else if (mf) VBX_SP_LAUNCH_SPEC(false, true);
+        else VBX_SP_LAUNCH_SPEC(false, false);
+        return 0;
+    }
     if (L.interp && mf && L.n != SP_N) {                     // a padded frame whose MFCC bins are interpolated from the transform's
         a.ip = L.ip;
         const size_t li = lds > (size_t)L.ip.lds_bytes ? lds : (((size_t)L.ip.lds_bytes + 15) & ~(size_t)15);
@@ -279,6 +311,7 @@ int launch_analyze(hipStream_t s, const spectral_launch_t &L) {
     else if (mf) VBX_SP_LAUNCH(false, true, true);
     else VBX_SP_LAUNCH(false, false, true);
 #undef VBX_SP_LAUNCH
+#undef VBX_SP_LAUNCH_SPEC
     return 0;
 }
 

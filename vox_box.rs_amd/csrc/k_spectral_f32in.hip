@@ -8,7 +8,7 @@
 
 namespace vbx {
 
-void launch_analyze_f32in(hipStream_t s, const spectral_args_t &a, unsigned grid, size_t lds, bool lpc, bool mfcc, bool waves3) {
+void launch_analyze_f32in(hipStream_t s, const spectral_args_1200_t &a, unsigned grid, size_t lds, bool lpc, bool mfcc, bool waves3) {
     const dim3 g(grid), b(64);
 #define VBX_SP32_LAUNCH(LPC_, MF_)                                                                                \
     do {                                                                                                           \

@@ -178,6 +178,7 @@ int vbx_ctx_create(vbx_ctx **out, int device, void *hip_stream) {
     { const char *e = std::getenv("VBX_MFCC_MFMA"); ctx->mfcc_force_mfma = e && e[0] == '1'; }
     { const char *e = std::getenv("VBX_MFCC_CZT"); ctx->mfcc_czt = e ? (e[0] == '1' ? 1 : 0) : -1; }
     { const char *e = std::getenv("VBX_MFCC_DEFER"); ctx->mfcc_defer = (e && e[0] == '0') ? 0 : 1; }
+    { const char *e = std::getenv("VBX_SPECTRAL_SPEC"); ctx->spectral_spec = (e && e[0] == '0') ? 0 : 1; }
     { const char *e = std::getenv("VBX_LPC_EXACT"); ctx->lpc_policy = (e && e[0] == '0') ? VBX_LPC_POLICY_PLAIN : VBX_LPC_POLICY_EXACT; }
     { const char *e = std::getenv("VBX_POW2_SPLIT"); ctx->pow2_split = e ? (e[0] == '0' ? 0 : 1) : -1; }
     { const char *e = std::getenv("VBX_MFCC_INTERP"); ctx->mfcc_interp = e ? (e[0] == '0' ? 0 : 1) : -1; }
@@ -521,7 +522,9 @@ int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, const ch
     // (the 1200-point plan only: in the power-of-two kernels the deferred form changes the register allocation -- thirteen index registers
     // spilled across the second transform, 3 KB of scratch traffic per frame -- for the same ~1 %; they keep the tail)
     L.mfcc_defer = L.out_mfcc != nullptr && !L.mfcc_only && L.num_coeffs >= 1 && L.num_coeffs <= 16 && ctx->mfcc_defer && L.plan == SPECTRAL_PLAN_1200;
-    { Prof p(ctx, prof_name, st); ctx->last_spectral_split = launch_analyze(st, L); }
+    L.allow_spec = ctx->spectral_spec != 0;
+    ctx->last_analyze_spec = 0;
+    { Prof p(ctx, prof_name, st); ctx->last_spectral_split = launch_analyze(st, L, &ctx->last_analyze_spec); }
     if (L.mfcc_defer && L.out_lpc == nullptr) { Prof p(ctx, "mfcc_rows", st); launch_mfcc_rows(st, L.out_mfcc, L.F, L.mfcc_ld, L.num_coeffs, L.dct); }
     {
         Prof p(ctx, "pitch_direct_fallback", st);
@@ -1161,6 +1164,7 @@ int vbx_track_stitch_f64(vbx_ctx *ctx, vbx_resonance *formants, size_t n_frames,
 }
 
 int vbx_internal_last_spectral_split(vbx_ctx *ctx) { return ctx ? ctx->last_spectral_split : 0; }
+int vbx_internal_last_analyze_spec(vbx_ctx *ctx) { return ctx ? ctx->last_analyze_spec : 0; }
 int vbx_internal_last_mfcc_interp(vbx_ctx *ctx) { return ctx ? ctx->last_mfcc_interp : 0; }
 // Every MFCC kernel is profiled as "mfcc" and every pitch kernel as "pitch": these say which one the context's last call took.
 // MFCC: 1 the fused kernels' forward transform, 2 the same with interpolated bins, 3 chirp-z, 4 matrix-core two-stage DFT,

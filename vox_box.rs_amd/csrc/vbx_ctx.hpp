@@ -52,6 +52,8 @@ struct vbx_ctx {
     int mfcc_czt = -1;                                    // VBX_MFCC_CZT=0 / 1: never / wherever it fits (tests); -1: the measured choice
     int last_mfcc_interp = 0;                             // the last vbx_mfcc_f64 call took the interpolated form (tests)
     int last_spectral_split = 0;                          // the last fused / pitch call ran as two kernels (tests)
+    int last_analyze_spec = 0;                            // the instance of the 1200-point fused kernel launch_analyze took: 0 generic, 1 / 2 launch-specialised for f64 / PCM (tests)
+    int spectral_spec = 1;                                // VBX_SPECTRAL_SPEC=0: the generic instance of the 1200-point fused kernel everywhere (A/B, tests)
     int last_mfcc_form = 0;                               // which kernel the last vbx_mfcc_f64 call launched: VBX_MFCC_FORM_* below (tests)
     int last_pitch_form = 0;                              // the same for vbx_pitch_f64: 100 * kernel family + candidate list form (tests)
     int mfcc_defer = 1;                                   // VBX_MFCC_DEFER=0: log10 + DCT of the fused call's MFCC rows inside the frame's wavefront (rounds 2-5; A/B)

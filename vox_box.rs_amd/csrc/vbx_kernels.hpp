@@ -233,6 +233,7 @@ struct spectral_launch_t {
     int plan; int n;                                             // spectral_plan(n), frame length
     frames_t x;                                                  // PCM / float32 samples: full 1200-sample frames only (k_spectral.hip, k_spectral_f32in.hip)
     long F; long stride; const double *window; const double *lag_window; const double *tab;
+    bool allow_spec;                                             // the launch may take a launch-specialised instance (the context's VBX_SPECTRAL_SPEC switch; the fused frame loop sets it)
     bool mfcc_defer;                                             // the MFCC rows leave the kernel as filter sums; launch_mfcc_rows finishes them (num_coeffs <= 16)
     bool lag_rcp;                                                // lag_window[((n + 1) & ~1) + i] = RN(1 / lag_window[i]) (quotient_by_table, vbx_spectral.hpp)
     double sample_rate, threshold, fmin, fmax; int kmax;
@@ -251,7 +252,9 @@ struct spectral_launch_t {
 size_t spectral_split_row_bytes(int n, double sample_rate, double fmin);   // bytes per frame of that scratch, 0: the shape has no split form
 bool spectral_supported(int n, int lpc_order, int mfcc_nb, int mfcc_b_lo, int num_coeffs);
 bool spectral_list_parked(const spectral_launch_t &L);              // the whole-Vec list goes to the output row, not to LDS
-int launch_analyze(hipStream_t s, const spectral_launch_t &L);       // 1: the call ran as two kernels (SP_ANALYZE_SPLIT), 0: one
+// 1: the call ran as two kernels (SP_ANALYZE_SPLIT), 0: one.  *launched_spec: which instance of the 1200-point fused kernel was launched -- 0 the generic
+// one, 1 / 2 the one compiled for this launch's uniform choices on f64 / 16-bit PCM samples (SP_SPEC_*, vbx_spectral.hpp); written at the launch itself
+int launch_analyze(hipStream_t s, const spectral_launch_t &L, int *launched_spec = nullptr);
 // k_lpc_exact.hip: LPC::lpc(p) of the listed frames from double-double lag sums and a double-double recursion (the exact
 // answer rounded once), over a list only the device knows the length of
 // k_mfcc.hip: log10 (clamped at 1e-10) + DCT of rows of mel filter sums, in place, a lane per row (the deferred tail of MFCC::mfcc, vbx_mfcc_tail.hpp)

@@ -1048,13 +1048,17 @@ constexpr int PITCH_CELL_NB = VBX_EXP_CELL_NB_PITCH, REFINE_LIST_CELL_NB = VBX_E
 // the quad bound pass leaves the abscissa nn of candidates 0..15 in lane 4c for the refinement to read back instead of running
 // cand_from_peak again, and pick_best_pred answers "nothing left" from a ballot.  Every operation on every value is the one
 // the plain form does, in the same order: keys[], the picks and the outputs keep every bit.
-template <int STAGE = 0, int NB = 0, bool ONCE = false>
+// LATE (a callable, the launch-specialised instances of the 1200-point fused kernel): out_cand, cand_ld, out_count, status and work
+// are not the caller's to give at the call -- late(out_cand, cand_ld, out_count, status, work) sets them where the frame's last
+// stores begin, so that none of them is held (in scalar registers, or lanes of the spill register) across the refinement.  Nothing
+// before that point reads them in a build without VBX_EXP_PHASES / VBX_EXP_STOP, and `full` is then the caller's or none.
+template <int STAGE = 0, int NB = 0, bool ONCE = false, typename LATE = std::nullptr_t>
 __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitch_params_t &pp, long f,
                                                    double *__restrict__ out_cand, long cand_ld,
                                                    int32_t *__restrict__ out_count, int32_t *__restrict__ status,
                                                    unsigned long long *__restrict__ work, double unc_tol = 0.0,
                                                    double2 *full = nullptr, int *io_ncand = nullptr, int cand_cap = 0,
-                                                   uint16_t *list_at = nullptr) {
+                                                   uint16_t *list_at = nullptr, LATE late = nullptr) {
     const int lane = lane_id();
     const double sample_rate = pp.sample_rate, threshold = pp.threshold, fmin = pp.fmin, fmax = pp.fmax;
     const int kmax = pp.kmax;
@@ -1465,6 +1469,7 @@ __device__ __forceinline__ bool pitch_refine_store(double *ys, int n, const pitc
       else run_groups(std::integral_constant<int, RG>{}, std::false_type{});
     }
 #undef VBX_BAR
+    if constexpr (!std::is_same<LATE, std::nullptr_t>::value) late(out_cand, cand_ld, out_count, status, work);
     VBX_PHASE(work, f, 9);
     const int total_cand = ncand + 1;
     st = __any(st & 4) ? 4 : 0;

@@ -78,6 +78,52 @@ struct spectral_args_t {
                                                              // refine_list_kernel holds (refine_far_kernel takes them with the whole curve)
 };
 
+// The 1200-point plan's argument block: spectral_args_t without what only the power-of-two plans, their split form, the
+// autocorrelation-only form and the interpolated bins read.  analyze_kernel (vbx_spectral_1200.hpp) takes it in every form but
+// SP_AC_ONLY and the interpolated ones, which keep the whole block.  What the frame's LAST stores need -- the candidate rows, the
+// count, the status, the work counters, the list of unsure frames -- fills bytes [64, 128) of the block, one 64-byte line of the
+// argument segment: the launch-specialised instances read it there when they need it, with ONE request (a read of the argument
+// segment is a request to the fabric every time: with a read at each of three places of use the bench's measured traffic rose by
+// 390 bytes per frame, 8 %).
+struct spectral_args_1200_t {
+    const double *frames; long n_frames; long stride; const double *window; const double *lag_window;
+    const double2 *tab;
+    int n; int mfcc_q; int pcm; int num_coeffs;
+    double *out_cand; long cand_ld; int32_t *out_count; int32_t *pitch_status; unsigned long long *work;        // [64, 128)
+    int32_t *unsure_list; int32_t *unsure_count; int nb;
+    pitch_params_t pp;
+    double *out_lpc; long lpc_ld;
+    double *out_mfcc; long mfcc_ld; int32_t *mfcc_status;
+    const int32_t *bins; const double *slopes; const double *dct;
+    explicit spectral_args_1200_t(const spectral_args_t &a)
+        : frames(a.frames), n_frames(a.n_frames), stride(a.stride), window(a.window), lag_window(a.lag_window), tab(a.tab), n(a.n),
+          mfcc_q(a.mfcc_q), pcm(a.pcm), num_coeffs(a.num_coeffs),
+          out_cand(a.out_cand), cand_ld(a.cand_ld), out_count(a.out_count), pitch_status(a.pitch_status), work(a.work),
+          unsure_list(a.unsure_list), unsure_count(a.unsure_count), nb(a.nb), pp(a.pp),
+          out_lpc(a.out_lpc), lpc_ld(a.lpc_ld), out_mfcc(a.out_mfcc), mfcc_ld(a.mfcc_ld), mfcc_status(a.mfcc_status),
+          bins(a.bins), slopes(a.slopes), dct(a.dct) {}
+};
+static_assert(offsetof(spectral_args_1200_t, out_cand) == 64 && offsetof(spectral_args_1200_t, nb) + sizeof(int) <= 128, "the last stores' arguments: one 64-byte line");
+__host__ __device__ constexpr bool sp_wide_args(int mode) { return mode == SP_AC_ONLY || sp_is_interp(mode); }
+
+// SPEC (analyze_kernel, TIN = sp_launch_f64_t / sp_launch_pcm16_t): what is the same for every frame of a launch, decided AT the launch for the three-wavefront instances of
+// full frames -- the fused frame loop's own call.  A SPEC instance is compiled for: the reciprocal table behind the
+// lag window present (SP_FLAG_LAG_RCP; the ANALYSIS window's presence is not among them: it stays a run-time test, vbx_spectral_1200.hpp), candidates kept in the lanes (no whole-Vec list: pp.full_off == 0), f64 roundings (pp.f32 == 0), the whole curve
+// (pp.ncurve == 0), and with MFCC at most sixteen coefficients whose log10 + DCT are deferred; SP_SPEC_PCM16: 16-bit PCM samples,
+// otherwise f64.  It holds one arm of each of those choices and none of the other arm's pointers, and it reads the arguments that
+// only the frame's last stores need (the candidate rows, their leading dimension, the count, status and work pointers) from the
+// argument segment where they are used: one scalar load there instead of registers -- or lanes of the spill register -- held
+// across the refinement.  Every floating-point operation is the generic instance's, in its order: the records keep every bit
+// (tests/test_gpu_analyze_launch_variants.py).  spectral_spec (k_spectral.hip) is the launch's choice, made inside launch_analyze.
+constexpr int SP_SPEC_NONE = 0, SP_SPEC_F64 = 1, SP_SPEC_PCM16 = 2;
+// what analyze_kernel's TIN says in a launch-specialised instance: the sample type AND that the launch's choices are compiled in
+// (the kernel's name stays analyze_kernel<LPC, MFCC, FULL, SP_ANALYZE, 3, ...>: tools and the benchmark find it by that prefix)
+struct sp_launch_f64_t {};
+struct sp_launch_pcm16_t {};
+template <typename TIN> constexpr int sp_spec_of() {
+    return std::is_same<TIN, sp_launch_f64_t>::value ? SP_SPEC_F64 : std::is_same<TIN, sp_launch_pcm16_t>::value ? SP_SPEC_PCM16 : SP_SPEC_NONE;
+}
+
 // The last SP_TAIL lags of the curve.  The lag window falls below 1e-8 there (1e-10 .. 1e-17 over the last twelve lags), so
 // the transforms' rounding error (~1e-16 S[0]) would be amplified into y by 1 / w_lag.  For an even frame length those
 // entries only enter sinc sums under a taper that vanishes with them, but an odd n reads y[n - 1] directly
@@ -147,7 +193,7 @@ constexpr int SP_LPC_P = SPECTRAL_LPC_ORDER;
 // k_spectral_pow2.hip
 // k_spectral_f32in.hip: the fused analysis of full 1200-sample frames whose samples are float32 (a.frames carries the float pointer);
 // launch_analyze calls it with the geometry it worked out for the f64 form
-void launch_analyze_f32in(hipStream_t s, const spectral_args_t &a, unsigned grid, size_t lds, bool lpc, bool mfcc, bool waves3);
+void launch_analyze_f32in(hipStream_t s, const spectral_args_1200_t &a, unsigned grid, size_t lds, bool lpc, bool mfcc, bool waves3);
 int launch_analyze_pow2(hipStream_t s, const spectral_launch_t &L, spectral_args_t &a);      // 1: ran in the split form
 
 }  // namespace vbx

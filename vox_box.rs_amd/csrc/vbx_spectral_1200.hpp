@@ -235,9 +235,33 @@ __host__ __device__ constexpr bool sp_front_end_once(bool mfcc, bool full, int w
     return VBX_EXP_FRONT_END_ONCE != 0 && !(!mfcc && full && waves >= 3 && !f32);
 }
 __host__ __device__ constexpr int sp_cell_blocks(int waves, bool f32) { return f32 ? VBX_EXP_CELL_NB_F32IN : VBX_EXP_CELL_NB; }
+template <int MODE> using sp_args_of = typename std::conditional<sp_wide_args(MODE), spectral_args_t, spectral_args_1200_t>::type;
+// The kernel's own argument block where it lies, in the argument segment (the block is the kernel's only argument: offset 0), for the
+// SPEC instances' fields that are read where they are used.  The pointer passes through an empty asm at every use, so that the
+// compiler can neither move the scalar load up to the kernel's entry nor merge it with the entry's loads -- which is how sixteen
+// dwords of output pointers came to be held, in lanes of the spill register, from the first transform to the frame's last store.
+template <typename ARGS>
+__device__ __forceinline__ const __attribute__((address_space(4))) ARGS *sp_args_where_used() {
+    const __attribute__((address_space(4))) ARGS *p = (const __attribute__((address_space(4))) ARGS *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+// TIN = sp_launch_f64_t / sp_launch_pcm16_t: f64 / 16-bit PCM samples with the launch-uniform choices compiled in (SP_SPEC_*,
+// vbx_spectral.hpp); three-wavefront SP_ANALYZE instances of full frames only.
 template <bool LPC, bool MFCC, bool FULL, int MODE = SP_ANALYZE, int WAVES = VBX_SPECTRAL_WAVES, typename TIN = double>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_only(MODE) ? 2 : WAVES, sp_is_mfcc_only(MODE) ? 4 : WAVES))) void analyze_kernel(const spectral_args_t a) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_only(MODE) ? 2 : WAVES, sp_is_mfcc_only(MODE) ? 4 : WAVES))) void analyze_kernel(const sp_args_of<MODE> a) {
     constexpr bool F32 = std::is_same<TIN, float>::value;
+    using args_t = sp_args_of<MODE>;
+    constexpr int SPEC = sp_spec_of<TIN>();
+    static_assert(SPEC == SP_SPEC_NONE || (FULL && MODE == SP_ANALYZE && WAVES >= 3), "the launch-specialised form: full f64 / PCM frames, three wavefronts");
+    constexpr bool SP = SPEC != SP_SPEC_NONE;
+    // launch-uniform choices: a SPEC instance's at compile time, the generic instance's from the argument block -- written as macros so
+    // that the generic instances hold, use for use, the expressions they always held.
+    // (NOT the window's presence: with it a constant, a sample's window product feeds the first butterfly's addition directly and
+    // the compiler contracts the two into one FMA -- a transform that differs in its last bits from the generic instance's, where the
+    // choice between x w and x stands between them.  Measured: LPC and pitch columns of 67 frames moved by up to 1e-11.)
+#define VBX_SP_PCM_IN (SP ? SPEC == SP_SPEC_PCM16 : (a.pcm & SP_FLAG_PCM) != 0)
+#define VBX_SP_LAG_RCP (SP || (a.pcm & SP_FLAG_LAG_RCP) != 0)
     static_assert(!F32 || (FULL && MODE == SP_ANALYZE), "float samples: the fused analysis of full frames");
     static_assert(MODE != SP_MFCC_ONLY || (MFCC && FULL && !LPC), "the MFCC-only form needs the full frame and has no lag sums");
     static_assert(MODE != SP_AC_ONLY || (!MFCC && !LPC), "the autocorrelation-only form");
@@ -277,7 +301,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_o
                 xs32[q] = float2{lo, hi};
                 wv[q] = (a.window != nullptr) ? (((uintptr_t)a.window & 15) == 0 ? *reinterpret_cast<const double2 *>(a.window + i)
                                                                                   : double2{a.window[i], a.window[i + 1]}) : double2{1.0, 1.0};
-            } else if (FULL && (a.pcm & SP_FLAG_PCM)) {
+            } else if (FULL && VBX_SP_PCM_IN) {
                 // 16-bit PCM in: 960 B of new samples per frame instead of 3840 (the host-fed case: PCIe carries the PCM);
                 // widened here exactly as vbx_pcm16_to_f64 would have (bit-identical frames, tests/test_gpu_frontend.py)
                 int lo, hi;
@@ -507,9 +531,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_o
         }
         wave_sync();
         VBX_PHASE(a.work, f, 13);
+        if constexpr (SP) {
+            // at most sixteen coefficients, log10 + DCT deferred: the one tail, without the DCT table
+            mfcc_tail_q(pu, pd, en, a.bins, nullptr, a.num_coeffs, b_lo, lane, a.out_mfcc + f * a.mfcc_ld, nullptr, f, true);
+            if (a.mfcc_status != nullptr && lane == 0) a.mfcc_status[f] = 0;
+        } else {
         if (a.num_coeffs <= 16) mfcc_tail_q(pu, pd, en, a.bins, a.dct, a.num_coeffs, b_lo, lane, a.out_mfcc + f * a.mfcc_ld, a.work, f, (a.pcm & SP_FLAG_MFCC_DEFER) != 0);
         else mfcc_tail_m(pu, pd, en, a.bins, a.dct, a.num_coeffs, b_lo, lane, a.out_mfcc + f * a.mfcc_ld);
         if (a.mfcc_status != nullptr && lane == 0) a.mfcc_status[f] = 0;
+        }
         wave_sync();
     }
 
@@ -539,12 +569,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_o
         for (int s = 0; s < 11; s++) {
             const int i = 2 * jj[s];
             if (jj[s] >= 0 && i < n) {
-                const double xs = F32 ? (double)x32[i] : (FULL && (a.pcm & SP_FLAG_PCM)) ? pcm16_value(x16[i]) : xf[i];
+                const double xs = F32 ? (double)x32[i] : (FULL && VBX_SP_PCM_IN) ? pcm16_value(x16[i]) : xf[i];
                 const double xe = (a.window != nullptr) ? xs * a.window[i] : xs;
                 r_e[s] = (r_e[s] - x0 * xe) + x0;
             }
             if (jj[s] >= 0 && i + 1 < n) {
-                const double xs = F32 ? (double)x32[i + 1] : (FULL && (a.pcm & SP_FLAG_PCM)) ? pcm16_value(x16[i + 1]) : xf[i + 1];
+                const double xs = F32 ? (double)x32[i + 1] : (FULL && VBX_SP_PCM_IN) ? pcm16_value(x16[i + 1]) : xf[i + 1];
                 const double xo = (a.window != nullptr) ? xs * a.window[i + 1] : xs;
                 r_o[s] = (r_o[s] - x0 * xo) + x0;
             }
@@ -583,7 +613,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_o
     double *ys = smem;
     wave_sync();                                             // every lane is done with the exchange buffer
     // uniform: the table's reciprocals serve (quotient_by_table, vbx_spectral.hpp) unless the scale is not a normal finite number
-    const bool by_table = (a.pcm & SP_FLAG_LAG_RCP) != 0 && fabs(scale) < 1e290 && fabs(scale) > 1e-290;
+    const bool by_table = VBX_SP_LAG_RCP && fabs(scale) < 1e290 && fabs(scale) > 1e-290;
     const double *lag_rcp = a.lag_window + lag_rcp_offset(n);
     if (by_table) {
         // (window entries and reciprocals of a few slots requested together, without a condition -- entry 0 stands in for a slot
@@ -652,11 +682,31 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_o
     // with w_lag >= 1/6 on the searched half.  SP_UNC_EPS bounds the error of a DIFFERENCE of two entries with a wide
     // margin; frames with a peak decision inside it go to the direct-sum kernel (launch_pitch_list).
     const double unc_tol = SP_UNC_EPS * fabs(s0) * scale;
+    if constexpr (SP) {
+        // the list in the lanes, f64 roundings, the whole curve: the launch's own values of full_off / f32 / ncurve, as constants; the
+        // output arguments arrive inside pitch_refine_store, at the frame's last stores (`late`)
+        pitch_params_t pp;
+        pp.sample_rate = a.pp.sample_rate; pp.threshold = a.pp.threshold; pp.fmin = a.pp.fmin; pp.fmax = a.pp.fmax; pp.kmax = a.pp.kmax;
+        pp.full_off = 0; pp.f32 = 0; pp.ncurve = 0;
+        auto late = [&](auto &out_cand, auto &cand_ld, auto &out_count, auto &status, auto &work) __attribute__((always_inline)) {
+            const auto *l = sp_args_where_used<args_t>();
+            out_cand = l->out_cand; cand_ld = l->cand_ld; out_count = l->out_count; status = l->pitch_status; work = l->work;
+        };
+        if (!pitch_refine_store<0, sp_cell_blocks(WAVES, F32), sp_front_end_once(MFCC, FULL, WAVES, F32)>(ys, n, pp, f, nullptr, 0, nullptr, nullptr, nullptr, unc_tol, nullptr,
+                                                                                                        nullptr, 0, nullptr, late)) {
+            const auto *l = sp_args_where_used<args_t>();
+            int32_t *const unsure_count = l->unsure_count;
+            if (lane == 0) l->unsure_list[atomicAdd(unsure_count, 1)] = (int32_t)f;
+        }
+        return;
+    }
     double2 *full = a.pp.full_off > 0 ? reinterpret_cast<double2 *>(reinterpret_cast<char *>(smem) + a.pp.full_off)
                   : a.pp.full_off < 0 ? reinterpret_cast<double2 *>(a.out_cand + f * a.cand_ld) : nullptr;
     if (!pitch_refine_store<0, sp_cell_blocks(WAVES, F32), sp_front_end_once(MFCC, FULL, WAVES, F32)>(ys, n, a.pp, f, a.out_cand, a.cand_ld, a.out_count, a.pitch_status, a.work, unc_tol, full)) {
         if (lane == 0) a.unsure_list[atomicAdd(a.unsure_count, 1)] = (int32_t)f;
     }
 }
+#undef VBX_SP_PCM_IN
+#undef VBX_SP_LAG_RCP
 
 }  // namespace vbx

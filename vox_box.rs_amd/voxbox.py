@@ -343,6 +343,7 @@ def load_library():
         "vbx_internal_estimate_formants_counted": (C.c_int, [vp, vp, sz, sz, vp, vp, sz, vp, sz, vp, vp]),
         "vbx_internal_last_roots_direct_count": (C.c_int, [vp, vp]),
         "vbx_internal_last_spectral_split": (C.c_int, [vp]),
+        "vbx_internal_last_analyze_spec": (C.c_int, [vp]),
         "vbx_internal_last_mfcc_interp": (C.c_int, [vp]),
         "vbx_internal_last_mfcc_form": (C.c_int, [vp]),
         "vbx_internal_last_pitch_form": (C.c_int, [vp]),
