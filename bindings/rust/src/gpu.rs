@@ -365,6 +365,26 @@ impl Gpu {
         Ok(Session { gpu: self, raw, format, sample_frame_bytes, frame_len, stride, record_ld: rec + (rec & 1), kmax: tk.map(|t| t.kmax) })
     }
 
+    /// A pool of `max_streams` independent live streams on this context (`vbx_pool_open`): mono audio in `format`, frames of at
+    /// most `VBX_MAX_FRAME_LEN` samples, blocks of at most `max_block` samples and ticks of at most `max_tick` samples in all.
+    /// Everything is allocated and warmed here.
+    #[allow(clippy::too_many_arguments)]
+    pub fn pool(&self, format: i32, frame_len: usize, stride: usize, params: &AnalysisParams, ext: Option<&AnalysisExt>,
+                track: Option<(usize, &PitchPathParams)>, max_streams: usize, max_block: usize, max_tick: usize) -> GpuResult<Pool<'_>> {
+        let fmt = ffi::VbxHostAudio { format, channels: 1, channel: 0, reserved: 0, chunk_frames: 0 };
+        let p = params.to_ffi();
+        let e = ext.map(|x| x.to_ffi());
+        let e_ptr = e.as_ref().map_or(ptr::null(), |x| x as *const _);
+        let tk = track.map(|(kmax, path)| ffi::VbxPitchTrackParams { kmax, path: path.raw() });
+        let rec = unsafe { ffi::vbx_record_doubles_ex(&p, e_ptr) };
+        let mut raw: *mut ffi::VbxPool = ptr::null_mut();
+        self.check(unsafe {
+            ffi::vbx_pool_open(self.raw, &fmt, frame_len, stride, &p, e_ptr, tk.as_ref().map_or(ptr::null(), |t| t as *const _), max_streams,
+                               max_block, max_tick, &mut raw)
+        })?;
+        Ok(Pool { gpu: self, raw, sample_bytes: sample_src_bytes(format), record_ld: rec + (rec & 1), kmax: tk.map(|t| t.kmax) })
+    }
+
     /// ONE live session for several channels of a stream (`vbx_session_open_channels`): a stereo interface, a microphone array.
     /// `select` holds distinct channels in any order (at most `VBX_HOST_MAX_CHANNELS`); every [`SessionChannels::push`] uploads the
     /// block once and runs one frame-loop call over all of them, and entry `k` of what it returns is, bit for bit, what a
@@ -593,6 +613,102 @@ impl<'g> Session<'g> {
             ffi::vbx_session_path_bind(self.raw, peak_ref, max_pending, rows.path.as_mut_ptr(), 2, rows.index.as_mut_ptr(),
                                        rows.forced.as_mut_ptr(), rows.commit.as_mut_ptr())
         })
+    }
+}
+
+/// What one tick of a [`Pool`] delivered: the rows of all its entries in ONE set of arrays, entry `i`'s rows at
+/// `[rows[i].row_start, rows[i].row_start + rows[i].n_rows)`; `delivered` is `None` when the tick completed no frame.
+pub struct PoolRows<'g> {
+    pub rows: Vec<ffi::VbxPoolRows>,
+    pub delivered: Option<SessionRows<'g>>,
+}
+
+/// A pool of independent live streams ([`Gpu::pool`]): `max_streams` slots that share a sample format (mono), a frame shape and a
+/// parameter set, each with its own timeline; closed on drop.  One tick takes `(slot, block)` entries of any sizes, any subset of the
+/// slots, in any order -- one upload and a fixed number of launches whatever their number -- and per slot the rows of all ticks equal,
+/// bit for bit, what a one-channel [`Session`] delivers for the same blocks, marks and resets.  The online pitch path is not offered
+/// for pool slots: run [`Gpu`]'s pitch path over a call's lists when the call ends.
+pub struct Pool<'g> {
+    gpu: &'g Gpu,
+    raw: *mut ffi::VbxPool,
+    sample_bytes: usize,
+    record_ld: usize,
+    kmax: Option<usize>,
+}
+
+impl<'g> Pool<'g> {
+    /// `(sample frames consumed, frames delivered, sample frames carried)` of one slot (`vbx_pool_info`).
+    pub fn info(&self, stream: i32) -> GpuResult<(usize, usize, usize)> {
+        let (mut a, mut b, mut c) = (0usize, 0usize, 0usize);
+        self.gpu.check(unsafe { ffi::vbx_pool_info(self.raw, stream, &mut a, &mut b, &mut c) })?;
+        Ok((a, b, c))
+    }
+
+    fn deliver(&self, entries: &[ffi::VbxPoolEntry], cap_rows: usize, device: bool) -> GpuResult<PoolRows<'g>> {
+        // (cap_rows: no fewer rows than the tick delivers -- a block of n samples completes at most n / stride + 1 frames)
+        let mut rows = vec![ffi::VbxPoolRows::default(); entries.len()];
+        let cap = cap_rows.max(1);
+        let data = self.gpu.alloc::<f64>(cap * self.record_ld)?;
+        let status3 = self.gpu.alloc::<i32>(3 * cap)?;
+        let lists = match self.kmax {
+            Some(k) => Some((self.gpu.alloc::<ffi::VbxPitch>(cap * k)?, self.gpu.alloc::<i32>(cap)?, self.gpu.alloc::<f64>(cap)?)),
+            None => None,
+        };
+        let outputs = lists.as_ref().map(|(c, k, p)| ffi::VbxPitchTrackOutputs {
+            cand: c.as_mut_ptr(), count: k.as_mut_ptr(), peak: p.as_mut_ptr(), index: ptr::null_mut(),
+        });
+        let o_ptr = outputs.as_ref().map_or(ptr::null(), |o| o as *const _);
+        let mut total = 0usize;
+        self.gpu.check(unsafe {
+            if device {
+                ffi::vbx_pool_push_device(self.raw, entries.as_ptr(), entries.len(), data.as_mut_ptr(), self.record_ld, status3.as_mut_ptr(), cap,
+                                          o_ptr, rows.as_mut_ptr(), &mut total)
+            } else {
+                ffi::vbx_pool_push(self.raw, entries.as_ptr(), entries.len(), data.as_mut_ptr(), self.record_ld, status3.as_mut_ptr(), cap, o_ptr,
+                                   rows.as_mut_ptr(), &mut total)
+            }
+        })?;
+        debug_assert!(total <= cap);
+        let delivered = if total == 0 {
+            None
+        } else {
+            // (the three status rows are `cap` entries apart: Records keeps that as its frame count's stride)
+            Some(SessionRows { records: Records { data, status3, n_frames: cap, record_ld: self.record_ld }, lists })
+        };
+        Ok(PoolRows { rows, delivered })
+    }
+
+    /// One tick from host memory (`vbx_pool_push`): `(slot, samples)` entries, the samples as bytes of the pool's format.  Returns
+    /// when every block has been read; the rows are ordered on the context's stream.
+    pub fn push(&self, entries: &[(i32, &[u8])], stride: usize) -> GpuResult<PoolRows<'g>> {
+        let e: Vec<ffi::VbxPoolEntry> = entries.iter().map(|(s, b)| ffi::VbxPoolEntry {
+            stream: *s, block: if b.is_empty() { ptr::null() } else { b.as_ptr() as *const c_void }, n_sample_frames: b.len() / self.sample_bytes,
+        }).collect();
+        let cap = e.iter().map(|x| x.n_sample_frames / stride.max(1) + 1).sum();
+        self.deliver(&e, cap, false)
+    }
+
+    /// The same for blocks in device memory (`vbx_pool_push_device`): `(slot, address, samples)`, read in stream order.
+    pub fn push_device(&self, entries: &[(i32, *const c_void, usize)], stride: usize) -> GpuResult<PoolRows<'g>> {
+        let e: Vec<ffi::VbxPoolEntry> = entries.iter().map(|(s, b, n)| ffi::VbxPoolEntry { stream: *s, block: *b, n_sample_frames: *n }).collect();
+        let cap = e.iter().map(|x| x.n_sample_frames / stride.max(1) + 1).sum();
+        self.deliver(&e, cap, true)
+    }
+
+    /// The next frame the slot delivers starts a new utterance (`vbx_pool_mark_utterance`); nothing is launched.
+    pub fn mark_utterance(&self, stream: i32) -> GpuResult<()> {
+        self.gpu.check(unsafe { ffi::vbx_pool_mark_utterance(self.raw, stream) })
+    }
+
+    /// The slot behaves as that of a freshly opened pool (`vbx_pool_reset_stream`): how a slot is reused for the next call.
+    pub fn reset_stream(&self, stream: i32) -> GpuResult<()> {
+        self.gpu.check(unsafe { ffi::vbx_pool_reset_stream(self.raw, stream) })
+    }
+}
+
+impl Drop for Pool<'_> {
+    fn drop(&mut self) {
+        unsafe { ffi::vbx_pool_close(self.raw) };
     }
 }
 
@@ -1995,6 +2111,24 @@ pub fn sample_out_bytes(format: c_int) -> usize {
         ffi::VBX_SAMPLE_F32 => 4,
         _ => 8,
     }
+}
+
+/// One tick of a session pool (`vbx_pool_plan`; host arithmetic only): per entry its slot's `(consumed, utt_frame)` and the block's
+/// `n_new`.  Returns per entry the slot's session plan, its rows in the tick's outputs, the frames it has in the tick's frame-loop
+/// call (0: no frame completes) and its first frame in the tick's plane (-1 then); then the tick's total rows and call frames.
+pub fn pool_plan(consumed: &[usize], utt_frame: &[usize], n_new: &[usize], frame_len: usize, stride: usize)
+                 -> GpuResult<(Vec<ffi::VbxPoolPlanRow>, usize, usize)> {
+    assert!(consumed.len() == utt_frame.len() && consumed.len() == n_new.len(), "one (consumed, utt_frame, n_new) per entry");
+    let mut rows = vec![ffi::VbxPoolPlanRow::default(); consumed.len()];
+    let (mut total, mut call) = (0usize, 0usize);
+    let rc = unsafe {
+        ffi::vbx_pool_plan(consumed.as_ptr(), utt_frame.as_ptr(), n_new.as_ptr(), consumed.len(), frame_len, stride, rows.as_mut_ptr(), &mut total,
+                           &mut call)
+    };
+    if rc != ffi::VBX_SUCCESS {
+        return Err(GpuError { code: rc, message: last_error(ptr::null()) });
+    }
+    Ok((rows, total, call))
 }
 
 /// What a push of `n_new` sample frames does to a live session that has consumed `consumed` sample frames and whose current

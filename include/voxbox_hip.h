@@ -1178,6 +1178,103 @@ int vbx_analyze_clips(vbx_ctx *ctx, const void *const *h_clip /* [n_clips] DEVIC
                       double *out_records, size_t record_ld, int32_t *status3 /* [3, total_rows] */,
                       const vbx_pitch_track_outputs *h_outputs /* arrays of total_rows rows */);
 
+/* ------------------------------------------------------------------ a pool of live streams (ABI 5, added) */
+
+/* A gateway or a call-centre tap carries hundreds to thousands of INDEPENDENT calls at once, each delivering a packet per tick.
+ * One vbx_session per call costs a launch chain per call and tick (about 0.29 ms a push); a multi-channel
+ * session (section 5i) shares one cut into blocks and one list of marks between its channels, which independent calls do not have.
+ * A session pool is max_streams stream SLOTS on one context that share one sample format (mono), one frame shape and one parameter
+ * set, each slot with its own timeline: samples consumed, utterance start, carried tail, tracker state.  One TICK, vbx_pool_push,
+ * hands over a list of (slot, block) entries -- any sizes, any subset of the slots, in any order -- and delivers the rows of the
+ * frames each block completes, entry after entry, into ONE set of output arrays.  The kernel launches and host-to-device copies of a
+ * tick do not depend on how many streams it holds.
+ * Contract: for every slot, concatenate the rows all ticks delivered for it -- the records, the three status rows and, in the tracked
+ * form, cand / count / peak: the result equals, bit for bit, what a one-channel vbx_session opened with the same arguments writes when
+ * it is given the same blocks, marks and resets in the same order (by that session's contract: the resident call on the stream's
+ * concatenated blocks with the marks as h_seg_start) -- for every way of cutting every stream into blocks, every assignment of blocks
+ * to ticks (streams that skip ticks, a tick of one entry, a tick that completes no frame, an empty tick), every entry order within a
+ * tick, all eight sample formats, the plain, tracked and ext forms and every LPC policy (the context's at the time of the tick;
+ * tests/test_gpu_pool.py).  A NaN or Inf in one stream touches no other stream's rows.
+ * vbx_pool_open: h_fmt as for vbx_session_open with channels == 1, channel == 0, chunk_frames == 0 and reserved == 0 (streams are
+ * mono); frame_len <= VBX_MAX_FRAME_LEN (the long-frame kernels choose how they split a frame's sums from the frame count of the
+ * call, so only a per-stream call gives the resident call's bits: use one vbx_session per stream there); a block holds at most
+ * max_block_sample_frames, a tick's blocks together at most max_tick_sample_frames.  Everything is allocated here: two carry
+ * regions per slot of VBX_SHARD_WARM_FRAMES * stride + frame_len - 1 elements (rounded up to 16 bytes), the tick's plane, two pinned
+ * staging buffers and two raw device slots of the tick's largest byte count plus its table, the chunk-local records, status rows and
+ * lists of the largest frame-loop call, max_streams tracker state rows; the largest shape is warmed by one frame-loop call with
+ * max_streams segments on zeroed memory, which is also where everything only the frame loop's parts know is rejected.  Afterwards no
+ * tick allocates or drains a stream on its own account.
+ * vbx_pool_push: h_entries is a HOST array; entry i names a slot and a block of n_sample_frames samples in HOST memory
+ * (vbx_pool_push_device: in DEVICE memory, read in stream order).  Entry i delivers n_rows_i = hi - lo of vbx_session_plan for its
+ * slot into rows [row_start_i, row_start_i + n_rows_i) of every output array, row_start the prefix sum in entry order; h_rows[i] =
+ * {row_start, n_rows} and *h_total_rows are reported on the host (both optional; vbx_pool_plan tells them beforehand).  out_records
+ * [total_rows, record_ld] (device, 16-byte aligned), status3 row j at status3 + j * status_ld (optional), and in the tracked form
+ * h_outputs as for vbx_session_push: cand and count required, peak when silence_threshold != 0, index must be NULL; columns 0-1 of
+ * the records are not written.  An entry with n_sample_frames == 0 is a no-op with zero rows; an empty tick succeeds and queues
+ * nothing; a tick that completes no frame only updates the carried tails.  The host form returns when every block has been read:
+ * the blocks are gathered by memcpy into the pool's pinned staging, so the caller's memory is free on return, and the host runs at
+ * most two ticks ahead.
+ * Per tick, whatever the number of entries: ONE upload -- the gathered blocks and the tick's device table in
+ * one pinned buffer and one copy on the context's stream (the device form: the table alone); ONE pool_ingest_<fmt> launch that
+ * writes, through the table, every entry's plane region (the samples from read_from on: the slot's carried tail, then the block, as
+ * the type the frame loop reads natively, the gap of fewer than `stride` elements behind a region zero-filled) and every entry's new
+ * carried tail into the slot's OTHER carry region (each slot keeps its own ping-pong: a slot that is not pushed keeps its tail);
+ * ONE frame-loop call over the plane with every entry a segment of its own (the rows between two regions lie behind an entry's own
+ * frames in its own segment: the causal tracker cannot carry them into a delivered row, and they are never delivered); ONE
+ * tracker_stitch_pool launch that repairs, a lane per entry, the rows of every entry that continues an utterance from its slot's
+ * state row; ONE pool_deliver launch that copies each entry's own rows to the caller's rows and its last formant row to the state.
+ * vbx_pool_mark_utterance / vbx_pool_reset_stream are host bookkeeping and launch nothing: the next frame the slot delivers starts a
+ * new utterance; a reset slot behaves like a freshly opened session (its first push has continues_prev == 0 and reads nothing of
+ * the stale tail and state) -- this is how a slot is reused for the next call.  vbx_pool_info reports a slot's sample frames
+ * consumed, frames delivered and sample frames carried; vbx_pool_close frees the pool behind the work queued on the context's stream
+ * (close every pool before its context).
+ * The online pitch path (vbx_session_path_bind) is NOT offered for pool slots: the tracked form delivers the lists, and the caller
+ * runs vbx_pitch_path_f64 over a call's rows when the call ends, as an unbound session's caller does.  A pool, sessions and any other
+ * entry point may share one context; a tick may WAIT ON THE HOST for the staged upload of two ticks ago and is not capturable into a
+ * graph; afterwards the vbx_internal_last_* probes describe the tick's frame-loop call and there is no state for vbx_track_stitch_f64.
+ * vbx_pool_plan: pure host arithmetic, no GPU -- per entry (consumed, utt_frame, n_new) of its slot: the vbx_session_plan_t, its rows,
+ * `frames` = m = warm + n_rows analysed (0 when no frame completes) and plane_frame (-1 then); per tick total_rows and call_frames.
+ * Layout (as vbx_clips_plan's): the first entry with frames has plane_frame 0; its plane region holds samples [read_from, (hi - 1) *
+ * stride + frame_len) of its stream from element plane_frame * stride on; the next entry with frames starts ceil(span / stride)
+ * frames behind it; call_frames = plane_frame_last + m_last, and the segment list is the list of plane_frames.
+ * VBX_E_INVALID, before anything is queued and with the pool left usable and its state unchanged: a NULL where an argument is
+ * required; a slot outside [0, max_streams); a slot listed twice in one tick; a block larger than max_block_sample_frames; a tick
+ * whose lengths sum past max_tick_sample_frames; a device block off its type's alignment (PCM24 and the 8-bit formats: any
+ * address); vbx_session_push's rules for the output arrays applied to total_rows; frame_len > VBX_MAX_FRAME_LEN; channels != 1;
+ * max_streams == 0 or a largest call beyond 0x7fffffff frames. */
+typedef struct vbx_pool vbx_pool;
+typedef struct {
+    int32_t stream;            /* the slot, in [0, max_streams) */
+    const void *block;         /* n_sample_frames mono samples of the pool's format (host memory; _device: device memory) */
+    size_t n_sample_frames;
+} vbx_pool_entry;
+typedef struct { int64_t row_start; int64_t n_rows; } vbx_pool_rows;
+typedef struct {
+    vbx_session_plan_t plan;   /* the slot's push */
+    int64_t row_start;         /* first output row of the entry (prefix sum of n_rows in entry order) */
+    int64_t n_rows;            /* plan.hi - plan.lo */
+    int64_t frames;            /* frames the entry has in the tick's frame-loop call: plan.warm + n_rows; 0: no frame completes */
+    int64_t plane_frame;       /* its first frame in the tick's plane; -1: no frame completes */
+} vbx_pool_plan_row;
+int vbx_pool_plan(const size_t *h_consumed, const size_t *h_utt_frame, const size_t *h_n_new, size_t n_entries,
+                  size_t frame_len, size_t stride, vbx_pool_plan_row *h_rows /* [n_entries] */, size_t *h_total_rows,
+                  size_t *h_call_frames);
+int vbx_pool_open(vbx_ctx *ctx, const vbx_host_audio *h_fmt /* channels 1, channel 0, chunk_frames 0, reserved 0 */,
+                  size_t frame_len, size_t stride, const vbx_analysis_params *h_params, const vbx_analysis_ext *h_ext,
+                  const vbx_pitch_track_params *h_track, size_t max_streams, size_t max_block_sample_frames,
+                  size_t max_tick_sample_frames, vbx_pool **out);
+int vbx_pool_push(vbx_pool *pool, const vbx_pool_entry *h_entries, size_t n_entries,
+                  double *out_records /* device */, size_t record_ld, int32_t *status3 /* device, optional */, size_t status_ld,
+                  const vbx_pitch_track_outputs *h_outputs /* device arrays of total_rows rows */,
+                  vbx_pool_rows *h_rows /* [n_entries], optional */, size_t *h_total_rows);
+int vbx_pool_push_device(vbx_pool *pool, const vbx_pool_entry *h_entries, size_t n_entries,
+                         double *out_records, size_t record_ld, int32_t *status3, size_t status_ld,
+                         const vbx_pitch_track_outputs *h_outputs, vbx_pool_rows *h_rows, size_t *h_total_rows);
+int vbx_pool_mark_utterance(vbx_pool *pool, int32_t stream);   /* the next frame the slot delivers starts a new utterance */
+int vbx_pool_reset_stream(vbx_pool *pool, int32_t stream);     /* the slot behaves as that of a freshly opened pool */
+int vbx_pool_info(const vbx_pool *pool, int32_t stream, size_t *h_consumed, size_t *h_frames, size_t *h_carried);
+void vbx_pool_close(vbx_pool *pool);
+
 /* ------------------------------------------------------------------ multi-GPU: frame-range sharding */
 
 /* The reference has no distribution of any kind; frames are independent (the tracker per utterance), so a long

@@ -650,6 +650,36 @@ __global__ __launch_bounds__(64) void tracker_stitch_all_kernel(const trk_in_t i
     }
 }
 
+// tracker_stitch_all_kernel's step for every entry of a session pool's tick in ONE launch, taken from the tick's table instead of a
+// fixed plane pitch: an entry that continues an utterance has its rows [plane_frame + warm, plane_frame + frames) repaired from its
+// slot's state row (warm >= 1 there: at least one warm-up frame precedes them inside the entry's own segment).  One LANE per entry,
+// 64 entries to a wavefront: with thousands of entries a block each would leave 63 of 64 lanes idle around a chain of dependent steps.
+template <int NE>
+__global__ __launch_bounds__(64) void tracker_stitch_pool_kernel(const trk_in_t in_, const pool_entry_t *__restrict__ tab, long n_entries,
+                                                                 const double *__restrict__ state) {
+    const long i = (long)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n_entries) return;
+    if (!tab[i].continues_prev) return;
+    // every lane walks its own rows: the scan's loops diverge, and their masks take the scalar registers the launch's uniform
+    // pointers would otherwise sit in -- those are held per lane instead (the same values: no scalar register is spilled)
+    trk_in_t in = in_;
+    asm volatile("" : "+v"(in.res), "+v"(in.out), "+v"(in.res_count), "+v"(in.frame_status), "+v"(in.out_ld), "+v"(in.general),
+                 "+v"(in.n_res));
+    const long first = tab[i].plane_frame + tab[i].warm, stop = tab[i].plane_frame + tab[i].frames;
+    const double *state_in = state + (long)tab[i].slot * 2 * NS;
+    double ef[NS], eb[NS];
+#pragma unroll
+    for (int e = 0; e < NS; e++) { ef[e] = 0.0; eb[e] = 0.0; }
+#pragma unroll
+    for (int e = 0; e < NE; e++) { ef[e] = state_in[2 * e]; eb[e] = state_in[2 * e + 1]; }
+    if (tab[i].warm > 0 && trk_row_is<NE>(in, first - 1, ef, eb)) return;
+    for (long f = first; f < stop; f++) {
+        trk_frame<NE>(in, f, ef, eb);
+        if (trk_row_is<NE>(in, f, ef, eb)) break;              // met the rows already there: the rest follows from them
+        trk_store_row<NE>(in, f, ef, eb);
+    }
+}
+
 // VBX_TRACKER_GENERAL=1 (read per launch): the general step on every frame instead of the index form
 static int tracker_general() { const char *e = getenv("VBX_TRACKER_GENERAL"); return (e && atoi(e) != 0) ? 1 : 0; }
 
@@ -717,6 +747,23 @@ void launch_tracker_stitch_all(hipStream_t s, const res_t *res, long F, int n_re
                                const double *state, long n_sel) {
     trk_in_t in{res, F, n_res, res_count, nullptr, 1, nullptr, frame_status, reinterpret_cast<double *>(out), out_ld, tracker_general()};
 #define VBX_TRK_ST(NE) hipLaunchKernelGGL(tracker_stitch_all_kernel<NE>, dim3((unsigned)n_sel), dim3(64), 0, s, in, plane_frames, first, stop, state)
+    switch (n_est) {
+        case 1: VBX_TRK_ST(1); break;
+        case 2: VBX_TRK_ST(2); break;
+        case 3: VBX_TRK_ST(3); break;
+        case 4: VBX_TRK_ST(4); break;
+        case 5: VBX_TRK_ST(5); break;
+        default: VBX_TRK_ST(6); break;
+    }
+#undef VBX_TRK_ST
+}
+
+void launch_tracker_stitch_pool(hipStream_t s, const res_t *res, long F, int n_res, const int32_t *res_count, int n_est,
+                                const int32_t *frame_status, res_t *out, long out_ld, const pool_entry_t *tab, long n_entries,
+                                const double *state) {
+    if (n_entries <= 0) return;
+    trk_in_t in{res, F, n_res, res_count, nullptr, 1, nullptr, frame_status, reinterpret_cast<double *>(out), out_ld, tracker_general()};
+#define VBX_TRK_ST(NE) hipLaunchKernelGGL(tracker_stitch_pool_kernel<NE>, dim3((unsigned)((n_entries + 63) / 64)), dim3(64), 0, s, in, tab, n_entries, state)
     switch (n_est) {
         case 1: VBX_TRK_ST(1); break;
         case 2: VBX_TRK_ST(2); break;

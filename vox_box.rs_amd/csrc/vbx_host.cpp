@@ -538,6 +538,52 @@ int vbx_session_channels_plan(size_t consumed, size_t utt_frame, size_t n_new, s
     return VBX_SUCCESS;
 }
 
+// One tick of a session pool (vbx_pool_push): vbx_session_plan's arithmetic per entry -- every slot has its own timeline -- the
+// entries' rows in the tick's outputs, and the layout of the one plane the tick's frame-loop call runs over.  An entry with frames
+// analyses m = warm + n_rows of them from its stream's sample read_from on: a region of span = (m - 1) * stride + frame_len
+// elements at element plane_frame * stride.  The next entry with frames starts ceil(span / stride) frames behind it (vbx_clips_plan's
+// rule), so the gap between two regions is shorter than one hop and every frame of [plane_frame, plane_frame + m) reads its own
+// entry's samples only.
+int vbx_pool_plan(const size_t *h_consumed, const size_t *h_utt_frame, const size_t *h_n_new, size_t n_entries, size_t frame_len,
+                  size_t stride, vbx_pool_plan_row *h_rows, size_t *h_total_rows, size_t *h_call_frames) {
+    if (h_total_rows) *h_total_rows = 0;
+    if (h_call_frames) *h_call_frames = 0;
+    if (frame_len < 1 || stride < 1) return fail(nullptr, VBX_E_INVALID, "vbx_pool_plan: frame_len and stride must be >= 1");
+    if (n_entries > 0 && (!h_consumed || !h_utt_frame || !h_n_new || !h_rows)) return fail(nullptr, VBX_E_INVALID, "vbx_pool_plan: null array");
+    if (stride > ((size_t)1 << 40) || frame_len > ((size_t)1 << 40)) return fail(nullptr, VBX_E_INVALID, "vbx_pool_plan: frame_len or stride too large");
+    // first: nothing is written for a tick that is refused
+    size_t total = 0, next = 0, call = 0;
+    for (size_t i = 0; i < n_entries; i++) {
+        vbx_session_plan_t p{};
+        if (h_n_new[i] > ((size_t)1 << 48)) return fail(nullptr, VBX_E_INVALID, "vbx_pool_plan: n_new too large");
+        int rc = vbx_session_plan(h_consumed[i], h_utt_frame[i], h_n_new[i], frame_len, stride, &p);
+        if (rc != VBX_SUCCESS) return fail(nullptr, rc, "vbx_pool_plan: bad entry (vbx_session_plan refuses it)");
+        const size_t nf = p.hi - p.lo;
+        if (nf == 0) continue;
+        const size_t m = p.warm + nf, span = (m - 1) * stride + frame_len;
+        if (nf > 0x7fffffffull - total || next + m > 0x7fffffffull) return fail(nullptr, VBX_E_INVALID, "vbx_pool_plan: more than 0x7fffffff frames in one call");
+        total += nf;
+        call = next + m;
+        next += span / stride + (span % stride != 0);
+    }
+    size_t row = 0;
+    next = 0;
+    for (size_t i = 0; i < n_entries; i++) {
+        vbx_pool_plan_row &r = h_rows[i];
+        vbx_session_plan(h_consumed[i], h_utt_frame[i], h_n_new[i], frame_len, stride, &r.plan);
+        const size_t nf = r.plan.hi - r.plan.lo;
+        r.row_start = (int64_t)row; r.n_rows = (int64_t)nf; r.frames = 0; r.plane_frame = -1;
+        if (nf == 0) continue;
+        const size_t m = r.plan.warm + nf, span = (m - 1) * stride + frame_len;
+        r.frames = (int64_t)m; r.plane_frame = (int64_t)next;
+        next += span / stride + (span % stride != 0);
+        row += nf;
+    }
+    if (h_total_rows) *h_total_rows = total;
+    if (h_call_frames) *h_call_frames = call;
+    return VBX_SUCCESS;
+}
+
 // A batch of clips (vbx_analyze_clips): each clip's rows in the outputs, the group that analyses it and where it lies in that
 // group's packed plane.  Groups are greedy runs of whole clips in order.  Inside a group clip b's sample 0 lies at element
 // plane_frame_b * stride; the next clip with frames starts ceil(len_b / stride) frames behind it, so the gap between them is shorter
@@ -599,5 +645,16 @@ size_t session_carry_samples(size_t frame_len, size_t stride, size_t max_block) 
 }
 
 size_t session_max_frames(size_t stride, size_t max_block) { return max_block / stride + 1 + (size_t)VBX_SHARD_WARM_FRAMES; }
+
+// keep_from >= (hi - WARM) * stride and consumed + n_new < hi * stride + frame_len (vbx_session_plan): the tail is shorter than
+// WARM hops and a frame
+size_t pool_carry_samples(size_t frame_len, size_t stride) { return (size_t)VBX_SHARD_WARM_FRAMES * stride + frame_len - 1; }
+
+// An entry of n samples analyses m <= WARM + n / stride + 1 frames and takes m - 1 + ceil(frame_len / stride) frames of the plane
+// (the last one: m, which is no more); at most min(max_streams, max_tick) entries hold a sample, their lengths sum to max_tick.
+size_t pool_max_call_frames(size_t frame_len, size_t stride, size_t max_streams, size_t max_tick) {
+    const size_t e = max_streams < max_tick ? max_streams : max_tick;
+    return e * ((size_t)VBX_SHARD_WARM_FRAMES + frame_len / stride + (frame_len % stride != 0)) + max_tick / stride;
+}
 
 }  // namespace vbx

@@ -45,6 +45,11 @@ void resample_fill(size_t m, double resample_ratio, int32_t *index, double *frac
 size_t session_carry_samples(size_t frame_len, size_t stride, size_t max_block);
 // the most frames one push's frame-loop call covers: the frames max_block samples can complete, and the warm-up
 size_t session_max_frames(size_t stride, size_t max_block);
+// ---- a session pool's geometry (vbx_pool_plan is an entry point) ----
+// elements a slot's carried tail never exceeds: VBX_SHARD_WARM_FRAMES hops and a frame less one sample
+size_t pool_carry_samples(size_t frame_len, size_t stride);
+// the most frames one tick's frame-loop call covers (vbx_pool_plan's call_frames), for ticks of at most max_tick samples in all
+size_t pool_max_call_frames(size_t frame_len, size_t stride, size_t max_streams, size_t max_tick);
 
 // table kinds of vbx_internal_host_table (tests, tools/host_property_check.py)
 enum { HOST_TABLE_WINDOW, HOST_TABLE_LAG_F32, HOST_TABLE_GOERTZEL, HOST_TABLE_DFT2, HOST_TABLE_MFMA, HOST_TABLE_DCT,

@@ -428,6 +428,46 @@ void launch_tracker_stitch_all(hipStream_t s, const res_t *res, long F, int n_re
                                const int32_t *frame_status, res_t *out, long out_ld, long plane_frames, long first, long stop,
                                const double *state, long n_sel);
 
+// k_pool.hip: the launches a session pool's tick (vbx_pool_push) puts around its one frame-loop call.  One table entry per pushed
+// block of at least one sample, in the tick's order: off, row_start and carry_g0 ascend.  A sample of the slot's stream is named
+// by its position relative to `consumed`, the first sample of the block: negative positions lie in the old tail.
+struct pool_entry_t {
+    const void *src;                                      // the block (device), its format's alignment: n_new samples
+    const void *old;                                      // the slot's carried tail (the plane's type): old_len elements, the last one at position -1
+    void *carry;                                          // the slot's OTHER carry buffer: the new tail goes here
+    uint64_t n_new, old_len;
+    uint64_t off, span;                                   // the entry's plane region: elements [off, off + span); span 0: no frame (off: the next region's)
+    int64_t first;                                        // position of the region's element 0 (read_from - consumed)
+    uint64_t carry_g0, carry_len;                         // the new tail: carry_len elements, its first 16-byte group in the launch's carry space
+    int64_t carry_first;                                  // position of the new tail's element 0 (keep_from - consumed)
+    int64_t plane_frame, frames, warm;                    // the entry's segment: frames [plane_frame, plane_frame + frames), the first `warm` not delivered
+    int64_t row_start, n_rows;                            // its rows in the caller's arrays (n_rows = frames - warm; 0: none)
+    int32_t slot, continues_prev;                         // the stream slot (its state row); the tracker continues from that row
+    uint64_t pad;                                         // (144 bytes: the blocks uploaded behind the table start on a 16-byte boundary)
+};
+// ingest: plane[0, total) (the format's output type, launch_unpack's bits) = every entry's region, zeros between a region's end and
+// the next entry's off; and every entry's new tail into its carry.  carry_groups: the 16-byte groups of all the tails.  Every
+// element is written once; nothing before an old tail's element 0, past its old_len or past a block's n_new is read.
+void launch_pool_ingest(hipStream_t s, int format, const pool_entry_t *tab, size_t n, size_t total, void *plane, size_t carry_groups);
+// deliver: clips_deliver's scheme from the pool's table -- rows [plane_frame + warm, + n_rows) of the call's staging into rows
+// [row_start, ...) of the destinations -- and the n_state formant doubles (columns 2 ...) of every delivering entry's last row into
+// state + slot * 2 * VBX_FORMANT_SLOTS_K.  dst_st: the three status rows' bases (null: none).
+struct pool_deliver_t {
+    const pool_entry_t *tab; size_t n, rows;
+    const double *src; size_t src_ld, c0, c1; double *dst; size_t dst_ld;
+    const int32_t *src_st; size_t src_n; int32_t *dst_st[3];
+    const double *src_cand; double *dst_cand; size_t kmax;
+    const int32_t *src_count; int32_t *dst_count;
+    const double *src_peak; double *dst_peak;
+    double *state; size_t n_state;
+};
+void launch_pool_deliver(hipStream_t s, const pool_deliver_t &d);
+// k_tracker.hip: launch_tracker_stitch for every entry of a pool's tick in ONE launch, a lane per entry: an entry with
+// continues_prev has its rows [plane_frame + warm, plane_frame + frames) continued from state + slot * 2 * VBX_FORMANT_SLOTS_K
+void launch_tracker_stitch_pool(hipStream_t s, const res_t *res, long F, int n_res, const int32_t *res_count, int n_est,
+                                const int32_t *frame_status, res_t *out, long out_ld, const pool_entry_t *tab, long n_entries,
+                                const double *state);
+
 // k_front_ex.hip: RMS::rms of the rectangular frame (launch_rms with a null window, bit for bit) of any sample type, written at
 // out_rms + f * rms_ld; out_peak non-null: launch_frame_peak from the same read
 void launch_frame_rms(hipStream_t s, frames_t x, long F, int n, long stride, double *out_rms, long rms_ld, double *out_peak);

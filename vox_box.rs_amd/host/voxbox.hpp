@@ -513,6 +513,59 @@ private:
     vbx_session *s_ = nullptr;
 };
 
+// A pool of independent live streams (vbx_pool_*): max_streams slots on one context that share a sample format (mono), a frame shape
+// and a parameter set, each with its own timeline.  One tick -- push -- takes (slot, block) entries of any sizes, any subset of the
+// slots, in any order, and delivers every entry's rows into ONE set of device arrays, entry after entry (rows[i] tells where), from
+// one upload and a fixed number of launches.  Per slot the rows of all ticks equal, bit for bit, a one-channel session's for the same
+// blocks, marks and resets.  Frames of at most VBX_MAX_FRAME_LEN samples; the online pitch path is not offered for pool slots.
+using PoolEntry = vbx_pool_entry;
+using PoolRows = vbx_pool_rows;
+using PoolPlanRow = vbx_pool_plan_row;
+struct PoolPlan { std::vector<PoolPlanRow> rows; size_t total_rows = 0, call_frames = 0; };
+inline PoolPlan pool_plan(const size_t *h_consumed, const size_t *h_utt_frame, const size_t *h_n_new, size_t n_entries, size_t frame_len,
+                          size_t stride) {
+    PoolPlan p;
+    p.rows.resize(n_entries);
+    if (vbx_pool_plan(h_consumed, h_utt_frame, h_n_new, n_entries, frame_len, stride, p.rows.data(), &p.total_rows, &p.call_frames) != VBX_SUCCESS)
+        throw Error(VBX_E_INVALID, "pool_plan: bad argument");
+    return p;
+}
+class pool {
+public:
+    pool(Context &c, const HostAudio &fmt, size_t frame_len, size_t stride, const AnalysisParams &p, const AnalysisExt *ext,
+         const PitchTrackParams *track, size_t max_streams, size_t max_block, size_t max_tick) : c_(c) {
+        c.check(vbx_pool_open(c.get(), &fmt, frame_len, stride, &p, ext, track, max_streams, max_block, max_tick, &p_));
+    }
+    ~pool() { vbx_pool_close(p_); }
+    pool(const pool &) = delete;
+    pool &operator=(const pool &) = delete;
+    // returns the tick's total rows; h_rows (optional): n_entries entries
+    size_t push(const PoolEntry *h_entries, size_t n_entries, double *records, size_t record_ld, int32_t *status3 = nullptr,
+                size_t status_ld = 0, const PitchTrackOutputs *outputs = nullptr, PoolRows *h_rows = nullptr) {
+        size_t n = 0;
+        c_.check(vbx_pool_push(p_, h_entries, n_entries, records, record_ld, status3, status_ld, outputs, h_rows, &n));
+        return n;
+    }
+    size_t push_device(const PoolEntry *h_entries, size_t n_entries, double *records, size_t record_ld, int32_t *status3 = nullptr,
+                       size_t status_ld = 0, const PitchTrackOutputs *outputs = nullptr, PoolRows *h_rows = nullptr) {
+        size_t n = 0;
+        c_.check(vbx_pool_push_device(p_, h_entries, n_entries, records, record_ld, status3, status_ld, outputs, h_rows, &n));
+        return n;
+    }
+    void mark_utterance(int32_t stream) { c_.check(vbx_pool_mark_utterance(p_, stream)); }
+    void reset_stream(int32_t stream) { c_.check(vbx_pool_reset_stream(p_, stream)); }
+    struct Info { size_t consumed, frames, carried; };
+    Info info(int32_t stream) const {
+        Info i{};
+        c_.check(vbx_pool_info(p_, stream, &i.consumed, &i.frames, &i.carried));
+        return i;
+    }
+    vbx_pool *get() const { return p_; }
+private:
+    Context &c_;
+    vbx_pool *p_ = nullptr;
+};
+
 // A live session over several channels (vbx_session_open_channels / vbx_session_push_channels): ONE session, one upload and one
 // frame-loop call per push for every selected channel of a stream -- a stereo interface, a microphone array.  select: n_sel distinct
 // channels in any order; out: n_sel entries (a host array), entry k the device outputs of channel select[k] for this push's rows.

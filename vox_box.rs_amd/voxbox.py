@@ -226,6 +226,34 @@ class SessionChannelsPlan(C.Structure):
         return d
 
 
+class PoolEntry(C.Structure):
+    """vbx_pool_entry: one (slot, block) of a session pool's tick -- the stream slot, the block's address (host memory for push,
+    device memory for push_device) and its length in samples."""
+    _fields_ = [("stream", C.c_int32), ("block", C.c_void_p), ("n_sample_frames", C.c_size_t)]
+
+
+class PoolRows(C.Structure):
+    """vbx_pool_rows: where a tick put one entry's rows -- [row_start, row_start + n_rows) of every output array."""
+    _fields_ = [("row_start", C.c_int64), ("n_rows", C.c_int64)]
+
+
+class PoolPlanRow(C.Structure):
+    """vbx_pool_plan_row: one entry of vbx_pool_plan -- the slot's SessionPlan (`plan`), its rows in the tick's outputs, the frames
+    m = warm + n_rows it has in the tick's frame-loop call (0: no frame completes) and its first frame in the tick's plane (-1 then)."""
+    _fields_ = [("plan", SessionPlan), ("row_start", C.c_int64), ("n_rows", C.c_int64), ("frames", C.c_int64), ("plane_frame", C.c_int64)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "plan"}
+        d["plan"] = self.plan.as_dict()
+        return d
+
+
+class _PoolIngestEntry(C.Structure):
+    # vbx_internal_pool_ingest's entry (tests): block, old tail and carry destination on the device, positions relative to the block
+    _fields_ = [("d_block", C.c_void_p), ("n_new", C.c_size_t), ("d_old", C.c_void_p), ("old_len", C.c_size_t), ("d_carry", C.c_void_p),
+                ("first", C.c_int64), ("span", C.c_size_t), ("carry_first", C.c_int64), ("carry_len", C.c_size_t)]
+
+
 class PathCommit(C.Structure):
     """vbx_path_commit (device memory): what one push of the online pitch path committed -- `first`: the frame (counted since
     open / reset) of output row 0; `n`: rows written; `n_forced`: how many of them were forced at the cap; `pending`: frames held."""
@@ -397,6 +425,17 @@ def load_library():
         "vbx_analyze_clips": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), sz, C.POINTER(ClipFormat), sz, sz, C.POINTER(AnalysisParams),
                                         C.POINTER(AnalysisExt), C.POINTER(PitchTrackParams), vp, sz, vp, C.POINTER(PitchTrackOutputs)]),
         "vbx_internal_clips_pack": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(sz), sz, sz, vp, C.POINTER(sz)]),
+        "vbx_pool_plan": (C.c_int, [C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), sz, sz, sz, C.POINTER(PoolPlanRow), C.POINTER(sz), C.POINTER(sz)]),
+        "vbx_pool_open": (C.c_int, [vp, C.POINTER(HostAudio), sz, sz, C.POINTER(AnalysisParams), C.POINTER(AnalysisExt),
+                                    C.POINTER(PitchTrackParams), sz, sz, sz, C.POINTER(vp)]),
+        "vbx_pool_push": (C.c_int, [vp, C.POINTER(PoolEntry), sz, vp, sz, vp, sz, C.POINTER(PitchTrackOutputs), C.POINTER(PoolRows), C.POINTER(sz)]),
+        "vbx_pool_push_device": (C.c_int, [vp, C.POINTER(PoolEntry), sz, vp, sz, vp, sz, C.POINTER(PitchTrackOutputs), C.POINTER(PoolRows),
+                                           C.POINTER(sz)]),
+        "vbx_pool_mark_utterance": (C.c_int, [vp, C.c_int32]),
+        "vbx_pool_reset_stream": (C.c_int, [vp, C.c_int32]),
+        "vbx_pool_info": (C.c_int, [vp, C.c_int32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
+        "vbx_pool_close": (None, [vp]),
+        "vbx_internal_pool_ingest": (C.c_int, [vp, i32, C.POINTER(_PoolIngestEntry), sz, sz, vp, C.POINTER(sz)]),
         "vbx_find_formants_resampled_f64": (C.c_int, [vp, vp, sz, sz, sz, dbl, dbl, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp]),
         "vbx_shard_range": (C.c_int, [sz, i32, i32, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
         "vbx_shard_samples": (C.c_int, [sz, sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
@@ -555,6 +594,19 @@ def clips_plan(lengths, frame_len, stride, group_frames=0):
         raise VoxBoxError("vbx_clips_plan: bad argument")
     out = np.array([rows[i].as_tuple() for i in range(ln.size)], dtype=np.int64).reshape(ln.size, 4)
     return out, int(total.value), int(groups.value)
+
+
+def pool_plan(consumed, utt_frame, n_new, frame_len, stride):
+    """vbx_pool_plan: one tick of a session pool -- per entry the slot's (consumed, utt_frame) and the block's n_new (sequences of
+    equal length).  Returns (rows, total_rows, call_frames): rows a list of PoolPlanRow, one per entry.  Host arithmetic only."""
+    a, b, c = (np.ascontiguousarray(v, dtype=np.uint64).reshape(-1) for v in (consumed, utt_frame, n_new))
+    assert a.size == b.size == c.size
+    rows = (PoolPlanRow * max(a.size, 1))()
+    total, call = C.c_size_t(), C.c_size_t()
+    p = lambda v: v.ctypes.data_as(C.POINTER(C.c_size_t))
+    if load_library().vbx_pool_plan(p(a), p(b), p(c), a.size, int(frame_len), int(stride), rows, C.byref(total), C.byref(call)) != 0:
+        raise VoxBoxError("vbx_pool_plan: bad argument")
+    return [rows[i] for i in range(a.size)], int(total.value), int(call.value)
 
 
 def session_plan(consumed, utt_frame, n_new, frame_len, stride):
@@ -896,6 +948,125 @@ class SessionChannels:
         with no staging and no host wait."""
         return self._push(self.vb.L.vbx_session_push_channels_device, _ptr(block), int(n_sample_frames), out, status, outputs, record_ld,
                           status_ld)
+
+
+class Pool:
+    """vbx_pool: max_streams independent live streams (slots) on one context that share a sample format (mono), a frame shape and
+    a parameter set, each with its own timeline (VoxBox.pool).  One tick -- push -- takes (slot, block) entries of any sizes, any
+    subset of the slots, in any order, and delivers every entry's rows into one set of arrays from ONE upload and a fixed number of
+    launches.  Per slot, concatenating what the ticks return gives, bit for bit, what a one-channel Session returns for the same
+    blocks, marks and resets."""
+
+    def __init__(self, vb, params, ext, track, format, frame_len, stride, max_streams, max_block, max_tick):
+        self.vb, self.params, self.ext, self.track = vb, params, ext, track
+        self.format, self.frame_len, self.stride = int(format), int(frame_len), int(stride)
+        self.max_streams, self.max_block, self.max_tick = int(max_streams), int(max_block), int(max_tick)
+        hf = HostAudio.make(self.format, 1, 0, 0)
+        h = C.c_void_p()
+        vb._check(vb.L.vbx_pool_open(vb.ctx, C.byref(hf), self.frame_len, self.stride, C.byref(params),
+                                     None if ext is None else C.byref(ext), None if track is None else C.byref(track),
+                                     self.max_streams, self.max_block, self.max_tick, C.byref(h)))
+        self.handle = h
+        vb._sessions.add(self)
+        self.rec = int(vb.L.vbx_record_doubles_ex(C.byref(params), None if ext is None else C.byref(ext)))
+
+    def info(self, stream):
+        """(sample frames consumed, frames delivered, sample frames carried) of one slot"""
+        a, b, c = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self.vb._check(self.vb.L.vbx_pool_info(self.handle, int(stream), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def rows_of(self, entries):
+        """what a tick of (slot, n_sample_frames) entries would deliver now: (rows [n, 2] of (row_start, n_rows), total_rows)"""
+        ce, n_new = [], []
+        for slot, n in entries:
+            c = self.info(slot)[0]
+            ce.append(frame_count(c, self.frame_len, self.stride))
+            n_new.append(frame_count(c + int(n), self.frame_len, self.stride) - ce[-1])
+        starts = np.concatenate([[0], np.cumsum(n_new)]).astype(np.int64)
+        return np.stack([starts[:-1], np.asarray(n_new, np.int64)], axis=1).reshape(-1, 2), int(starts[-1])
+
+    def _push(self, fn, ents, keep, out, status, outputs, record_ld, status_ld):
+        vb = self.vb
+        n_e = len(ents)
+        h_e = (PoolEntry * max(n_e, 1))(*[PoolEntry(int(s), a, int(n)) for s, a, n in ents])
+        h_r = (PoolRows * max(n_e, 1))()
+        got = C.c_size_t()
+        _, n = self.rows_of([(s, k) for s, _, k in ents])
+        ld = int(record_ld) if record_ld is not None else self.rec + (self.rec & 1)
+        rows = lambda: np.array([(h_r[i].row_start, h_r[i].n_rows) for i in range(n_e)], dtype=np.int64).reshape(n_e, 2)
+        if out is not None:
+            po = None
+            if outputs is not None:
+                po = outputs if isinstance(outputs, PitchTrackOutputs) else PitchTrackOutputs(*[_ptr(a) for a in outputs])
+            vb._check(fn(self.handle, h_e, n_e, _ptr(out), ld, _ptr(status), int(status_ld) if status_ld is not None else n,
+                         None if po is None else C.byref(po), h_r, C.byref(got)))
+            return rows(), int(got.value)
+        assert status is None and outputs is None, "status= and outputs= go with out="
+        own = []
+        try:
+            o, st, lists, po = None, None, (), None
+            if n:
+                o, st = vb.empty((n, ld)), vb.empty((3, n), np.int32)
+                own += [o, st]
+                if self.track is not None:
+                    # columns 0-1 are the caller's path to fill (vbx_pitch_path_f64 over a call's rows): NaN until then
+                    vb._check(vb.L.vbx_memset(vb.ctx, o.ptr, 0xFF, o.nbytes))
+                    lists = (vb.empty((n, int(self.track.kmax), 2)), vb.empty(n, np.int32), vb.empty(n))
+                    own += list(lists)
+                    po = PitchTrackOutputs(lists[0].ptr, lists[1].ptr, lists[2].ptr, None)
+            vb._check(fn(self.handle, h_e, n_e, _ptr(o), ld, _ptr(st), n, None if po is None else C.byref(po), h_r, C.byref(got)))
+            assert got.value == n
+            if n == 0:
+                res = (np.empty((0, ld)), np.empty((3, 0), np.int32))
+                if self.track is not None:
+                    res = res + (np.empty((0, int(self.track.kmax), 2)), np.empty(0, np.int32), np.empty(0))
+                return (rows(),) + res
+            return (rows(), o.numpy(), st.numpy()) + tuple(a.numpy() for a in lists)
+        finally:
+            for d in own:
+                d.free()
+
+    def push(self, entries, out=None, status=None, outputs=None, record_ld=None, status_ld=None):
+        """vbx_pool_push: one tick.  entries: a sequence of (slot, block), block in HOST memory -- a 1-D numpy array of the pool's
+        sample type, or bytes / a uint8 array of packed 24-bit PCM or of the pool's 8-bit format.  Returns (rows, records [total, ld],
+        status3 [3, total]) and in the tracked form also (cand [total, kmax, 2], count, peak), columns 0-1 of the records left as
+        NaN; rows is an int64 array [n_entries, 2] of every entry's (row_start, n_rows).  With out= (device records; status= and
+        outputs= = (cand, count, peak, None) device buffers, status_ld= the status rows' leading dimension, default total): returns
+        (rows, total)."""
+        ents, keep = [], []
+        for slot, block in entries:
+            k, fmt, addr, channels, n_sf = VoxBox._host_audio(block, self.format, 1, None)
+            assert fmt == self.format and channels == 1, "the block is not in the pool's format"
+            keep.append(k)
+            ents.append((slot, addr if n_sf else None, n_sf))
+        return self._push(self.vb.L.vbx_pool_push, ents, keep, out, status, outputs, record_ld, status_ld)
+
+    def push_device(self, entries, out=None, status=None, outputs=None, record_ld=None, status_ld=None):
+        """vbx_pool_push_device: the same for blocks in DEVICE memory -- entries: a sequence of (slot, block, n_sample_frames), block
+        a device buffer or a raw address -- read in stream order on the context's stream; only the tick's table is uploaded."""
+        ents = [(slot, _ptr(block) if int(n) else None, int(n)) for slot, block, n in entries]
+        return self._push(self.vb.L.vbx_pool_push_device, ents, None, out, status, outputs, record_ld, status_ld)
+
+    def mark_utterance(self, stream):
+        """vbx_pool_mark_utterance: the next frame the slot delivers starts a new utterance (host bookkeeping, nothing is launched)"""
+        self.vb._check(self.vb.L.vbx_pool_mark_utterance(self.handle, int(stream)))
+
+    def reset_stream(self, stream):
+        """vbx_pool_reset_stream: the slot behaves as that of a freshly opened pool -- how a slot is reused for the next call"""
+        self.vb._check(self.vb.L.vbx_pool_reset_stream(self.handle, int(stream)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.vb.L.vbx_pool_close(self.handle)
+            self.handle = None
+            self.vb._sessions.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def commit_of(vb, commit):
@@ -1866,6 +2037,18 @@ class VoxBox:
         assert frame_len and stride
         return SessionChannels(self, params, ext, track, format, channels, select, frame_len, stride,
                                int(max_block) if max_block is not None else 100 * int(stride))
+
+    def pool(self, params, ext=None, track=None, format=SAMPLE_ULAW, frame_len=None, stride=None, max_streams=None, max_block=None,
+             max_tick=None):
+        """vbx_pool_open: a session pool on this context -- max_streams slots of mono audio in `format` (SAMPLE_*), each a live
+        stream of its own, fed by ticks of (slot, block) entries (Pool.push): one upload, one frame-loop call and a fixed number of
+        launches per tick whatever the number of streams.  Blocks hold at most max_block samples (default 100 * stride), a tick's
+        blocks together at most max_tick (default max_streams * max_block).  Frames of at most 4096 samples; the online pitch path
+        is not offered for pool slots.  Everything is allocated and warmed here; a Pool is also a context manager."""
+        assert frame_len and stride and max_streams
+        mb = int(max_block) if max_block is not None else 100 * int(stride)
+        return Pool(self, params, ext, track, format, frame_len, stride, max_streams, mb,
+                    int(max_tick) if max_tick is not None else int(max_streams) * mb)
 
     def path_stream(self, kmax, params=None, peak_ref=1.0, max_pending=64):
         """vbx_path_stream_open: an online pitch path on this context over lists of kmax candidates per frame (PathStream.push).
