@@ -7,7 +7,10 @@ as tests/test_gpu_parity.py scales them: every filter's energy is then well abov
 
 Batch sizes: one frame more than the kernel's frames per block, so the last wavefront (or block) is partial: 17 for the few-lag kernel and
 the one-pass Burg (9 at frames of up to 512 samples), 64 / G + 1 for the direct Burg; the kernels that take one frame per block get 6 frames,
-3 from 2048 samples up.  Truth is computed for at most 12 rows of a batch (3 from 2048 samples up), the first and the last always."""
+3 from 2048 samples up.  Truth is computed for at most 12 rows of a batch (3 from 2048 samples up), the first and the last always.
+
+Two groups hold what a caller of the library runs: find_formants at a resample_ratio on every path of the resampled loaders (appended to
+CASES: unwindowed frames, 17 per batch) and the MFCC columns of the fused frame loop (FUSED_CASES, a list and an input of its own)."""
 import numpy as np
 
 import extended_truth as xt
@@ -114,11 +117,99 @@ CASES = [
     # -- find_formants at resample_ratio 1 / 4: the frame resampled inside the one-pass Burg's lag kernel (no window: find_formants has none)
     Case("burg-one-pass-resampled-1200x12", "burg_resampled", 1200, 17, kernels={"burg_lags_resampled"}, rect=True, cls=2, order=12, ratio=0.25),
 ]
+
+
+def _rs(n, ratio, tag, p, m, kernels, cls):
+    """find_formants at a resample_ratio, one case per loader path of tests/test_gpu_analyze_ex.py::SHAPES (m: the resampled length)"""
+    return Case(f"burg-resampled-{n}-{tag}x{p}", "burg_resampled", n, 17, kernels=kernels, rect=True, cls=cls, order=p, ratio=ratio, m=m)
+
+
+_DIRECT, _ONE_PASS, _DENSE = {"burg_resampled"}, {"burg_lags_resampled", "burg_recursion"}, {"resample", "burg_lags", "burg_recursion"}
+# appended, never inserted: frames() takes a case's input offset from its index in CASES
+CASES += [
+    # -- the direct recursion on the resampled view: 4 frames per wavefront (the formant_extraction example's own shape and ratio), m below
+    #    the one-pass forms' 256, an odd m that ends inside a lane, orders off the one-pass list (order 20: 32 lanes per frame)
+    _rs(500, 10000.0 / 44100.0, "r10000:44100", 13, 114, _DIRECT, 1), _rs(1200, 10000.0 / 48000.0, "r10000:48000", 12, 250, _DIRECT, 1),
+    _rs(1103, 10000.0 / 44100.0, "r10000:44100", 13, 251, _DIRECT, 1), _rs(1200, 0.25, "r1:4", 5, 300, _DIRECT, 1),
+    _rs(1200, 0.25, "r1:4", 20, 300, _DIRECT, 1),
+    # -- the one-pass lag kernel on the resampled view at 16 and 20 samples per lane, and upsampling (the last outputs read past the frame)
+    _rs(2048, 0.5, "r1:2", 16, 1024, _ONE_PASS, 2), _rs(2400, 0.5, "r1:2", 12, 1200, _ONE_PASS, 2), _rs(200, 1.5, "r3:2", 8, 300, _ONE_PASS, 2),
+    # -- the dense fallback: resampled into a batch, then the plain one-pass form (m = 2048; a source frame beyond VBX_MAX_FRAME_LEN)
+    _rs(4096, 0.5, "r1:2", 12, 2048, _DENSE, 2), _rs(5000, 0.2, "r1:5", 12, 1000, _DENSE, 2),
+]
 BY_ID = {c.id: c for c in CASES}
 assert len(BY_ID) == len(CASES)
 
 FAMILY_OF = {"autocorr": "autocorrelation", "mfcc": "mfcc", "burg_direct": "burg_direct", "burg_fast": "burg_direct"}
 EST0 = np.array([[320.0, 1.0], [1440.0, 1.0], [2760.0, 1.0], [3200.0, 1.0]])
+
+
+# ---- the fused frame loop's MFCC columns (vbx_analyze_frames_*: the kernel profiled as `analyze`) ----------------------------------------
+# One case per instance of the fused kernel that computes MFCC next to pitch and LPC.  Input: one contiguous stretch of the stream,
+# (F - 1) hop + n samples from the speech fixture's first sample, times 40 (the MFCC scaling above); F = 67 frames -- more than one
+# wavefront of frames, so they are dealt across the XCDs.  The two longest cases need 139,264 samples: 43,264 more than the fixture's
+# two voiced seconds, so their stretch runs on into the stream's unvoiced second (their last compared row is noise at 0.05 * 40).
+FUSED_F = 67
+FUSED_SAMPLES = (FUSED_F - 1) * 2048 + 4096
+PCM_GAIN = 3180.0                                            # 16-bit units per unit of the scaled stretch: its peak, 10.29, lands at 32,720
+
+
+class FusedCase:
+    """n / hop; sample: f64, pcm16 or f32; ctx_env: the switches a context of its own is created under; spec / split / mfcc_rows / interp:
+    what vbx_internal_last_analyze_spec, vbx_internal_last_spectral_split and vbx_profile_names must say, and whether the frame's bins lie
+    between the transform's (2 * spectral_plan_nc(plan) % n != 0: the fused call has no probe for that)."""
+
+    def __init__(self, tag, n, hop, plan, spec=0, split=0, mfcc_rows=False, sample="f64", ctx_env=None, nc=13, lpc_order=12):
+        self.id, self.n, self.hop, self.plan, self.F = f"fused-mfcc-{n}-{tag}", n, hop, plan, FUSED_F
+        self.spec, self.split, self.mfcc_rows, self.sample, self.ctx_env = spec, split, mfcc_rows, sample, ctx_env or {}
+        self.family, self.lpc_order = "mfcc", lpc_order
+        self.p = dict(nc=nc, lo=100.0, hi=8000.0, sr=SR)
+        self.interp = (2 * plan) % n != 0
+
+    def __repr__(self):
+        return self.id
+
+
+FUSED_CASES = [
+    # -- 1200 / 480, the headline shape: the launch-specialised instance with the tail deferred into the LPC rows kernel; without LPC
+    #    (mfcc_rows finishes the rows); 20 coefficients (generic instance, tail in the wavefront); the two switches; PCM; float32
+    FusedCase("default", 1200, 480, 1200, spec=1), FusedCase("no-lpc", 1200, 480, 1200, spec=1, mfcc_rows=True, lpc_order=0),
+    FusedCase("20-coefficients", 1200, 480, 1200, nc=20), FusedCase("generic", 1200, 480, 1200, ctx_env={"VBX_SPECTRAL_SPEC": "0"}),
+    FusedCase("tail-in-the-wavefront", 1200, 480, 1200, ctx_env={"VBX_MFCC_DEFER": "0"}),
+    FusedCase("pcm16", 1200, 480, 1200, spec=2, sample="pcm16"), FusedCase("float32", 1200, 480, 1200, sample="f32"),
+    # -- zero-padded frames in the 1200 plan: every 3rd and every 4th bin of its 2400 points
+    FusedCase("every-3rd-bin", 800, 320, 1200), FusedCase("every-4th-bin", 600, 240, 1200),
+    # -- the power-of-two plans (512: every 4th bin of the 1024 plan's 2048 points); 4096 as two kernels and as one
+    FusedCase("pow2", 1024, 512, 1024), FusedCase("every-4th-bin", 512, 256, 1024), FusedCase("pow2", 2048, 1024, 2048),
+    FusedCase("split", 4096, 2048, 4096, split=1), FusedCase("one-kernel", 4096, 2048, 4096, ctx_env={"VBX_POW2_SPLIT": "0"}),
+    # -- bins interpolated from the transform's: one instance per plan, and an odd length
+    FusedCase("interp", 700, 350, 1024), FusedCase("interp", 1103, 441, 1200), FusedCase("interp-odd", 1199, 480, 1200),
+    FusedCase("interp", 1600, 640, 2048), FusedCase("interp", 3000, 1200, 4096, split=1), FusedCase("interp", 4000, 2000, 4096, split=1),
+]
+assert len({c.id for c in FUSED_CASES}) == len(FUSED_CASES) and all(c.plan == fft_transform(c.n) or (2 * 1200) % c.n == 0 for c in FUSED_CASES)
+assert [c.id for c in FUSED_CASES if c.interp] == [f"fused-mfcc-{n}-interp" + ("-odd" if n == 1199 else "") for n in (700, 1103, 1199, 1600, 3000, 4000)]
+
+
+def fused_audio(case, stream):
+    """(what is uploaded, the f64 samples the kernel's arithmetic starts from) for a stream of at least FUSED_SAMPLES samples.  PCM: the
+    widened sample is int16 / 32767 (vbx_pcm16_to_f64: one correctly rounded division); float32: the float cast to f64, exactly."""
+    a = stream[:(case.F - 1) * case.hop + case.n] * 40.0
+    if case.sample == "pcm16":
+        pcm = np.rint(a * PCM_GAIN).astype(np.int16)
+        return pcm, pcm.astype(np.float64) / 32767.0
+    if case.sample == "f32":
+        f = a.astype(np.float32)
+        return f, f.astype(np.float64)
+    return a, a
+
+
+def fused_frames(case, wide, oracle):
+    """[F, n]: the windowed frames of the compared rows (zero rows elsewhere), the window product in f64 as the oracle takes it"""
+    X = np.zeros((case.F, case.n))
+    w = oracle.window("hanning", case.n)
+    for f in rows(case):
+        X[f] = wide[f * case.hop:f * case.hop + case.n] * w
+    return X
 
 
 def host_speech():
@@ -167,6 +258,20 @@ def oracle_row(oracle, case, x):
     return co
 
 
+def burg_view(case, x):
+    """what Burg's recursion runs on: the frame itself, or -- find_formants at a resample_ratio -- its resampled view under the periodic
+    Hanning window, in long double"""
+    if case.family != "burg_resampled":
+        return x
+    x = xt.resample_linear(x, case.p["ratio"])
+    return x * xt.periodic_hanning(x.size)
+
+
+def burg_len(case):
+    """the length Burg's kernels see (what chooses the direct recursion's lane group)"""
+    return int(np.ceil(case.p["ratio"] * case.n)) if case.family == "burg_resampled" else case.n
+
+
 _TRUTH = {}
 
 
@@ -179,11 +284,7 @@ def truth_row(oracle, case, X, f, reverse=False):
         elif case.family == "mfcc":
             _TRUTH[key] = xt.mfcc(X[f], bins_of(oracle, case), reverse)
         else:
-            x = X[f]
-            if case.family == "burg_resampled":
-                x = xt.resample_linear(x, case.p["ratio"])
-                x = x * xt.periodic_hanning(x.size)
-            t = xt.burg(x, case.p["order"], reverse)
+            t = xt.burg(burg_view(case, X[f]), case.p["order"], reverse)
             assert t is not None, (case, f)
             _TRUTH[key] = (t, None)
     return _TRUTH[key]

@@ -101,11 +101,12 @@ def interpolate_sinc(y, offset, nx, x, depth, reverse=False):
 
 
 def resample_linear(x, ratio):
-    """oracle/vbx_oracle.c:834 (the linear converter in front of find_formants at a resample_ratio).  The steps of the interpolation
-    value are discrete decisions: they are exact here only when 1 / ratio is an integer, which is what the cases use (the output is then
-    every (1 / ratio)-th sample)."""
+    """oracle/vbx_oracle.c:834 (the linear converter in front of find_formants at a resample_ratio), at any ratio.  The interpolation
+    value v is the reference's own discrete stepping: advanced in f64 exactly as oracle/vbx_oracle.c:841-850 advances it
+    (v += 1.0 / ratio, v -= 1.0 -- the rounding of 1 / ratio and of every step is part of WHICH point the converter evaluates, and the
+    library's (li, frac) table is held to it bit for bit by tests/test_host_tables.py).  Only (right - left) * v + left is redone in
+    long double.  tests/test_extended_truth_math.py checks that against exact rationals at a ratio whose inverse is no integer."""
     step = 1.0 / ratio
-    assert step == int(step), ratio
     x = ld(x)
     n = x.size
     m = int(np.ceil(ratio * n))

@@ -111,6 +111,35 @@ def test_levinson_is_exact_at_order_4():
         assert all(_within_ulps(got[j], exact[j]) for j in range(5)), trial
 
 
+def _resample_exact(x, ratio):
+    """oracle/vbx_oracle.c:834-851 in rationals: the interpolation value stepped in f64 as there, the interpolation itself exact"""
+    n, m = len(x), int(math.ceil(ratio * len(x)))
+    at = lambda i: x[i] if i < n else Fraction(0)
+    left, right, nxt, v, step, out = at(0), at(1), 2, 0.0, 1.0 / ratio, []
+    for _ in range(m):
+        while v >= 1.0:
+            left, right, nxt, v = right, at(nxt), nxt + 1, v - 1.0
+        out.append((right - left) * Fraction(v) + left)
+        v += step
+    return out
+
+
+@pytest.mark.parametrize("n,ratio", [(23, 10000.0 / 44100.0), (40, 10000.0 / 48000.0), (9, 1.5), (16, 0.25), (2, 64.0 / 3.0)])
+def test_resampling_is_exact_at_ratios_whose_inverse_is_no_integer(oracle, n, ratio):
+    """The long-double converter against exact rationals, its length and its sampling points against the oracle's: down by the example's
+    10000 / 44100, up by 3 / 2 (the last outputs interpolate towards the zero past the frame).  Three roundings at 2^-64 with M = max |x|:
+    right - left (at most 2 M), its product with v < 1 (at most 2 M), the sum (at most M): within 5 * 2^-64 M of the exact value (an
+    output may be far smaller than M: ulps of the value itself would not be a bound)."""
+    x = np.random.default_rng(n).uniform(-1, 1, n)
+    got, exact = xt.resample_linear(x, ratio), _resample_exact([Fraction(float(v)) for v in x], ratio)
+    assert got.size == len(exact) == oracle.resampled_len(n, ratio) and got.size >= 2
+    bound = 5 * Fraction(2) ** -64 * Fraction(float(np.max(np.abs(x))))
+    assert all(abs(_frac(got[k]) - exact[k]) <= bound for k in range(got.size))
+    assert np.max(np.abs(oracle.resample_linear(x, ratio) - np.array([float(e) for e in exact]))) <= 2.0 ** -52
+    if ratio > 1.0:
+        assert exact[-1] != x[-1] and abs(exact[-1]) < abs(Fraction(float(x[-1])))      # between the last sample and the zero after it
+
+
 def test_the_all_bins_case_needs_every_bin_of_the_half_spectrum(oracle):
     c = ac.BY_ID["mfcc-1000-all-bins"]
     b = ac.bins_of(oracle, c)
@@ -136,6 +165,34 @@ def test_truth_resolves_the_oracle_and_inputs_are_well_conditioned(oracle, speec
     want = ac.rows(case)
     assert want[0] == 0 and want[-1] == case.F - 1 and len(want) <= (3 if case.n >= 2048 else 12)
     assert X[-1, 0] != 0.0                                   # the fold's seed counts on the last row
+    keep, out, e_o, truth = ac.compared_rows(oracle, case, X)
+    assert len(out) <= len(want) // 8, (case, "excluded rows", out)
+    e_rev = max(xt.row_error(ac.truth_row(oracle, case, X, f, reverse=True)[0], truth[f]) for f in keep)
+    _conditions(case.id, max(e_o.values()), e_rev)
+
+
+@pytest.fixture(scope="module")
+def fused_stream():
+    import importlib
+    import __graft_entry__ as g
+    g.load_package()
+    return importlib.import_module(g.PKG_NAME + ".synth").synth_speech(ac.FUSED_SAMPLES, sample_offset=ac.SPEECH_OFFSET)
+
+
+@pytest.mark.parametrize("case", ac.FUSED_CASES, ids=lambda c: c.id)
+def test_fused_mfcc_truth_resolves_the_oracle_and_inputs_are_well_conditioned(oracle, speech, fused_stream, case):
+    """The same three conditions for the fused frame loop's MFCC cases (tests/test_gpu_accuracy.py::test_fused_mfcc): rows of the windowed
+    stretch, 16-bit and float32 samples widened exactly."""
+    assert np.array_equal(fused_stream[:speech.size], speech)                      # the fixture's own samples, continued
+    up, wide = ac.fused_audio(case, fused_stream)
+    assert wide.size == (case.F - 1) * case.hop + case.n <= fused_stream.size
+    if case.sample == "pcm16":
+        assert up.dtype == np.int16 and 32000 < np.abs(up.astype(np.int32)).max() <= 32767
+    if case.sample == "f32":
+        assert up.dtype == np.float32 and not np.array_equal(wide, fused_stream[:wide.size] * 40.0)
+    X = ac.fused_frames(case, wide, oracle)
+    want = ac.rows(case)
+    assert want[0] == 0 and want[-1] == case.F - 1 and len(want) == (3 if case.n >= 2048 else 12)
     keep, out, e_o, truth = ac.compared_rows(oracle, case, X)
     assert len(out) <= len(want) // 8, (case, "excluded rows", out)
     e_rev = max(xt.row_error(ac.truth_row(oracle, case, X, f, reverse=True)[0], truth[f]) for f in keep)
