@@ -9,6 +9,8 @@
 #include "vbx_device.hpp"
 #include "vbx_kernels.hpp"
 
+#include <type_traits>
+
 namespace vbx {
 
 constexpr int NS = VBX_FORMANT_SLOTS_K;   // 6
@@ -683,6 +685,19 @@ __global__ __launch_bounds__(64) void tracker_stitch_pool_kernel(const trk_in_t 
 // VBX_TRACKER_GENERAL=1 (read per launch): the general step on every frame instead of the index form
 static int tracker_general() { const char *e = getenv("VBX_TRACKER_GENERAL"); return (e && atoi(e) != 0) ? 1 : 0; }
 
+// f(std::integral_constant<int, NE>) for the launch's n_est: the kernels are instantiated for 1..6 estimates (anything else takes 6)
+template <class Fn>
+static void with_n_est(int n_est, Fn &&f) {
+    switch (n_est) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 5: f(std::integral_constant<int, 5>{}); break;
+        default: f(std::integral_constant<int, 6>{}); break;
+    }
+}
+
 size_t tracker_chunked_workspace_bytes(long F) {
     const size_t G = (size_t)((F + TRK_CHUNK - 1) / TRK_CHUNK);
     return G * (2 * 2 * NS * sizeof(double) + 2 * sizeof(int32_t) + sizeof(int64_t)) + ((G + 63) / 64 + 1) * sizeof(unsigned long long) + 64;
@@ -705,57 +720,34 @@ void launch_tracker_chunked(hipStream_t s, const res_t *res, long F, int n_res, 
     sp.redo = reinterpret_cast<int32_t *>(w);
     const dim3 block(64), grid_c((unsigned)((G + 63) / 64)), grid_s((unsigned)in.n_seg);
     const int rounds = (F / (in.n_seg > 0 ? in.n_seg : 1) > 8192) ? TRK_ROUNDS_LONG : TRK_ROUNDS;
-#define VBX_TRK_CH(NE)                                                                             \
-    do {                                                                                           \
-        hipLaunchKernelGGL(tracker_spec_kernel<NE>, grid_c, block, 0, s, in, sp, G);               \
-        for (int r = 0; r < rounds; r++) {                                                         \
-            hipLaunchKernelGGL(tracker_check_kernel<NE>, grid_c, block, 0, s, in, sp, G);          \
-            hipLaunchKernelGGL(tracker_repair_kernel<NE>, grid_c, block, 0, s, in, sp, G);         \
-        }                                                                                          \
-        hipLaunchKernelGGL(tracker_check_kernel<NE>, grid_c, block, 0, s, in, sp, G);              \
-        hipLaunchKernelGGL(tracker_sweep_kernel<NE>, grid_s, block, 0, s, in, sp);                 \
-    } while (0)
-    switch (n_est) {
-        case 1: VBX_TRK_CH(1); break;
-        case 2: VBX_TRK_CH(2); break;
-        case 3: VBX_TRK_CH(3); break;
-        case 4: VBX_TRK_CH(4); break;
-        case 5: VBX_TRK_CH(5); break;
-        default: VBX_TRK_CH(6); break;
-    }
-#undef VBX_TRK_CH
+    with_n_est(n_est, [&](auto ne) {
+        constexpr int NE = decltype(ne)::value;
+        hipLaunchKernelGGL(tracker_spec_kernel<NE>, grid_c, block, 0, s, in, sp, G);
+        for (int r = 0; r < rounds; r++) {
+            hipLaunchKernelGGL(tracker_check_kernel<NE>, grid_c, block, 0, s, in, sp, G);
+            hipLaunchKernelGGL(tracker_repair_kernel<NE>, grid_c, block, 0, s, in, sp, G);
+        }
+        hipLaunchKernelGGL(tracker_check_kernel<NE>, grid_c, block, 0, s, in, sp, G);
+        hipLaunchKernelGGL(tracker_sweep_kernel<NE>, grid_s, block, 0, s, in, sp);
+    });
 }
 
 void launch_tracker_stitch(hipStream_t s, const res_t *res, long F, int n_res, const int32_t *res_count, int n_est,
                            const int32_t *frame_status, res_t *out, long out_ld, long first, long stop,
                            const double *state_in, int32_t *changed) {
     trk_in_t in{res, F, n_res, res_count, nullptr, 1, nullptr, frame_status, reinterpret_cast<double *>(out), out_ld, tracker_general()};
-#define VBX_TRK_ST(NE) hipLaunchKernelGGL(tracker_stitch_kernel<NE>, dim3(1), dim3(64), 0, s, in, first, stop, state_in, changed)
-    switch (n_est) {
-        case 1: VBX_TRK_ST(1); break;
-        case 2: VBX_TRK_ST(2); break;
-        case 3: VBX_TRK_ST(3); break;
-        case 4: VBX_TRK_ST(4); break;
-        case 5: VBX_TRK_ST(5); break;
-        default: VBX_TRK_ST(6); break;
-    }
-#undef VBX_TRK_ST
+    with_n_est(n_est, [&](auto ne) {
+        hipLaunchKernelGGL(tracker_stitch_kernel<decltype(ne)::value>, dim3(1), dim3(64), 0, s, in, first, stop, state_in, changed);
+    });
 }
 
 void launch_tracker_stitch_all(hipStream_t s, const res_t *res, long F, int n_res, const int32_t *res_count, int n_est,
                                const int32_t *frame_status, res_t *out, long out_ld, long plane_frames, long first, long stop,
                                const double *state, long n_sel) {
     trk_in_t in{res, F, n_res, res_count, nullptr, 1, nullptr, frame_status, reinterpret_cast<double *>(out), out_ld, tracker_general()};
-#define VBX_TRK_ST(NE) hipLaunchKernelGGL(tracker_stitch_all_kernel<NE>, dim3((unsigned)n_sel), dim3(64), 0, s, in, plane_frames, first, stop, state)
-    switch (n_est) {
-        case 1: VBX_TRK_ST(1); break;
-        case 2: VBX_TRK_ST(2); break;
-        case 3: VBX_TRK_ST(3); break;
-        case 4: VBX_TRK_ST(4); break;
-        case 5: VBX_TRK_ST(5); break;
-        default: VBX_TRK_ST(6); break;
-    }
-#undef VBX_TRK_ST
+    with_n_est(n_est, [&](auto ne) {
+        hipLaunchKernelGGL(tracker_stitch_all_kernel<decltype(ne)::value>, dim3((unsigned)n_sel), dim3(64), 0, s, in, plane_frames, first, stop, state);
+    });
 }
 
 void launch_tracker_stitch_pool(hipStream_t s, const res_t *res, long F, int n_res, const int32_t *res_count, int n_est,
@@ -763,16 +755,9 @@ void launch_tracker_stitch_pool(hipStream_t s, const res_t *res, long F, int n_r
                                 const double *state) {
     if (n_entries <= 0) return;
     trk_in_t in{res, F, n_res, res_count, nullptr, 1, nullptr, frame_status, reinterpret_cast<double *>(out), out_ld, tracker_general()};
-#define VBX_TRK_ST(NE) hipLaunchKernelGGL(tracker_stitch_pool_kernel<NE>, dim3((unsigned)((n_entries + 63) / 64)), dim3(64), 0, s, in, tab, n_entries, state)
-    switch (n_est) {
-        case 1: VBX_TRK_ST(1); break;
-        case 2: VBX_TRK_ST(2); break;
-        case 3: VBX_TRK_ST(3); break;
-        case 4: VBX_TRK_ST(4); break;
-        case 5: VBX_TRK_ST(5); break;
-        default: VBX_TRK_ST(6); break;
-    }
-#undef VBX_TRK_ST
+    with_n_est(n_est, [&](auto ne) {
+        hipLaunchKernelGGL(tracker_stitch_pool_kernel<decltype(ne)::value>, dim3((unsigned)((n_entries + 63) / 64)), dim3(64), 0, s, in, tab, n_entries, state);
+    });
 }
 
 void launch_tracker(hipStream_t s, const res_t *res, long F, int n_res, const int32_t *res_count,
@@ -781,17 +766,10 @@ void launch_tracker(hipStream_t s, const res_t *res, long F, int n_res, const in
     const int bs = 64;
     const dim3 grid((unsigned)((n_seg + bs - 1) / bs)), block(bs);
     double *o = reinterpret_cast<double *>(out);
-#define VBX_TRK(NE) hipLaunchKernelGGL(tracker_kernel<NE>, grid, block, 0, s, res, F, n_res, res_count, seg_start, n_seg, \
-                                       est_init, frame_status, o, out_ld, t0, tc, tracker_general())
-    switch (n_est) {
-        case 1: VBX_TRK(1); break;
-        case 2: VBX_TRK(2); break;
-        case 3: VBX_TRK(3); break;
-        case 4: VBX_TRK(4); break;
-        case 5: VBX_TRK(5); break;
-        default: VBX_TRK(6); break;
-    }
-#undef VBX_TRK
+    with_n_est(n_est, [&](auto ne) {
+        hipLaunchKernelGGL(tracker_kernel<decltype(ne)::value>, grid, block, 0, s, res, F, n_res, res_count, seg_start, n_seg, est_init, frame_status, o, out_ld,
+                           t0, tc, tracker_general());
+    });
 }
 
 }  // namespace vbx

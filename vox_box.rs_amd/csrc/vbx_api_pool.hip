@@ -1,6 +1,6 @@
 // vbx_api_pool.hip -- a session pool: many independent live streams on one context, analysed from one upload and one launch chain
-// per tick (vbx_pool_*).
-#include "vbx_ctx.hpp"
+// per tick (vbx_pool_*).  What a tick shares with a session's push is the live core's (vbx_live.hpp).
+#include "vbx_live.hpp"
 
 #include <cstring>
 #include <string>
@@ -28,24 +28,16 @@ struct pool_slot_t {
 
 // max_streams slots that share a format, a frame shape and a parameter set.  The pool owns everything a tick writes before the
 // caller's arrays: the carry regions (slot k's two regions at elements (2 k + b) * carry_cap), the tick's plane, the two pinned
-// staging buffers with their raw device slots (table first, the gathered blocks behind it), the chunk-local records / status rows /
-// lists of the largest frame-loop call and the state rows.  The frame loop's own workspaces are the context's.
+// staging buffers with their raw device slots (the ring: table first, the gathered blocks behind it) and the core's chunk-local
+// buffers of the largest frame-loop call and max_streams state rows.
 struct vbx_pool {
-    vbx_ctx *ctx = nullptr;
-    int fmt = 0;
-    size_t frame_len = 0, stride = 0, max_streams = 0, max_block = 0, max_tick = 0;
-    vbx_analysis_params p{}; vbx_analysis_ext ext{}; vbx_pitch_track_params track{};
-    bool have_ext = false, have_track = false;
-    size_t rec = 0, ld_c = 0, call_max = 0, plane_cap = 0, carry_cap = 0, raw_bytes = 0;
+    live_core_t core;
+    size_t max_streams = 0, max_block = 0, max_tick = 0;
+    size_t call_max = 0, plane_cap = 0, carry_cap = 0;
     std::vector<pool_slot_t> slots;
     uint64_t ticks = 0;                                   // vbx_pool_push calls so far (the duplicate check's stamp)
-    size_t uploads = 0;                                   // ticks that uploaded: upload k stages through slot k & 1
     void *carry = nullptr, *plane = nullptr;
-    void *stage[2] = {nullptr, nullptr}, *raw[2] = {nullptr, nullptr};
-    hipEvent_t staged[2] = {nullptr, nullptr};
-    double *c_rec = nullptr; int32_t *c_st = nullptr;
-    vbx_pitch *c_cand = nullptr; int32_t *c_count = nullptr; double *c_peak = nullptr;
-    double *state = nullptr;                              // max_streams rows of 2 * VBX_FORMANT_SLOTS doubles
+    live_ring_t ring;
     // a tick's host scratch, kept between ticks so that none allocates
     std::vector<size_t> h_consumed, h_utt, h_new;
     std::vector<vbx_pool_plan_row> rows;
@@ -54,29 +46,11 @@ struct vbx_pool {
 };
 
 static void pool_free(vbx_pool *q) {
-    for (int i = 0; i < 2; i++) {
-        if (q->stage[i]) hipHostFree(q->stage[i]);
-        if (q->raw[i]) hipFree(q->raw[i]);
-        if (q->staged[i]) hipEventDestroy(q->staged[i]);
-    }
+    q->ring.free();
     if (q->carry) hipFree(q->carry);
     if (q->plane) hipFree(q->plane);
-    if (q->c_rec) hipFree(q->c_rec);
-    if (q->c_st) hipFree(q->c_st);
-    if (q->c_cand) hipFree(q->c_cand);
-    if (q->c_count) hipFree(q->c_count);
-    if (q->c_peak) hipFree(q->c_peak);
-    if (q->state) hipFree(q->state);
+    live_free(q->core);
     delete q;
-}
-
-// the frame loop on frames [0, n) of the pool's plane into the chunk-local buffers, every entry a segment (q->seg)
-static int pool_analyze(vbx_pool *q, const char *fn, size_t n, bool want_peak) {
-    vbx_pitch_track_outputs to{};
-    to.cand = q->c_cand; to.count = q->c_count; to.peak = want_peak ? q->c_peak : nullptr;
-    return analyze_ex(q->ctx, fn, frames_t(q->plane, sample_plane_kind(q->fmt)), n, q->frame_len, q->stride, &q->p,
-                      q->have_ext ? &q->ext : nullptr, q->have_track ? &q->track : nullptr, q->seg.data(), q->seg.size(), q->c_rec, q->ld_c,
-                      q->c_st, q->have_track ? &to : nullptr, true);
 }
 
 int vbx_pool_open(vbx_ctx *ctx, const vbx_host_audio *h_fmt, size_t frame_len, size_t stride, const vbx_analysis_params *h_p,
@@ -87,72 +61,43 @@ int vbx_pool_open(vbx_ctx *ctx, const vbx_host_audio *h_fmt, size_t frame_len, s
     VBX_REQUIRE(ctx, out != nullptr, "null output");
     *out = nullptr;
     VBX_REQUIRE(ctx, h_fmt != nullptr && h_p != nullptr, "null argument");
-    VBX_REQUIRE(ctx, sample_format_ok(h_fmt->format), "unknown sample format");
-    VBX_REQUIRE(ctx, h_fmt->channels == 1 && h_fmt->channel == 0, "a pool's streams are mono: channels must be 1 and channel 0");
-    VBX_REQUIRE(ctx, h_fmt->reserved == 0 && h_fmt->chunk_frames == 0, "reserved and chunk_frames must be 0");
+    int rc = live_check_audio(ctx, fn, h_fmt, h_fmt->channels == 1 && h_fmt->channel == 0, "a pool's streams are mono: channels must be 1 and channel 0");
+    if (rc != VBX_SUCCESS) return rc;
     VBX_REQUIRE(ctx, max_streams >= 1, "max_streams must be >= 1");
     VBX_REQUIRE(ctx, max_block >= 1 && max_tick >= max_block, "need 1 <= max_block_sample_frames <= max_tick_sample_frames");
     VBX_REQUIRE(ctx, frame_len >= 1 && frame_len <= VBX_MAX_FRAME_LEN, "frame_len must be in [1, VBX_MAX_FRAME_LEN]: longer frames take one vbx_session per stream");
     VBX_REQUIRE(ctx, stride >= 1 && stride <= ((size_t)1 << 40), "stride must be in [1, 2^40]");
     VBX_REQUIRE(ctx, max_streams <= 0x7fffffffull && max_tick <= ((size_t)1 << 40), "max_streams or max_tick_sample_frames too large");
-    VBX_REQUIRE(ctx, !h_p->formant_order || (h_p->n_est >= 1 && h_p->n_est <= VBX_FORMANT_SLOTS), "n_est must be in [1, 6]");
+    if ((rc = live_check_n_est(ctx, fn, h_p)) != VBX_SUCCESS) return rc;
     const size_t call_max = pool_max_call_frames(frame_len, stride, max_streams, max_tick);
     VBX_REQUIRE(ctx, call_max <= 0x7fffffffull, "too many frames for one launch");
-    if (h_track) {
-        vbx_pitch_path_params path = h_track->path;
-        if (path.time_step == 0.0) path.time_step = (double)stride / h_p->sample_rate;
-        int rc = check_pitch_path(ctx, fn, path, call_max, h_track->kmax, true, nullptr, 0);
-        if (rc != VBX_SUCCESS) return rc;
-    }
+    const live_core_t core = live_make(ctx, h_fmt->format, frame_len, stride, h_p, h_ext, h_track);
+    if ((rc = live_check_path(core, fn, call_max)) != VBX_SUCCESS) return rc;
     VBX_HIP(ctx, hipSetDevice(ctx->device));
     vbx_pool *q = new vbx_pool();
-    q->ctx = ctx; q->fmt = h_fmt->format;
-    q->frame_len = frame_len; q->stride = stride; q->max_streams = max_streams; q->max_block = max_block; q->max_tick = max_tick;
-    q->p = *h_p;
-    if (h_ext) { q->ext = *h_ext; q->have_ext = true; }
-    if (h_track) { q->track = *h_track; q->have_track = true; }
-    q->rec = vbx_record_doubles_ex(h_p, h_ext);
-    q->ld_c = q->rec + (q->rec & 1);
+    q->core = core; q->max_streams = max_streams; q->max_block = max_block; q->max_tick = max_tick;
     q->call_max = call_max;
     q->plane_cap = call_max * stride + frame_len;
     q->carry_cap = (pool_carry_samples(frame_len, stride) + 7) & ~(size_t)7;      // whole 16-byte groups for every element type
     const size_t e_max = max_streams < max_tick ? max_streams : max_tick;         // entries that hold a sample
-    q->raw_bytes = e_max * sizeof(pool_entry_t) + max_tick * sample_src_bytes(q->fmt) + 16 * e_max;
+    const size_t raw_bytes = e_max * sizeof(pool_entry_t) + max_tick * sample_src_bytes(core.fmt) + 16 * e_max;
     q->slots.resize(max_streams);
     q->h_consumed.reserve(max_streams); q->h_utt.reserve(max_streams); q->h_new.reserve(max_streams);
     q->rows.reserve(max_streams); q->tab.reserve(e_max); q->seg.reserve(max_streams);
-    const size_t ob = sample_out_bytes(q->fmt), kmax = h_track ? h_track->kmax : 0, nbuf = call_max;
-#define POOL_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { hipStreamSynchronize(ctx->stream); pool_free(q); \
-        return fail(ctx, VBX_E_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
-    POOL_HIP(hipMalloc(&q->carry, 2 * max_streams * q->carry_cap * ob));    // (hipMalloc: 256-byte aligned bases)
-    POOL_HIP(hipMemsetAsync(q->carry, 0, 2 * max_streams * q->carry_cap * ob, ctx->stream));
-    POOL_HIP(hipMalloc(&q->plane, q->plane_cap * ob));
-    POOL_HIP(hipMemsetAsync(q->plane, 0, q->plane_cap * ob, ctx->stream));
-    for (int i = 0; i < 2; i++) {
-        POOL_HIP(hipHostMalloc(&q->stage[i], q->raw_bytes, hipHostMallocDefault));
-        POOL_HIP(hipMalloc(&q->raw[i], q->raw_bytes));
-        POOL_HIP(hipEventCreateWithFlags(&q->staged[i], hipEventDisableTiming));
-    }
-    POOL_HIP(hipMalloc((void **)&q->c_rec, nbuf * q->ld_c * sizeof(double)));
-    POOL_HIP(hipMalloc((void **)&q->c_st, 3 * nbuf * sizeof(int32_t)));
-    if (h_track) {
-        POOL_HIP(hipMalloc((void **)&q->c_cand, nbuf * kmax * sizeof(vbx_pitch)));
-        POOL_HIP(hipMalloc((void **)&q->c_count, nbuf * sizeof(int32_t)));
-        POOL_HIP(hipMalloc((void **)&q->c_peak, nbuf * sizeof(double)));
-    }
-    POOL_HIP(hipMalloc((void **)&q->state, max_streams * 2 * VBX_FORMANT_SLOTS * sizeof(double)));
-    POOL_HIP(hipMemsetAsync(q->state, 0, max_streams * 2 * VBX_FORMANT_SLOTS * sizeof(double), ctx->stream));
-#undef POOL_HIP
-    // the largest shape a tick can ask for, on the zeroed plane, with as many segments as a tick can have entries: the context's
-    // workspaces and tables are as large as they will ever have to be, and what only the frame loop's parts know is rejected here
+    const size_t ob = sample_out_bytes(core.fmt);
+    LIVE_HIP(ctx, hipMalloc(&q->carry, 2 * max_streams * q->carry_cap * ob), pool_free(q));    // (hipMalloc: 256-byte aligned bases)
+    LIVE_HIP(ctx, hipMemsetAsync(q->carry, 0, 2 * max_streams * q->carry_cap * ob, ctx->stream), pool_free(q));
+    LIVE_HIP(ctx, hipMalloc(&q->plane, q->plane_cap * ob), pool_free(q));
+    LIVE_HIP(ctx, hipMemsetAsync(q->plane, 0, q->plane_cap * ob, ctx->stream), pool_free(q));
+    rc = q->ring.alloc(ctx, raw_bytes, raw_bytes);
+    if (rc == VBX_SUCCESS) rc = live_alloc(q->core, call_max, max_streams);
+    if (rc != VBX_SUCCESS) { pool_free(q); return rc; }
+    // the warm-up: the largest shape a tick can ask for, on the zeroed plane, with as many segments as a tick can have entries
     const size_t per = call_max / e_max;
     for (size_t k = 0; k < e_max; k++) q->seg.push_back((int64_t)(k * per));
-    int rc = pool_analyze(q, fn, nbuf, true);
-    if (rc == VBX_SUCCESS) rc = check_launch(ctx, fn);
+    rc = live_warm_up(q->core, fn, q->plane, call_max, q->seg.data(), q->seg.size(), [&] { pool_free(q); });
+    if (rc != VBX_SUCCESS) return rc;
     q->seg.clear();
-    ctx->last_track.res = nullptr;                        // the chunk-local rows are no track of the caller's
-    ctx->last_track.n_est = 0;
-    if (rc != VBX_SUCCESS) { const std::string why = ctx->last_error; hipStreamSynchronize(ctx->stream); vbx_sync(ctx); pool_free(q); return fail(ctx, rc, why); }
     *out = q;
     return VBX_SUCCESS;
 }
@@ -161,12 +106,13 @@ static int pool_push_impl(vbx_pool *q, const char *fn, const vbx_pool_entry *h_e
                           size_t record_ld, int32_t *status3, size_t status_ld, const vbx_pitch_track_outputs *h_out, vbx_pool_rows *h_rows,
                           size_t *h_total) {
     if (!q) return fail(nullptr, VBX_E_INVALID, std::string(fn) + ": null pool");
-    vbx_ctx *ctx = q->ctx;
+    const live_core_t &c = q->core;
+    vbx_ctx *ctx = c.ctx;
     if (h_total) *h_total = 0;
     if (n_entries == 0) return VBX_SUCCESS;
     VBX_REQUIRE_FN(ctx, fn, h_entries != nullptr, "null entries");
     // ---- everything that can be refused, before anything is queued or any slot changes
-    const size_t sb = sample_src_bytes(q->fmt), ob = sample_out_bytes(q->fmt);
+    const size_t sb = sample_src_bytes(c.fmt), ob = sample_out_bytes(c.fmt), stride = c.stride;
     const uint64_t stamp = ++q->ticks;
     size_t sum = 0, n_live = 0;
     const char *why = nullptr;
@@ -180,7 +126,7 @@ static int pool_push_impl(vbx_pool *q, const char *fn, const vbx_pool_entry *h_e
         if (e.block == nullptr) why = "null block";
         else if (e.n_sample_frames > q->max_block) why = "a block is larger than the pool's max_block_sample_frames";
         else if (e.n_sample_frames > q->max_tick - sum) why = "the tick's blocks are larger than the pool's max_tick_sample_frames";
-        else if (on_device && q->fmt != VBX_SAMPLE_PCM24 && (uintptr_t)e.block % sb != 0) why = "a block needs its type's alignment";
+        else if (on_device && c.fmt != VBX_SAMPLE_PCM24 && (uintptr_t)e.block % sb != 0) why = "a block needs its type's alignment";
         sum += e.n_sample_frames;
         n_live++;
     }
@@ -191,22 +137,15 @@ static int pool_push_impl(vbx_pool *q, const char *fn, const vbx_pool_entry *h_e
         q->h_consumed[i] = s.consumed; q->h_utt[i] = s.utt_frame; q->h_new[i] = h_entries[i].n_sample_frames;
     }
     size_t total = 0, call_frames = 0;
-    if (vbx_pool_plan(q->h_consumed.data(), q->h_utt.data(), q->h_new.data(), n_entries, q->frame_len, q->stride, q->rows.data(), &total,
+    if (vbx_pool_plan(q->h_consumed.data(), q->h_utt.data(), q->h_new.data(), n_entries, c.frame_len, stride, q->rows.data(), &total,
                       &call_frames) != VBX_SUCCESS)
         return fail(ctx, VBX_E_INVALID, std::string(fn) + ": bad pool plan");
     VBX_REQUIRE_FN(ctx, fn, call_frames <= q->call_max, "the tick's frame-loop call is larger than the pool was opened for");
     bool want_peak = false;
     if (total) {
-        VBX_REQUIRE_FN(ctx, fn, out_records != nullptr, "null argument");
-        VBX_REQUIRE_FN(ctx, fn, ((uintptr_t)out_records & 15) == 0, "records must be 16-byte aligned");
-        VBX_REQUIRE_FN(ctx, fn, record_ld >= q->rec && record_ld % 2 == 0, "record_ld must be even and >= vbx_record_doubles(params)");
-        VBX_REQUIRE_FN(ctx, fn, status3 == nullptr || status_ld >= total, "status_ld must be >= the rows the tick delivers");
-        if (q->have_track) {
-            VBX_REQUIRE_FN(ctx, fn, h_out != nullptr && h_out->cand != nullptr && h_out->count != nullptr, "the tracked form needs h_outputs->cand and ->count");
-            VBX_REQUIRE_FN(ctx, fn, q->track.path.silence_threshold == 0.0 || h_out->peak != nullptr, "a silence_threshold needs h_outputs->peak");
-            VBX_REQUIRE_FN(ctx, fn, h_out->index == nullptr, "h_outputs->index must be NULL: the caller runs the path (vbx_pitch_path_f64)");
-            want_peak = h_out->peak != nullptr;
-        }
+        const vbx_channel_outputs o{out_records, status3, h_out};
+        int rc = live_check_outputs(c, fn, LIVE_OUT_ALL, "h_outputs", o, record_ld, status_ld, total, "status_ld must be >= the rows the tick delivers", &want_peak);
+        if (rc != VBX_SUCCESS) return rc;
     }
     for (size_t i = 0; i < n_entries; i++) if (h_rows) { h_rows[i].row_start = q->rows[i].row_start; h_rows[i].n_rows = q->rows[i].n_rows; }
     if (h_total) *h_total = total;
@@ -214,10 +153,10 @@ static int pool_push_impl(vbx_pool *q, const char *fn, const vbx_pool_entry *h_e
 
     // ---- the table, and in the host form the blocks behind it, in one pinned buffer
     VBX_HIP(ctx, hipSetDevice(ctx->device));
-    const int slot = (int)(q->uploads & 1);
-    VBX_HIP(ctx, hipEventSynchronize(q->staged[slot]));   // the upload of two ticks ago has left the staging buffer
-    char *stage = static_cast<char *>(q->stage[slot]);
-    const char *raw = static_cast<const char *>(q->raw[slot]);
+    char *stage = nullptr;
+    int rc = q->ring.acquire(ctx, &stage);
+    if (rc != VBX_SUCCESS) return rc;
+    const char *raw = static_cast<const char *>(q->ring.raw[q->ring.slot()]);
     size_t at = n_live * sizeof(pool_entry_t);            // where the next block goes (16-byte aligned)
     q->tab.clear(); q->seg.clear();
     size_t carry_groups = 0, plane_total = 0, next_off = 0;
@@ -245,14 +184,14 @@ static int pool_push_impl(vbx_pool *q, const char *fn, const vbx_pool_entry *h_e
         e.row_start = r.row_start; e.n_rows = r.n_rows;
         e.slot = he.stream; e.continues_prev = 0;
         if (r.n_rows) {
-            e.span = ((size_t)r.frames - 1) * q->stride + q->frame_len;
+            e.span = ((size_t)r.frames - 1) * stride + q->core.frame_len;
             e.first = (int64_t)r.plan.read_from - (int64_t)c;
             e.plane_frame = r.plane_frame; e.frames = r.frames; e.warm = (int64_t)r.plan.warm;
-            e.off = (size_t)r.plane_frame * q->stride;
+            e.off = (size_t)r.plane_frame * stride;
             e.continues_prev = r.plan.continues_prev;
             any_continues = any_continues || r.plan.continues_prev;
             plane_total = e.off + e.span;
-            next_off = e.off + (e.span / q->stride + (e.span % q->stride != 0)) * q->stride;
+            next_off = e.off + (e.span / stride + (e.span % stride != 0)) * stride;
             q->seg.push_back(r.plane_frame);
         }
         e.carry_first = (int64_t)r.plan.keep_from - (int64_t)c;
@@ -265,44 +204,31 @@ static int pool_push_impl(vbx_pool *q, const char *fn, const vbx_pool_entry *h_e
         q->tab.push_back(e);
     }
     std::memcpy(stage, q->tab.data(), n_live * sizeof(pool_entry_t));
-    const size_t up_bytes = on_device ? n_live * sizeof(pool_entry_t) : at;
-    VBX_HIP(ctx, hipMemcpyAsync(q->raw[slot], stage, up_bytes, hipMemcpyHostToDevice, ctx->stream));      // ONE upload
-    VBX_HIP(ctx, hipEventRecord(q->staged[slot], ctx->stream));
-    q->uploads++;
-    const pool_entry_t *d_tab = static_cast<const pool_entry_t *>(q->raw[slot]);
-    { Prof p(ctx, k_pool_ingest_names[sample_name_slot(q->fmt)]);
-      launch_pool_ingest(ctx->stream, q->fmt, d_tab, n_live, plane_total, q->plane, carry_groups); }
+    const pool_entry_t *d_tab = reinterpret_cast<const pool_entry_t *>(raw);
+    if ((rc = q->ring.upload(ctx, on_device ? n_live * sizeof(pool_entry_t) : at)) != VBX_SUCCESS) return rc;      // ONE upload
+    { Prof p(ctx, k_pool_ingest_names[sample_name_slot(c.fmt)]);
+      launch_pool_ingest(ctx->stream, c.fmt, d_tab, n_live, plane_total, q->plane, carry_groups); }
     for (size_t i = 0; i < n_entries; i++) {              // the slots' timelines: the tails are where the ingest puts them
         if (h_entries[i].n_sample_frames == 0) continue;
         pool_slot_t &s = q->slots[(size_t)h_entries[i].stream];
         s.cur ^= 1; s.consumed += h_entries[i].n_sample_frames; s.keep_from = q->rows[i].plan.keep_from; s.frames += (size_t)q->rows[i].n_rows;
     }
     if (total) {
-        int rc = pool_analyze(q, fn, call_frames, want_peak);
-        if (rc != VBX_SUCCESS) return rc;
+        if ((rc = live_analyze(c, fn, q->plane, call_frames, q->seg.data(), q->seg.size(), want_peak)) != VBX_SUCCESS) return rc;
         // the entries that continue an utterance: their trackers go on from the true state, the formant row of the slot's last frame delivered
-        if (any_continues && q->p.formant_order) {
+        if (any_continues && c.p.formant_order) {
+            if ((rc = live_take_last_track(c, fn, call_frames)) != VBX_SUCCESS) return rc;
             const auto &lt = ctx->last_track;
-            if (lt.res == nullptr || lt.out != reinterpret_cast<res_t *>(q->c_rec + 2) || lt.F != (long)call_frames)
-                return fail(ctx, VBX_E_RUNTIME, std::string(fn) + ": the frame loop left no track to stitch");
-            { Prof p(ctx, "tracker_stitch_pool");
-              launch_tracker_stitch_pool(ctx->stream, lt.res, lt.F, VBX_MAX_RESONANCES, lt.cnt, lt.n_est, lt.st, lt.out, lt.out_ld, d_tab, (long)n_live,
-                                         q->state); }
+            Prof p(ctx, "tracker_stitch_pool");
+            launch_tracker_stitch_pool(ctx->stream, lt.res, lt.F, VBX_MAX_RESONANCES, lt.cnt, lt.n_est, lt.st, lt.out, lt.out_ld, d_tab, (long)n_live, c.state);
         }
         pool_deliver_t d{};
-        d.tab = d_tab; d.n = n_live; d.rows = total;
-        d.src = q->c_rec; d.src_ld = q->ld_c; d.c0 = q->have_track ? 2 : 0; d.c1 = q->rec; d.dst = out_records; d.dst_ld = record_ld;
-        d.src_st = q->c_st; d.src_n = call_frames;
+        live_deliver_source(d, c, call_frames, want_peak);
+        d.tab = d_tab; d.n = n_live; d.rows = total; d.dst = out_records; d.dst_ld = record_ld;
         for (int k = 0; k < 3; k++) d.dst_st[k] = status3 ? status3 + (size_t)k * status_ld : nullptr;
-        if (q->have_track) {
-            d.src_cand = reinterpret_cast<const double *>(q->c_cand); d.dst_cand = reinterpret_cast<double *>(h_out->cand); d.kmax = q->track.kmax;
-            d.src_count = q->c_count; d.dst_count = h_out->count;
-            if (want_peak) { d.src_peak = q->c_peak; d.dst_peak = h_out->peak; }
-        }
-        if (q->p.formant_order) { d.state = q->state; d.n_state = 2 * q->p.n_est; }
+        if (c.have_track) { d.dst_cand = reinterpret_cast<double *>(h_out->cand); d.dst_count = h_out->count; d.dst_peak = h_out->peak; }
         { Prof p(ctx, "pool_deliver"); launch_pool_deliver(ctx->stream, d); }
-        ctx->last_track.res = nullptr;                    // the chunk-local rows are no track of the caller's: nothing to stitch
-        ctx->last_track.n_est = 0;
+        live_drop_last_track(ctx);
     }
     return check_launch(ctx, fn);
 }
@@ -320,15 +246,15 @@ int vbx_pool_push_device(vbx_pool *pool, const vbx_pool_entry *h_entries, size_t
 
 int vbx_pool_mark_utterance(vbx_pool *pool, int32_t stream) {
     if (!pool) return fail(nullptr, VBX_E_INVALID, "vbx_pool_mark_utterance: null pool");
-    VBX_REQUIRE(pool->ctx, stream >= 0 && (size_t)stream < pool->max_streams, "a stream outside [0, max_streams)");
+    VBX_REQUIRE(pool->core.ctx, stream >= 0 && (size_t)stream < pool->max_streams, "a stream outside [0, max_streams)");
     pool_slot_t &s = pool->slots[(size_t)stream];
-    s.utt_frame = vbx_frame_count(s.consumed, pool->frame_len, pool->stride);
+    s.utt_frame = vbx_frame_count(s.consumed, pool->core.frame_len, pool->core.stride);
     return VBX_SUCCESS;
 }
 
 int vbx_pool_reset_stream(vbx_pool *pool, int32_t stream) {
     if (!pool) return fail(nullptr, VBX_E_INVALID, "vbx_pool_reset_stream: null pool");
-    VBX_REQUIRE(pool->ctx, stream >= 0 && (size_t)stream < pool->max_streams, "a stream outside [0, max_streams)");
+    VBX_REQUIRE(pool->core.ctx, stream >= 0 && (size_t)stream < pool->max_streams, "a stream outside [0, max_streams)");
     // (nothing is queued: the next ingest keeps nothing of the tail, and a first push of an utterance stitches from no state)
     pool_slot_t &s = pool->slots[(size_t)stream];
     s.consumed = 0; s.utt_frame = 0; s.frames = 0; s.keep_from = 0;
@@ -337,7 +263,7 @@ int vbx_pool_reset_stream(vbx_pool *pool, int32_t stream) {
 
 int vbx_pool_info(const vbx_pool *pool, int32_t stream, size_t *h_consumed, size_t *h_frames, size_t *h_carried) {
     if (!pool) return fail(nullptr, VBX_E_INVALID, "vbx_pool_info: null pool");
-    VBX_REQUIRE(pool->ctx, stream >= 0 && (size_t)stream < pool->max_streams, "a stream outside [0, max_streams)");
+    VBX_REQUIRE(pool->core.ctx, stream >= 0 && (size_t)stream < pool->max_streams, "a stream outside [0, max_streams)");
     const pool_slot_t &s = pool->slots[(size_t)stream];
     if (h_consumed) *h_consumed = s.consumed;
     if (h_frames) *h_frames = s.frames;
@@ -347,10 +273,7 @@ int vbx_pool_info(const vbx_pool *pool, int32_t stream, size_t *h_consumed, size
 
 void vbx_pool_close(vbx_pool *pool) {
     if (!pool) return;
-    hipSetDevice(pool->ctx->device);
-    hipStreamSynchronize(pool->ctx->stream);              // the pool's buffers may still be read by queued work
-    if (pool->ctx->side) hipStreamSynchronize(pool->ctx->side);
-    if (pool->ctx->trk) hipStreamSynchronize(pool->ctx->trk);
+    live_drain(pool->core.ctx);
     pool_free(pool);
 }
 

@@ -6,6 +6,7 @@ EstimateFormants / FormantExtractor, MFCC::mfcc, vox_box::find_formants); each t
 batch of frames instead of one slice.  Arguments named ``x`` may be a host numpy array
 (uploaded for the call) or a DeviceArray / raw device pointer (used in place).
 """
+import contextlib
 import ctypes as C
 import os
 import re
@@ -727,22 +728,74 @@ def _ptr(a):
     raise TypeError(f"not a device buffer: {type(a)}")
 
 
-class Session:
-    """vbx_session: one channel of one stream of audio analysed block by block (VoxBox.session).  Concatenating what the pushes
-    return gives, bit for bit, what the resident frame loop returns on the concatenated blocks."""
+class _Live:
+    """What Session, SessionChannels and Pool share: the handle's life, the record width and the outputs a push owns when the caller
+    passes none."""
+    _close_name = "vbx_session_close"
 
-    def __init__(self, vb, params, ext, track, format, channels, channel, frame_len, stride, max_block):
+    def _open(self, vb, params, ext, track, fn, before, after):
+        """fn(ctx, *before, params, ext, track, *after, &handle)"""
         self.vb, self.params, self.ext, self.track = vb, params, ext, track
-        self.format, self.channels, self.channel = int(format), int(channels), int(channel)
-        self.frame_len, self.stride, self.max_block = int(frame_len), int(stride), int(max_block)
-        hf = HostAudio.make(self.format, self.channels, self.channel, 0)
         h = C.c_void_p()
-        vb._check(vb.L.vbx_session_open(vb.ctx, C.byref(hf), self.frame_len, self.stride, C.byref(params),
-                                        None if ext is None else C.byref(ext), None if track is None else C.byref(track),
-                                        self.max_block, C.byref(h)))
+        vb._check(fn(vb.ctx, *before, C.byref(params), None if ext is None else C.byref(ext), None if track is None else C.byref(track), *after,
+                     C.byref(h)))
         self.handle = h
         vb._sessions.add(self)
         self.rec = int(vb.L.vbx_record_doubles_ex(C.byref(params), None if ext is None else C.byref(ext)))
+
+    def _ld(self, record_ld):
+        return int(record_ld) if record_ld is not None else self.rec + (self.rec & 1)
+
+    @staticmethod
+    def _lists(outputs):
+        """outputs= as a PitchTrackOutputs (or None)"""
+        if outputs is None or isinstance(outputs, PitchTrackOutputs):
+            return outputs
+        return PitchTrackOutputs(*[_ptr(a) for a in outputs])
+
+    @contextlib.contextmanager
+    def _owned(self, n, ld, sets=1):
+        """`sets` sets of device outputs of n rows (none when n == 0), freed on exit: per set ((records, status3[, cand, count, peak]),
+        the lists' PitchTrackOutputs or None)"""
+        vb, own, out = self.vb, [], []
+        try:
+            for _ in range(sets if n else 0):
+                arrays, po = (vb.empty((n, ld)), vb.empty((3, n), np.int32)), None
+                own += arrays
+                if self.track is not None:
+                    # columns 0-1 are the caller's path to fill (vbx_pitch_path_f64 over an utterance's rows): NaN until then
+                    vb._check(vb.L.vbx_memset(vb.ctx, arrays[0].ptr, 0xFF, arrays[0].nbytes))
+                    lists = (vb.empty((n, int(self.track.kmax), 2)), vb.empty(n, np.int32), vb.empty(n))
+                    own += lists
+                    arrays, po = arrays + lists, PitchTrackOutputs(lists[0].ptr, lists[1].ptr, lists[2].ptr, None)
+                out.append((arrays, po))
+            yield out
+        finally:
+            for d in own:
+                d.free()
+
+    def _empty(self, ld):
+        """what a push that completes no frame returns"""
+        res = (np.empty((0, ld)), np.empty((3, 0), np.int32))
+        if self.track is not None:
+            res = res + (np.empty((0, int(self.track.kmax), 2)), np.empty(0, np.int32), np.empty(0))
+        return res
+
+    def close(self):
+        if getattr(self, "handle", None):
+            getattr(self.vb.L, self._close_name)(self.handle)
+            self.handle = None
+            self.vb._sessions.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class _SessionLive(_Live):
+    """what the two kinds of session share beyond that: one timeline"""
 
     def info(self):
         """(sample frames consumed, frames delivered, sample frames carried)"""
@@ -755,43 +808,42 @@ class Session:
         c = self.info()[0]
         return frame_count(c + int(n_sample_frames), self.frame_len, self.stride) - frame_count(c, self.frame_len, self.stride)
 
+    def mark_utterance(self):
+        """vbx_session_mark_utterance: the next frame delivered starts a new utterance (a seg_start entry of the resident call).
+        On a bound session (bind_path) the rest of the ended utterance's contour is committed by this call."""
+        self.vb._check(self.vb.L.vbx_session_mark_utterance(self.handle))
+
+    def reset(self):
+        """vbx_session_reset: drop the carried samples and all state -- as a freshly opened session."""
+        self.vb._check(self.vb.L.vbx_session_reset(self.handle))
+
+
+class Session(_SessionLive):
+    """vbx_session: one channel of one stream of audio analysed block by block (VoxBox.session).  Concatenating what the pushes
+    return gives, bit for bit, what the resident frame loop returns on the concatenated blocks."""
+
+    def __init__(self, vb, params, ext, track, format, channels, channel, frame_len, stride, max_block):
+        self.format, self.channels, self.channel = int(format), int(channels), int(channel)
+        self.frame_len, self.stride, self.max_block = int(frame_len), int(stride), int(max_block)
+        hf = HostAudio.make(self.format, self.channels, self.channel, 0)
+        self._open(vb, params, ext, track, vb.L.vbx_session_open, (C.byref(hf), self.frame_len, self.stride), (self.max_block,))
+
     def _push(self, fn, addr, n_sf, out, status, outputs, record_ld, status_ld):
         vb = self.vb
         n = self.frames_of(n_sf)
         got = C.c_size_t()
+        ld = self._ld(record_ld)
         if out is not None:
-            po = None
-            if outputs is not None:
-                po = outputs if isinstance(outputs, PitchTrackOutputs) else PitchTrackOutputs(*[_ptr(a) for a in outputs])
-            ld = int(record_ld) if record_ld is not None else self.rec + (self.rec & 1)
+            po = self._lists(outputs)
             vb._check(fn(self.handle, addr, n_sf, _ptr(out), ld, _ptr(status), int(status_ld) if status_ld is not None else n,
                          None if po is None else C.byref(po), C.byref(got)))
             return None
         assert status is None and outputs is None, "status= and outputs= go with out="
-        ld = int(record_ld) if record_ld is not None else self.rec + (self.rec & 1)
-        own = []
-        try:
-            o, st, lists, po = None, None, (), None
-            if n:
-                o, st = vb.empty((n, ld)), vb.empty((3, n), np.int32)
-                own += [o, st]
-                if self.track is not None:
-                    # columns 0-1 are the caller's path to fill (vbx_pitch_path_f64 over an utterance's rows): NaN until then
-                    vb._check(vb.L.vbx_memset(vb.ctx, o.ptr, 0xFF, o.nbytes))
-                    lists = (vb.empty((n, int(self.track.kmax), 2)), vb.empty(n, np.int32), vb.empty(n))
-                    own += list(lists)
-                    po = PitchTrackOutputs(lists[0].ptr, lists[1].ptr, lists[2].ptr, None)
-            vb._check(fn(self.handle, addr, n_sf, _ptr(o), ld, _ptr(st), n, None if po is None else C.byref(po), C.byref(got)))
+        with self._owned(n, ld) as sets:
+            arrays, po = sets[0] if n else ((None, None), None)
+            vb._check(fn(self.handle, addr, n_sf, _ptr(arrays[0]), ld, _ptr(arrays[1]), n, None if po is None else C.byref(po), C.byref(got)))
             assert got.value == n
-            if n == 0:
-                res = (np.empty((0, ld)), np.empty((3, 0), np.int32))
-                if self.track is not None:
-                    res = res + (np.empty((0, int(self.track.kmax), 2)), np.empty(0, np.int32), np.empty(0))
-                return res
-            return (o.numpy(), st.numpy()) + tuple(a.numpy() for a in lists)
-        finally:
-            for d in own:
-                d.free()
+            return tuple(a.numpy() for a in arrays) if n else self._empty(ld)
 
     def push(self, block, out=None, status=None, outputs=None, record_ld=None, status_ld=None):
         """vbx_session_push: the next block of the stream, from HOST memory -- a numpy array of the session's sample type shaped
@@ -808,11 +860,6 @@ class Session:
         the context's stream with no staging and no host wait."""
         return self._push(self.vb.L.vbx_session_push_device, _ptr(block), int(n_sample_frames), out, status, outputs, record_ld, status_ld)
 
-    def mark_utterance(self):
-        """vbx_session_mark_utterance: the next frame delivered starts a new utterance (a seg_start entry of the resident call).
-        On a bound session (bind_path) the rest of the ended utterance's contour is committed by this call."""
-        self.vb._check(self.vb.L.vbx_session_mark_utterance(self.handle))
-
     def bind_path(self, out_path, commit, peak_ref=1.0, max_pending=64, path_ld=2, out_index=None, out_forced=None):
         """vbx_session_path_bind: every push of this tracked session also commits the decided rows of the pitch contour (the
         online path, PathStream) into device buffers -- out_path (rows path_ld doubles apart), out_index (int32) and out_forced
@@ -822,57 +869,27 @@ class Session:
         self.vb._check(self.vb.L.vbx_session_path_bind(self.handle, float(peak_ref), int(max_pending), _ptr(out_path), int(path_ld),
                                                        _ptr(out_index), _ptr(out_forced), _ptr(commit)))
 
-    def reset(self):
-        """vbx_session_reset: drop the carried samples and all state -- as a freshly opened session."""
-        self.vb._check(self.vb.L.vbx_session_reset(self.handle))
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.vb.L.vbx_session_close(self.handle)
-            self.handle = None
-            self.vb._sessions.discard(self)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class SessionChannels:
+class SessionChannels(_SessionLive):
     """vbx_session opened with vbx_session_open_channels: every selected channel of one stream of interleaved audio analysed block
     by block from ONE session -- one upload and one frame-loop call per push whatever the number of channels
     (VoxBox.session_channels).  Per channel, concatenating what the pushes return gives, bit for bit, what a one-channel Session
     on that channel returns for the same blocks."""
 
     def __init__(self, vb, params, ext, track, format, channels, select, frame_len, stride, max_block):
-        self.vb, self.params, self.ext, self.track = vb, params, ext, track
         self.format, self.channels = int(format), int(channels)
         self.select = np.ascontiguousarray(np.arange(self.channels) if select is None else select, dtype=np.int32)
         self.n_sel = int(self.select.size)
         self.frame_len, self.stride, self.max_block = int(frame_len), int(stride), int(max_block)
         hf = HostAudio.make(self.format, self.channels, 0, 0)
-        h = C.c_void_p()
-        vb._check(vb.L.vbx_session_open_channels(vb.ctx, C.byref(hf), self.select.ctypes.data, self.n_sel, self.frame_len, self.stride,
-                                                 C.byref(params), None if ext is None else C.byref(ext),
-                                                 None if track is None else C.byref(track), self.max_block, C.byref(h)))
-        self.handle = h
-        vb._sessions.add(self)
-        self.rec = int(vb.L.vbx_record_doubles_ex(C.byref(params), None if ext is None else C.byref(ext)))
-
-    info = Session.info
-    frames_of = Session.frames_of
-    mark_utterance = Session.mark_utterance
-    reset = Session.reset
-    close = Session.close
-    __enter__ = Session.__enter__
-    __exit__ = Session.__exit__
+        self._open(vb, params, ext, track, vb.L.vbx_session_open_channels,
+                   (C.byref(hf), self.select.ctypes.data, self.n_sel, self.frame_len, self.stride), (self.max_block,))
 
     def _push(self, fn, addr, n_sf, out, status, outputs, record_ld, status_ld):
         vb, K = self.vb, self.n_sel
         n = self.frames_of(n_sf)
         got = C.c_size_t()
-        ld = int(record_ld) if record_ld is not None else self.rec + (self.rec & 1)
+        ld = self._ld(record_ld)
         entries = (ChannelOutputs * max(K, 1))()
         if out is not None:
             for per_channel in (out, status, outputs):
@@ -881,43 +898,20 @@ class SessionChannels:
             for i in range(K):
                 entries[i].records = _ptr(out[i])
                 entries[i].status3 = None if status is None else _ptr(status[i])
-                o = None if outputs is None else outputs[i]
-                if o is not None:
-                    pos[i] = o if isinstance(o, PitchTrackOutputs) else PitchTrackOutputs(*[_ptr(a) for a in o])
+                pos[i] = None if outputs is None else self._lists(outputs[i])
+                if pos[i] is not None:
                     entries[i].outputs = C.pointer(pos[i])
             vb._check(fn(self.handle, addr, n_sf, entries, ld, int(status_ld) if status_ld is not None else n, C.byref(got)))
             return None
         assert status is None and outputs is None, "status= and outputs= go with out="
-        own, res, pos = [], [], []
-        try:
-            per = []
-            for i in range(K if n else 0):
-                o, st = vb.empty((n, ld)), vb.empty((3, n), np.int32)
-                own += [o, st]
-                lists = ()
-                entries[i].records, entries[i].status3 = o.ptr, st.ptr
-                if self.track is not None:
-                    # columns 0-1 are the caller's path to fill (vbx_pitch_path_f64 over an utterance's rows): NaN until then
-                    vb._check(vb.L.vbx_memset(vb.ctx, o.ptr, 0xFF, o.nbytes))
-                    lists = (vb.empty((n, int(self.track.kmax), 2)), vb.empty(n, np.int32), vb.empty(n))
-                    own += list(lists)
-                    pos.append(PitchTrackOutputs(lists[0].ptr, lists[1].ptr, lists[2].ptr, None))
-                    entries[i].outputs = C.pointer(pos[-1])
-                per.append((o, st) + lists)
+        with self._owned(n, ld, K) as sets:
+            for i, (arrays, po) in enumerate(sets):
+                entries[i].records, entries[i].status3 = arrays[0].ptr, arrays[1].ptr
+                if po is not None:
+                    entries[i].outputs = C.pointer(po)
             vb._check(fn(self.handle, addr, n_sf, entries, ld, n, C.byref(got)))
             assert got.value == n
-            for i in range(K):
-                if n == 0:
-                    r = (np.empty((0, ld)), np.empty((3, 0), np.int32))
-                    if self.track is not None:
-                        r = r + (np.empty((0, int(self.track.kmax), 2)), np.empty(0, np.int32), np.empty(0))
-                else:
-                    r = tuple(a.numpy() for a in per[i])
-                res.append(r)
-            return res
-        finally:
-            for d in own:
-                d.free()
+            return [tuple(a.numpy() for a in arrays) for arrays, _ in sets] if n else [self._empty(ld) for _ in range(K)]
 
     def push(self, block, out=None, status=None, outputs=None, record_ld=None, status_ld=None):
         """vbx_session_push_channels: the next block of the stream, from HOST memory -- what Session.push takes ([T, channels]
@@ -950,25 +944,20 @@ class SessionChannels:
                           status_ld)
 
 
-class Pool:
+class Pool(_Live):
     """vbx_pool: max_streams independent live streams (slots) on one context that share a sample format (mono), a frame shape and
     a parameter set, each with its own timeline (VoxBox.pool).  One tick -- push -- takes (slot, block) entries of any sizes, any
     subset of the slots, in any order, and delivers every entry's rows into one set of arrays from ONE upload and a fixed number of
     launches.  Per slot, concatenating what the ticks return gives, bit for bit, what a one-channel Session returns for the same
     blocks, marks and resets."""
+    _close_name = "vbx_pool_close"
 
     def __init__(self, vb, params, ext, track, format, frame_len, stride, max_streams, max_block, max_tick):
-        self.vb, self.params, self.ext, self.track = vb, params, ext, track
         self.format, self.frame_len, self.stride = int(format), int(frame_len), int(stride)
         self.max_streams, self.max_block, self.max_tick = int(max_streams), int(max_block), int(max_tick)
         hf = HostAudio.make(self.format, 1, 0, 0)
-        h = C.c_void_p()
-        vb._check(vb.L.vbx_pool_open(vb.ctx, C.byref(hf), self.frame_len, self.stride, C.byref(params),
-                                     None if ext is None else C.byref(ext), None if track is None else C.byref(track),
-                                     self.max_streams, self.max_block, self.max_tick, C.byref(h)))
-        self.handle = h
-        vb._sessions.add(self)
-        self.rec = int(vb.L.vbx_record_doubles_ex(C.byref(params), None if ext is None else C.byref(ext)))
+        self._open(vb, params, ext, track, vb.L.vbx_pool_open, (C.byref(hf), self.frame_len, self.stride),
+                   (self.max_streams, self.max_block, self.max_tick))
 
     def info(self, stream):
         """(sample frames consumed, frames delivered, sample frames carried) of one slot"""
@@ -993,39 +982,19 @@ class Pool:
         h_r = (PoolRows * max(n_e, 1))()
         got = C.c_size_t()
         _, n = self.rows_of([(s, k) for s, _, k in ents])
-        ld = int(record_ld) if record_ld is not None else self.rec + (self.rec & 1)
+        ld = self._ld(record_ld)
         rows = lambda: np.array([(h_r[i].row_start, h_r[i].n_rows) for i in range(n_e)], dtype=np.int64).reshape(n_e, 2)
         if out is not None:
-            po = None
-            if outputs is not None:
-                po = outputs if isinstance(outputs, PitchTrackOutputs) else PitchTrackOutputs(*[_ptr(a) for a in outputs])
+            po = self._lists(outputs)
             vb._check(fn(self.handle, h_e, n_e, _ptr(out), ld, _ptr(status), int(status_ld) if status_ld is not None else n,
                          None if po is None else C.byref(po), h_r, C.byref(got)))
             return rows(), int(got.value)
         assert status is None and outputs is None, "status= and outputs= go with out="
-        own = []
-        try:
-            o, st, lists, po = None, None, (), None
-            if n:
-                o, st = vb.empty((n, ld)), vb.empty((3, n), np.int32)
-                own += [o, st]
-                if self.track is not None:
-                    # columns 0-1 are the caller's path to fill (vbx_pitch_path_f64 over a call's rows): NaN until then
-                    vb._check(vb.L.vbx_memset(vb.ctx, o.ptr, 0xFF, o.nbytes))
-                    lists = (vb.empty((n, int(self.track.kmax), 2)), vb.empty(n, np.int32), vb.empty(n))
-                    own += list(lists)
-                    po = PitchTrackOutputs(lists[0].ptr, lists[1].ptr, lists[2].ptr, None)
-            vb._check(fn(self.handle, h_e, n_e, _ptr(o), ld, _ptr(st), n, None if po is None else C.byref(po), h_r, C.byref(got)))
+        with self._owned(n, ld) as sets:
+            arrays, po = sets[0] if n else ((None, None), None)
+            vb._check(fn(self.handle, h_e, n_e, _ptr(arrays[0]), ld, _ptr(arrays[1]), n, None if po is None else C.byref(po), h_r, C.byref(got)))
             assert got.value == n
-            if n == 0:
-                res = (np.empty((0, ld)), np.empty((3, 0), np.int32))
-                if self.track is not None:
-                    res = res + (np.empty((0, int(self.track.kmax), 2)), np.empty(0, np.int32), np.empty(0))
-                return (rows(),) + res
-            return (rows(), o.numpy(), st.numpy()) + tuple(a.numpy() for a in lists)
-        finally:
-            for d in own:
-                d.free()
+            return (rows(),) + (tuple(a.numpy() for a in arrays) if n else self._empty(ld))
 
     def push(self, entries, out=None, status=None, outputs=None, record_ld=None, status_ld=None):
         """vbx_pool_push: one tick.  entries: a sequence of (slot, block), block in HOST memory -- a 1-D numpy array of the pool's
@@ -1055,18 +1024,6 @@ class Pool:
     def reset_stream(self, stream):
         """vbx_pool_reset_stream: the slot behaves as that of a freshly opened pool -- how a slot is reused for the next call"""
         self.vb._check(self.vb.L.vbx_pool_reset_stream(self.handle, int(stream)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.vb.L.vbx_pool_close(self.handle)
-            self.handle = None
-            self.vb._sessions.discard(self)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 def commit_of(vb, commit):
