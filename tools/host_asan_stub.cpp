@@ -7,7 +7,8 @@ static thread_local std::string g_err;
 extern "C" int vbx_internal_fail(vbx_ctx *, int code, const char *msg) { g_err = msg ? msg : ""; return code; }
 extern "C" const char *vbx_last_error(const vbx_ctx *) { return g_err.c_str(); }
 
-// -DVBX_HOST_ASAN_MAIN: a stand-alone program over the host arithmetic of a session pool's tick (vbx_pool_plan), for
+// -DVBX_HOST_ASAN_MAIN: a stand-alone program over the host arithmetic of a session pool's tick (vbx_pool_plan) and of the fused frame
+// loop's launches (launch_ranges_host), for
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -DVBX_HOST_ASAN_MAIN -Iinclude
 //       vox_box.rs_amd/csrc/vbx_host.cpp tools/host_asan_stub.cpp -o host_asan_pool && ./host_asan_pool
 // a few thousand random ticks at five frame shapes, the rows written into exactly sized heap arrays; it checks the prefix sums and
@@ -18,6 +19,7 @@ extern "C" const char *vbx_last_error(const vbx_ctx *) { return g_err.c_str(); }
 #include <vector>
 
 #include "voxbox_hip.h"
+#include "../vox_box.rs_amd/csrc/vbx_host.hpp"
 
 int main() {
     const size_t shapes[5][2] = {{400, 160}, {1200, 480}, {200, 80}, {100, 250}, {1, 1}};
@@ -52,6 +54,29 @@ int main() {
         }
     }
     std::printf("vbx_pool_plan: %zu random ticks, all rules hold\n", ticks);
+    // the fused frame loop's launches (launch_ranges_host): random utterance starts (with repeats: empty utterances) against a frame-by-frame
+    // statement of the same rule; the arrays are exactly sized vectors
+    size_t plans = 0;
+    for (int t = 0; t < 3000; t++, plans++) {
+        const size_t F = 1 + rnd(5000), L = 1 + rnd(t % 3 == 0 ? 40 : 1500), ns = rnd(12);
+        std::vector<int64_t> starts;
+        if (ns) { starts.push_back(0); for (size_t i = 1; i < ns; i++) starts.push_back(rnd(4) == 0 ? starts.back() : starts.back() + (int64_t)rnd(F - (size_t)starts.back() + 1)); }
+        std::vector<int64_t> seg, stitch; std::vector<size_t> off;
+        vbx::launch_ranges_host(ns ? starts.data() : nullptr, ns, F, L, seg, off, stitch);
+        const size_t launches = (F + L - 1) / L;
+        if (off.size() != launches + 1 || stitch.size() != launches || off.back() != seg.size()) return 6;
+        for (size_t j = 0; j < launches; j++) {
+            const size_t f0 = j * L, f1 = f0 + L < F ? f0 + L : F;
+            std::vector<int64_t> want{0};
+            bool here = f0 == 0;
+            for (int64_t s : starts) { if ((size_t)s == f0) here = true; if ((size_t)s > f0 && (size_t)s < f1) want.push_back(s - (int64_t)f0); }
+            if (off[j + 1] - off[j] != want.size()) return 7;
+            for (size_t i = 0; i < want.size(); i++) if (seg[off[j] + i] != want[i]) return 8;
+            const int64_t cont = here ? 0 : (want.size() > 1 ? want[1] : (int64_t)(f1 - f0));
+            if (stitch[j] != cont || cont < 0 || (size_t)cont > f1 - f0) return 9;
+        }
+    }
+    std::printf("launch_ranges_host: %zu random plans, all rules hold\n", plans);
     return 0;
 }
 #endif

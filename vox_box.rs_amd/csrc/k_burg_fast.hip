@@ -60,5 +60,10 @@ void launch_burg_recursion(hipStream_t s, long F, int p, frame_map_t map, long i
     VBX_BF_DISPATCH(VBX_BF_CALL)
 #undef VBX_BF_CALL
 }
+void launch_burg_recursion_at(hipStream_t s, const double *scratch, int32_t *list, long F, int p, long i0, long m, double *out, int32_t *status) {
+#define VBX_BF_CALL(PP) launch_burg_recursion_p<PP>(s, scratch, F, frame_map_t{0, 0, 0}, i0, m, out, status, list)
+    VBX_BF_DISPATCH(VBX_BF_CALL)
+#undef VBX_BF_CALL
+}
 
 }  // namespace vbx

@@ -205,6 +205,10 @@ bool spectral_list_parked(const spectral_launch_t &L) {
 // everything it was compiled for in place; every other launch -- and every launch of an experiment build that reads the work
 // pointer or the count early (VBX_EXP_PHASES, VBX_EXP_STOP) -- takes the generic one.  L.allow_spec: the context's
 // VBX_SPECTRAL_SPEC switch (0: the generic one; A/B, tests).  w3, extra: launch_analyze's own three-wavefront decision and LDS list.
+static bool spectral_want3() {
+    static const bool want3 = [] { const char *e = getenv("VBX_SPECTRAL_W3"); return e == nullptr || atoi(e) != 0; }();
+    return want3;
+}
 static int spectral_spec(const spectral_launch_t &L, bool w3, size_t extra) {
 #if defined(VBX_EXP_PHASES) || VBX_EXP_STOP != 0
     return SP_SPEC_NONE;
@@ -215,6 +219,19 @@ static int spectral_spec(const spectral_launch_t &L, bool w3, size_t extra) {
     if (L.out_mfcc != nullptr && !(L.mfcc_defer && L.num_coeffs <= 16)) return SP_SPEC_NONE;
     return L.x.kind == SAMPLE_PCM16 ? SP_SPEC_PCM16 : SP_SPEC_F64;
 #endif
+}
+
+// Would launch_analyze take a launch-specialised instance for L -- the only ones with a form that leaves Burg's lag sums (BURG)?
+// The same geometry and the same tests as there.
+bool spectral_burg_fusable(const spectral_launch_t &L) {
+    if (L.plan != SPECTRAL_PLAN_1200 || L.n != SP_N || L.mfcc_only || L.out_r != nullptr) return false;
+    const size_t base = spectral_lds_bytes(L.n);
+    size_t extra = pitch_full_list_bytes(L.n, L.kmax);
+    if (spectral_list_parked(L)) extra = 0;
+    const int spec = spectral_spec(L, spectral_want3() && extra == 0 && 12 * (base + extra) <= 160 * 1024, extra);
+    // (PCM frames with MFCC and without LPC: that BURG form spills two registers where the instance it rides on spills none -- such calls keep burg_lags_kernel)
+    if (spec == SP_SPEC_PCM16 && L.out_mfcc != nullptr && L.out_lpc == nullptr) return false;
+    return spec != SP_SPEC_NONE;
 }
 
 int launch_analyze(hipStream_t s, const spectral_launch_t &L, int *launched_spec) {
@@ -237,8 +254,15 @@ int launch_analyze(hipStream_t s, const spectral_launch_t &L, int *launched_spec
     a.pcm = (L.x.kind == SAMPLE_PCM16 ? SP_FLAG_PCM : 0) | (L.lag_rcp ? SP_FLAG_LAG_RCP : 0) | ((L.mfcc_defer && L.num_coeffs <= 16) ? SP_FLAG_MFCC_DEFER : 0);
     a.mfcc_q = (L.plan != SPECTRAL_PLAN_NONE && L.n > 0) ? (2 * spectral_plan_nc(L.plan)) / L.n : 2;
     a.ip = mfcc_interp_t{};
+    a.burg_scratch = nullptr; a.burg_window = nullptr; a.burg_f0 = 0;
+    if (L.burg_scratch != nullptr) {
+        // Burg's lag sums from the frame's own wavefront: frames [burg_f0, burg_f0 + burg_nf) of the batch, launch-specialised instances only
+        // (refused HERE, before any branch below could launch another instance over a narrowed range)
+        if (!spectral_burg_fusable(L) || (((uintptr_t)L.burg_window) & 15) != 0 || L.burg_window == nullptr || L.burg_f0 < 0 || L.burg_nf < 1 || L.burg_f0 + L.burg_nf > L.F) return -1;
+        a.burg_scratch = L.burg_scratch; a.burg_window = L.burg_window; a.burg_f0 = L.burg_f0; a.n_frames = L.burg_nf;
+    }
     if (L.plan != SPECTRAL_PLAN_1200) return launch_analyze_pow2(s, L, a);
-    const dim3 grid((unsigned)L.F), block(64);
+    const dim3 grid((unsigned)a.n_frames), block(64);
     const size_t base = spectral_lds_bytes(L.n);
     size_t extra = pitch_full_list_bytes(L.n, L.kmax);
     a.pp.full_off = extra ? (int)base : 0;
@@ -248,6 +272,7 @@ int launch_analyze(hipStream_t s, const spectral_launch_t &L, int *launched_spec
     if (spectral_list_parked(L)) { a.pp.full_off = -1; extra = 0; }
     const size_t lds = base + extra;
     const bool lpc = L.out_lpc != nullptr, mf = L.out_mfcc != nullptr;
+    const spectral_args_1200_burg_t a12b(a);                 // (the BURG instances')
     const spectral_args_1200_t a12(a);                       // the block without the other plans' fields (the interpolated and autocorrelation-only forms take `a`)
     if (L.mfcc_only) {                                       // n == SP_N, or a padded frame with interpolated bins
         if (L.interp && L.n != SP_N) {
@@ -268,7 +293,7 @@ int launch_analyze(hipStream_t s, const spectral_launch_t &L, int *launched_spec
     // cost more than the third wavefront brought.  Round 4: with the twiddle products in pinned batches (twiddle_tight) the
     // 168-register instances spill 12-29 registers instead of 146-171, and three wavefronts win everywhere: pitch at kmax = 1
     // 33.7 -> 37.8 M frames/s, the fused loop (the headline) 30.0 -> 33.5 M.  VBX_SPECTRAL_W3=0: two wavefronts as before (A/B).
-    static const bool want3 = [] { const char *e = getenv("VBX_SPECTRAL_W3"); return e == nullptr || atoi(e) != 0; }();
+    const bool want3 = spectral_want3();
     const bool w3 = want3 && extra == 0 && 12 * lds <= 160 * 1024;
     if (L.x.kind == SAMPLE_F32) {
         launch_analyze_f32in(s, a12, (unsigned)L.F, lds, lpc, mf, w3);
@@ -279,18 +304,27 @@ int launch_analyze(hipStream_t s, const spectral_launch_t &L, int *launched_spec
         if (w3) hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, FULL_, SP_ANALYZE, 3>), grid, block, lds, s, a12);      \
         else hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, FULL_>), grid, block, lds, s, a12);                        \
     } while (0)
-#define VBX_SP_LAUNCH_SPEC(LPC_, MF_)                                                                                                          \
+#define VBX_SP_LAUNCH_SPEC(LPC_, MF_, SUFFIX_, A_)                                                                                             \
     do {                                                                                                                                        \
-        if (spec == SP_SPEC_PCM16) hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, true, SP_ANALYZE, 3, sp_launch_pcm16_t>), grid, block, lds, s, a12);   \
-        else hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, true, SP_ANALYZE, 3, sp_launch_f64_t>), grid, block, lds, s, a12);          \
+        if (spec == SP_SPEC_PCM16) hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, true, SP_ANALYZE, 3, sp_launch_pcm16##SUFFIX_>), grid, block, lds, s, A_);   \
+        else hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, true, SP_ANALYZE, 3, sp_launch_f64##SUFFIX_>), grid, block, lds, s, A_);          \
     } while (0)
     const int spec = spectral_spec(L, w3, extra);
+    if (L.burg_scratch != nullptr) {
+        if (spec == SP_SPEC_NONE) return -1;                 // (spectral_burg_fusable said otherwise, or was not asked)
+        if (launched_spec) *launched_spec = spec;
+        if (lpc && mf) VBX_SP_LAUNCH_SPEC(true, true, _burg_t, a12b);
+        else if (lpc) VBX_SP_LAUNCH_SPEC(true, false, _burg_t, a12b);
+        else if (mf) hipLaunchKernelGGL((analyze_kernel<false, true, true, SP_ANALYZE, 3, sp_launch_f64_burg_t>), grid, block, lds, s, a12b);   // (f64 only: spectral_burg_fusable)
+        else VBX_SP_LAUNCH_SPEC(false, false, _burg_t, a12b);
+        return 0;
+    }
     if (spec != SP_SPEC_NONE) {
         if (launched_spec) *launched_spec = spec;            // (set here, at the branch that launches it)
-        if (lpc && mf) VBX_SP_LAUNCH_SPEC(true, true);
-        else if (lpc) VBX_SP_LAUNCH_SPEC(true, false);
-        else if (mf) VBX_SP_LAUNCH_SPEC(false, true);
-        else VBX_SP_LAUNCH_SPEC(false, false);
+        if (lpc && mf) VBX_SP_LAUNCH_SPEC(true, true, _t, a12);
+        else if (lpc) VBX_SP_LAUNCH_SPEC(true, false, _t, a12);
+        else if (mf) VBX_SP_LAUNCH_SPEC(false, true, _t, a12);
+        else VBX_SP_LAUNCH_SPEC(false, false, _t, a12);
         return 0;
     }
     if (L.interp && mf && L.n != SP_N) {                     // a padded frame whose MFCC bins are interpolated from the transform's

@@ -179,6 +179,9 @@ int vbx_ctx_create(vbx_ctx **out, int device, void *hip_stream) {
     { const char *e = std::getenv("VBX_MFCC_CZT"); ctx->mfcc_czt = e ? (e[0] == '1' ? 1 : 0) : -1; }
     { const char *e = std::getenv("VBX_MFCC_DEFER"); ctx->mfcc_defer = (e && e[0] == '0') ? 0 : 1; }
     { const char *e = std::getenv("VBX_SPECTRAL_SPEC"); ctx->spectral_spec = (e && e[0] == '0') ? 0 : 1; }
+    { const char *e = std::getenv("VBX_BURG_FUSED"); ctx->burg_fused = (e && e[0] == '0') ? 0 : 1; }
+    { const char *e = std::getenv("VBX_BURG_FUSED_MIN_FRAMES"); if (e && atol(e) >= 1) ctx->burg_fused_min_frames = atol(e); }
+    { const char *e = std::getenv("VBX_ANALYZE_LAUNCH_FRAMES"); if (e && atol(e) >= 1) ctx->analyze_launch_frames = atol(e); }
     { const char *e = std::getenv("VBX_LPC_EXACT"); ctx->lpc_policy = (e && e[0] == '0') ? VBX_LPC_POLICY_PLAIN : VBX_LPC_POLICY_EXACT; }
     { const char *e = std::getenv("VBX_POW2_SPLIT"); ctx->pow2_split = e ? (e[0] == '0' ? 0 : 1) : -1; }
     { const char *e = std::getenv("VBX_MFCC_INTERP"); ctx->mfcc_interp = e ? (e[0] == '0' ? 0 : 1) : -1; }
@@ -221,6 +224,8 @@ void vbx_ctx_destroy(vbx_ctx *ctx) {
     if (ctx->ev_peak) hipEventDestroy(ctx->ev_peak);
     for (auto &e : ctx->ev_slice) if (e) hipEventDestroy(e);
     if (ctx->ev_trk) hipEventDestroy(ctx->ev_trk);
+    for (auto &e : ctx->ev_bf_launch) if (e) hipEventDestroy(e);
+    for (auto &e : ctx->ev_bf_free) if (e) hipEventDestroy(e);
     if (ctx->trk) { hipStreamSynchronize(ctx->trk); hipStreamDestroy(ctx->trk); }
     if (ctx->copy) { hipStreamSynchronize(ctx->copy); hipStreamDestroy(ctx->copy); }
     for (int i = 0; i < 2; i++) {
@@ -483,7 +488,21 @@ namespace vbx {
 
 // The FFT-based kernel (k_spectral.hip) followed by the direct-sum kernel on the frames whose peak decisions lie
 // inside the FFT's rounding error (normally none; curves that are exactly zero over a stretch, e.g. a few impulses).
-int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, const char *prof_name) {
+// (what launch_spectral decides about the launch from the context, before launch_analyze sees it)
+static void spectral_launch_choices(const vbx_ctx *ctx, spectral_launch_t &L) {
+    // MFCC::mfcc's log10 + DCT out of the frame's wavefront (mfcc_tail_q's `defer`): the kernel leaves the filter sums in the row
+    // (the 1200-point plan only: in the power-of-two kernels the deferred form changes the register allocation -- thirteen index registers
+    // spilled across the second transform, 3 KB of scratch traffic per frame -- for the same ~1 %; they keep the tail)
+    L.mfcc_defer = L.out_mfcc != nullptr && !L.mfcc_only && L.num_coeffs >= 1 && L.num_coeffs <= 16 && ctx->mfcc_defer && L.plan == SPECTRAL_PLAN_1200;
+    L.allow_spec = ctx->spectral_spec != 0;
+}
+bool spectral_burg_fusable_call(vbx_ctx *ctx, const spectral_launch_t &L0) {
+    spectral_launch_t L = L0;
+    spectral_launch_choices(ctx, L);
+    return spectral_burg_fusable(L);
+}
+
+int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, const char *prof_name, const analyze_ranges_t *rg) {
     void *w = nullptr;
     int rc = ws_get(ctx, vbx_ctx::WS_UNSURE, ((size_t)L.F + 4) * sizeof(int32_t), &w);
     if (rc != VBX_SUCCESS) return rc;
@@ -518,13 +537,26 @@ int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, const ch
             else { (void)hipGetLastError(); ctx->curve_failed_bytes = need; ctx->last_error = before; g_last_error = before; }
         }
     }
-    // MFCC::mfcc's log10 + DCT out of the frame's wavefront (mfcc_tail_q's `defer`): the kernel leaves the filter sums in the row
-    // (the 1200-point plan only: in the power-of-two kernels the deferred form changes the register allocation -- thirteen index registers
-    // spilled across the second transform, 3 KB of scratch traffic per frame -- for the same ~1 %; they keep the tail)
-    L.mfcc_defer = L.out_mfcc != nullptr && !L.mfcc_only && L.num_coeffs >= 1 && L.num_coeffs <= 16 && ctx->mfcc_defer && L.plan == SPECTRAL_PLAN_1200;
-    L.allow_spec = ctx->spectral_spec != 0;
+    spectral_launch_choices(ctx, L);
     ctx->last_analyze_spec = 0;
-    { Prof p(ctx, prof_name, st); ctx->last_spectral_split = launch_analyze(st, L, &ctx->last_analyze_spec); }
+    if (rg == nullptr) { Prof p(ctx, prof_name, st); ctx->last_spectral_split = launch_analyze(st, L, &ctx->last_analyze_spec); }
+    else {
+        // the same kernel in launches of rg->launch_frames frames, each leaving Burg's lag sums of its frames for the side stream
+        ctx->last_spectral_split = 0;
+        int j = 0;
+        for (long f0 = 0; f0 < L.F; f0 += rg->launch_frames, j++) {
+            const long nf = (L.F - f0 < rg->launch_frames) ? L.F - f0 : rg->launch_frames;
+            rc = rg->before(j);
+            if (rc != VBX_SUCCESS) return rc;
+            L.burg_scratch = rg->scratch[j & 1]; L.burg_window = rg->burg_window; L.burg_f0 = f0; L.burg_nf = nf;
+            int launched;
+            { Prof p(ctx, prof_name, st); launched = launch_analyze(st, L, &ctx->last_analyze_spec); }
+            L.burg_scratch = nullptr;
+            if (launched < 0) return fail(ctx, VBX_E_RUNTIME, "launch_spectral: no instance of the fused kernel leaves Burg's lag sums for this launch");
+            rc = rg->after(j, f0, nf);
+            if (rc != VBX_SUCCESS) return rc;
+        }
+    }
     if (L.mfcc_defer && L.out_lpc == nullptr) { Prof p(ctx, "mfcc_rows", st); launch_mfcc_rows(st, L.out_mfcc, L.F, L.mfcc_ld, L.num_coeffs, L.dct); }
     {
         Prof p(ctx, "pitch_direct_fallback", st);
@@ -766,6 +798,12 @@ bool burg_order_ok(size_t frame_len, size_t n_coeffs) {
 // their RESAMPLED view -- n is then the resampled length m and window its periodic Hanning window.  The shapes the resampled
 // loaders take (k_burg_resampled.hip) never exist as a batch; the others are resampled into a context-owned dense batch, a
 // chunk of frames at a time, and take this function's plain form -- the same kernels at the same parameters either way.
+// experiment builds (-DVBX_EXP_BURG_LAGS_ONLY, tools/experiments/burg_gate.py, profiles/burg_fused/gate.txt): the formant chain stops behind the lag kernel
+#ifdef VBX_EXP_BURG_LAGS_ONLY
+constexpr bool BURG_LAGS_ONLY = true;
+#else
+constexpr bool BURG_LAGS_ONLY = false;
+#endif
 constexpr size_t EX_DENSE_BYTES = size_t(256) << 20;          // the dense fallback's batch: at most this, or one resampled frame
 static const char *const k_kind_names[3] = {"f64", "pcm16", "float32"};      // by sample_kind_t, for messages
 
@@ -824,8 +862,9 @@ int run_burg(vbx_ctx *ctx, hipStream_t stm, frames_t x, long F, int n, long stri
               const bool ok = rp ? launch_burg_lags_resampled(stm, x, F, n, stride, window, rp->rs, p, map, i0, m, w)
                                  : launch_burg_lags(stm, x, F, n, stride, window, p, map, i0, m, w);
               if (!ok) return fail(ctx, VBX_E_RUNTIME, std::string(lags_name) + ": no " + k_kind_names[x.kind] + " lag kernel at order " + std::to_string(p)); }
-            { Prof pr(ctx, "burg_recursion", stm); launch_burg_recursion(stm, F, p, map, i0, m, coeffs, st, w); }
+            if (!BURG_LAGS_ONLY) { Prof pr(ctx, "burg_recursion", stm); launch_burg_recursion(stm, F, p, map, i0, m, coeffs, st, w); }
         }
+        if (BURG_LAGS_ONLY) return VBX_SUCCESS;
         { Prof pr(ctx, list_name, stm);
           if (rp) launch_burg_resampled_list(stm, x, F, n, stride, window, rp->rs, p, coeffs, st, list + 2, list);
           else launch_burg_list(stm, x, F, n, stride, window, p, coeffs, st, list + 2, list); }
@@ -1096,6 +1135,9 @@ int run_find_formants(vbx_ctx *ctx, hipStream_t stm, frames_t x, size_t n_frames
     if (n_slices == 1) {
         rc = run_burg(ctx, stm, x, F, (int)frame_len, (long)stride, hann, p, coeffs, st, frame_map_t{0, 0, 0}, rp);                // :75
         if (rc != VBX_SUCCESS) return rc;
+#ifdef VBX_EXP_BURG_LAGS_ONLY
+        return check_launch(ctx, "vbx_find_formants_f64");          // (nothing behind Burg's lag kernel: the records' formant columns are not written)
+#endif
         rc = run_formant_resonances(ctx, stm, coeffs, F, p, sample_rate, res, cnt, st);                                            // :80-110
         if (rc != VBX_SUCCESS) return rc;
         rc = run_tracker(ctx, stm, chunked, res, F, VBX_MAX_RESONANCES, cnt, d_seg, (long)nseg, d_est, (int)n_est, st,
@@ -1120,6 +1162,93 @@ int run_find_formants(vbx_ctx *ctx, hipStream_t stm, frames_t x, size_t n_frames
     }
     VBX_HIP(ctx, hipEventRecord(ctx->ev_trk, ctx->trk));
     VBX_HIP(ctx, hipStreamWaitEvent(stm, ctx->ev_trk, 0));                // join: the formant tracks are complete on stm
+    return check_launch(ctx, "vbx_find_formants_f64");
+}
+
+// ---- find_formants behind the fused frame loop's launches (vbx_api_frames.hip): Burg's lag sums come from the analyze kernel ----
+// The chain of run_find_formants' unsliced path, a range of frames at a time and without its lag kernel: what the records hold is the
+// same bit for bit (the recursion reads the same scratch; the resonance rows are per frame; the scan by ranges + stitch is the
+// chunked scan's own repair step with the previous range in the role of the previous chunk).
+static size_t fr_scratch_doubles(long launch_frames, int p) { return (size_t)(3 * (p + 1)) * (size_t)((launch_frames + 63) & ~63L); }
+
+int find_formants_ranges_begin(vbx_ctx *ctx, hipStream_t side, frames_t x, size_t n_frames, size_t stride, double sample_rate, size_t n_coeffs,
+                               const int64_t *h_seg_start, size_t n_segments, const vbx_resonance *h_est_init, size_t n_est,
+                               vbx_resonance *out_formants, size_t formants_ld, int32_t *status, long launch_frames, formants_ranges_t *R) {
+    VBX_REQUIRE(ctx, h_est_init && out_formants, "null argument");
+    VBX_REQUIRE(ctx, (int)n_coeffs == SPECTRAL_BURG_ORDER && launch_frames >= 1, "the fused lag sums are order 12");
+    VBX_REQUIRE(ctx, n_est >= 1 && n_est <= VBX_FORMANT_SLOTS, "n_est must be in [1, 6]");
+    VBX_REQUIRE(ctx, formants_ld >= 2 * n_est && formants_ld % 2 == 0, "formant rows must be 16-byte aligned and hold n_est entries");
+    const long F = (long)n_frames; const int p = (int)n_coeffs;
+    if (launch_frames > F) launch_frames = F;
+    int rc; void *w = nullptr;
+    R->side = side; R->x = x; R->F = F; R->stride = (long)stride; R->sample_rate = sample_rate; R->p = p; R->n_est = (int)n_est;
+    rc = ws_get(ctx, vbx_ctx::WS_COEFFS, n_frames * n_coeffs * sizeof(double), &w); if (rc) return rc; R->coeffs = (double *)w;
+    rc = ws_get(ctx, vbx_ctx::WS_RES, n_frames * VBX_MAX_RESONANCES * sizeof(vbx_resonance), &w); if (rc) return rc; R->res = (res_t *)w;
+    rc = ws_get(ctx, vbx_ctx::WS_COUNT, n_frames * sizeof(int32_t), &w); if (rc) return rc; R->cnt = (int32_t *)w;
+    R->st = status;
+    if (!R->st) { rc = ws_get(ctx, vbx_ctx::WS_STATUS, n_frames * sizeof(int32_t), &w); if (rc) return rc; R->st = (int32_t *)w; }
+    // the ring of two launch-sized scratch buffers, then the direct list: count, the call's total, indices [F]
+    const size_t sd = fr_scratch_doubles(launch_frames, p);
+    rc = ws_get(ctx, vbx_ctx::WS_BURG_LIST, 2 * sd * sizeof(double) + ((size_t)F + 2) * sizeof(int32_t), &w); if (rc) return rc;
+    R->scratch[0] = (double *)w; R->scratch[1] = (double *)w + sd; R->list = (int32_t *)((double *)w + 2 * sd);
+    rc = ws_get(ctx, vbx_ctx::WS_ROOTS_LIST, 4 * sizeof(int32_t), &w); if (rc) return rc; R->redo = (int32_t *)w;
+    R->chunked = tracker_wants_chunks(h_seg_start, n_segments, n_frames);
+    R->trk_ws = nullptr;
+    if (R->chunked) { rc = ws_get(ctx, vbx_ctx::WS_TRK, tracker_chunked_workspace_bytes(launch_frames), &R->trk_ws); if (rc) return rc; }
+    VBX_HIP(ctx, ctx->tables.window(VBX_WINDOW_HANNING_PERIODIC, SPECTRAL_N, &R->hann));   // src/lib.rs:65-70
+    rc = upload_segments(ctx, side, h_seg_start, n_segments, n_frames, &R->d_seg, &R->nseg);
+    if (rc != VBX_SUCCESS) return rc;
+    rc = upload_estimates(ctx, side, h_est_init, n_est, &R->d_est);
+    if (rc != VBX_SUCCESS) return rc;
+    R->d_range_seg = nullptr;
+    if (R->chunked) {
+        std::vector<int64_t> seg;
+        launch_ranges_host(R->d_seg ? h_seg_start : nullptr, n_segments, n_frames, (size_t)launch_frames, seg, R->off, R->stitch);
+        void *d = nullptr;
+        rc = stage_upload(ctx, 4, vbx_ctx::WS_RANGE_SEG, seg.data(), seg.size() * sizeof(int64_t), side, &d);
+        if (rc != VBX_SUCCESS) return rc;
+        R->d_range_seg = (const int64_t *)d;
+    }
+    ctx->burg_list_count = R->list;
+    ctx->roots_list_count = R->redo;
+    VBX_HIP(ctx, hipMemsetAsync(R->list, 0, sizeof(int32_t), side));
+    VBX_HIP(ctx, hipMemsetAsync(R->redo, 0, sizeof(int32_t), side));
+    R->out = (res_t *)out_formants; R->out_ld = (long)formants_ld;
+    ctx->last_track.res = R->res; ctx->last_track.cnt = R->cnt; ctx->last_track.st = R->st; ctx->last_track.F = F;
+    ctx->last_track.n_est = (int)n_est; ctx->last_track.out = R->out; ctx->last_track.out_ld = R->out_ld;
+    return VBX_SUCCESS;
+}
+
+int find_formants_ranges_step(vbx_ctx *ctx, formants_ranges_t *R, int j, long f0, long nf) {
+    hipStream_t stm = R->side;
+    const int p = R->p;
+    { Prof pr(ctx, "burg_recursion", stm); launch_burg_recursion_at(stm, R->scratch[j & 1], R->list, R->F, p, f0, nf, R->coeffs, R->st); }
+    VBX_HIP(ctx, hipEventRecord(ctx->ev_bf_free[j & 1], stm));                      // the scratch may be written again
+    { Prof pr(ctx, "burg_direct_list", stm); launch_burg_list(stm, R->x, R->F, SPECTRAL_N, R->stride, R->hann, p, R->coeffs, R->st, R->list + 2, R->list); }
+    launch_count_accumulate(stm, R->list, R->list + 1, j == 0);                     // list[1]: the call's total (vbx_internal_last_burg_direct_count)
+    VBX_HIP(ctx, hipMemsetAsync(R->list, 0, sizeof(int32_t), stm));                 // the next launch's list starts empty
+    { Prof pr(ctx, "formant_resonances", stm);
+      launch_formant_resonances_fast(stm, R->coeffs + f0 * (long)p, nf, p, R->sample_rate, R->res + f0 * (long)VBX_MAX_RESONANCES, R->cnt + f0, R->st + f0,
+                                     frame_map_t{0, 0, 0}, R->redo); }
+    if (R->chunked) {
+        // the chunked scan of this range alone, then -- a range that begins inside an utterance -- its first rows again from the row before it
+        // (tracker_stitch_kernel on the range's own view, first = 0: it always redoes, the row before the range IS the true state)
+        Prof pr(ctx, "tracker_chunked", stm);
+        res_t *out = reinterpret_cast<res_t *>(reinterpret_cast<double *>(R->out) + f0 * R->out_ld);
+        launch_tracker_chunked(stm, R->res + f0 * (long)VBX_MAX_RESONANCES, nf, VBX_MAX_RESONANCES, R->cnt + f0, R->d_range_seg + R->off[j],
+                               (long)(R->off[j + 1] - R->off[j]), R->d_est, R->n_est, R->st + f0, out, R->out_ld, R->trk_ws);
+        if (R->stitch[j] > 0)
+            launch_tracker_stitch(stm, R->res + f0 * (long)VBX_MAX_RESONANCES, nf, VBX_MAX_RESONANCES, R->cnt + f0, R->n_est, R->st + f0, out, R->out_ld,
+                                  0, (long)R->stitch[j], reinterpret_cast<const double *>(R->out) + (f0 - 1) * R->out_ld, nullptr);
+    }
+    return VBX_SUCCESS;
+}
+
+int find_formants_ranges_end(vbx_ctx *ctx, formants_ranges_t *R) {
+    if (!R->chunked) {                                      // short utterances in a small call: one lane per utterance, once, behind the last range
+        Prof p(ctx, "tracker", R->side);
+        launch_tracker(R->side, R->res, R->F, VBX_MAX_RESONANCES, R->cnt, R->d_seg, (long)R->nseg, R->d_est, R->n_est, R->st, R->out, R->out_ld);
+    }
     return check_launch(ctx, "vbx_find_formants_f64");
 }
 

@@ -17,6 +17,8 @@ static int ensure_side_stream(vbx_ctx *ctx) {
     VBX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
     VBX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
     VBX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_peak, hipEventDisableTiming));
+    for (auto &e : ctx->ev_bf_launch) VBX_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto &e : ctx->ev_bf_free) VBX_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return VBX_SUCCESS;
 }
 
@@ -148,12 +150,24 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, frames_t own, size_
         { Prof p(ctx, k_peak_names[own.kind], side); launch_frame_peak(side, own, (long)n_frames, (long)frame_len, (long)stride, tk_peak); }
         VBX_HIP(ctx, hipEventRecord(ctx->ev_peak, side));
     }
-    if (h_p->formant_order) {
+    // Burg's lag sums from the analyze kernel's own wavefronts instead of a second pass over the audio (analyze_kernel<.., BURG>): large
+    // calls of full 1200-sample f64 / PCM frames with find_formants at order 12 on the same frames.  The formant chain then runs behind
+    // the analyze kernel launch by launch (below, at the launch); the launch itself has the last word (spectral_burg_fusable_call).
+    const bool burg_fused_shape = ctx->burg_fused && fused && h_p->formant_order == (size_t)SPECTRAL_BURG_ORDER && frame_len == (size_t)SPECTRAL_N &&
+                                  x.p == own.p && (own.kind == SAMPLE_F64 || own.kind == SAMPLE_PCM16) && !(ex && ex->rp) &&
+                                  (long)n_frames >= ctx->burg_fused_min_frames && burg_fast_supported((int)frame_len, SPECTRAL_BURG_ORDER) &&
+                                  formant_resonances_fast_supported(SPECTRAL_BURG_ORDER);
+    auto formants_beside = [&]() -> int {
         vbx_resonance est[VBX_FORMANT_SLOTS];
         for (size_t e = 0; e < h_p->n_est; e++) est[e] = h_p->est_init[e];
-        rc = run_find_formants(ctx, side, x, n_frames, frame_len, stride, ex ? ex->formant_rate : h_p->sample_rate, h_p->formant_order,
-                               h_seg_start, n_segments, est, h_p->n_est, (vbx_resonance *)(out_records + c_form), record_ld,
-                               nullptr, nullptr, nullptr, st_form, ex ? ex->rp : nullptr);
+        return run_find_formants(ctx, side, x, n_frames, frame_len, stride, ex ? ex->formant_rate : h_p->sample_rate, h_p->formant_order,
+                                 h_seg_start, n_segments, est, h_p->n_est, (vbx_resonance *)(out_records + c_form), record_ld,
+                                 nullptr, nullptr, nullptr, st_form, ex ? ex->rp : nullptr);
+    };
+    if (burg_fused_shape) {
+        // (decided at the launch, below: every other side-stream kernel of such a call precedes the formant chain either way)
+    } else if (h_p->formant_order) {
+        rc = formants_beside();
         if (rc != VBX_SUCCESS) return rc;
     } else {
         ctx->last_track.res = nullptr;                        // no tracks in these records: nothing for vbx_track_stitch_f64 to continue
@@ -176,7 +190,7 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, frames_t own, size_
         Prof p(ctx, "frame_rms", side);
         launch_frame_rms(side, own, (long)n_frames, (int)frame_len, (long)stride, out_records + c_rms, (long)record_ld, nullptr);
     }
-    VBX_HIP(ctx, hipEventRecord(ctx->ev_join, side));
+    if (!burg_fused_shape) VBX_HIP(ctx, hipEventRecord(ctx->ev_join, side));
     if (fused) {
         const double *lagw = nullptr, *tab = nullptr; bool lag_rcp = false;
         VBX_HIP(ctx, ctx->tables.window(VBX_WINDOW_HANNING_LAG, frame_len, &lagw, &lag_rcp));
@@ -206,7 +220,41 @@ static int analyze_frames_impl(vbx_ctx *ctx, const char *fn, frames_t own, size_
             L.bins = d_bins; L.slopes = slopes; L.dct = dct; L.num_coeffs = (int)h_p->mfcc_coeffs; L.nb = nb;
             L.interp = interp_mfcc; L.ip = ip;
         }
-        rc = launch_spectral(ctx, ctx->stream, L, "analyze");
+        if (burg_fused_shape && spectral_burg_fusable_call(ctx, L)) {
+            formants_ranges_t R{};
+            vbx_resonance est[VBX_FORMANT_SLOTS];
+            for (size_t e = 0; e < h_p->n_est; e++) est[e] = h_p->est_init[e];
+            rc = find_formants_ranges_begin(ctx, side, x, n_frames, stride, ex ? ex->formant_rate : h_p->sample_rate, h_p->formant_order, h_seg_start,
+                                            n_segments, est, h_p->n_est, (vbx_resonance *)(out_records + c_form), record_ld, st_form,
+                                            ctx->analyze_launch_frames, &R);
+            if (rc != VBX_SUCCESS) return rc;
+            analyze_ranges_t rg;
+            rg.launch_frames = ctx->analyze_launch_frames < (long)n_frames ? ctx->analyze_launch_frames : (long)n_frames;
+            rg.scratch[0] = R.scratch[0]; rg.scratch[1] = R.scratch[1]; rg.burg_window = R.hann;
+            // launch j + 2 writes the scratch launch j wrote: behind the recursion that reads it
+            rg.before = [&](int j) -> int {
+                if (j >= 2) VBX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_bf_free[j & 1], 0));
+                return VBX_SUCCESS;
+            };
+            // ... and the side stream takes launch j's frames from there, beside launch j + 1
+            rg.after = [&](int j, long f0, long nf) -> int {
+                VBX_HIP(ctx, hipEventRecord(ctx->ev_bf_launch[j & 1], ctx->stream));
+                VBX_HIP(ctx, hipStreamWaitEvent(side, ctx->ev_bf_launch[j & 1], 0));
+                return find_formants_ranges_step(ctx, &R, j, f0, nf);
+            };
+            rc = launch_spectral(ctx, ctx->stream, L, "analyze", &rg);
+            if (rc != VBX_SUCCESS) return rc;
+            rc = find_formants_ranges_end(ctx, &R);
+            if (rc != VBX_SUCCESS) return rc;
+            VBX_HIP(ctx, hipEventRecord(ctx->ev_join, side));
+        } else {
+            if (burg_fused_shape) {                           // the launch takes another instance after all: the chain beside it, as for every other call
+                rc = formants_beside();
+                if (rc != VBX_SUCCESS) return rc;
+                VBX_HIP(ctx, hipEventRecord(ctx->ev_join, side));
+            }
+            rc = launch_spectral(ctx, ctx->stream, L, "analyze");
+        }
     } else if (tk) {
         rc = run_pitch(ctx, ctx->stream, x.f64(), n_frames, frame_len, stride, hann, h_p->sample_rate, h_p->pitch_threshold,
                        h_p->pitch_fmin, h_p->pitch_fmax, tk->kmax, tk_cand, 2 * tk->kmax, tk_count, st_pitch);

@@ -139,6 +139,47 @@ __device__ __forceinline__ bool burg_from_lags(const double *c_, const double *h
     return ok && (BF_KAPPA_EPS * kappa * big <= BF_TARGET * floor_j);               // false for NaN
 }
 
+// The lag sums' arithmetic, shared by burg_lags_kernel and the fused form of analyze_kernel (vbx_spectral_1200.hpp, BURG), so that the
+// two cannot drift: the scratch they leave is the same bit for bit.
+// ext[0, EPL): the lane's windowed samples (a lane past the frame's end: zeros).  The NL - 1 neighbours come from the next lane, every
+// lag is summed by two accumulators over the lane's even and odd samples, and the lane's NL partial sums go to row `lane` of the
+// transpose buffer TR[64][NL | 1] (LDS).
+template <int EPL, int NL>
+__device__ __forceinline__ void burg_lag_parts(double (&ext)[EPL + NL - 1], double *TR, int lane) {
+    constexpr int TS = NL | 1;
+#pragma unroll
+    for (int e = EPL; e < EPL + NL - 1; e++) ext[e] = from_next_lane(ext[e - EPL]);
+    double part[NL];
+#pragma unroll
+    for (int lag = 0; lag < NL; lag++) {
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int e = 0; e < EPL; e += 2) { s0 = fma(ext[e], ext[e + lag], s0); s1 = fma(ext[e + 1], ext[e + 1 + lag], s1); }
+        part[lag] = s0 + s1;
+    }
+#pragma unroll
+    for (int lag = 0; lag < NL; lag++) TR[lane * TS + lag] = part[lag];
+}
+// ... and, behind a wave_sync, the transposing reduction: four lanes per lag add sixteen rows each in row order, then two quad exchanges.
+// put(lag, total) runs in the lag's first lane (lane 4 (lag % 16)).
+template <int NL, typename PUT>
+__device__ __forceinline__ void burg_lag_totals(const double *TR, int lane, PUT &&put) {
+    constexpr int TS = NL | 1;
+    const int red_lag = lane >> 2, red_part = lane & 3;
+#pragma unroll
+    for (int lbase = 0; lbase < NL; lbase += 16) {   // 16 lags per sweep (4 lanes per lag)
+        const int rl = lbase + red_lag;
+        double tot = 0.0;
+        if (rl < NL) {
+#pragma unroll
+            for (int t = 0; t < 16; t++) tot += TR[(red_part * 16 + t) * TS + rl];
+        }
+        tot += dpp_f64<DPP_QUAD_XOR1>(tot);
+        tot += dpp_f64<0x4E>(tot);               // quad_perm [2,3,0,1]
+        if (red_part == 0 && rl < NL) put(rl, tot);
+    }
+}
+
 // EPL: samples per lane (frame_len <= 64 EPL).  P: the order.  TIN: double, int16_t = 16-bit PCM widened in registers, or float =
 // float32 samples (k_burg_lags_f32in*.hip), widened -- exactly -- when the window product is formed.
 // One wavefront works through BF_FPW frames as autocorr_fewlags_kernel does (k_lpc.hip: EPL samples per lane in registers,
@@ -225,7 +266,6 @@ __global__ __launch_bounds__(64) void burg_lags_kernel(
     raw_t cur[RAW], nxt[RAW], nx2[RAW];
     load_frame(0, cur);
     if (nf > 1) load_frame(1, nxt);
-    const int red_lag = lane >> 2, red_part = lane & 3;
 
     for (int g = 0; g < nf; g++) {
         if (g + 2 < nf) load_frame(g + 2, nx2);
@@ -241,18 +281,7 @@ __global__ __launch_bounds__(64) void burg_lags_kernel(
 #pragma unroll
             for (int e = 0; e < EPL; e++) ext[e] = (double)cur[e] * wreg[e];
         }
-#pragma unroll
-        for (int e = EPL; e < EPL + NL - 1; e++) ext[e] = from_next_lane(ext[e - EPL]);
-        double part[NL];
-#pragma unroll
-        for (int lag = 0; lag < NL; lag++) {
-            double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-            for (int e = 0; e < EPL; e += 2) { s0 = fma(ext[e], ext[e + lag], s0); s1 = fma(ext[e + 1], ext[e + 1 + lag], s1); }
-            part[lag] = s0 + s1;
-        }
-#pragma unroll
-        for (int lag = 0; lag < NL; lag++) TR[lane * TS + lag] = part[lag];
+        burg_lag_parts<EPL, NL>(ext, TR, lane);
         // the frame's first and last P + 1 samples
         if (lane * EPL <= P || (lane + 1) * EPL >= n - 1 - P) {
 #pragma unroll
@@ -263,18 +292,7 @@ __global__ __launch_bounds__(64) void burg_lags_kernel(
             }
         }
         wave_sync();
-#pragma unroll
-        for (int lbase = 0; lbase < NL; lbase += 16) {   // 16 lags per sweep (4 lanes per lag)
-            const int rl = lbase + red_lag;
-            double tot = 0.0;
-            if (rl < NL) {
-#pragma unroll
-                for (int t = 0; t < 16; t++) tot += TR[(red_part * 16 + t) * TS + rl];
-            }
-            tot += dpp_f64<DPP_QUAD_XOR1>(tot);
-            tot += dpp_f64<0x4E>(tot);               // quad_perm [2,3,0,1]
-            if (red_part == 0 && rl < NL) REC[rl * FPW + g] = tot;
-        }
+        burg_lag_totals<NL>(TR, lane, [&](int rl, double tot) { REC[rl * FPW + g] = tot; });
         wave_sync();
 #pragma unroll
         for (int e = 0; e < RAW; e++) { cur[e] = nxt[e]; nxt[e] = nx2[e]; }

@@ -10,6 +10,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -41,7 +42,7 @@ struct vbx_ctx {
     std::string arch;
     int cu_count = 0;
     // workspaces (grown on demand, never shrunk)
-    enum { WS_COEFFS, WS_RES, WS_COUNT, WS_STATUS, WS_MISC, WS_SEG, WS_EST, WS_UNSURE, WS_F32_IN, WS_F32_OUT, WS_TRK, WS_BURG_LIST, WS_ROOTS_LIST, WS_LONG, WS_LONG2, WS_CZT, WS_CURVE, WS_LPC_LIST, WS_PATH, WS_PATH_TAB, WS_TRACK, WS_EX, WS_HOST, WS_HOST_TYPED, WS_CLIPS_TAB, WS_CLIPS_PLANE, WS_CLIPS_ROWS, WS_CLIPS_LISTS, WS_N };
+    enum { WS_COEFFS, WS_RES, WS_COUNT, WS_STATUS, WS_MISC, WS_SEG, WS_EST, WS_UNSURE, WS_F32_IN, WS_F32_OUT, WS_TRK, WS_BURG_LIST, WS_ROOTS_LIST, WS_LONG, WS_LONG2, WS_CZT, WS_CURVE, WS_LPC_LIST, WS_PATH, WS_PATH_TAB, WS_TRACK, WS_EX, WS_HOST, WS_HOST_TYPED, WS_CLIPS_TAB, WS_CLIPS_PLANE, WS_CLIPS_ROWS, WS_CLIPS_LISTS, WS_RANGE_SEG, WS_N };
     void *ws[WS_N] = {nullptr};
     const int32_t *burg_list_count = nullptr;             // device counter of the last one-pass Burg call (tests)
     const int32_t *roots_list_count = nullptr;            // the same for the resonance kernel of find_formants
@@ -81,12 +82,22 @@ struct vbx_ctx {
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_peak = nullptr;                         // vbx_analyze_frames_tracked_*: the side stream's frame peaks exist (the path waits for it)
+    // the fused frame loop with Burg's lag sums from the analyze kernel (vbx_api_frames.hip): read once, at context creation
+    int burg_fused = 1;                                   // VBX_BURG_FUSED=0: burg_lags_kernel beside the analyze kernel, as before (A/B, tests)
+    // VBX_BURG_FUSED_MIN_FRAMES: calls of fewer frames keep that path (tests lower it).  The formant chain of the last launches runs behind the
+    // analyze kernel with nothing to hide it (~2 ms), where the lag kernel beside the analyze kernel costs the call ~1 ms per million frames
+    // more than the fused block does.  Measured at 1200 / 480 against the parent's path (profiles/burg_fused/by_length.txt):
+    // 4 % slower at 1.08 M frames, equal at 2.16 M, 2.5 % faster at 4.5 M
+    long burg_fused_min_frames = 3145728;
+    long analyze_launch_frames = 524288;                  // VBX_ANALYZE_LAUNCH_FRAMES: frames per launch of the fused path (tests lower it)
+    hipEvent_t ev_bf_launch[2] = {nullptr, nullptr};      // launch j has left its lag sums in scratch j & 1 (the side stream waits for it)
+    hipEvent_t ev_bf_free[2] = {nullptr, nullptr};        // the recursion is through with that scratch (launch j + 2 waits for it)
     hipStream_t trk = nullptr;                            // the tracker's time slices (run_find_formants)
     hipEvent_t ev_slice[8] = {nullptr}, ev_trk = nullptr;
     // pinned staging of the small host arrays (segment starts, initial estimates): the caller's arrays may be
     // freed on return, and an upload whose content has not changed since the last call is skipped
-    enum { N_STAGE = 4 };
-    void *stage[N_STAGE] = {nullptr};                     // 0: segment starts, 1: initial estimates, 2: the pitch path's chunk table, 3: vbx_analyze_clips' clip table
+    enum { N_STAGE = 5 };
+    void *stage[N_STAGE] = {nullptr};                     // 0: segment starts, 1: initial estimates, 2: the pitch path's chunk table, 3: vbx_analyze_clips' clip table, 4: the fused frame loop's per-launch utterance starts
     size_t stage_cap[N_STAGE] = {0};
     std::vector<char> staged[N_STAGE];                    // content now on the device
     hipEvent_t stage_ev[N_STAGE] = {nullptr};             // completion of the last staged copy
@@ -172,7 +183,30 @@ int upload_estimates(vbx_ctx *ctx, hipStream_t st, const vbx_resonance *h_est, s
 
 struct resample_plan_t { resample_src_t rs; size_t n_src, m; bool direct; };
 
-int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, const char *prof_name);
+// launch_spectral in launches of rg->launch_frames frames, each leaving Burg's lag sums of its frames in scratch[j & 1] (spectral_launch_t:
+// burg_*); before(j) / after(j, f0, nf) run around launch j's analyze kernel (the formant chain of those frames: find_formants_ranges_*)
+struct analyze_ranges_t {
+    long launch_frames; double *scratch[2]; const double *burg_window;
+    std::function<int(int)> before; std::function<int(int, long, long)> after;
+};
+int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, const char *prof_name, const analyze_ranges_t *rg = nullptr);
+// Would launch_spectral's launch of L take an instance that can leave Burg's lag sums?  (L as the caller hands it to launch_spectral)
+bool spectral_burg_fusable_call(vbx_ctx *ctx, const spectral_launch_t &L);
+// find_formants on the side stream behind the analyze kernel's launches, a range of frames at a time (vbx_api.hip): _begin takes the
+// workspaces (the scratch ring among them), uploads and clears what run_find_formants would; _step runs the recursion, the direct list,
+// the resonances and -- chunked scans -- the tracker of frames [f0, f0 + nf) from the lag sums launch j left; _end what is left.
+struct formants_ranges_t {
+    hipStream_t side; frames_t x; long F, stride; double sample_rate; int p, n_est;
+    const double *hann; double *coeffs; res_t *res; int32_t *cnt, *st, *list, *redo; double *scratch[2];
+    const res_t *d_est; const int64_t *d_seg; size_t nseg; bool chunked;
+    res_t *out; long out_ld; void *trk_ws;
+    const int64_t *d_range_seg; std::vector<size_t> off; std::vector<int64_t> stitch;
+};
+int find_formants_ranges_begin(vbx_ctx *ctx, hipStream_t side, frames_t x, size_t n_frames, size_t stride, double sample_rate, size_t n_coeffs,
+                               const int64_t *h_seg_start, size_t n_segments, const vbx_resonance *h_est_init, size_t n_est,
+                               vbx_resonance *out_formants, size_t formants_ld, int32_t *status, long launch_frames, formants_ranges_t *R);
+int find_formants_ranges_step(vbx_ctx *ctx, formants_ranges_t *R, int j, long f0, long nf);
+int find_formants_ranges_end(vbx_ctx *ctx, formants_ranges_t *R);
 const char *pitch_shape_error(size_t frame_len, size_t kmax);
 int run_pitch(vbx_ctx *ctx, hipStream_t st, const double *x, size_t n_frames, size_t frame_len, size_t stride,
               const double *window, double sample_rate, double threshold, double fmin, double fmax,

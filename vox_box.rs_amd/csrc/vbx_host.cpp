@@ -657,4 +657,24 @@ size_t pool_max_call_frames(size_t frame_len, size_t stride, size_t max_streams,
     return e * ((size_t)VBX_SHARD_WARM_FRAMES + frame_len / stride + (frame_len % stride != 0)) + max_tick / stride;
 }
 
+void launch_ranges_host(const int64_t *seg_start, size_t n_seg, size_t n_frames, size_t launch_frames,
+                        std::vector<int64_t> &seg, std::vector<size_t> &off, std::vector<int64_t> &stitch) {
+    seg.clear(); off.clear(); stitch.clear();
+    if (launch_frames == 0) launch_frames = 1;
+    if (seg_start == nullptr) n_seg = 0;
+    size_t k = 0;                                            // the first start not yet passed
+    for (size_t f0 = 0; f0 < n_frames; f0 += launch_frames) {
+        const size_t f1 = (n_frames - f0 < launch_frames) ? n_frames : f0 + launch_frames;
+        off.push_back(seg.size());
+        seg.push_back(0);
+        bool starts_here = (f0 == 0);
+        while (k < n_seg && (size_t)seg_start[k] <= f0) { starts_here = starts_here || (size_t)seg_start[k] == f0; k++; }
+        const size_t first_inside = seg.size();
+        while (k < n_seg && (size_t)seg_start[k] < f1) seg.push_back(seg_start[k++] - (int64_t)f0);
+        // rows that continue the utterance before the launch: up to the first start inside it, or all of them
+        stitch.push_back(starts_here ? 0 : (first_inside < seg.size() ? seg[first_inside] : (int64_t)(f1 - f0)));
+    }
+    off.push_back(seg.size());
+}
+
 }  // namespace vbx

@@ -51,6 +51,14 @@ size_t pool_carry_samples(size_t frame_len, size_t stride);
 // the most frames one tick's frame-loop call covers (vbx_pool_plan's call_frames), for ticks of at most max_tick samples in all
 size_t pool_max_call_frames(size_t frame_len, size_t stride, size_t max_streams, size_t max_tick);
 
+// ---- the fused frame loop cut into launches (analyze_frames with Burg's lag sums from the analyze kernel, vbx_api_frames.hip) ----
+// Launch j covers frames [j L, min((j + 1) L, F)).  The tracker scans each launch's rows alone, as if an utterance began with the
+// launch: seg[off[j] .. off[j + 1]) are the utterance starts of that scan, relative to the launch's first frame -- a 0, then every
+// start of seg_start (null: one utterance) strictly inside the launch; stitch[j] is the number of rows from the launch's first that
+// continue an utterance begun before it (0: an utterance starts with the launch) -- those are repaired from the row before them.
+void launch_ranges_host(const int64_t *seg_start, size_t n_seg, size_t n_frames, size_t launch_frames,
+                        std::vector<int64_t> &seg, std::vector<size_t> &off, std::vector<int64_t> &stitch);
+
 // table kinds of vbx_internal_host_table (tests, tools/host_property_check.py)
 enum { HOST_TABLE_WINDOW, HOST_TABLE_LAG_F32, HOST_TABLE_GOERTZEL, HOST_TABLE_DFT2, HOST_TABLE_MFMA, HOST_TABLE_DCT,
        HOST_TABLE_SLOPES, HOST_TABLE_RESAMPLE, HOST_TABLE_KINDS };

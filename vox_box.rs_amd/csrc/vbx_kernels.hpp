@@ -89,6 +89,9 @@ int32_t *burg_fast_list(void *ws, long F, int p);
 bool launch_burg_lags(hipStream_t s, frames_t x, long F, int n, long stride, const double *window, int p, frame_map_t map, long i0,
                       long m, void *ws);
 void launch_burg_recursion(hipStream_t s, long F, int p, frame_map_t map, long i0, long m, double *out, int32_t *status, void *ws);
+// the recursion on a scratch somebody else filled (the fused frame loop's launches: analyze_kernel<.., BURG>): frames [i0, i0 + m) of the batch,
+// tile t of `scratch` holding frames [i0 + 64 t, i0 + 64 t + 64); list: [0] count, indices from [2]
+void launch_burg_recursion_at(hipStream_t s, const double *scratch, int32_t *list, long F, int p, long i0, long m, double *out, int32_t *status);
 
 void launch_count_accumulate(hipStream_t s, const int32_t *count, int32_t *total, bool reset);   // total = (reset ? 0 : total) + count
 
@@ -188,6 +191,7 @@ void launch_extremum_points(hipStream_t s, const double *y, int ylen, long offse
 // the reference's own test and example shapes (tests/lib.rs:56, examples/pitch_detection.rs:23) and everything between.
 constexpr int SPECTRAL_N = 1200;
 constexpr int SPECTRAL_LPC_ORDER = 12;
+constexpr int SPECTRAL_BURG_ORDER = 12;                        // the Burg order whose lag sums the 1200-point fused kernel can leave beside its own work (spectral_launch_t: burg_*)
 constexpr int SPECTRAL_TAB_COMPLEX = 60 * 20 + 3 * 20 + 601;    // W_1200^(n' ka) | W_60^(c kb) | W_2400^m
 enum { SPECTRAL_PLAN_NONE = 0, SPECTRAL_PLAN_1200 = 1, SPECTRAL_PLAN_1024 = 2, SPECTRAL_PLAN_2048 = 3, SPECTRAL_PLAN_4096 = 4,
        SPECTRAL_PLANS = 5 };
@@ -248,7 +252,12 @@ struct spectral_launch_t {
     bool whole_curve;                                            // keep every lag of the curve in LDS (VBX_PITCH_CURVE_CUT=0; tests)
     bool interp; mfcc_interp_t ip;                               // MFCC by interpolation of the transform's bins (device pointers)
     double *curve_ws; size_t curve_ws_bytes;                     // scratch for the split form of the 4096-point plan (lag curves between its two kernels); NULL: fused
+    // non-NULL: ONE launch over frames [burg_f0, burg_f0 + burg_nf) of the batch that also leaves Burg's order-12 lag sums and edge samples of those
+    // frames (under burg_window, find_formants' periodic Hanning window) in burg_scratch, tiled as burg_recursion_kernel reads it (launch-local frame
+    // index).  Only where spectral_burg_fusable(L) holds.
+    double *burg_scratch; const double *burg_window; long burg_f0, burg_nf;
 };
+bool spectral_burg_fusable(const spectral_launch_t &L);             // launch_analyze would take a launch-specialised instance (k_spectral.hip)
 size_t spectral_split_row_bytes(int n, double sample_rate, double fmin);   // bytes per frame of that scratch, 0: the shape has no split form
 bool spectral_supported(int n, int lpc_order, int mfcc_nb, int mfcc_b_lo, int num_coeffs);
 bool spectral_list_parked(const spectral_launch_t &L);              // the whole-Vec list goes to the output row, not to LDS

@@ -76,6 +76,7 @@ struct spectral_args_t {
                                                              // fallback list, -2: to far_list), then its candidates' lags as uint16 (scan_curve_kernel -> refine_list_kernel)
     int32_t *far_list;                                       // [0]: count, [4..]: batch-local indices of frames with a candidate whose PEAK lies beyond the lags
                                                              // refine_list_kernel holds (refine_far_kernel takes them with the whole curve)
+    double *burg_scratch; const double *burg_window; long burg_f0;      // analyze_kernel<.., BURG> (1200-point plan): below
 };
 
 // The 1200-point plan's argument block: spectral_args_t without what only the power-of-two plans, their split form, the
@@ -103,6 +104,13 @@ struct spectral_args_1200_t {
           out_lpc(a.out_lpc), lpc_ld(a.lpc_ld), out_mfcc(a.out_mfcc), mfcc_ld(a.mfcc_ld), mfcc_status(a.mfcc_status),
           bins(a.bins), slopes(a.slopes), dct(a.dct) {}
 };
+// ... and the block of analyze_kernel<.., BURG>: the same, then the launch's scratch tiles for burg_recursion_kernel, find_formants'
+// periodic Hanning window and the frame of the batch the launch starts at (every other instance keeps the block it had)
+struct spectral_args_1200_burg_t : spectral_args_1200_t {
+    double *burg_scratch; const double *burg_window; long burg_f0;
+    explicit spectral_args_1200_burg_t(const spectral_args_t &a)
+        : spectral_args_1200_t(a), burg_scratch(a.burg_scratch), burg_window(a.burg_window), burg_f0(a.burg_f0) {}
+};
 static_assert(offsetof(spectral_args_1200_t, out_cand) == 64 && offsetof(spectral_args_1200_t, nb) + sizeof(int) <= 128, "the last stores' arguments: one 64-byte line");
 __host__ __device__ constexpr bool sp_wide_args(int mode) { return mode == SP_AC_ONLY || sp_is_interp(mode); }
 
@@ -120,8 +128,13 @@ constexpr int SP_SPEC_NONE = 0, SP_SPEC_F64 = 1, SP_SPEC_PCM16 = 2;
 // (the kernel's name stays analyze_kernel<LPC, MFCC, FULL, SP_ANALYZE, 3, ...>: tools and the benchmark find it by that prefix)
 struct sp_launch_f64_t {};
 struct sp_launch_pcm16_t {};
+// ... and that the frame's wavefront also leaves Burg's lag sums (BURG, vbx_spectral_1200.hpp)
+struct sp_launch_f64_burg_t {};
+struct sp_launch_pcm16_burg_t {};
+template <typename TIN> constexpr bool sp_burg_of() { return std::is_same<TIN, sp_launch_f64_burg_t>::value || std::is_same<TIN, sp_launch_pcm16_burg_t>::value; }
 template <typename TIN> constexpr int sp_spec_of() {
-    return std::is_same<TIN, sp_launch_f64_t>::value ? SP_SPEC_F64 : std::is_same<TIN, sp_launch_pcm16_t>::value ? SP_SPEC_PCM16 : SP_SPEC_NONE;
+    return (std::is_same<TIN, sp_launch_f64_t>::value || std::is_same<TIN, sp_launch_f64_burg_t>::value) ? SP_SPEC_F64 :
+           (std::is_same<TIN, sp_launch_pcm16_t>::value || std::is_same<TIN, sp_launch_pcm16_burg_t>::value) ? SP_SPEC_PCM16 : SP_SPEC_NONE;
 }
 
 // The last SP_TAIL lags of the curve.  The lag window falls below 1e-8 there (1e-10 .. 1e-17 over the last twelve lags), so
@@ -183,6 +196,7 @@ __device__ __forceinline__ void levinson_regs(const double (&r)[P + 1], double (
 }
 
 constexpr int SP_LPC_P = SPECTRAL_LPC_ORDER;
+constexpr int SP_BURG_P = SPECTRAL_BURG_ORDER;                                // the Burg order whose lag sums the fused kernel can leave beside its own work (BURG)
 
 // LPC::lpc inside the fused call (round 6).  Rounds 1-5 ran the recursion in the frame's wavefront: sixty-four lanes on the same
 // thirteen values, twelve IEEE divisions, ~450 vector instructions per frame for what ONE lane can do.  The kernels now store the

@@ -10,6 +10,7 @@
 #include "vbx_mfcc_interp.hpp"
 #include "vbx_pitch_refine.hpp"
 #include "vbx_spectral.hpp"
+#include "vbx_burg_fast.hpp"
 
 namespace vbx {
 
@@ -235,7 +236,8 @@ __host__ __device__ constexpr bool sp_front_end_once(bool mfcc, bool full, int w
     return VBX_EXP_FRONT_END_ONCE != 0 && !(!mfcc && full && waves >= 3 && !f32);
 }
 __host__ __device__ constexpr int sp_cell_blocks(int waves, bool f32) { return f32 ? VBX_EXP_CELL_NB_F32IN : VBX_EXP_CELL_NB; }
-template <int MODE> using sp_args_of = typename std::conditional<sp_wide_args(MODE), spectral_args_t, spectral_args_1200_t>::type;
+template <int MODE, typename TIN = double> using sp_args_of = typename std::conditional<sp_wide_args(MODE), spectral_args_t,
+                                                         typename std::conditional<sp_burg_of<TIN>(), spectral_args_1200_burg_t, spectral_args_1200_t>::type>::type;
 // The kernel's own argument block where it lies, in the argument segment (the block is the kernel's only argument: offset 0), for the
 // SPEC instances' fields that are read where they are used.  The pointer passes through an empty asm at every use, so that the
 // compiler can neither move the scalar load up to the kernel's entry nor merge it with the entry's loads -- which is how sixteen
@@ -248,13 +250,21 @@ __device__ __forceinline__ const __attribute__((address_space(4))) ARGS *sp_args
 }
 // TIN = sp_launch_f64_t / sp_launch_pcm16_t: f64 / 16-bit PCM samples with the launch-uniform choices compiled in (SP_SPEC_*,
 // vbx_spectral.hpp); three-wavefront SP_ANALYZE instances of full frames only.
+// BURG (TIN = sp_launch_f64_burg_t / sp_launch_pcm16_burg_t: launch-specialised instances only): the frame's wavefront also leaves what burg_recursion_kernel<SP_BURG_P> reads -- the order-12
+// lag sums of the frame under the PERIODIC Hanning window (find_formants' own, not the pitch window) and its first and last 13
+// windowed samples -- in the launch's scratch tile, bit for bit what burg_lags_kernel<20, 12, TIN> writes there (the arithmetic is
+// that kernel's own: burg_lag_parts / burg_lag_totals, vbx_burg_fast.hpp).  The block runs FIRST, while the frame's registers are
+// free: twenty contiguous samples per lane (a second read of cache lines the wavefront requests anyway a moment later), the
+// transpose buffer in the exchange buffer.  The launch covers frames [a.burg_f0, a.burg_f0 + a.n_frames) of the batch.
 template <bool LPC, bool MFCC, bool FULL, int MODE = SP_ANALYZE, int WAVES = VBX_SPECTRAL_WAVES, typename TIN = double>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_only(MODE) ? 2 : WAVES, sp_is_mfcc_only(MODE) ? 4 : WAVES))) void analyze_kernel(const sp_args_of<MODE> a) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_only(MODE) ? 2 : WAVES, sp_is_mfcc_only(MODE) ? 4 : WAVES))) void analyze_kernel(const sp_args_of<MODE, TIN> a) {
     constexpr bool F32 = std::is_same<TIN, float>::value;
-    using args_t = sp_args_of<MODE>;
+    using args_t = sp_args_of<MODE, TIN>;
     constexpr int SPEC = sp_spec_of<TIN>();
+    constexpr bool BURG = sp_burg_of<TIN>();
     static_assert(SPEC == SP_SPEC_NONE || (FULL && MODE == SP_ANALYZE && WAVES >= 3), "the launch-specialised form: full f64 / PCM frames, three wavefronts");
     constexpr bool SP = SPEC != SP_SPEC_NONE;
+    static_assert(!BURG || SP, "Burg's lag sums ride on the launch-specialised instances only");
     // launch-uniform choices: a SPEC instance's at compile time, the generic instance's from the argument block -- written as macros so
     // that the generic instances hold, use for use, the expressions they always held.
     // (NOT the window's presence: with it a constant, a sample's window product feeds the first butterfly's addition directly and
@@ -270,8 +280,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_o
     constexpr bool PITCH = !sp_is_mfcc_only(MODE);           // the second transform runs
     constexpr bool INTERP = sp_is_interp(MODE);              // MFCC's bins lie between the transform's (mfcc_interp_t, vbx_kernels.hpp)
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    const long f = xcd_item(blockIdx.x, a.n_frames);            // neighbouring frames on the same XCD: their overlap hits its L2
-    if (f >= a.n_frames) return;
+    const long fl = xcd_item(blockIdx.x, a.n_frames);           // neighbouring frames on the same XCD: their overlap hits its L2
+    if (fl >= a.n_frames) return;
+    long f = fl;
+    if constexpr (BURG) f += a.burg_f0;                         // (BURG: fl counts inside the launch, f inside the batch)
     const int lane = lane_id();
     const int np = (lane < 60) ? lane : 59;
     const int n = FULL ? SP_N : a.n;                         // frame length, <= SP_N (shorter: longer zero padding)
@@ -280,6 +292,80 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_o
     // stage-2 twiddles into LDS, behind the exchange buffer and the mel sums (fft1200; ordered by the first exchange's wave_sync)
     double2 *t2 = reinterpret_cast<double2 *>(reinterpret_cast<char *>(smem) + SP_T2_LDS_OFFSET);
     VBX_PHASE_INIT();
+
+    if constexpr (BURG) {
+        // ---- Burg's lag sums and edge samples of this frame: lane l holds samples [20 l, 20 l + 20) times the periodic Hanning window ----
+        constexpr int EPL = 20, NL = SP_BURG_P + 1, TS = NL | 1;
+        static_assert(64 * EPL >= SP_N && 60 * EPL == SP_N, "sixty lanes of twenty samples, lanes 60..63 zero as in burg_lags_kernel<20, ..>");
+        static_assert((64 * TS + 3 * NL) * 8 <= SP_T2_LDS_OFFSET, "transpose buffer and record inside the exchange buffer");
+        double *TR = smem, *REC = smem + 64 * TS;
+        double ext[EPL + NL - 1];
+        // (the block's own copy of the lane index, opaque to the compiler: nothing derived from it here is kept for the frame's loads below,
+        // whose registers are counted to the last one)
+        int lane = lane_id();
+        asm volatile("" : "+v"(lane));
+        const int np = (lane < 60) ? lane : 59;
+        {
+            const double2 *wv = reinterpret_cast<const double2 *>(a.burg_window + np * EPL);     // (the table is 16-byte aligned: launch_analyze)
+            if (VBX_SP_PCM_IN) {
+                const int16_t *xb = reinterpret_cast<const int16_t *>(a.frames) + f * a.stride + np * EPL;
+                if ((((uintptr_t)xb) & 3) == 0) {
+#pragma unroll
+                    for (int e = 0; e < EPL; e += 2) {
+                        const int w = *reinterpret_cast<const int *>(xb + e);
+                        const double2 h = wv[e / 2];
+                        ext[e] = pcm16_value((int)(short)(w & 0xffff)) * h.x;
+                        ext[e + 1] = pcm16_value(w >> 16) * h.y;
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < EPL; e += 2) {
+                        const int lo = xb[e], hi = xb[e + 1];
+                        const double2 h = wv[e / 2];
+                        ext[e] = pcm16_value(lo) * h.x;
+                        ext[e + 1] = pcm16_value(hi) * h.y;
+                    }
+                }
+            } else {
+                const double *xb = xf + np * EPL;
+                if ((((uintptr_t)xf) & 15) == 0) {                 // uniform: ten 16-byte loads per lane
+#pragma unroll
+                    for (int e = 0; e < EPL; e += 2) {
+                        const double2 v = *reinterpret_cast<const double2 *>(xb + e);
+                        const double2 h = wv[e / 2];
+                        ext[e] = v.x * h.x; ext[e + 1] = v.y * h.y;
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < EPL; e += 2) {
+                        const double lo = xb[e], hi = xb[e + 1];
+                        const double2 h = wv[e / 2];
+                        ext[e] = lo * h.x; ext[e + 1] = hi * h.y;
+                    }
+                }
+            }
+            if (lane >= 60) {                                      // past the frame's end: the zeros they are in burg_lags_kernel
+#pragma unroll
+                for (int e = 0; e < EPL; e++) ext[e] = 0.0;
+            }
+        }
+        burg_lag_parts<EPL, NL>(ext, TR, lane);
+        if (lane == 0) {                                           // x_w[0..12]
+#pragma unroll
+            for (int k = 0; k < NL; k++) REC[NL + k] = ext[k];
+        }
+        if (lane == 59) {                                          // x_w[1199 - k], k = 0..12
+#pragma unroll
+            for (int k = 0; k < NL; k++) REC[2 * NL + k] = ext[EPL - 1 - k];
+        }
+        wave_sync();
+        burg_lag_totals<NL>(TR, lane, [&](int rl, double tot) { REC[rl] = tot; });
+        wave_sync();
+        // the scratch is tiled [64 frames: one wavefront of the recursion][value][frame]
+        if (lane < 3 * NL) a.burg_scratch[(fl >> 6) * (3 * NL * 64) + lane * 64 + (fl & 63)] = REC[lane];
+        wave_sync();                                               // before the transform's first exchange takes the buffer
+        asm volatile("" ::: "memory");                             // the frame's own loads start behind this block: its registers are free again
+    }
 
     // ---- load: z[60 a + n'] = (xw[120 a + 2 n'], xw[120 a + 2 n' + 1]), a < 10 (the rest is the zero padding) ----
     double re[20], im[20];

@@ -1737,7 +1737,7 @@ class VoxBox:
         rec = int(self.L.vbx_record_doubles(C.byref(params)))
         ld = record_ld if record_ld is not None else rec + (rec & 1)
         seg = None if seg_start is None else np.ascontiguousarray(seg_start, dtype=np.int64)
-        o = out if out is not None else self.empty((F, ld))
+        o = out if out is not None else (self.zeros((F, ld)) if ld > rec else self.empty((F, ld)))      # (zeros where a row ends in a padding column, which no kernel writes: tests/test_gpu_lpc_reference.py compares whole rows of two contexts)
         st = status if status is not None else (self.empty((3, F), np.int32) if out is None else None)
         self._check(self.L.vbx_analyze_frames_f64(self.ctx, ptr, F, N, S, C.byref(params),
                                                   None if seg is None else seg.ctypes.data, 0 if seg is None else seg.size,
@@ -1766,7 +1766,7 @@ class VoxBox:
         rec = int(self.L.vbx_record_doubles(C.byref(params)))
         ld = record_ld if record_ld is not None else rec + (rec & 1)
         seg = None if seg_start is None else np.ascontiguousarray(seg_start, dtype=np.int64)
-        o = out if out is not None else self.empty((F, ld))
+        o = out if out is not None else (self.zeros((F, ld)) if ld > rec else self.empty((F, ld)))      # (zeros where a row ends in a padding column, which no kernel writes: tests/test_gpu_lpc_reference.py compares whole rows of two contexts)
         st = status if status is not None else (self.empty((3, F), np.int32) if out is None else None)
         self._check(self.L.vbx_analyze_frames_pcm16(self.ctx, ptr, F, int(frame_len), int(stride), C.byref(params),
                                                     None if seg is None else seg.ctypes.data, 0 if seg is None else seg.size,
@@ -1791,7 +1791,7 @@ class VoxBox:
             raise ValueError("lists=True returns the pitch path's lists: it needs track=")
         ld = record_ld if record_ld is not None else rec + (rec & 1)
         seg = None if seg_start is None else np.ascontiguousarray(seg_start, dtype=np.int64)
-        o = out if out is not None else self.empty((F, ld))
+        o = out if out is not None else (self.zeros((F, ld)) if ld > rec else self.empty((F, ld)))      # (zeros where a row ends in a padding column, which no kernel writes: tests/test_gpu_lpc_reference.py compares whole rows of two contexts)
         st = status if status is not None else (self.empty((3, F), np.int32) if out is None else None)
         if lists and (out is not None or outputs is not None):
             raise ValueError("lists=True returns host copies of library-allocated lists: it cannot be combined with out= or outputs= "
