@@ -98,7 +98,7 @@ CASES = [
     _ac(1280, 257, "tiles", ctx_env=MFMA), _ac(1281, 300, "tiles", ctx_env=MFMA),
     _ac(512, 512, "fft"), _ac(1024, 1024, "fft"), _ac(1103, 1103, "fft"), _ac(1200, 1200, "fft"),
     _ac(2047, 2047, "fft"), _ac(2048, 2048, "fft"), _ac(4095, 4095, "fft"), _ac(4096, 4096, "fft"),
-    _ac(4097, 40, "long"),
+    _ac(4097, 40, "long", splits=5),
     # -- MFCC, one case per form (run_mfcc, vbx_api.hip)
     _mf("fft", 1200, 1), _mf("fft", 2048, 1),
     _mf("interp", 1103, 2), _mf("interp", 3000, 2),
@@ -137,6 +137,25 @@ CASES += [
     # -- the dense fallback: resampled into a batch, then the plain one-pass form (m = 2048; a source frame beyond VBX_MAX_FRAME_LEN)
     _rs(4096, 0.5, "r1:2", 12, 2048, _DENSE, 2), _rs(5000, 0.2, "r1:5", 12, 1000, _DENSE, 2),
 ]
+
+
+def long_splits(F, n, lags):
+    """autocorr_long_splits() of k_long.hip, restated to CHOOSE the cases' frame counts: into how many partial sums a launch of F long frames
+    cuts each lag's sum -- enough for 1280 workgroups, at most one per 1024-sample chunk of the frame, at most 64.  What a case claims is
+    held to the library on the GPU: tests/test_gpu_accuracy.py asserts vbx_internal_last_autocorr_long_splits == the case's `splits`."""
+    groups, chunks = -(-lags // 1280), -(-n // 1024)
+    return max(1, min(-(-1280 // (F * groups)), chunks, 64))
+
+
+def _acl(n, lags, F, hop, splits):
+    assert long_splits(F, n, lags) == splits
+    return Case(f"autocorr-{n}x{lags}-long-{F}-frames-{splits}-splits", "autocorr", n, F, kernels={"autocorr_long"}, lags=lags, hop=hop, splits=splits)
+
+
+# -- the long-frame autocorrelation at every form of its summation split, which follows the launch's frame count: one sum per lag (what every
+#    large call runs), three partial sums, one per chunk of a 4097-sample frame alone, and the cap of 64 at 65,537 samples.  (autocorr-4097x40-long
+#    above: 3 frames, 5 splits.)  These batches are too large for frames 997 samples apart: a hop of their own.
+CASES += [_acl(4097, 40, 1280, 3, 1), _acl(4097, 40, 500, 101, 3), _acl(4097, 40, 1, 997, 5), _acl(65537, 13, 1, 997, 64)]
 BY_ID = {c.id: c for c in CASES}
 assert len(BY_ID) == len(CASES)
 
@@ -222,7 +241,8 @@ def host_speech():
 
 def frames(case, speech, oracle):
     k = CASES.index(case)
-    base, hop = 1000 + 3001 * (k % 8), 997
+    base, hop = 1000 + 3001 * (k % 8), case.p.get("hop", 997)
+    assert base + (case.F - 1) * hop + case.n <= speech.size, case
     X = np.stack([speech[base + t * hop:base + t * hop + case.n] for t in range(case.F)])
     if not case.rect:
         X = X * oracle.window("hanning", case.n)

@@ -38,7 +38,7 @@ What a caller of the library runs is held the same way (accuracy_cases.FUSED_CAS
 Their pitch, LPC and formant columns are not here: Brent (below), tests/test_gpu_lpc_exact.py, bit-equality with find_formants.
 
 Which kernel ran is asserted from vbx_profile_names and the library's probes (vbx_internal_last_mfcc_form, last_burg_direct_count,
-last_analyze_spec, last_spectral_split), as tests/test_gpu_layouts.py does.  The fused call has no probe for "bins interpolated": `analyze`
+last_analyze_spec, last_spectral_split, last_autocorr_long_splits), as tests/test_gpu_layouts.py does.  The fused call has no probe for "bins interpolated": `analyze`
 profiled, no MFCC kernel beside it and a frame that does not divide the transform leave launch_analyze no other form.
 vbx_autocorrelate_f64 has no plan probe: the profile name autocorr_fft plus the frame length decide the transform (spectral_plan(),
 restated in accuracy_cases.fft_transform), and the report test asserts that all four were reached.
@@ -123,6 +123,10 @@ def _call(ctx, case, X, monkeypatch):
     probe = {"kernels": sorted(names)}
     if case.family == "autocorr" and "autocorr_fft" in names:
         probe["fft_transform"] = ac.fft_transform(case.n)
+    if "autocorr_long" in case.kernels:
+        # into how many partial sums the launch cut each lag's sum: from the library, which reads it off the launch's own scratch size
+        probe["long_splits"] = int(ctx.L.vbx_internal_last_autocorr_long_splits(ctx.ctx))
+        assert probe["long_splits"] == case.p.get("splits", probe["long_splits"]) and probe["long_splits"] >= 1, (case, probe)
     if case.family == "mfcc":
         probe["mfcc_form"] = int(ctx.L.vbx_internal_last_mfcc_form(ctx.ctx))
         assert case.form is None or probe["mfcc_form"] == case.form, (case, probe)

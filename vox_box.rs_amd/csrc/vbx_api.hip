@@ -70,6 +70,8 @@ int get_bins_dev(vbx_ctx *ctx, size_t n, size_t k, double lo, double hi, double 
 int check_frames(vbx_ctx *ctx, const char *fn, const void *x, size_t n_frames, size_t frame_len, size_t stride,
                  size_t max_len) {
     if (!ctx) return fail(nullptr, VBX_E_INVALID, std::string(fn) + ": null context");
+    ctx->last_batching[0] = ctx->last_batching[1] = 0;      // (vbx_internal_last_batching: the loops of this call, batch_count_t)
+    ctx->last_autocorr_long_splits = 0;                     // (set by the call's last long-frame autocorrelation launch)
     ctx->lpc_list_armed = false;   // every frame-batch call: only one that arms the LPC probe's list (below) sets it again
     ctx->path_last = false;        // (and vbx_internal_last_path_chunks_redone answers -1 until the next path call)
     ctx->shard.live = false;       // (and vbx_pitch_path_shard_enter_f64 / _finish_f64 are refused until the next _begin)
@@ -398,6 +400,8 @@ static int run_autocorrelate(vbx_ctx *ctx, hipStream_t st, const double *x, size
         int rc = ws_get(ctx, vbx_ctx::WS_LONG, autocorr_long_scratch_bytes((long)n_frames, (long)frame_len, (long)n_lags), &w);
         if (rc != VBX_SUCCESS) return rc;
         Prof p(ctx, "autocorr_long", st);
+        // (the scratch holds one partial sum per split, lag and frame: its size says into how many the launch cuts a lag's sum)
+        ctx->last_autocorr_long_splits = (int)(autocorr_long_scratch_bytes((long)n_frames, (long)frame_len, (long)n_lags) / (n_frames * n_lags * sizeof(double)));
         launch_autocorr_long(st, x, (long)n_frames, (long)frame_len, (long)stride, window, (long)n_lags, out, (double *)w);
         return VBX_SUCCESS;
     }
@@ -521,7 +525,7 @@ int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, const ch
         ctx->lpc_list_armed = true;
     }
     // the 4096-point plan runs as two kernels with the lag curves in a scratch buffer between them (vbx_spectral.hpp, SP_ANALYZE_SPLIT):
-    // batches of up to 131,072 frames (~10 KB each)
+    // batches of a little over 131,072 frames (~10 KB each; the scratch grants 16 bytes a frame more than launch_pow2_u divides it by: 131,193 at 4096 samples)
     L.curve_ws = nullptr; L.curve_ws_bytes = 0;
     const size_t rowb = (ctx->pow2_split != 0 && !L.whole_curve && !L.mfcc_only && L.out_r == nullptr && pitch_full_list_bytes(L.n, L.kmax) == 0)
                             ? spectral_split_row_bytes(L.n, L.sample_rate, L.fmin) : 0;      // (a list region in LDS, kmax > 64: the fused kernel)
@@ -539,6 +543,8 @@ int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, const ch
     }
     spectral_launch_choices(ctx, L);
     ctx->last_analyze_spec = 0;
+    long split_batching[2] = {0, 0};
+    L.batching = split_batching;
     if (rg == nullptr) { Prof p(ctx, prof_name, st); ctx->last_spectral_split = launch_analyze(st, L, &ctx->last_analyze_spec); }
     else {
         // the same kernel in launches of rg->launch_frames frames, each leaving Burg's lag sums of its frames for the side stream
@@ -557,6 +563,8 @@ int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, const ch
             if (rc != VBX_SUCCESS) return rc;
         }
     }
+    L.batching = nullptr;
+    note_batching(ctx, split_batching[0], split_batching[1]);
     if (L.mfcc_defer && L.out_lpc == nullptr) { Prof p(ctx, "mfcc_rows", st); launch_mfcc_rows(st, L.out_mfcc, L.F, L.mfcc_ld, L.num_coeffs, L.dct); }
     {
         Prof p(ctx, "pitch_direct_fallback", st);
@@ -620,7 +628,9 @@ int run_pitch(vbx_ctx *ctx, hipStream_t st, const double *x, size_t n_frames, si
         void *w2 = nullptr;
         rc = ws_get(ctx, vbx_ctx::WS_LONG2, pitch_long_scratch_bytes((long)per, (long)frame_len), &w2);
         if (rc != VBX_SUCCESS) return rc;
+        batch_count_t batches(ctx, (long)per);
         for (size_t f0 = 0; f0 < n_frames; f0 += per) {
+            batches.launched();
             const size_t m = (n_frames - f0 < per) ? n_frames - f0 : per;
             double *r = pitch_long_r(w2);
             rc = run_autocorrelate(ctx, st, x + f0 * stride, m, frame_len, stride, window, frame_len, r);      // :402
@@ -821,7 +831,9 @@ int run_burg(vbx_ctx *ctx, hipStream_t stm, frames_t x, long F, int n, long stri
         int32_t *total = (int32_t *)w;                            // [1]: the guard's count over the whole call
         double *dense = (double *)((char *)w + 16);
         bool counted = false;
+        batch_count_t batches(ctx, per);
         for (long f0 = 0; f0 < F; f0 += per) {
+            batches.launched();
             const long nf = (F - f0 < per) ? F - f0 : per;
             { Prof pr(ctx, "resample", stm); launch_resample(stm, x.f64() + f0 * stride, nf, (int)rp->n_src, stride, rp->rs.li, rp->rs.frac, n, dense); }
             rc = run_burg(ctx, stm, dense, nf, n, (long)n, window, p, coeffs + f0 * (long)p, st + f0);
@@ -842,9 +854,12 @@ int run_burg(vbx_ctx *ctx, hipStream_t stm, frames_t x, long F, int n, long stri
         void *w = nullptr;
         int rc = ws_get(ctx, vbx_ctx::WS_LONG, burg_long_scratch_bytes(per, n), &w);
         if (rc != VBX_SUCCESS) return rc;
+        batch_count_t batches(ctx, per);
         Prof pr(ctx, "burg_long", stm);
-        for (long f0 = 0; f0 < F; f0 += per)
+        for (long f0 = 0; f0 < F; f0 += per) {
+            batches.launched();
             launch_burg_long(stm, x.f64(), f0, (f0 + per < F) ? f0 + per : F, F, n, stride, window, p, coeffs, st, (double *)w);
+        }
         return VBX_SUCCESS;
     }
     if (burg_fast_supported(n, p)) {
@@ -1293,6 +1308,14 @@ int vbx_track_stitch_f64(vbx_ctx *ctx, vbx_resonance *formants, size_t n_frames,
 }
 
 int vbx_internal_last_spectral_split(vbx_ctx *ctx) { return ctx ? ctx->last_spectral_split : 0; }
+int vbx_internal_last_autocorr_long_splits(vbx_ctx *ctx) { return ctx ? ctx->last_autocorr_long_splits : 0; }
+// {launches made, frames per launch} of the host loop that cut the last frame-batch call's frames into the most launches (batch_count_t); 0, 0: it ran none
+int vbx_internal_last_batching(vbx_ctx *ctx, long *h_batches, long *h_frames_per_batch) {
+    VBX_REQUIRE(ctx, ctx != nullptr, "null context");
+    if (h_batches) *h_batches = ctx->last_batching[0];
+    if (h_frames_per_batch) *h_frames_per_batch = ctx->last_batching[1];
+    return VBX_SUCCESS;
+}
 int vbx_internal_last_analyze_spec(vbx_ctx *ctx) { return ctx ? ctx->last_analyze_spec : 0; }
 int vbx_internal_last_mfcc_interp(vbx_ctx *ctx) { return ctx ? ctx->last_mfcc_interp : 0; }
 // Every MFCC kernel is profiled as "mfcc" and every pitch kernel as "pitch": these say which one the context's last call took.

@@ -219,7 +219,9 @@ int vbx_lpc_burg_f32(vbx_ctx *ctx, const float *x, size_t n_frames, size_t frame
     void *w = nullptr;
     rc = ws_get(ctx, vbx_ctx::WS_F32_IN, burg_f32_exact_scratch_bytes(chunk, (int)frame_len), &w);
     if (rc != VBX_SUCCESS) return rc;
+    batch_count_t batches(ctx, chunk);
     for (long f0 = 0; f0 < (long)n_frames; f0 += chunk) {
+        batches.launched();
         const long f1 = (f0 + chunk < (long)n_frames) ? f0 + chunk : (long)n_frames;
         Prof p(ctx, "burg_f32_exact");
         launch_burg_f32_exact(ctx->stream, x, f0, f1, (long)n_frames, (int)frame_len, (long)stride, window, (int)n_coeffs, out, status, (float *)w);

@@ -53,6 +53,8 @@ struct vbx_ctx {
     int mfcc_czt = -1;                                    // VBX_MFCC_CZT=0 / 1: never / wherever it fits (tests); -1: the measured choice
     int last_mfcc_interp = 0;                             // the last vbx_mfcc_f64 call took the interpolated form (tests)
     int last_spectral_split = 0;                          // the last fused / pitch call ran as two kernels (tests)
+    long last_batching[2] = {0, 0};                       // {launches, frames per launch} of the host loop that cut the last call's frames into the most launches (batch_count_t; tests)
+    int last_autocorr_long_splits = 0;                    // partial sums per lag of the last long-frame autocorrelation launch, from its scratch size (tests)
     int last_analyze_spec = 0;                            // the instance of the 1200-point fused kernel launch_analyze took: 0 generic, 1 / 2 launch-specialised for f64 / PCM (tests)
     int spectral_spec = 1;                                // VBX_SPECTRAL_SPEC=0: the generic instance of the 1200-point fused kernel everywhere (A/B, tests)
     int last_mfcc_form = 0;                               // which kernel the last vbx_mfcc_f64 call launched: VBX_MFCC_FORM_* below (tests)
@@ -143,6 +145,18 @@ namespace vbx {
 // records msg as the thread's and the context's last error and returns code
 int fail(vbx_ctx *ctx, int code, const std::string &msg);
 int check_launch(vbx_ctx *ctx, const char *what);
+// A host loop that cuts a call's frames into launches of `per` counts them as they happen (vbx_internal_last_batching): launched() once per
+// trip, the record is made when the loop is left, however it is left.  A call that runs several such loops keeps the one with the most
+// launches (the later one of two equals); check_frames clears the record.
+inline void note_batching(vbx_ctx *ctx, long launches, long per) {
+    if (launches > 0 && launches >= ctx->last_batching[0]) { ctx->last_batching[0] = launches; ctx->last_batching[1] = per; }
+}
+struct batch_count_t {
+    vbx_ctx *ctx; long per, n = 0;
+    batch_count_t(vbx_ctx *c, long frames_per_launch) : ctx(c), per(frames_per_launch) {}
+    void launched() { n++; }
+    ~batch_count_t() { note_batching(ctx, n, per); }
+};
 
 #define VBX_HIP(ctx, expr)                                                                     \
     do {                                                                                       \

@@ -256,6 +256,7 @@ struct spectral_launch_t {
     // frames (under burg_window, find_formants' periodic Hanning window) in burg_scratch, tiled as burg_recursion_kernel reads it (launch-local frame
     // index).  Only where spectral_burg_fusable(L) holds.
     double *burg_scratch; const double *burg_window; long burg_f0, burg_nf;
+    long *batching;                                              // non-NULL: the split form counts {its launches of the first kernel, frames per launch} here (host memory; tests)
 };
 bool spectral_burg_fusable(const spectral_launch_t &L);             // launch_analyze would take a launch-specialised instance (k_spectral.hip)
 size_t spectral_split_row_bytes(int n, double sample_rate, double fmin);   // bytes per frame of that scratch, 0: the shape has no split form

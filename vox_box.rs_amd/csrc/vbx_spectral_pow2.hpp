@@ -760,7 +760,9 @@ int launch_pow2_u(hipStream_t s, const spectral_launch_t &L, spectral_args_t &a)
             a.curve = L.curve_ws; a.curve_ld = (long)row_doubles; a.curve_tol = L.curve_ws + cap * row_doubles;
             a.curve_list = reinterpret_cast<int32_t *>(a.curve_tol + cap); a.list_ld = (long)list_ints;
             a.far_list = a.curve_list + cap * list_ints;     // [4 + cap] int32
+            if (L.batching) { L.batching[0] = 0; L.batching[1] = (long)cap; }
             for (long f0 = 0; f0 < L.F; f0 += (long)cap) {
+                if (L.batching) L.batching[0]++;
                 a.f0 = f0; a.n_batch = (L.F - f0 < (long)cap) ? L.F - f0 : (long)cap;
                 const dim3 g((unsigned)a.n_batch);
                 if (full) {

@@ -372,6 +372,8 @@ def load_library():
         "vbx_internal_estimate_formants_counted": (C.c_int, [vp, vp, sz, sz, vp, vp, sz, vp, sz, vp, vp]),
         "vbx_internal_last_roots_direct_count": (C.c_int, [vp, vp]),
         "vbx_internal_last_spectral_split": (C.c_int, [vp]),
+        "vbx_internal_last_batching": (C.c_int, [vp, vp, vp]),
+        "vbx_internal_last_autocorr_long_splits": (C.c_int, [vp]),
         "vbx_internal_last_analyze_spec": (C.c_int, [vp]),
         "vbx_internal_last_mfcc_interp": (C.c_int, [vp]),
         "vbx_internal_last_mfcc_form": (C.c_int, [vp]),
@@ -2218,6 +2220,13 @@ class VoxBox:
         n = C.c_int32(0)
         self._check(self.L.vbx_internal_last_burg_direct_count(self.ctx, C.byref(n)))
         return int(n.value)
+
+    def last_batching(self):
+        """(launches, frames per launch) of the host loop that cut the last frame-batch call's frames into the most launches (test probe);
+        (0, 0) if the call ran no such loop."""
+        b, per = C.c_long(0), C.c_long(0)
+        self._check(self.L.vbx_internal_last_batching(self.ctx, C.byref(b), C.byref(per)))
+        return int(b.value), int(per.value)
 
     def last_lpc_exact_count(self):
         """Frames of the last fused analyze call whose Levinson row the conditioning probe handed to the double-double recursion
