@@ -192,19 +192,10 @@ bool mfcc_interp_fill(int plan, int n, int b_lo, int nb, void *h_table, mfcc_int
     return d->lds_bytes <= cap;
 }
 
-// The whole-Vec candidate list of the 1200-point plan lives in the frame's own output row (launch_analyze below) ...
-// (the parked list is read and written as double2: only where the rows are 16-byte aligned -- cand_ld is even, so the base
-// decides; a caller's vbx_pitch array at 8 mod 16 keeps the list in LDS, the same candidates in the same order)
-bool spectral_list_parked(const spectral_launch_t &L) {
-    const bool rows16 = (((uintptr_t)L.out_cand) & 15) == 0 && (L.cand_ld & 1) == 0;
-    return L.plan == SPECTRAL_PLAN_1200 && pitch_full_list_bytes(L.n, L.kmax) != 0 && L.kmax >= pitch_full_list_entries(L.n) &&
-           L.out_r == nullptr && !L.mfcc_only && rows16;
-}
-
 // The launch-specialised instance (SP_SPEC_*, vbx_spectral.hpp) serves the three-wavefront launch of full f64 / PCM frames with
 // everything it was compiled for in place; every other launch -- and every launch of an experiment build that reads the work
 // pointer or the count early (VBX_EXP_PHASES, VBX_EXP_STOP) -- takes the generic one.  L.allow_spec: the context's
-// VBX_SPECTRAL_SPEC switch (0: the generic one; A/B, tests).  w3, extra: launch_analyze's own three-wavefront decision and LDS list.
+// VBX_SPECTRAL_SPEC switch (0: the generic one; A/B, tests).  w3, extra: choose_analyze's own three-wavefront decision and LDS list.
 static bool spectral_want3() {
     static const bool want3 = [] { const char *e = getenv("VBX_SPECTRAL_W3"); return e == nullptr || atoi(e) != 0; }();
     return want3;
@@ -221,29 +212,78 @@ static int spectral_spec(const spectral_launch_t &L, bool w3, size_t extra) {
 #endif
 }
 
-// Would launch_analyze take a launch-specialised instance for L -- the only ones with a form that leaves Burg's lag sums (BURG)?
-// The same geometry and the same tests as there.
-bool spectral_burg_fusable(const spectral_launch_t &L) {
-    if (L.plan != SPECTRAL_PLAN_1200 || L.n != SP_N || L.mfcc_only || L.out_r != nullptr) return false;
+// THE choice (vbx_kernels.hpp): which instance of which family serves L, with what geometry -- or none (refused).
+analyze_choice_t choose_analyze(const spectral_launch_t &L) {
+    analyze_choice_t c{};
+    c.plan = L.plan; c.sample = L.x.kind; c.burg = L.burg_scratch != nullptr; c.spec = SP_SPEC_NONE;
+    // (PCM / float32: full 1200-sample frames only -- the host side asks for nothing else; Burg's lag sums: launch-specialised instances only)
+    c.refused = L.x.kind != SAMPLE_F64 && (L.plan != SPECTRAL_PLAN_1200 || L.n != SP_N);
+    if (c.refused) return c;
+    if (L.plan != SPECTRAL_PLAN_1200) {
+        if (c.burg) c.refused = true; else c = choose_analyze_pow2(L);
+        return c;
+    }
+    c.family = SP_FAMILY_1200;
     const size_t base = spectral_lds_bytes(L.n);
     size_t extra = pitch_full_list_bytes(L.n, L.kmax);
-    if (spectral_list_parked(L)) extra = 0;
-    const int spec = spectral_spec(L, spectral_want3() && extra == 0 && 12 * (base + extra) <= 160 * 1024, extra);
-    // (PCM frames with MFCC and without LPC: that BURG form spills two registers where the instance it rides on spills none -- such calls keep burg_lags_kernel)
-    if (spec == SP_SPEC_PCM16 && L.out_mfcc != nullptr && L.out_lpc == nullptr) return false;
-    return spec != SP_SPEC_NONE;
+    c.list = extra ? SP_LIST_LDS : SP_LIST_LANES; c.full_off = extra ? (int)base : 0;
+    // kmax = VBX_PITCH_MAX_CANDIDATES(frame_len) (the whole Vec of every frame fits its output row): the refined candidates
+    // are parked in the row itself instead of an extra LDS region, which keeps the frame state at 13.5 KB = twelve
+    // wavefronts per CU (the form compiled for three wavefronts per SIMD, below).  The parked list is read and written as double2: only
+    // where the rows are 16-byte aligned -- cand_ld is even, so the base decides; a caller's vbx_pitch array at 8 mod 16 keeps the list
+    // in LDS, the same candidates in the same order.
+    const bool rows16 = (((uintptr_t)L.out_cand) & 15) == 0 && (L.cand_ld & 1) == 0;
+    if (extra != 0 && L.kmax >= pitch_full_list_entries(L.n) && L.out_r == nullptr && !L.mfcc_only && rows16) { c.list = SP_LIST_PARKED; c.full_off = -1; extra = 0; }
+    c.lds = base + extra;
+    c.lpc = L.out_lpc != nullptr; c.mf = L.out_mfcc != nullptr; c.full = L.n == SP_N; c.waves = VBX_SPECTRAL_WAVES; c.mode = SP_ANALYZE;
+    const bool interp = L.interp && L.n != SP_N;             // a padded frame whose MFCC bins are interpolated from the transform's
+    const size_t lds_ip = ((size_t)L.ip.lds_bytes + 15) & ~(size_t)15;
+    // Three wavefronts per SIMD (twelve frames of 13.5 KB fill the CU's LDS; 168 registers) wherever the frame state allows it,
+    // i.e. no full-list region in LDS.  Round 3 had it for pitch alone from kmax = 2 (the refinement is a chain of dependent
+    // operations that two wavefronts do not cover); at kmax = 1 and in the fused loop the transforms' ~55 spilled registers
+    // cost more than the third wavefront brought.  Round 4: with the twiddle products in pinned batches (twiddle_tight) the
+    // 168-register instances spill 12-29 registers instead of 146-171, and three wavefronts win everywhere: pitch at kmax = 1
+    // 33.7 -> 37.8 M frames/s, the fused loop (the headline) 30.0 -> 33.5 M.  VBX_SPECTRAL_W3=0: two wavefronts as before (A/B).
+    auto waves_for = [&](size_t lds) { return (spectral_want3() && extra == 0 && 12 * lds <= 160 * 1024) ? 3 : VBX_SPECTRAL_WAVES; };
+    if (L.mfcc_only) {                                       // n == SP_N, or a padded frame with interpolated bins
+        c.lpc = false; c.mf = true; c.full = !interp; c.mode = interp ? SP_MFCC_ONLY_INTERP : SP_MFCC_ONLY;
+        c.lds = (interp && (size_t)L.ip.lds_bytes >= spectral_lds_bytes(0)) ? lds_ip : spectral_lds_bytes(0);
+    } else if (L.out_r != nullptr) {                         // autocorrelate(n_lags) alone
+        c.lpc = c.mf = false; c.mode = SP_AC_ONLY; c.lds = spectral_lds_bytes(0);
+    } else if (L.x.kind == SAMPLE_F32) {
+        c.family = SP_FAMILY_F32IN; c.waves = waves_for(c.lds);
+    } else if (const int spec = spectral_spec(L, waves_for(c.lds) == 3, extra); spec != SP_SPEC_NONE) {
+        c.spec = spec; c.waves = 3;
+    } else if (interp && c.mf) {
+        c.mode = SP_ANALYZE_INTERP;
+        if ((size_t)L.ip.lds_bytes >= c.lds) c.lds = lds_ip;
+        c.waves = waves_for(c.lds);
+    } else c.waves = waves_for(c.lds);                       // a full frame, or a padded one: MFCC from the transform's own bins when its length divides 2400
+    c.refused = !sp_1200_instance(c.lpc, c.mf, c.full, c.mode, c.waves, c.spec, c.burg, c.family == SP_FAMILY_F32IN);
+    return c;
 }
 
-int launch_analyze(hipStream_t s, const spectral_launch_t &L, int *launched_spec) {
-    if (launched_spec) *launched_spec = SP_SPEC_NONE;
-    // (PCM / float32: full 1200-sample frames only -- the host side asks for nothing else)
-    if (L.x.kind != SAMPLE_F64 && (L.plan != SPECTRAL_PLAN_1200 || L.n != SP_N)) return -1;
+// Would launch_analyze leave Burg's lag sums (BURG) for L?  The choice's own answer to L with that request.
+bool spectral_burg_fusable(const spectral_launch_t &L) {
+    static double requested;                                 // (any address: the choice reads no memory)
+    spectral_launch_t Q = L;
+    Q.burg_scratch = &requested;
+    return !choose_analyze(Q).refused;
+}
+
+int launch_analyze(hipStream_t s, const spectral_launch_t &L, analyze_choice_t *acted) {
+    analyze_choice_t c = choose_analyze(L);
+    // Burg's lag sums from the frame's own wavefront: frames [burg_f0, burg_f0 + burg_nf) of the batch (refused before anything is launched)
+    if (c.burg && ((((uintptr_t)L.burg_window) & 15) != 0 || L.burg_window == nullptr || L.burg_f0 < 0 || L.burg_nf < 1 || L.burg_f0 + L.burg_nf > L.F)) c.refused = true;
+    if (acted) *acted = c;
+    if (c.refused) return 0;
     spectral_args_t a;
     a.frames = static_cast<const double *>(L.x.p);           // (the kernels take PCM / float32 through the f64 argument: a.pcm says PCM, k_spectral_f32in.hip is compiled for float32)
-    a.n_frames = L.F; a.stride = L.stride; a.window = L.window; a.lag_window = L.lag_window;
+    a.n_frames = c.burg ? L.burg_nf : L.F; a.stride = L.stride; a.window = L.window; a.lag_window = L.lag_window;
     a.tab = reinterpret_cast<const double2 *>(L.tab);
     a.n = L.n;
     a.pp.sample_rate = L.sample_rate; a.pp.threshold = L.threshold; a.pp.fmin = L.fmin; a.pp.fmax = L.fmax; a.pp.kmax = L.kmax; a.pp.f32 = 0;
+    a.pp.full_off = c.full_off; a.pp.ncurve = c.ncurve;
     a.out_cand = reinterpret_cast<double *>(L.out_cand); a.cand_ld = L.cand_ld; a.out_count = L.out_count;
     a.pitch_status = L.pitch_status; a.work = L.work;
     a.out_lpc = L.out_lpc; a.lpc_ld = L.lpc_ld;
@@ -253,100 +293,21 @@ int launch_analyze(hipStream_t s, const spectral_launch_t &L, int *launched_spec
     a.out_r = L.out_r; a.n_lags = L.n_lags;
     a.pcm = (L.x.kind == SAMPLE_PCM16 ? SP_FLAG_PCM : 0) | (L.lag_rcp ? SP_FLAG_LAG_RCP : 0) | ((L.mfcc_defer && L.num_coeffs <= 16) ? SP_FLAG_MFCC_DEFER : 0);
     a.mfcc_q = (L.plan != SPECTRAL_PLAN_NONE && L.n > 0) ? (2 * spectral_plan_nc(L.plan)) / L.n : 2;
-    a.ip = mfcc_interp_t{};
-    a.burg_scratch = nullptr; a.burg_window = nullptr; a.burg_f0 = 0;
-    if (L.burg_scratch != nullptr) {
-        // Burg's lag sums from the frame's own wavefront: frames [burg_f0, burg_f0 + burg_nf) of the batch, launch-specialised instances only
-        // (refused HERE, before any branch below could launch another instance over a narrowed range)
-        if (!spectral_burg_fusable(L) || (((uintptr_t)L.burg_window) & 15) != 0 || L.burg_window == nullptr || L.burg_f0 < 0 || L.burg_nf < 1 || L.burg_f0 + L.burg_nf > L.F) return -1;
-        a.burg_scratch = L.burg_scratch; a.burg_window = L.burg_window; a.burg_f0 = L.burg_f0; a.n_frames = L.burg_nf;
-    }
-    if (L.plan != SPECTRAL_PLAN_1200) return launch_analyze_pow2(s, L, a);
-    const dim3 grid((unsigned)a.n_frames), block(64);
-    const size_t base = spectral_lds_bytes(L.n);
-    size_t extra = pitch_full_list_bytes(L.n, L.kmax);
-    a.pp.full_off = extra ? (int)base : 0;
-    // kmax = VBX_PITCH_MAX_CANDIDATES(frame_len) (the whole Vec of every frame fits its output row): the refined candidates
-    // are parked in the row itself instead of an extra LDS region, which keeps the frame state at 13.5 KB = twelve
-    // wavefronts per CU (the form compiled for three wavefronts per SIMD, below)
-    if (spectral_list_parked(L)) { a.pp.full_off = -1; extra = 0; }
-    const size_t lds = base + extra;
-    const bool lpc = L.out_lpc != nullptr, mf = L.out_mfcc != nullptr;
-    const spectral_args_1200_burg_t a12b(a);                 // (the BURG instances')
-    const spectral_args_1200_t a12(a);                       // the block without the other plans' fields (the interpolated and autocorrelation-only forms take `a`)
-    if (L.mfcc_only) {                                       // n == SP_N, or a padded frame with interpolated bins
-        if (L.interp && L.n != SP_N) {
-            a.ip = L.ip;
-            const size_t li = spectral_lds_bytes(0) > (size_t)L.ip.lds_bytes ? spectral_lds_bytes(0) : (((size_t)L.ip.lds_bytes + 15) & ~(size_t)15);
-            hipLaunchKernelGGL((analyze_kernel<false, true, false, SP_MFCC_ONLY_INTERP>), grid, block, li, s, a);
-        } else hipLaunchKernelGGL((analyze_kernel<false, true, true, SP_MFCC_ONLY>), grid, block, spectral_lds_bytes(0), s, a12);
-        return 0;
-    }
-    if (L.out_r != nullptr) {                                // autocorrelate(n_lags) alone
-        if (L.n == SP_N) hipLaunchKernelGGL((analyze_kernel<false, false, true, SP_AC_ONLY>), grid, block, spectral_lds_bytes(0), s, a);
-        else hipLaunchKernelGGL((analyze_kernel<false, false, false, SP_AC_ONLY>), grid, block, spectral_lds_bytes(0), s, a);
-        return 0;
-    }
-    // Three wavefronts per SIMD (twelve frames of 13.5 KB fill the CU's LDS; 168 registers) wherever the frame state allows it,
-    // i.e. no full-list region in LDS.  Round 3 had it for pitch alone from kmax = 2 (the refinement is a chain of dependent
-    // operations that two wavefronts do not cover); at kmax = 1 and in the fused loop the transforms' ~55 spilled registers
-    // cost more than the third wavefront brought.  Round 4: with the twiddle products in pinned batches (twiddle_tight) the
-    // 168-register instances spill 12-29 registers instead of 146-171, and three wavefronts win everywhere: pitch at kmax = 1
-    // 33.7 -> 37.8 M frames/s, the fused loop (the headline) 30.0 -> 33.5 M.  VBX_SPECTRAL_W3=0: two wavefronts as before (A/B).
-    const bool want3 = spectral_want3();
-    const bool w3 = want3 && extra == 0 && 12 * lds <= 160 * 1024;
-    if (L.x.kind == SAMPLE_F32) {
-        launch_analyze_f32in(s, a12, (unsigned)L.F, lds, lpc, mf, w3);
-        return 0;
-    }
-#define VBX_SP_LAUNCH(LPC_, MF_, FULL_)                                                                              \
-    do {                                                                                                              \
-        if (w3) hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, FULL_, SP_ANALYZE, 3>), grid, block, lds, s, a12);      \
-        else hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, FULL_>), grid, block, lds, s, a12);                        \
-    } while (0)
-#define VBX_SP_LAUNCH_SPEC(LPC_, MF_, SUFFIX_, A_)                                                                                             \
-    do {                                                                                                                                        \
-        if (spec == SP_SPEC_PCM16) hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, true, SP_ANALYZE, 3, sp_launch_pcm16##SUFFIX_>), grid, block, lds, s, A_);   \
-        else hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, true, SP_ANALYZE, 3, sp_launch_f64##SUFFIX_>), grid, block, lds, s, A_);          \
-    } while (0)
-    const int spec = spectral_spec(L, w3, extra);
-    if (L.burg_scratch != nullptr) {
-        if (spec == SP_SPEC_NONE) return -1;                 // (spectral_burg_fusable said otherwise, or was not asked)
-        if (launched_spec) *launched_spec = spec;
-        if (lpc && mf) VBX_SP_LAUNCH_SPEC(true, true, _burg_t, a12b);
-        else if (lpc) VBX_SP_LAUNCH_SPEC(true, false, _burg_t, a12b);
-        else if (mf) hipLaunchKernelGGL((analyze_kernel<false, true, true, SP_ANALYZE, 3, sp_launch_f64_burg_t>), grid, block, lds, s, a12b);   // (f64 only: spectral_burg_fusable)
-        else VBX_SP_LAUNCH_SPEC(false, false, _burg_t, a12b);
-        return 0;
-    }
-    if (spec != SP_SPEC_NONE) {
-        if (launched_spec) *launched_spec = spec;            // (set here, at the branch that launches it)
-        if (lpc && mf) VBX_SP_LAUNCH_SPEC(true, true, _t, a12);
-        else if (lpc) VBX_SP_LAUNCH_SPEC(true, false, _t, a12);
-        else if (mf) VBX_SP_LAUNCH_SPEC(false, true, _t, a12);
-        else VBX_SP_LAUNCH_SPEC(false, false, _t, a12);
-        return 0;
-    }
-    if (L.interp && mf && L.n != SP_N) {                     // a padded frame whose MFCC bins are interpolated from the transform's
-        a.ip = L.ip;
-        const size_t li = lds > (size_t)L.ip.lds_bytes ? lds : (((size_t)L.ip.lds_bytes + 15) & ~(size_t)15);
-        const bool w3i = want3 && extra == 0 && 12 * li <= 160 * 1024;
-        if (lpc) { if (w3i) hipLaunchKernelGGL((analyze_kernel<true, true, false, SP_ANALYZE_INTERP, 3>), grid, block, li, s, a);
-                   else hipLaunchKernelGGL((analyze_kernel<true, true, false, SP_ANALYZE_INTERP>), grid, block, li, s, a); }
-        else { if (w3i) hipLaunchKernelGGL((analyze_kernel<false, true, false, SP_ANALYZE_INTERP, 3>), grid, block, li, s, a);
-               else hipLaunchKernelGGL((analyze_kernel<false, true, false, SP_ANALYZE_INTERP>), grid, block, li, s, a); }
-    } else if (L.n != SP_N) {                                // a padded frame; MFCC from the transform's own bins when its length divides 2400
-        if (lpc && mf) VBX_SP_LAUNCH(true, true, false);
-        else if (mf) VBX_SP_LAUNCH(false, true, false);
-        else if (lpc) VBX_SP_LAUNCH(true, false, false);
-        else VBX_SP_LAUNCH(false, false, false);
-    } else if (lpc && mf) VBX_SP_LAUNCH(true, true, true);
-    else if (lpc) VBX_SP_LAUNCH(true, false, true);
-    else if (mf) VBX_SP_LAUNCH(false, true, true);
-    else VBX_SP_LAUNCH(false, false, true);
-#undef VBX_SP_LAUNCH
-#undef VBX_SP_LAUNCH_SPEC
-    return 0;
+    a.ip = (sp_is_interp(c.mode) || sp_is_split(c.mode)) ? L.ip : mfcc_interp_t{};
+    a.burg_scratch = c.burg ? L.burg_scratch : nullptr; a.burg_window = c.burg ? L.burg_window : nullptr; a.burg_f0 = c.burg ? L.burg_f0 : 0;
+    if (c.family == SP_FAMILY_POW2) return launch_analyze_pow2(s, L, c, a);
+    if (c.family == SP_FAMILY_F32IN) return launch_analyze_f32in(s, c, a) ? 1 : 0;
+    constexpr int W2 = VBX_SPECTRAL_WAVES;
+    const bool w3 = c.waves == 3, pcm = c.spec == SP_SPEC_PCM16;
+    const bool launched =
+        c.mode == SP_MFCC_ONLY_INTERP ? sp_launch_1200<SP_MFCC_ONLY_INTERP, W2, double>(s, c, a) :
+        c.mode == SP_MFCC_ONLY ? sp_launch_1200<SP_MFCC_ONLY, W2, double>(s, c, a) :
+        c.mode == SP_AC_ONLY ? sp_launch_1200<SP_AC_ONLY, W2, double>(s, c, a) :
+        c.mode == SP_ANALYZE_INTERP ? (w3 ? sp_launch_1200<SP_ANALYZE_INTERP, 3, double>(s, c, a) : sp_launch_1200<SP_ANALYZE_INTERP, W2, double>(s, c, a)) :
+        c.burg ? (pcm ? sp_launch_1200<SP_ANALYZE, 3, sp_launch_pcm16_burg_t>(s, c, a) : sp_launch_1200<SP_ANALYZE, 3, sp_launch_f64_burg_t>(s, c, a)) :
+        c.spec != SP_SPEC_NONE ? (pcm ? sp_launch_1200<SP_ANALYZE, 3, sp_launch_pcm16_t>(s, c, a) : sp_launch_1200<SP_ANALYZE, 3, sp_launch_f64_t>(s, c, a)) :
+        w3 ? sp_launch_1200<SP_ANALYZE, 3, double>(s, c, a) : sp_launch_1200<SP_ANALYZE, W2, double>(s, c, a);
+    return launched ? 1 : 0;
 }
 
 }  // namespace vbx

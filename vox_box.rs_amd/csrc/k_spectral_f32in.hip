@@ -8,18 +8,8 @@
 
 namespace vbx {
 
-void launch_analyze_f32in(hipStream_t s, const spectral_args_1200_t &a, unsigned grid, size_t lds, bool lpc, bool mfcc, bool waves3) {
-    const dim3 g(grid), b(64);
-#define VBX_SP32_LAUNCH(LPC_, MF_)                                                                                \
-    do {                                                                                                           \
-        if (waves3) hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, true, SP_ANALYZE, 3, float>), g, b, lds, s, a);                     \
-        else hipLaunchKernelGGL((analyze_kernel<LPC_, MF_, true, SP_ANALYZE, VBX_SPECTRAL_WAVES, float>), g, b, lds, s, a);           \
-    } while (0)
-    if (lpc && mfcc) VBX_SP32_LAUNCH(true, true);
-    else if (lpc) VBX_SP32_LAUNCH(true, false);
-    else if (mfcc) VBX_SP32_LAUNCH(false, true);
-    else VBX_SP32_LAUNCH(false, false);
-#undef VBX_SP32_LAUNCH
+bool launch_analyze_f32in(hipStream_t s, const analyze_choice_t &c, const spectral_args_t &a) {
+    return c.waves == 3 ? sp_launch_1200<SP_ANALYZE, 3, float>(s, c, a) : sp_launch_1200<SP_ANALYZE, VBX_SPECTRAL_WAVES, float>(s, c, a);
 }
 
 }  // namespace vbx

@@ -117,22 +117,17 @@ void launch_refine_curve(hipStream_t s, const spectral_args_t &a, size_t lds_sca
     hipLaunchKernelGGL(refine_far_kernel, dim3(gf), dim3(64), lds_scan, s, a);
 }
 
-// bytes per frame of the scratch between the kernels (the cut curve + its zeros, one tolerance, the candidate list), 0 where there is no split form
-size_t spectral_split_row_bytes(int n, double sample_rate, double fmin) {
-    if (spectral_plan(n) != SPECTRAL_PLAN_4096) return 0;
-    int nst = pitch_curve_entries(n, sample_rate, fmin);
-    const int reach = pitch_curve_reach(n, sample_rate, fmin);
-    if (nst <= 0 && (n & 1)) nst = n + 1;                    // an odd length's whole curve
-    if (nst <= 0 || reach <= 0) return 0;
-    return (size_t)(nst + Y_PAD + 1) * sizeof(double) + (spectral_split_list_ints(reach) + 1) * sizeof(int32_t) + 16;    // (+ far_list: one index per frame, the count)
+#define VBX_POW2_UNIT(U_)                                                                                                  \
+    analyze_choice_t choose_pow2_##U_(const spectral_launch_t &L);                                                         \
+    int launch_pow2_##U_(hipStream_t s, const spectral_launch_t &L, const analyze_choice_t &c, spectral_args_t &a);
+VBX_POW2_UNIT(u1) VBX_POW2_UNIT(u2) VBX_POW2_UNIT(u4)
+#undef VBX_POW2_UNIT
+
+analyze_choice_t choose_analyze_pow2(const spectral_launch_t &L) {
+    return L.plan == SPECTRAL_PLAN_1024 ? choose_pow2_u1(L) : L.plan == SPECTRAL_PLAN_2048 ? choose_pow2_u2(L) : choose_pow2_u4(L);
 }
-
-int launch_pow2_u1(hipStream_t s, const spectral_launch_t &L, spectral_args_t &a);
-int launch_pow2_u2(hipStream_t s, const spectral_launch_t &L, spectral_args_t &a);
-int launch_pow2_u4(hipStream_t s, const spectral_launch_t &L, spectral_args_t &a);
-
-int launch_analyze_pow2(hipStream_t s, const spectral_launch_t &L, spectral_args_t &a) {
-    return L.plan == SPECTRAL_PLAN_1024 ? launch_pow2_u1(s, L, a) : L.plan == SPECTRAL_PLAN_2048 ? launch_pow2_u2(s, L, a) : launch_pow2_u4(s, L, a);
+int launch_analyze_pow2(hipStream_t s, const spectral_launch_t &L, const analyze_choice_t &c, spectral_args_t &a) {
+    return L.plan == SPECTRAL_PLAN_1024 ? launch_pow2_u1(s, L, c, a) : L.plan == SPECTRAL_PLAN_2048 ? launch_pow2_u2(s, L, c, a) : launch_pow2_u4(s, L, c, a);
 }
 
 }  // namespace vbx

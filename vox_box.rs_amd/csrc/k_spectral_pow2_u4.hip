@@ -3,6 +3,7 @@
 
 namespace vbx {
 
-int launch_pow2_u4(hipStream_t s, const spectral_launch_t &L, spectral_args_t &a) { return launch_pow2_u<2, 2>(s, L, a); }
+analyze_choice_t choose_pow2_u4(const spectral_launch_t &L) { return choose_pow2_u<2, 2>(L); }
+int launch_pow2_u4(hipStream_t s, const spectral_launch_t &L, const analyze_choice_t &c, spectral_args_t &a) { return launch_pow2_u<2, 2>(s, L, c, a); }
 
 }  // namespace vbx

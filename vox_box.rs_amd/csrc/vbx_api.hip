@@ -524,13 +524,14 @@ int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, const ch
         VBX_HIP(ctx, hipMemsetAsync(L.lpc_count, 0, sizeof(int32_t), st));
         ctx->lpc_list_armed = true;
     }
-    // the 4096-point plan runs as two kernels with the lag curves in a scratch buffer between them (vbx_spectral.hpp, SP_ANALYZE_SPLIT):
-    // batches of a little over 131,072 frames (~10 KB each; the scratch grants 16 bytes a frame more than launch_pow2_u divides it by: 131,193 at 4096 samples)
+    spectral_launch_choices(ctx, L);
+    // the 4096-point plan runs as two kernels with the lag curves in a scratch buffer between them (vbx_spectral.hpp, SP_ANALYZE_SPLIT), in
+    // batches of a little over SPECTRAL_SPLIT_FRAMES frames (~10 KB each; the choice's bytes per frame grant 16 more than it divides the scratch by: 131,193 at 4096 samples).
+    // Whether the shape splits at all, and its bytes per frame, are the choice's own answer (a list region in LDS, kmax > 64: the fused kernel).
     L.curve_ws = nullptr; L.curve_ws_bytes = 0;
-    const size_t rowb = (ctx->pow2_split != 0 && !L.whole_curve && !L.mfcc_only && L.out_r == nullptr && pitch_full_list_bytes(L.n, L.kmax) == 0)
-                            ? spectral_split_row_bytes(L.n, L.sample_rate, L.fmin) : 0;      // (a list region in LDS, kmax > 64: the fused kernel)
+    const size_t rowb = ctx->pow2_split != 0 ? choose_analyze(L).split_row_bytes : 0;
     if (rowb) {
-        const size_t frames = (size_t)L.F < 131072 ? (size_t)L.F : 131072;
+        const size_t frames = L.F < SPECTRAL_SPLIT_FRAMES ? (size_t)L.F : (size_t)SPECTRAL_SPLIT_FRAMES;
         const size_t need = (frames < 1024 ? 1024 : frames) * rowb + 64;
         void *cw = nullptr;
         // (no memory for it: the fused form.  A size that failed once is not asked for again on every call -- each attempt drains the
@@ -541,30 +542,32 @@ int launch_spectral(vbx_ctx *ctx, hipStream_t st, spectral_launch_t &L, const ch
             else { (void)hipGetLastError(); ctx->curve_failed_bytes = need; ctx->last_error = before; g_last_error = before; }
         }
     }
-    spectral_launch_choices(ctx, L);
-    ctx->last_analyze_spec = 0;
-    long split_batching[2] = {0, 0};
-    L.batching = split_batching;
-    if (rg == nullptr) { Prof p(ctx, prof_name, st); ctx->last_spectral_split = launch_analyze(st, L, &ctx->last_analyze_spec); }
+    analyze_choice_t acted{};
+    int launches = 0;
+    // what the launch did, for the probes (vbx_internal_last_*; vbx_pitch_f64's last_pitch_form: run_pitch, from the same choice)
+    auto record = [&] {
+        const bool split = !acted.refused && acted.per_launch > 0;       // (SP_ANALYZE_SPLIT / _INTERP_SPLIT: the only forms with batches)
+        ctx->last_spectral_split = split ? 1 : 0;
+        ctx->last_analyze_spec = acted.refused ? 0 : acted.spec;
+        note_batching(ctx, split ? launches : 0, acted.per_launch);
+    };
+    if (rg == nullptr) { Prof p(ctx, prof_name, st); launches = launch_analyze(st, L, &acted); }
     else {
         // the same kernel in launches of rg->launch_frames frames, each leaving Burg's lag sums of its frames for the side stream
-        ctx->last_spectral_split = 0;
         int j = 0;
         for (long f0 = 0; f0 < L.F; f0 += rg->launch_frames, j++) {
             const long nf = (L.F - f0 < rg->launch_frames) ? L.F - f0 : rg->launch_frames;
             rc = rg->before(j);
             if (rc != VBX_SUCCESS) return rc;
             L.burg_scratch = rg->scratch[j & 1]; L.burg_window = rg->burg_window; L.burg_f0 = f0; L.burg_nf = nf;
-            int launched;
-            { Prof p(ctx, prof_name, st); launched = launch_analyze(st, L, &ctx->last_analyze_spec); }
+            { Prof p(ctx, prof_name, st); launch_analyze(st, L, &acted); }
             L.burg_scratch = nullptr;
-            if (launched < 0) return fail(ctx, VBX_E_RUNTIME, "launch_spectral: no instance of the fused kernel leaves Burg's lag sums for this launch");
+            if (acted.refused) { record(); return fail(ctx, VBX_E_RUNTIME, "launch_spectral: no instance of the fused kernel leaves Burg's lag sums for this launch"); }
             rc = rg->after(j, f0, nf);
             if (rc != VBX_SUCCESS) return rc;
         }
     }
-    L.batching = nullptr;
-    note_batching(ctx, split_batching[0], split_batching[1]);
+    record();
     if (L.mfcc_defer && L.out_lpc == nullptr) { Prof p(ctx, "mfcc_rows", st); launch_mfcc_rows(st, L.out_mfcc, L.F, L.mfcc_ld, L.num_coeffs, L.dct); }
     {
         Prof p(ctx, "pitch_direct_fallback", st);
@@ -661,7 +664,7 @@ int run_pitch(vbx_ctx *ctx, hipStream_t st, const double *x, size_t n_frames, si
         L.whole_curve = ctx->pitch_whole_curve;
         L.out_cand = (pitch_t *)out_cand; L.cand_ld = (long)cand_ld; L.out_count = out_count; L.pitch_status = status;
         L.work = ctx->prof ? ctx->pitch_work : nullptr;
-        ctx->last_pitch_form = 100 * (3 + L.plan) + (pitch_full_list_bytes(L.n, L.kmax) == 0 ? 0 : spectral_list_parked(L) ? 2 : 1);
+        ctx->last_pitch_form = 100 * (3 + L.plan) + choose_analyze(L).list;      // (SP_LIST_*: 0 the lanes, 1 LDS, 2 the output row)
         return launch_spectral(ctx, st, L, "pitch");
     }
     {
@@ -1325,6 +1328,49 @@ int vbx_internal_last_mfcc_interp(vbx_ctx *ctx) { return ctx ? ctx->last_mfcc_in
 // + the candidate list (0 lane-resident, 1 LDS-resident, 2 parked in the output row).
 int vbx_internal_last_mfcc_form(vbx_ctx *ctx) { return ctx ? ctx->last_mfcc_form : 0; }
 int vbx_internal_last_pitch_form(vbx_ctx *ctx) { return ctx ? ctx->last_pitch_form : 0; }
+
+// Host only (no device, no context): what choose_analyze answers for a launch described in plain numbers (tests).
+// ip[18] = {n, sample kind (SAMPLE_*), kmax, LPC on, MFCC coefficients, nb, b_lo, interp, mfcc_defer, allow_spec, lag_rcp, whole_curve,
+// candidate base 16-byte aligned, cand_ld odd, mode (0 the analysis, 1 MFCC alone, 2 autocorrelation alone), n_lags, curve_ws_bytes,
+// BURG requested}; dp[2] = {sample rate, fmin}.  The plan is the one the callers take (spectral_plan_mfcc where MFCC joins or is
+// interpolated, spectral_plan otherwise; MFCC alone of 2048 / 2400 / 4096 samples: the half-size transform).  out[24] = {refused, family, plan,
+// lpc, mf, full, mode, waves, sample, spec, burg, list, full_off, lds, lds_scan, lds_refine, ncurve, reach, cand_cap, row_doubles,
+// list_ints, per_launch, split_row_bytes, spectral_burg_fusable(L)}.
+int vbx_internal_analyze_choice(const int64_t *ip, const double *dp, int64_t *out) {
+    if (!ip || !dp || !out || ip[0] < 2 || ip[0] > 0x3fffffff || ip[1] < 0 || ip[1] > SAMPLE_F32) return VBX_E_INVALID;
+    alignas(16) static double somewhere[4];                  // (addresses the choice compares with NULL or takes the low bits of: it reads no memory)
+    spectral_launch_t L{};
+    L.n = (int)ip[0]; L.x = frames_t(somewhere, (sample_kind_t)ip[1]); L.kmax = (int)ip[2]; L.num_coeffs = (int)ip[4]; L.nb = (int)ip[5];
+    const int mode = (int)ip[14];
+    L.interp = ip[7] != 0; L.mfcc_defer = ip[8] != 0; L.allow_spec = ip[9] != 0; L.lag_rcp = ip[10] != 0; L.whole_curve = ip[11] != 0;
+    L.mfcc_only = mode == 1;
+    L.plan = spectral_plan(L.n);
+    if (L.mfcc_only && !L.interp && (L.n == 2048 || L.n == 2400 || L.n == 4096)) L.plan = L.n == 2048 ? SPECTRAL_PLAN_1024 : L.n == 2400 ? SPECTRAL_PLAN_1200 : SPECTRAL_PLAN_2048;
+    else if (L.num_coeffs != 0 && (L.interp || spectral_supported_plan(spectral_plan_mfcc(L.n), L.n, 0, L.nb, (int)ip[6], L.num_coeffs))) L.plan = spectral_plan_mfcc(L.n);
+    if (L.plan == SPECTRAL_PLAN_NONE) {                      // (no transform serves the length: the callers never reach launch_analyze)
+        std::memset(out, 0, 24 * sizeof(int64_t));
+        out[0] = 1;
+        return VBX_SUCCESS;
+    }
+    if (L.interp) {
+        std::vector<char> h(mfcc_interp_table_bytes(L.plan, L.nb), 0);
+        if (!mfcc_interp_fill(L.plan, L.n, (int)ip[6], L.nb, h.data(), &L.ip)) return VBX_E_INVALID;
+    }
+    L.F = 1; L.sample_rate = dp[0]; L.fmin = dp[1];
+    L.out_cand = reinterpret_cast<pitch_t *>(reinterpret_cast<char *>(somewhere) + (ip[12] ? 0 : 8)); L.cand_ld = 2 * (long)L.kmax + (ip[13] ? 1 : 0);
+    if (mode == 0 && ip[3]) L.out_lpc = somewhere;
+    if (mode != 2 && L.num_coeffs != 0) L.out_mfcc = somewhere;
+    if (mode == 2) { L.out_r = somewhere; L.n_lags = (int)ip[15]; }
+    if (ip[16] > 0) { L.curve_ws = somewhere; L.curve_ws_bytes = (size_t)ip[16]; }
+    const bool fusable = spectral_burg_fusable(L);
+    if (ip[17]) { L.burg_scratch = somewhere; L.burg_window = somewhere; L.burg_nf = 1; }
+    const analyze_choice_t c = choose_analyze(L);
+    const int64_t v[24] = {c.refused, c.family, c.plan, c.lpc, c.mf, c.full, c.mode, c.waves, c.sample, c.spec, c.burg, c.list, c.full_off,
+                           (int64_t)c.lds, (int64_t)c.lds_scan, (int64_t)c.lds_refine, c.ncurve, c.reach, c.cand_cap, (int64_t)c.row_doubles,
+                           (int64_t)c.list_ints, c.per_launch, (int64_t)c.split_row_bytes, fusable};
+    std::memcpy(out, v, sizeof v);
+    return VBX_SUCCESS;
+}
 
 // Host only (no device, no context): the tables of the MFCC bins interpolated inside the fused kernel (mfcc_interp_t) for one shape,
 // for tests that hold the interpolation to the frame's exact DFT.  desc[8] = {M, threads per frame, slots, taps, jmin, jmax,

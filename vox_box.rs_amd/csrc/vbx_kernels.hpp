@@ -256,15 +256,30 @@ struct spectral_launch_t {
     // frames (under burg_window, find_formants' periodic Hanning window) in burg_scratch, tiled as burg_recursion_kernel reads it (launch-local frame
     // index).  Only where spectral_burg_fusable(L) holds.
     double *burg_scratch; const double *burg_window; long burg_f0, burg_nf;
-    long *batching;                                              // non-NULL: the split form counts {its launches of the first kernel, frames per launch} here (host memory; tests)
 };
-bool spectral_burg_fusable(const spectral_launch_t &L);             // launch_analyze would take a launch-specialised instance (k_spectral.hip)
-size_t spectral_split_row_bytes(int n, double sample_rate, double fmin);   // bytes per frame of that scratch, 0: the shape has no split form
+// What launch_analyze launches for L, decided in ONE place (choose_analyze: k_spectral.hip for the 1200-point kernel and its float32
+// unit, vbx_spectral_pow2.hpp for the power-of-two kernels) and read by everything that needs to know: the launch itself, the
+// scratch launch_spectral sizes, spectral_burg_fusable, the probes (vbx_internal_last_*, vbx_internal_analyze_choice).
+enum { SP_FAMILY_1200 = 0, SP_FAMILY_F32IN = 1, SP_FAMILY_POW2 = 2 };
+enum { SP_LIST_LANES = 0, SP_LIST_LDS = 1, SP_LIST_PARKED = 2 };   // the candidates stay in the lanes (no whole-Vec list) / the list's own LDS region / the frame's output row
+constexpr long SPECTRAL_SPLIT_FRAMES = 131072;                  // frames per launch launch_spectral sizes the split form's scratch for
+struct analyze_choice_t {
+    bool refused;                                                // no instance serves L: nothing is launched
+    int family, plan;                                            // SP_FAMILY_*, SPECTRAL_PLAN_*
+    bool lpc, mf, full; int mode;                                // the instance's LPC, MFCC, FULL and MODE (SP_ANALYZE, .., vbx_spectral.hpp)
+    int waves;                                                   // wavefronts per SIMD it is compiled for
+    int sample, spec; bool burg;                                 // SAMPLE_*, SP_SPEC_*, and whether it also leaves Burg's lag sums
+    int list, full_off;                                          // SP_LIST_*, pitch_params_t::full_off
+    size_t lds, lds_scan, lds_refine;                            // dynamic LDS of the (first) kernel; split form: of refine_far_kernel and refine_list_kernel
+    int ncurve;                                                  // lags of the curve the refinement keeps (0: all)
+    int reach, cand_cap; size_t row_doubles, list_ints; long per_launch;      // split form: the scratch row, the candidate list, frames per launch
+    size_t split_row_bytes;                                      // scratch bytes per frame with which the shape WOULD split (0: never; launch_spectral sizes WS_CURVE)
+};
+analyze_choice_t choose_analyze(const spectral_launch_t &L);       // reads L alone: no HIP call, no context
+bool spectral_burg_fusable(const spectral_launch_t &L);             // choose_analyze with a BURG request: some instance leaves Burg's lag sums for L
 bool spectral_supported(int n, int lpc_order, int mfcc_nb, int mfcc_b_lo, int num_coeffs);
-bool spectral_list_parked(const spectral_launch_t &L);              // the whole-Vec list goes to the output row, not to LDS
-// 1: the call ran as two kernels (SP_ANALYZE_SPLIT), 0: one.  *launched_spec: which instance of the 1200-point fused kernel was launched -- 0 the generic
-// one, 1 / 2 the one compiled for this launch's uniform choices on f64 / 16-bit PCM samples (SP_SPEC_*, vbx_spectral.hpp); written at the launch itself
-int launch_analyze(hipStream_t s, const spectral_launch_t &L, int *launched_spec = nullptr);
+// choose, fill the argument block, launch: returns the launches of the (first) kernel it made -- 0: refused -- and, in *acted, the choice it acted on
+int launch_analyze(hipStream_t s, const spectral_launch_t &L, analyze_choice_t *acted = nullptr);
 // k_lpc_exact.hip: LPC::lpc(p) of the listed frames from double-double lag sums and a double-double recursion (the exact
 // answer rounded once), over a list only the device knows the length of
 // k_mfcc.hip: log10 (clamped at 1e-10) + DCT of rows of mel filter sums, in place, a lane per row (the deferred tail of MFCC::mfcc, vbx_mfcc_tail.hpp)

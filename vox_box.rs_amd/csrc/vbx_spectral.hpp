@@ -4,6 +4,8 @@
 // Levinson recursion.
 #pragma once
 
+#include <type_traits>
+#include <utility>
 #include "vbx_device.hpp"
 #include "vbx_kernels.hpp"
 #include "vbx_pitch_refine.hpp"
@@ -122,7 +124,7 @@ __host__ __device__ constexpr bool sp_wide_args(int mode) { return mode == SP_AC
 // only the frame's last stores need (the candidate rows, their leading dimension, the count, status and work pointers) from the
 // argument segment where they are used: one scalar load there instead of registers -- or lanes of the spill register -- held
 // across the refinement.  Every floating-point operation is the generic instance's, in its order: the records keep every bit
-// (tests/test_gpu_analyze_launch_variants.py).  spectral_spec (k_spectral.hip) is the launch's choice, made inside launch_analyze.
+// (tests/test_gpu_analyze_launch_variants.py).  spectral_spec (k_spectral.hip) is the launch's choice, part of choose_analyze.
 constexpr int SP_SPEC_NONE = 0, SP_SPEC_F64 = 1, SP_SPEC_PCM16 = 2;
 // what analyze_kernel's TIN says in a launch-specialised instance: the sample type AND that the launch's choices are compiled in
 // (the kernel's name stays analyze_kernel<LPC, MFCC, FULL, SP_ANALYZE, 3, ...>: tools and the benchmark find it by that prefix)
@@ -204,10 +206,23 @@ constexpr int SP_BURG_P = SPECTRAL_BURG_ORDER;                                //
 // row per LANE, in place -- the same operations in the same order (bit-identical rows), 64 x fewer instructions, and the
 // conditioning probe + double-double redo of ill-conditioned rows (k_lpc_exact.hip) ride on that kernel for nothing.
 
-// k_spectral_pow2.hip
-// k_spectral_f32in.hip: the fused analysis of full 1200-sample frames whose samples are float32 (a.frames carries the float pointer);
-// launch_analyze calls it with the geometry it worked out for the f64 form
-void launch_analyze_f32in(hipStream_t s, const spectral_args_1200_t &a, unsigned grid, size_t lds, bool lpc, bool mfcc, bool waves3);
-int launch_analyze_pow2(hipStream_t s, const spectral_launch_t &L, spectral_args_t &a);      // 1: ran in the split form
+// The instance's LPC / MFCC / FULL flags, from run-time values to template arguments, ONCE for every family: f(lpc, mf, full) with three
+// std::bool_constant's.  f launches the instance where the family's constexpr predicate (sp_1200_instance, pow2_instance) says it
+// exists -- so that exactly those are compiled -- and says whether it did.
+template <typename F>
+inline bool sp_with_flags(bool lpc, bool mf, bool full, F &&f) {
+    auto with_full = [&](auto l, auto m) { return full ? f(l, m, std::true_type{}) : f(l, m, std::false_type{}); };
+    auto with_mf = [&](auto l) { return mf ? with_full(l, std::true_type{}) : with_full(l, std::false_type{}); };
+    return lpc ? with_mf(std::true_type{}) : with_mf(std::false_type{});
+}
+// ... and the mode: f(std::integral_constant<int, M>) for the one M of the list that c's mode is
+template <int... M, typename F>
+inline bool sp_with_mode(int mode, std::integer_sequence<int, M...>, F &&f) { return ((mode == M && f(std::integral_constant<int, M>{})) || ...); }
+
+// k_spectral_f32in.hip: the float32 instances of the 1200-point kernel (c.family == SP_FAMILY_F32IN), launched from launch_analyze's choice and argument block
+bool launch_analyze_f32in(hipStream_t s, const analyze_choice_t &c, const spectral_args_t &a);
+// k_spectral_pow2.hip and its units: the power-of-two kernels' choice and launch (c from choose_analyze_pow2); returns the launches of the first kernel
+analyze_choice_t choose_analyze_pow2(const spectral_launch_t &L);
+int launch_analyze_pow2(hipStream_t s, const spectral_launch_t &L, const analyze_choice_t &c, spectral_args_t &a);
 
 }  // namespace vbx

@@ -795,4 +795,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sp_is_mfcc_o
 #undef VBX_SP_PCM_IN
 #undef VBX_SP_LAG_RCP
 
+// Which instances of analyze_kernel exist, beside the (MODE, WAVES, TIN) its launchers name: the flags each form admits.  choose_analyze
+// (k_spectral.hip) asks it at run time -- a choice it rejects is a refusal --, sp_launch_1200 at compile time -- nothing else is compiled.
+__host__ __device__ constexpr bool sp_1200_instance(bool lpc, bool mf, bool full, int mode, int waves, int spec, bool burg, bool f32) {
+    if (f32 || spec != SP_SPEC_NONE || burg) {
+        if (mode != SP_ANALYZE || !full || (!f32 && waves != 3) || (burg && spec == SP_SPEC_NONE)) return false;
+        // (PCM frames with MFCC and without LPC: that BURG form spills two registers where the instance it rides on spills none -- such calls keep burg_lags_kernel)
+        return !(burg && spec == SP_SPEC_PCM16 && mf && !lpc);
+    }
+    return mode == SP_ANALYZE ? true : mode == SP_ANALYZE_INTERP ? (mf && !full) : waves != VBX_SPECTRAL_WAVES ? false :
+           mode == SP_MFCC_ONLY ? (!lpc && mf && full) : mode == SP_MFCC_ONLY_INTERP ? (!lpc && mf && !full) : mode == SP_AC_ONLY ? (!lpc && !mf) : false;
+}
+// the one launch site of analyze_kernel: the flags from the choice, the instance's own argument block from the whole one
+template <int MODE, int WAVES, typename TIN>
+inline bool sp_launch_1200(hipStream_t s, const analyze_choice_t &c, const spectral_args_t &a) {
+    return sp_with_flags(c.lpc, c.mf, c.full, [&](auto lpc, auto mf, auto full) {
+        constexpr bool LPC = decltype(lpc)::value, MF = decltype(mf)::value, FULL = decltype(full)::value;
+        if constexpr (sp_1200_instance(LPC, MF, FULL, MODE, WAVES, sp_spec_of<TIN>(), sp_burg_of<TIN>(), std::is_same<TIN, float>::value)) {
+            const sp_args_of<MODE, TIN> block(a);
+            hipLaunchKernelGGL((analyze_kernel<LPC, MF, FULL, MODE, WAVES, TIN>), dim3((unsigned)a.n_frames), dim3(64), c.lds, s, block);
+            return true;
+        } else return false;
+    });
+}
+
 }  // namespace vbx

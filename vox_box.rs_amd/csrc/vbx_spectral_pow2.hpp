@@ -318,8 +318,12 @@ __device__ __forceinline__ void fft_pow2(double (&re)[U][16], double (&im)[U][16
 // INTERP modes -- by interpolated bins).
 // MODE (vbx_spectral.hpp): SP_ANALYZE the fused analysis; SP_MFCC_ONLY MFCC::mfcc alone (the forward transform and the mel / DCT
 // tail only); SP_AC_ONLY Autocorrelate::autocorrelate alone (both transforms, the fold seed, the lag sums stored).
+// wavefronts per SIMD an instance is compiled for (at least; the attribute's second value, below, is the most)
+__host__ __device__ constexpr int pow2_waves_per_simd(int U, int W, int MODE) {
+    return (U == 1 && W == 1 && sp_is_analyze(MODE)) ? VBX_POW2_U1_WAVES : U == 4 ? 1 : (U == 2 && !sp_is_mfcc_only(MODE)) ? VBX_POW2_U2_WAVES : 2;
+}
 template <int U, bool LPC, bool MFCC, bool FULL, int MODE = SP_ANALYZE, int W = 1>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu((U == 1 && W == 1 && sp_is_analyze(MODE)) ? VBX_POW2_U1_WAVES : U == 4 ? 1 : (U == 2 && !sp_is_mfcc_only(MODE)) ? VBX_POW2_U2_WAVES : 2,
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(pow2_waves_per_simd(U, W, MODE),
                                                                      (U == 1 && W == 1 && sp_is_analyze(MODE)) ? VBX_POW2_U1_WAVES : U == 4 ? (!sp_is_mfcc_only(MODE) ? 1 : 2) : !sp_is_mfcc_only(MODE) ? 2 : 4)))
 void analyze_pow2_kernel(const spectral_args_t a) {
     // pinned twiddle batches where registers are short: Nc = 1024 at three wavefronts per SIMD, Nc = 2048 at two
@@ -703,102 +707,107 @@ void launch_refine_curve(hipStream_t s, const spectral_args_t &a, size_t lds_sca
 inline int spectral_split_cand_cap(int reach) { return ((reach / 4 + 8) + 7) & ~7; }
 inline size_t spectral_split_list_ints(int reach) { return (size_t)(1 + (spectral_split_cand_cap(reach) + 1) / 2 + 1) & ~(size_t)1; }
 
-// returns 1 when the call ran in the split form, 0 fused
-template <int U, int W = 1>
-int launch_pow2_u(hipStream_t s, const spectral_launch_t &L, spectral_args_t &a) {
-    const dim3 grid((unsigned)L.F), block(64 * W);
-    a.f0 = 0; a.n_batch = L.F; a.curve = nullptr; a.curve_ld = 0; a.curve_tol = nullptr; a.curve_list = nullptr; a.list_ld = 0; a.reach = 0; a.cand_cap = 0; a.far_list = nullptr;
-    a.pp.ncurve = (!L.whole_curve && L.out_r == nullptr && !L.mfcc_only) ? pitch_curve_entries(L.n, L.sample_rate, L.fmin) : 0;
-    const size_t base = pow2_lds_bytes<U, W>(L.n, L.nb, a.pp.ncurve), extra = pitch_full_list_bytes(L.n, L.kmax);
-    a.pp.full_off = extra ? (int)base : 0;
-    const size_t lds = base + extra;
-    const size_t lds_mfcc = pow2_lds_bytes<U, W>(0, L.nb), lds_ac = pow2_lds_bytes<U, W>(0, 0);
-    constexpr int NC = pow2_geom<U, W>::NC;
-    const bool lpc = L.out_lpc != nullptr, mf = L.out_mfcc != nullptr;
-    if (L.mfcc_only) {                                       // n == Nc, or (L.n == 2 Nc) the unpadded form
-        if (L.n == 2 * NC) {
-            if constexpr (U * W <= 2) hipLaunchKernelGGL((analyze_pow2_kernel<U, false, true, true, SP_MFCC_HALF, W>), grid, block, lds_mfcc, s, a);
-        } else if (L.interp && L.n != NC) {                  // a padded frame with interpolated bins
-            a.ip = L.ip;
-            const size_t li = lds_mfcc > (size_t)L.ip.lds_bytes ? lds_mfcc : (((size_t)L.ip.lds_bytes + 15) & ~(size_t)15);
-            hipLaunchKernelGGL((analyze_pow2_kernel<U, false, true, false, SP_MFCC_ONLY_INTERP, W>), grid, block, li, s, a);
-        } else hipLaunchKernelGGL((analyze_pow2_kernel<U, false, true, true, SP_MFCC_ONLY, W>), grid, block, lds_mfcc, s, a);
-        return 0;
-    }
-    if (L.out_r != nullptr) {                                // autocorrelate(n_lags) alone
-        if (L.n == NC) hipLaunchKernelGGL((analyze_pow2_kernel<U, false, false, true, SP_AC_ONLY, W>), grid, block, lds_ac, s, a);
-        else hipLaunchKernelGGL((analyze_pow2_kernel<U, false, false, false, SP_AC_ONLY, W>), grid, block, lds_ac, s, a);
-        return 0;
-    }
-    // The 4096-point plan in separate kernels (vbx_spectral.hpp, SP_ANALYZE_SPLIT; k_spectral_pow2.hip): transforms + LPC + MFCC per batch of
-    // frames, the lag curves through a scratch buffer, then the peak scan, the refinement at eleven frames per CU, the far frames.  Where the curve is cut (an even frame length at speech settings),
-    // the caller gave scratch and kmax needs no list region in LDS.
-    if constexpr (U * W == 4) {
-        // an odd frame length keeps its whole curve (a.pp.ncurve == 0: pitch_curve_entries) -- in the scratch row too, for the whole-curve
-        // kernel of the far frames; the scan and the refinement kernel need no more of it than of an even length's
-        const bool odd_ok = (L.n & 1) && !L.whole_curve && L.out_r == nullptr && !L.mfcc_only;
-        const int nst_row = a.pp.ncurve > 0 ? a.pp.ncurve : (odd_ok ? L.n + 1 : 0);
-        const size_t row_doubles = (size_t)(nst_row + Y_PAD);
-        const bool full = L.n == NC;
-        // Measured (tools/experiments/split_check.py, 2 h of audio per step, pipeline M frames/s fused -> split, all bit-identical):
-        // 2050 / 1024: 11.7 -> 13.3, 2500 / 1000: 11.1 -> 12.5, 3000 / 1200: 10.8 -> 11.9, 4000 / 2000: 9.3 -> 10.2, 4096 / 2048: 11.2 -> 12.1,
-        // 4096 / 1024: 11.3 -> 12.5; pitch at kmax = 8 (40,000 frames): 13.9 -> 9.1 ms.  Per frame at 4096 / 2048: transforms 37.3 ns,
-        // scan 4.3, refinement 21.0 (eleven frames per CU), far frames 2.1 -- against 69 ns fused.  (A first form without the scan kernel
-        // -- the whole curve and the full-size candidate list in the refinement kernel's LDS, six frames per CU at 4096 samples -- lost
-        // to the fused kernel from 3,800 samples on.)
-        const int reach = pitch_curve_reach(L.n, L.sample_rate, L.fmin);
-        const bool want = L.curve_ws != nullptr && nst_row > 0 && reach > 0 && extra == 0 && (full || !mf || L.interp);
-        const size_t list_ints = spectral_split_list_ints(reach > 0 ? reach : 16);
-        const size_t cap = (want && L.curve_ws_bytes > 64) ? (L.curve_ws_bytes - 64) / ((row_doubles + 1) * sizeof(double) + (list_ints + 1) * sizeof(int32_t)) : 0;
-        if (want && cap >= 1024) {
-            a.ip = L.ip;
-            size_t la = pow2_lds_bytes<U, W>(0, mf ? L.nb : 0);
-            if (mf && !full && (size_t)L.ip.lds_bytes > la) la = ((size_t)L.ip.lds_bytes + 15) & ~(size_t)15;
-            a.reach = reach; a.cand_cap = spectral_split_cand_cap(reach);
-            const size_t ls = ((size_t)pitch_refine_lds_bytes(L.n, a.pp.ncurve) + 16 + 15) & ~(size_t)15;      // (the whole-curve kernel: + the odd row's pair partner)
-            const size_t lr = ((size_t)pitch_refine_lds_bytes(L.n, reach, a.cand_cap) + 15) & ~(size_t)15;
-            a.curve = L.curve_ws; a.curve_ld = (long)row_doubles; a.curve_tol = L.curve_ws + cap * row_doubles;
-            a.curve_list = reinterpret_cast<int32_t *>(a.curve_tol + cap); a.list_ld = (long)list_ints;
-            a.far_list = a.curve_list + cap * list_ints;     // [4 + cap] int32
-            if (L.batching) { L.batching[0] = 0; L.batching[1] = (long)cap; }
-            for (long f0 = 0; f0 < L.F; f0 += (long)cap) {
-                if (L.batching) L.batching[0]++;
-                a.f0 = f0; a.n_batch = (L.F - f0 < (long)cap) ? L.F - f0 : (long)cap;
-                const dim3 g((unsigned)a.n_batch);
-                if (full) {
-                    if (mf && lpc) hipLaunchKernelGGL((analyze_pow2_kernel<U, true, true, true, SP_ANALYZE_SPLIT, W>), g, block, la, s, a);
-                    else if (mf) hipLaunchKernelGGL((analyze_pow2_kernel<U, false, true, true, SP_ANALYZE_SPLIT, W>), g, block, la, s, a);
-                    else if (lpc) hipLaunchKernelGGL((analyze_pow2_kernel<U, true, false, true, SP_ANALYZE_SPLIT, W>), g, block, la, s, a);
-                    else hipLaunchKernelGGL((analyze_pow2_kernel<U, false, false, true, SP_ANALYZE_SPLIT, W>), g, block, la, s, a);
-                } else if (mf && lpc) hipLaunchKernelGGL((analyze_pow2_kernel<U, true, true, false, SP_ANALYZE_INTERP_SPLIT, W>), g, block, la, s, a);
-                else if (mf) hipLaunchKernelGGL((analyze_pow2_kernel<U, false, true, false, SP_ANALYZE_INTERP_SPLIT, W>), g, block, la, s, a);
-                else if (lpc) hipLaunchKernelGGL((analyze_pow2_kernel<U, true, false, false, SP_ANALYZE_SPLIT, W>), g, block, la, s, a);
-                else hipLaunchKernelGGL((analyze_pow2_kernel<U, false, false, false, SP_ANALYZE_SPLIT, W>), g, block, la, s, a);
-                launch_refine_curve(s, a, ls, lr);
-            }
-            return 1;
-        }
-    }
-    if (L.interp && mf && L.n != NC) {         // a padded frame whose MFCC bins are interpolated from the transform's
-        a.ip = L.ip;
-        const size_t li = lds > (size_t)L.ip.lds_bytes ? lds : (((size_t)L.ip.lds_bytes + 15) & ~(size_t)15);
-        if (lpc) hipLaunchKernelGGL((analyze_pow2_kernel<U, true, true, false, SP_ANALYZE_INTERP, W>), grid, block, li, s, a);
-        else hipLaunchKernelGGL((analyze_pow2_kernel<U, false, true, false, SP_ANALYZE_INTERP, W>), grid, block, li, s, a);
-        return 0;
-    }
-    if (L.n != NC) {                           // a padded frame; MFCC from the transform's own bins when its length divides M (U = 1: 512)
-        if constexpr (U * W == 1) {
-            if (lpc && mf) { hipLaunchKernelGGL((analyze_pow2_kernel<U, true, true, false, SP_ANALYZE, W>), grid, block, lds, s, a); return 0; }
-            if (mf) { hipLaunchKernelGGL((analyze_pow2_kernel<U, false, true, false, SP_ANALYZE, W>), grid, block, lds, s, a); return 0; }
-        }
-        if (lpc) hipLaunchKernelGGL((analyze_pow2_kernel<U, true, false, false, SP_ANALYZE, W>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((analyze_pow2_kernel<U, false, false, false, SP_ANALYZE, W>), grid, block, lds, s, a);
-    } else if (lpc && mf) hipLaunchKernelGGL((analyze_pow2_kernel<U, true, true, true, SP_ANALYZE, W>), grid, block, lds, s, a);
-    else if (lpc) hipLaunchKernelGGL((analyze_pow2_kernel<U, true, false, true, SP_ANALYZE, W>), grid, block, lds, s, a);
-    else if (mf) hipLaunchKernelGGL((analyze_pow2_kernel<U, false, true, true, SP_ANALYZE, W>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((analyze_pow2_kernel<U, false, false, true, SP_ANALYZE, W>), grid, block, lds, s, a);
-    return 0;
+// Which instances of analyze_pow2_kernel<U, .., W> exist (uw = U * W: 1, 2, 4 for Nc = 1024, 2048, 4096): asked by choose_pow2_u at run time
+// -- a choice it rejects is a refusal --, by launch_pow2_u at compile time -- nothing else is compiled.
+__host__ __device__ constexpr bool pow2_instance(int uw, bool lpc, bool mf, bool full, int mode) {
+    return mode == SP_ANALYZE ? (full || !mf || uw == 1) :                       // a padded frame's MFCC from the transform's own bins: 512 in the 1024 plan only
+           mode == SP_ANALYZE_INTERP ? (mf && !full) :
+           mode == SP_ANALYZE_SPLIT ? (uw == 4 && (full || !mf)) : mode == SP_ANALYZE_INTERP_SPLIT ? (uw == 4 && mf && !full) :
+           mode == SP_MFCC_HALF ? (uw <= 2 && !lpc && mf && full) : mode == SP_MFCC_ONLY ? (!lpc && mf && full) :
+           mode == SP_MFCC_ONLY_INTERP ? (!lpc && mf && !full) : mode == SP_AC_ONLY ? (!lpc && !mf) : false;
 }
 
+// the power-of-two kernels' half of choose_analyze (k_spectral.hip)
+template <int U, int W = 1>
+analyze_choice_t choose_pow2_u(const spectral_launch_t &L) {
+    constexpr int NC = pow2_geom<U, W>::NC;
+    analyze_choice_t c{};
+    c.family = SP_FAMILY_POW2; c.plan = L.plan; c.sample = L.x.kind; c.spec = SP_SPEC_NONE;
+    const bool analysis = !L.whole_curve && L.out_r == nullptr && !L.mfcc_only;
+    c.ncurve = analysis ? pitch_curve_entries(L.n, L.sample_rate, L.fmin) : 0;
+    const size_t base = pow2_lds_bytes<U, W>(L.n, L.nb, c.ncurve), extra = pitch_full_list_bytes(L.n, L.kmax);
+    c.list = extra ? SP_LIST_LDS : SP_LIST_LANES; c.full_off = extra ? (int)base : 0;
+    c.lds = base + extra;
+    c.lpc = L.out_lpc != nullptr; c.mf = L.out_mfcc != nullptr; c.full = L.n == NC; c.mode = SP_ANALYZE;
+    const bool interp = L.interp && L.n != NC;                // a padded frame whose MFCC bins are interpolated from the transform's
+    const size_t lds_ip = ((size_t)L.ip.lds_bytes + 15) & ~(size_t)15;
+    if (L.mfcc_only) {                                       // n == Nc, or (L.n == 2 Nc) the unpadded form, or a padded frame with interpolated bins
+        const bool half = L.n == 2 * NC;
+        c.lpc = false; c.mf = true; c.full = half || !interp; c.mode = half ? SP_MFCC_HALF : interp ? SP_MFCC_ONLY_INTERP : SP_MFCC_ONLY;
+        c.lds = pow2_lds_bytes<U, W>(0, L.nb);
+        if (c.mode == SP_MFCC_ONLY_INTERP && (size_t)L.ip.lds_bytes >= c.lds) c.lds = lds_ip;
+    } else if (L.out_r != nullptr) {                         // autocorrelate(n_lags) alone
+        c.lpc = c.mf = false; c.mode = SP_AC_ONLY; c.lds = pow2_lds_bytes<U, W>(0, 0);
+    } else {
+        // The 4096-point plan in separate kernels (vbx_spectral.hpp, SP_ANALYZE_SPLIT; k_spectral_pow2.hip): transforms + LPC + MFCC per batch of
+        // frames, the lag curves through a scratch buffer, then the peak scan, the refinement at eleven frames per CU, the far frames.  Where the curve is cut (an even frame length at speech settings),
+        // the caller gave scratch and kmax needs no list region in LDS.
+        if constexpr (U * W == 4) {
+            // an odd frame length keeps its whole curve (c.ncurve == 0: pitch_curve_entries) -- in the scratch row too, for the whole-curve
+            // kernel of the far frames; the scan and the refinement kernel need no more of it than of an even length's
+            const int nst_row = c.ncurve > 0 ? c.ncurve : ((L.n & 1) && analysis ? L.n + 1 : 0);
+            // Measured (tools/experiments/split_check.py, 2 h of audio per step, pipeline M frames/s fused -> split, all bit-identical):
+            // 2050 / 1024: 11.7 -> 13.3, 2500 / 1000: 11.1 -> 12.5, 3000 / 1200: 10.8 -> 11.9, 4000 / 2000: 9.3 -> 10.2, 4096 / 2048: 11.2 -> 12.1,
+            // 4096 / 1024: 11.3 -> 12.5; pitch at kmax = 8 (40,000 frames): 13.9 -> 9.1 ms.  Per frame at 4096 / 2048: transforms 37.3 ns,
+            // scan 4.3, refinement 21.0 (eleven frames per CU), far frames 2.1 -- against 69 ns fused.  (A first form without the scan kernel
+            // -- the whole curve and the full-size candidate list in the refinement kernel's LDS, six frames per CU at 4096 samples -- lost
+            // to the fused kernel from 3,800 samples on.)
+            const int reach = pitch_curve_reach(L.n, L.sample_rate, L.fmin);
+            if (nst_row > 0 && reach > 0 && extra == 0 && (c.full || !c.mf || L.interp)) {
+                const size_t row_doubles = (size_t)(nst_row + Y_PAD), list_ints = spectral_split_list_ints(reach);
+                const size_t per_frame = (row_doubles + 1) * sizeof(double) + (list_ints + 1) * sizeof(int32_t);
+                c.split_row_bytes = per_frame + 16;          // (+ far_list: one index per frame, the count)
+                const size_t cap = (L.curve_ws != nullptr && L.curve_ws_bytes > 64) ? (L.curve_ws_bytes - 64) / per_frame : 0;
+                if (cap >= 1024) {
+                    c.mode = (c.mf && !c.full) ? SP_ANALYZE_INTERP_SPLIT : SP_ANALYZE_SPLIT;
+                    c.lds = pow2_lds_bytes<U, W>(0, c.mf ? L.nb : 0);
+                    if (c.mf && !c.full && (size_t)L.ip.lds_bytes > c.lds) c.lds = lds_ip;
+                    c.reach = reach; c.cand_cap = spectral_split_cand_cap(reach);
+                    c.lds_scan = ((size_t)pitch_refine_lds_bytes(L.n, c.ncurve) + 16 + 15) & ~(size_t)15;      // (the whole-curve kernel: + the odd row's pair partner)
+                    c.lds_refine = ((size_t)pitch_refine_lds_bytes(L.n, reach, c.cand_cap) + 15) & ~(size_t)15;
+                    c.row_doubles = row_doubles; c.list_ints = list_ints; c.per_launch = (long)cap;
+                }
+            }
+        }
+        if (!sp_is_split(c.mode) && interp && c.mf) {
+            c.mode = SP_ANALYZE_INTERP;
+            if ((size_t)L.ip.lds_bytes >= c.lds) c.lds = lds_ip;
+        } else if (!sp_is_split(c.mode) && !c.full && U * W != 1) c.mf = false;      // (a padded frame beyond the 1024 plan has no MFCC from the transform's own bins: the callers ask for none)
+    }
+    c.waves = pow2_waves_per_simd(U, W, c.mode);
+    c.refused = !pow2_instance(U * W, c.lpc, c.mf, c.full, c.mode);
+    return c;
+}
+
+// launches the choice: one kernel, or -- the split form -- the transforms and launch_refine_curve per batch of c.per_launch frames; returns the batches
+template <int U, int W = 1>
+int launch_pow2_u(hipStream_t s, const spectral_launch_t &L, const analyze_choice_t &c, spectral_args_t &a) {
+    a.f0 = 0; a.n_batch = L.F; a.curve = nullptr; a.curve_ld = 0; a.curve_tol = nullptr; a.curve_list = nullptr; a.list_ld = 0; a.reach = 0; a.cand_cap = 0; a.far_list = nullptr;
+    auto launch = [&](auto mode) {
+        return sp_with_flags(c.lpc, c.mf, c.full, [&](auto lpc, auto mf, auto full) {
+            constexpr bool LPC = decltype(lpc)::value, MF = decltype(mf)::value, FULL = decltype(full)::value;
+            constexpr int MODE = decltype(mode)::value;
+            if constexpr (pow2_instance(U * W, LPC, MF, FULL, MODE)) {
+                hipLaunchKernelGGL((analyze_pow2_kernel<U, LPC, MF, FULL, MODE, W>), dim3((unsigned)a.n_batch), dim3(64 * W), c.lds, s, a);
+                return true;
+            } else return false;
+        });
+    };
+    using modes = std::integer_sequence<int, SP_ANALYZE, SP_ANALYZE_INTERP, SP_ANALYZE_SPLIT, SP_ANALYZE_INTERP_SPLIT, SP_MFCC_HALF, SP_MFCC_ONLY, SP_MFCC_ONLY_INTERP, SP_AC_ONLY>;
+    auto launch_mode = [&] { return sp_with_mode(c.mode, modes{}, launch); };
+    if (!sp_is_split(c.mode)) return launch_mode() ? 1 : 0;
+    const size_t cap = (size_t)c.per_launch;
+    a.reach = c.reach; a.cand_cap = c.cand_cap;
+    a.curve = L.curve_ws; a.curve_ld = (long)c.row_doubles; a.curve_tol = L.curve_ws + cap * c.row_doubles;
+    a.curve_list = reinterpret_cast<int32_t *>(a.curve_tol + cap); a.list_ld = (long)c.list_ints;
+    a.far_list = a.curve_list + cap * c.list_ints;           // [4 + cap] int32
+    int batches = 0;
+    for (long f0 = 0; f0 < L.F; f0 += c.per_launch, batches++) {
+        a.f0 = f0; a.n_batch = (L.F - f0 < c.per_launch) ? L.F - f0 : c.per_launch;
+        launch_mode();
+        launch_refine_curve(s, a, c.lds_scan, c.lds_refine);
+    }
+    return batches;
+}
 
 }  // namespace vbx

@@ -378,6 +378,7 @@ def load_library():
         "vbx_internal_last_mfcc_interp": (C.c_int, [vp]),
         "vbx_internal_last_mfcc_form": (C.c_int, [vp]),
         "vbx_internal_last_pitch_form": (C.c_int, [vp]),
+        "vbx_internal_analyze_choice": (C.c_int, [vp, vp, vp]),
         "vbx_record_doubles": (sz, [C.POINTER(AnalysisParams)]),
         "vbx_analyze_frames_f64": (C.c_int, [vp, vp, sz, sz, sz, C.POINTER(AnalysisParams), vp, sz, vp, sz, vp]),
         "vbx_analyze_frames_pcm16": (C.c_int, [vp, vp, sz, sz, sz, C.POINTER(AnalysisParams), vp, sz, vp, sz, vp]),
