@@ -626,8 +626,8 @@ pub struct PoolRows<'g> {
 /// A pool of independent live streams ([`Gpu::pool`]): `max_streams` slots that share a sample format (mono), a frame shape and a
 /// parameter set, each with its own timeline; closed on drop.  One tick takes `(slot, block)` entries of any sizes, any subset of the
 /// slots, in any order -- one upload and a fixed number of launches whatever their number -- and per slot the rows of all ticks equal,
-/// bit for bit, what a one-channel [`Session`] delivers for the same blocks, marks and resets.  The online pitch path is not offered
-/// for pool slots: run [`Gpu`]'s pitch path over a call's lists when the call ends.
+/// bit for bit, what a one-channel [`Session`] delivers for the same blocks, marks and resets.  A tracked pool's live pitch contours
+/// come from [`Pool::bind_path`]: one more launch per tick, whatever the number of streams.
 pub struct Pool<'g> {
     gpu: &'g Gpu,
     raw: *mut ffi::VbxPool,
@@ -703,6 +703,28 @@ impl<'g> Pool<'g> {
     /// The slot behaves as that of a freshly opened pool (`vbx_pool_reset_stream`): how a slot is reused for the next call.
     pub fn reset_stream(&self, stream: i32) -> GpuResult<()> {
         self.gpu.check(unsafe { ffi::vbx_pool_reset_stream(self.raw, stream) })
+    }
+
+    /// The rows one slot's area of a bound pool's contour arrays needs at least (`vbx_pool_path_slot_rows`): `max_pending` +
+    /// ceil(`max_block` / `stride`).  Host arithmetic only.
+    pub fn path_slot_rows(max_pending: usize, max_block: usize, stride: usize) -> usize {
+        unsafe { ffi::vbx_pool_path_slot_rows(max_pending, max_block, stride) }
+    }
+
+    /// Every slot's contour from this tracked pool (`vbx_pool_path_bind`): every tick also commits, in one more launch whatever the
+    /// number of entries, the decided rows of each visited slot's pitch path into rows `[s * slot_rows, ...)` of `rows` and the
+    /// slot's `VbxPathCommit` into `rows.commit[s]` (`rows.commit` holds one record per slot, the other arrays `slot_rows` rows per
+    /// slot).  [`Pool::mark_utterance`] and [`Pool::reset_stream`] are deferred to the next tick's launch; an empty tick fetches a
+    /// marked slot's tail.  Before the first tick that queues work; afterwards only the destinations may change.  The arrays must
+    /// outlive the pool's ticks.
+    pub fn bind_path(&self, peak_ref: f64, max_pending: usize, slot_rows: usize, rows: &PathRows<'g>) -> GpuResult<()> {
+        let need = rows.commit.len() * slot_rows;
+        assert!(rows.path.len() >= need && rows.index.len() >= need && rows.forced.len() >= need, "output rows too small");
+        let out = ffi::VbxPoolPathOutputs {
+            out_path: rows.path.as_mut_ptr(), out_index: rows.index.as_mut_ptr(), out_forced: rows.forced.as_mut_ptr(),
+            d_commit: rows.commit.as_mut_ptr(),
+        };
+        self.gpu.check(unsafe { ffi::vbx_pool_path_bind(self.raw, peak_ref, max_pending, &out, 2, slot_rows) })
     }
 }
 

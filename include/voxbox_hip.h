@@ -1228,8 +1228,9 @@ int vbx_analyze_clips(vbx_ctx *ctx, const void *const *h_clip /* [n_clips] DEVIC
  * the stale tail and state) -- this is how a slot is reused for the next call.  vbx_pool_info reports a slot's sample frames
  * consumed, frames delivered and sample frames carried; vbx_pool_close frees the pool behind the work queued on the context's stream
  * (close every pool before its context).
- * The online pitch path (vbx_session_path_bind) is NOT offered for pool slots: the tracked form delivers the lists, and the caller
- * runs vbx_pitch_path_f64 over a call's rows when the call ends, as an unbound session's caller does.  A pool, sessions and any other
+ * The online pitch path (vbx_session_path_bind) of every slot comes from vbx_pool_path_bind, below: one more launch per tick,
+ * whatever the number of streams.  An unbound pool's caller runs vbx_pitch_path_f64 over a call's rows when the call ends, as an
+ * unbound session's caller does; a host-side delivery of the contour is NOT offered.  A pool, sessions and any other
  * entry point may share one context; a tick may WAIT ON THE HOST for the staged upload of two ticks ago and is not capturable into a
  * graph; afterwards the vbx_internal_last_* probes describe the tick's frame-loop call and there is no state for vbx_track_stitch_f64.
  * vbx_pool_plan: pure host arithmetic, no GPU -- per entry (consumed, utt_frame, n_new) of its slot: the vbx_session_plan_t, its rows,
@@ -1274,6 +1275,49 @@ int vbx_pool_mark_utterance(vbx_pool *pool, int32_t stream);   /* the next frame
 int vbx_pool_reset_stream(vbx_pool *pool, int32_t stream);     /* the slot behaves as that of a freshly opened pool */
 int vbx_pool_info(const vbx_pool *pool, int32_t stream, size_t *h_consumed, size_t *h_frames, size_t *h_carried);
 void vbx_pool_close(vbx_pool *pool);
+
+/* The live pitch contour of every slot (ABI 5, added): what vbx_session_path_bind is to a one-channel session.
+ * vbx_pool_path_bind, on a pool opened with h_track, gives every slot an online path of its own (vbx_path_stream_open's state and
+ * ring of max_pending frames, P = peak_ref, time_step == 0 meaning stride / sample_rate as in the tracked call) over the POOL-OWNED
+ * lists of a tick's frame-loop call -- the caller's h_outputs arrays are not read -- and from then on every vbx_pool_push /
+ * _push_device queues ONE more launch behind pool_deliver, pitch_path_online_pool, whatever the number of entries: a lane group per
+ * VISITED slot, which are every entry with n_sample_frames > 0 (one that completes no frame reports n = 0 and what is pending, as a
+ * bound session's push does) and every slot with a deferred mark or reset, listed in the tick or not.  The launch's table (slot,
+ * first list row, frame count, flags) travels in the tick's single pinned buffer and single copy.
+ * Layout: everything slot s commits in a tick goes to rows [s * slot_rows, s * slot_rows + n) of out_path (rows path_ld doubles
+ * apart; columns 0-1 are written), out_index and out_forced (both optional), and its vbx_path_commit to d_commit[s]: slot-indexed and
+ * fixed, because the committed counts exist only on the device.  slot_rows >= vbx_pool_path_slot_rows(max_pending,
+ * max_block_sample_frames, stride) = max_pending + ceil(max_block_sample_frames / stride): a slot never writes more than the frames
+ * it held plus the frames its block completes.  Rows past n, and the rows and records of slots a tick does not visit, are not touched:
+ * read d_commit[s] behind a tick that visited s.
+ * On a bound pool vbx_pool_mark_utterance and vbx_pool_reset_stream stay host bookkeeping that launches nothing; for the path they are
+ * DEFERRED to the next tick's launch.  A marked slot first ends its path utterance -- all pending frames go along the leader's trace
+ * with out_forced = 0, as end_utterance does -- and then scans its new frames, if any, as a new utterance; the rows of both follow
+ * each other in the slot's area and d_commit[s] is the merge of the two: `first` of the first, n and n_forced summed, `pending` of the
+ * last.  A reset slot has its path state zeroed first (vbx_path_stream_reset: pending frames are dropped, the counters restart at 0),
+ * before anything else for that slot: to keep the rest of a call's contour, mark, tick, then reset.  An EMPTY tick (n_entries == 0) on
+ * a bound pool with marked or reset slots queues the single upload and the single path launch for them -- the tail of a contour
+ * without audio; with nothing flagged it queues nothing, as before.
+ * Contract: for every slot, the rows, indices and forced flags of all ticks, concatenated, are those a bound one-channel session
+ * writes on the same blocks, marks and resets, bit for bit, for every cut into blocks, every assignment to ticks and every entry
+ * order (tests/test_gpu_pool_path.py); by that session's contract, with silence_threshold == 0 the unforced rows are columns 0-1 and
+ * `index` of the resident tracked call, and with silence_threshold > 0 those of the shard protocol with seg_peak = peak_ref.
+ * The first bind comes before the first tick that queues work and allocates the slots' states (zeroed) and rings; a later bind with
+ * the same peak_ref, max_pending and slot_rows only changes the destinations and keeps the state.  The binding lasts until
+ * vbx_pool_close; an unbound pool runs exactly what it ran before.
+ * VBX_E_INVALID, with nothing queued and the pool usable: a NULL pool, h_out, out_path or d_commit; a pool without h_track; a first bind
+ * after work was queued; a rebind that changes peak_ref, max_pending or slot_rows; path_ld < 2; max_pending of 0 or above 2^24;
+ * slot_rows below the minimum; silence_threshold > 0 with peak_ref negative or not finite.  An allocation failure (VBX_E_RUNTIME)
+ * leaves the pool unbound and usable. */
+typedef struct {
+    vbx_pitch *out_path;        /* device: max_streams * slot_rows rows, rows path_ld doubles apart */
+    int32_t *out_index;         /* device, optional: max_streams * slot_rows */
+    uint8_t *out_forced;        /* device, optional: max_streams * slot_rows */
+    vbx_path_commit *d_commit;  /* device: max_streams records */
+} vbx_pool_path_outputs;
+size_t vbx_pool_path_slot_rows(size_t max_pending, size_t max_block_sample_frames, size_t stride);  /* host arithmetic, no GPU */
+int vbx_pool_path_bind(vbx_pool *pool, double peak_ref, size_t max_pending,
+                       const vbx_pool_path_outputs *h_out, size_t path_ld, size_t slot_rows);
 
 /* ------------------------------------------------------------------ multi-GPU: frame-range sharding */
 

@@ -19,7 +19,7 @@ from .voxbox import (  # noqa: F401
     AnalysisParams, AnalysisExt, PitchPathParams, PitchTrackParams, PitchTrackOutputs, Comm, comm_unique_id, comm_live_count, gather_plan, shard_range, shard_samples,
     ShardPlan, shard_plan, shard_local_segments, mfcc_bins,
     Session, SessionPlan, session_plan, SessionChannels, SessionChannelsPlan, ChannelPathOutputs, session_channels_plan, PathStream, PathCommit, commit_of,
-    Pool, PoolEntry, PoolRows, PoolPlanRow, pool_plan,
+    Pool, PoolEntry, PoolRows, PoolPlanRow, pool_plan, PoolPathOutputs, pool_path_slot_rows,
     ClipFormat, ClipRow, clips_plan, CLIPS_MIN_GROUP_FRAMES, CLIPS_PLANE_BYTES,
     HostAudio, host_chunk_plan, HOST_DEFAULT_CHUNK_FRAMES, ChannelOutputs, HOST_MAX_CHANNELS,
     SAMPLE_PCM16, SAMPLE_PCM24, SAMPLE_PCM32, SAMPLE_F32, SAMPLE_F64, SAMPLE_U8, SAMPLE_ULAW, SAMPLE_ALAW, g711_table,

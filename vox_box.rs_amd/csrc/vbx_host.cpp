@@ -584,6 +584,15 @@ int vbx_pool_plan(const size_t *h_consumed, const size_t *h_utt_frame, const siz
     return VBX_SUCCESS;
 }
 
+// The rows one slot's area of a bound pool's contour arrays needs (vbx_pool_path_bind): a tick's path launch never writes more for a
+// slot than the frames it held pending, at most max_pending, plus the frames its block completes, at most ceil(n / stride) for a
+// block of n samples.  0: stride == 0, or the sum does not fit.
+size_t vbx_pool_path_slot_rows(size_t max_pending, size_t max_block_sample_frames, size_t stride) {
+    if (stride == 0) return 0;
+    const size_t done = max_block_sample_frames / stride + (max_block_sample_frames % stride != 0);
+    return (max_pending > SIZE_MAX - done) ? 0 : max_pending + done;
+}
+
 // A batch of clips (vbx_analyze_clips): each clip's rows in the outputs, the group that analyses it and where it lies in that
 // group's packed plane.  Groups are greedy runs of whole clips in order.  Inside a group clip b's sample 0 lies at element
 // plane_frame_b * stride; the next clip with frames starts ceil(len_b / stride) frames behind it, so the gap between them is shorter

@@ -650,5 +650,21 @@ void launch_pitch_path_online(hipStream_t s, const pp_par_t &P, int G, const pp_
 struct pp_online_ch_t { void *mem; pitch_t *out_path; int32_t *out_index; uint8_t *out_forced; pp_commit_t *commit; };
 struct pp_online_all_t { long plane_frames; size_t off_row, off_psi, off_idx; pp_online_ch_t ch[64]; };
 void launch_pitch_path_online_all(hipStream_t s, const pp_par_t &P, int G, const pp_online_t &O, const pp_online_all_t &A, int n_sel);
+// k_pitch_path_pool.hip: the same scan for every visited slot of a bound session pool's tick in ONE launch, a block per row of the
+// tick's path table (any number of rows: the table is device memory, uploaded with the tick's entry table).  Row k: the slot, its
+// frames' rows [row0, row0 + frames) of the lists P names (row 0 of the tick's frame-loop call; frames 0: none are read), and the
+// slot's deferred flags: RESET zeroes the slot's state first; MARK then ends the slot's utterance (a push of no frames with
+// end_utterance) before the frames are scanned as a new one, the rows of both following each other and the commits merged.
+// O: cap, peak and ld (its pointers and end are not read); slot s's allocation (pp_online_state_t, then the ring at off_row / off_psi
+// / off_idx bytes, vbx_path_stream_open's layout) lies at mem + s * slot_bytes, its rows at row s * slot_rows of out_path (ld doubles
+// apart), out_index and out_forced (either may be null), its merged commit at commit[s].
+enum : int32_t { PP_POOL_RESET = 1, PP_POOL_MARK = 2 };
+struct pp_pool_row_t { int32_t slot, flags; int64_t row0, frames; };
+struct pp_online_pool_t {
+    const pp_pool_row_t *tab;
+    char *mem; size_t slot_bytes, off_row, off_psi, off_idx;
+    pitch_t *out_path; int32_t *out_index; uint8_t *out_forced; pp_commit_t *commit; long slot_rows;
+};
+void launch_pitch_path_online_pool(hipStream_t s, const pp_par_t &P, int G, const pp_online_t &O, const pp_online_pool_t &A, long n_rows);
 
 }  // namespace vbx

@@ -517,10 +517,13 @@ private:
 // and a parameter set, each with its own timeline.  One tick -- push -- takes (slot, block) entries of any sizes, any subset of the
 // slots, in any order, and delivers every entry's rows into ONE set of device arrays, entry after entry (rows[i] tells where), from
 // one upload and a fixed number of launches.  Per slot the rows of all ticks equal, bit for bit, a one-channel session's for the same
-// blocks, marks and resets.  Frames of at most VBX_MAX_FRAME_LEN samples; the online pitch path is not offered for pool slots.
+// blocks, marks and resets.  Frames of at most VBX_MAX_FRAME_LEN samples; a tracked pool's live pitch contours come from bind_path.
 using PoolEntry = vbx_pool_entry;
 using PoolRows = vbx_pool_rows;
 using PoolPlanRow = vbx_pool_plan_row;
+using PoolPathOutputs = vbx_pool_path_outputs;
+// the rows one slot's area of a bound pool's contour arrays needs at least: max_pending + ceil(max_block / stride)
+inline size_t pool_path_slot_rows(size_t max_pending, size_t max_block, size_t stride) { return vbx_pool_path_slot_rows(max_pending, max_block, stride); }
 struct PoolPlan { std::vector<PoolPlanRow> rows; size_t total_rows = 0, call_frames = 0; };
 inline PoolPlan pool_plan(const size_t *h_consumed, const size_t *h_utt_frame, const size_t *h_n_new, size_t n_entries, size_t frame_len,
                           size_t stride) {
@@ -554,6 +557,12 @@ public:
     }
     void mark_utterance(int32_t stream) { c_.check(vbx_pool_mark_utterance(p_, stream)); }
     void reset_stream(int32_t stream) { c_.check(vbx_pool_reset_stream(p_, stream)); }
+    // every slot's contour from a tracked pool (vbx_pool_path_bind): every tick also commits, in ONE more launch, the decided rows of
+    // each visited slot's pitch path into rows [s * slot_rows, ...) of the bound device arrays and its PathCommit into d_commit[s];
+    // marks and resets are deferred to the next tick's launch, and an empty tick fetches a marked slot's tail
+    void bind_path(double peak_ref, size_t max_pending, const PoolPathOutputs &out, size_t path_ld, size_t slot_rows) {
+        c_.check(vbx_pool_path_bind(p_, peak_ref, max_pending, &out, path_ld, slot_rows));
+    }
     struct Info { size_t consumed, frames, carried; };
     Info info(int32_t stream) const {
         Info i{};

@@ -202,6 +202,12 @@ class ChannelPathOutputs(C.Structure):
     _fields_ = [("out_path", C.c_void_p), ("out_index", C.c_void_p), ("out_forced", C.c_void_p), ("d_commit", C.c_void_p)]
 
 
+class PoolPathOutputs(C.Structure):
+    """vbx_pool_path_outputs: where the online pitch paths of a bound session pool write (device pointers) -- slot s's committed
+    rows from row s * slot_rows of out_path, out_index and out_forced (both optional), its PathCommit at d_commit[s]."""
+    _fields_ = [("out_path", C.c_void_p), ("out_index", C.c_void_p), ("out_forced", C.c_void_p), ("d_commit", C.c_void_p)]
+
+
 class SessionPlan(C.Structure):
     """vbx_session_plan_t: what one push does to a live session -- the frames [lo, hi) it delivers, the warm frames analysed before
     them, whether the tracker continues from the last delivered row, the first sample frame the analysis reads and the first one
@@ -439,6 +445,8 @@ def load_library():
         "vbx_pool_reset_stream": (C.c_int, [vp, C.c_int32]),
         "vbx_pool_info": (C.c_int, [vp, C.c_int32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
         "vbx_pool_close": (None, [vp]),
+        "vbx_pool_path_slot_rows": (sz, [sz, sz, sz]),
+        "vbx_pool_path_bind": (C.c_int, [vp, dbl, sz, C.POINTER(PoolPathOutputs), sz, sz]),
         "vbx_internal_pool_ingest": (C.c_int, [vp, i32, C.POINTER(_PoolIngestEntry), sz, sz, vp, C.POINTER(sz)]),
         "vbx_find_formants_resampled_f64": (C.c_int, [vp, vp, sz, sz, sz, dbl, dbl, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp]),
         "vbx_shard_range": (C.c_int, [sz, i32, i32, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
@@ -611,6 +619,12 @@ def pool_plan(consumed, utt_frame, n_new, frame_len, stride):
     if load_library().vbx_pool_plan(p(a), p(b), p(c), a.size, int(frame_len), int(stride), rows, C.byref(total), C.byref(call)) != 0:
         raise VoxBoxError("vbx_pool_plan: bad argument")
     return [rows[i] for i in range(a.size)], int(total.value), int(call.value)
+
+
+def pool_path_slot_rows(max_pending, max_block, stride):
+    """vbx_pool_path_slot_rows: the rows one slot's area of a bound pool's contour arrays needs at least -- max_pending +
+    ceil(max_block / stride).  Host arithmetic only."""
+    return int(load_library().vbx_pool_path_slot_rows(int(max_pending), int(max_block), int(stride)))
 
 
 def session_plan(consumed, utt_frame, n_new, frame_len, stride):
@@ -1027,6 +1041,19 @@ class Pool(_Live):
     def reset_stream(self, stream):
         """vbx_pool_reset_stream: the slot behaves as that of a freshly opened pool -- how a slot is reused for the next call"""
         self.vb._check(self.vb.L.vbx_pool_reset_stream(self.handle, int(stream)))
+
+    def bind_path(self, out_path, commit, peak_ref=1.0, max_pending=64, path_ld=2, slot_rows=None, out_index=None, out_forced=None):
+        """vbx_pool_path_bind: every tick of this tracked pool also commits, in ONE more launch whatever the number of streams, the
+        decided rows of every visited slot's pitch contour (the online path, as Session.bind_path) into device buffers of
+        max_streams * slot_rows rows -- out_path (rows path_ld doubles apart), out_index (int32) and out_forced (uint8), both
+        optional; slot s writes from row s * slot_rows -- and slot s's PathCommit into commit[s] (device, max_streams records of 32
+        bytes; read them behind a sync).  slot_rows defaults to pool_path_slot_rows(max_pending, max_block, stride).  On a bound
+        pool mark_utterance and reset_stream are deferred to the next tick's launch; an empty tick fetches a marked slot's tail.
+        Before the first tick that queues work; afterwards only the destinations may change.  Returns slot_rows."""
+        rows = pool_path_slot_rows(max_pending, self.max_block, self.stride) if slot_rows is None else int(slot_rows)
+        po = PoolPathOutputs(_ptr(out_path), _ptr(out_index), _ptr(out_forced), _ptr(commit))
+        self.vb._check(self.vb.L.vbx_pool_path_bind(self.handle, float(peak_ref), int(max_pending), C.byref(po), int(path_ld), rows))
+        return rows
 
 
 def commit_of(vb, commit):
@@ -2003,8 +2030,8 @@ class VoxBox:
         """vbx_pool_open: a session pool on this context -- max_streams slots of mono audio in `format` (SAMPLE_*), each a live
         stream of its own, fed by ticks of (slot, block) entries (Pool.push): one upload, one frame-loop call and a fixed number of
         launches per tick whatever the number of streams.  Blocks hold at most max_block samples (default 100 * stride), a tick's
-        blocks together at most max_tick (default max_streams * max_block).  Frames of at most 4096 samples; the online pitch path
-        is not offered for pool slots.  Everything is allocated and warmed here; a Pool is also a context manager."""
+        blocks together at most max_tick (default max_streams * max_block).  Frames of at most 4096 samples; a tracked pool's
+        live pitch contours come from Pool.bind_path.  Everything is allocated and warmed here; a Pool is also a context manager."""
         assert frame_len and stride and max_streams
         mb = int(max_block) if max_block is not None else 100 * int(stride)
         return Pool(self, params, ext, track, format, frame_len, stride, max_streams, mb,
