@@ -1088,6 +1088,27 @@ impl<'g> FrameBatch<'g> {
         ))
     }
 
+    /// Boersma's candidates with an unquantised lag (`vbx_pitch_boersma_f64`: the refinement the crate's comment describes, with
+    /// Q5 / Q6 / Q8 undone): `[F, kmax]` rows, the full candidate count and the status, `1 <= kmax <= 63`.  The lists are what the
+    /// pitch path takes; the crate's own rows stay with `pitch_all`.
+    pub fn pitch_boersma_all(&self, sample_rate: f64, threshold: f64, min: f64, max: f64, kmax: usize) -> GpuResult<(Vec<Pitch<f64>>, Vec<i32>, Vec<FrameStatus>)> {
+        let f = self.n_frames;
+        let cand = self.gpu.alloc::<ffi::VbxPitch>(f * kmax)?;
+        let count = self.gpu.alloc::<i32>(f)?;
+        let status = self.gpu.alloc::<i32>(f)?;
+        self.gpu.check(unsafe {
+            ffi::vbx_pitch_boersma_f64(
+                self.gpu.raw, self.samples.as_ptr(), f, self.frame_len, self.stride, self.win_ptr(), sample_rate, threshold, min, max, kmax,
+                cand.as_mut_ptr(), count.as_mut_ptr(), status.as_mut_ptr(),
+            )
+        })?;
+        Ok((
+            cand.to_vec()?.iter().map(|p| Pitch::new(p.frequency, p.strength)).collect(),
+            count.to_vec()?,
+            status.to_vec()?.iter().map(|&s| FrameStatus::from_code(s)).collect(),
+        ))
+    }
+
     fn pitch_raw(&self, sample_rate: f64, threshold: f64, min: f64, max: f64, kmax: usize) -> GpuResult<(Vec<ffi::VbxPitch>, Vec<i32>, Vec<i32>)> {
         let f = self.n_frames;
         let cand = self.gpu.alloc::<ffi::VbxPitch>(f * kmax)?;

@@ -229,6 +229,56 @@ int vbx_pitch_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_l
                   const double *window, double sample_rate, double threshold, double fmin, double fmax,
                   size_t kmax, vbx_pitch *out_cand, int32_t *out_count, int32_t *status);
 
+/* Boersma's (1993) pitch candidates with an UNQUANTISED lag (ABI 5, added): the algorithm the crate's comment describes
+ * (src/periodic.rs:382-395: "Second pass maximizes the function more accurately using ... sinc interpolation and the Brent ...
+ * maximization") and its code misses -- SURVEY Appendix A, Q5 (a sign slip in the parabola), Q6 (interpolate_sinc's left and right
+ * sample indices swapped) and Q8 (brent_maximize minimises, the closure does not negate) together put every refined candidate of
+ * vbx_pitch_f64 on the INTEGER lag next to the peak: up to half a lag, 1.1e-3 .. 1.5e-3 relative in the speech range.  This call
+ * undoes the three and nothing else; vbx_pitch_f64 still returns the crate's rows.  Arguments, layouts, alignment rules and the
+ * asynchronous stream contract are vbx_pitch_f64's; out_cand [F, kmax], out_count [F] and status [F] (may be NULL) are what
+ * vbx_pitch_path_f64 and vbx_path_stream_push take.
+ * Definition (the contract; IEEE binary64; N = frame_len, H = floor(N / 2); tests/pitch_boersma_model.py is its executable form):
+ *   1 curve      y[0 .. N) is Pitched::pitch's curve, unchanged (src/periodic.rs:400-411): the autocorrelation with the Q1 seed,
+ *                normalised by the largest |r| over all lags (Q2), divided by the accumulated-phase lag window (Q3).
+ *   2 peaks      strict local maxima y[k-1] < y[k] > y[k+1], 1 <= k < H - 1, in ascending k (Q4, unchanged).
+ *   3 lag        dr = 0.5 (y[k+1] - y[k-1]), d2r = 2 y[k] - y[k-1] - y[k+1], x0 = k + dr / d2r, f0 = sample_rate / x0; the peak is
+ *                kept iff fmin < f0 < fmax.  (d2r > 0 and |dr / d2r| < 0.5 at a strict maximum; a peak whose computed
+ *                |dr / d2r| exceeds 1 -- cancellation in d2r between neighbours an ulp apart -- is dropped.)
+ *   4 S_depth(x) plain lag coordinates.  x < 0 gives y[0] (:40).  nl = floor(x), nr = nl + 1, phil = x - nl, phir = 1 - phil;
+ *                |x - nl| < 1e-10 gives y[nl], |x - nr| < 1e-10 gives y[nr] (:41-42); otherwise, with D = min(depth, nl),
+ *                  S = sum_{n=0..D-1} y[nl - n] sinc(pi (phil + n)) (0.5 + 0.5 cos(pi (phil + n) / (phil + D)))
+ *                    + sum_{n=0..D-1} y[nr + n] sinc(pi (phir + n)) (0.5 + 0.5 cos(pi (phir + n) / (phir + D))),  sinc(a) = sin(a) / a:
+ *                the reference's sum with each side reading its own samples.  The reference's term n = D of either side has the
+ *                taper 0.5 + 0.5 cos(pi) = 0 and is left out, so that the curve's last lag -- whose lag window is 0 or a rounding
+ *                residue, y[N-1] = 0/0 or x[0]/1e-17 -- cannot turn a sum into NaN.  No index is below 0 or above 2 nl <= N.
+ *   5 first pass s1 = S_30(x0), reflected: s1 > 1 becomes 1 / s1 (the reference's dead :433-435, live).  The unvoiced entry
+ *                (0, threshold) has s1 = threshold.
+ *   6 selection  Praat's rule.  L = the kept peaks in ascending k, then the unvoiced entry; out_count = len(L); m = min(kmax,
+ *                out_count); the m entries of L with the largest s1 are kept (a tie goes to the earlier position; a NaN s1 ranks
+ *                above every number), in L-order.
+ *   7 refinement for each kept voiced entry, brent_maximize's iteration (src/periodic.rs:103-188: the same golden constant, tol =
+ *                1e-10, sqrt(EPSILON) term, at most 60 iterations) on -S_1200 over [x0 - 1, x0 + 1] gives xmid;
+ *                frequency = sample_rate / xmid, strength = S_1200(xmid), reflected if it exceeds 1.
+ *   8 order      stable sort of the kept entries by descending strength (:453); entries past m are zero.
+ *   9 kmax       for kmax >= out_count the row is the frame's whole list and does not change with kmax (bit for bit among kmax
+ *                1..3 and among kmax >= 4; from 4 on four entries are refined at a time, 16 lanes each, which changes the last
+ *                bits of the sums: between the two classes an entry agrees to ~1e-7 relative in Hz).  For a smaller kmax the
+ *                rows are NOT prefixes of one another: selection is by the first-pass s1, the order by the refined strength.
+ *  10 status     VBX_FRAME_ERR_NAN with a zero row and count 0 only where a selected entry's s1 or final strength is NaN.  A
+ *                frame in which no comparison succeeds -- all zeros (the curve is NaN throughout), a NaN or Inf sample -- returns the
+ *                unvoiced entry alone with VBX_FRAME_OK and count 1, and so does any frame without a peak in range.
+ *                vbx_pitch_f64 reports the same status and count for such frames (tests/test_gpu_pitch_boersma.py).
+ * 16 <= frame_len <= 4096 and 1 <= kmax <= 63 (the path's cap).  VBX_E_INVALID, before a byte is written: anything else, a
+ * non-finite or non-positive sample_rate, fmin >= fmax (or either NaN), NULL x, out_cand or out_count, stride 0.  n_frames == 0
+ * succeeds.  The results carry the kernel's rounding, not the model's: frequencies agree with the model to ~1e-7 relative and
+ * strengths to ~1e-12 (Brent stops within 2 tol_act ~ 1e-5 lags of a stationary point, where S is flat); two runs are bit-identical.
+ * The fused frame loops (vbx_analyze_frames* and everything built on them), PCM / float input, frames beyond 4096 samples and an
+ * f32 instantiation are not covered: a caller composes these lists with vbx_frame_peak_f64 and vbx_pitch_path_f64
+ * (examples/pitch_boersma.c).  Cost: DESIGN.md section 5n. */
+int vbx_pitch_boersma_f64(vbx_ctx *ctx, const double *x, size_t n_frames, size_t frame_len, size_t stride,
+                          const double *window, double sample_rate, double threshold, double fmin, double fmax,
+                          size_t kmax, vbx_pitch *out_cand, int32_t *out_count, int32_t *status);
+
 /* The pitch PATH (added in ABI 5): the "third pass" of src/periodic.rs:394-395 -- "a path through these candidates that maximizes
  * both the smoothness of the pitch contour and the strength of the pitches" -- which PitchExtractor::new(candidates,
  * voiced_unvoiced_cost, voicing_threshold) (src/periodic.rs:320-354) takes the parameters of but never runs (its iterator

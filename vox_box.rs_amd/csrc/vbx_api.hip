@@ -199,6 +199,7 @@ int vbx_ctx_create(vbx_ctx **out, int device, void *hip_stream) {
         }
     }
     { const char *e = std::getenv("VBX_PITCH_MFMA"); ctx->pitch_force_mfma = e && e[0] == '1'; }
+    { const char *e = std::getenv("VBX_BOERSMA_GROUP"); ctx->boersma_group = (e && std::strcmp(e, "64") == 0) ? 64 : 16; }
     if (hip_stream) { ctx->stream = (hipStream_t)hip_stream; ctx->owns_stream = false; }
     else {
         e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);

@@ -75,6 +75,7 @@ struct vbx_ctx {
     std::vector<vbx::ProfRec> recs;
     std::map<std::string, std::pair<double, long>> prof_acc;
     std::map<std::string, int> prof_stream;               // name -> 0: the context's stream, 1: the side stream, 2: the tracker's
+    int boersma_group = 16;                               // lanes per refined entry of vbx_pitch_boersma_f64 from kmax 4 on (VBX_BOERSMA_GROUP=64: one entry per wavefront, A/B)
     bool pitch_force_mfma = false;                        // test hook: VBX_PITCH_MFMA=1 keeps the matrix-core pitch kernel on 1200-sample frames
     bool mfcc_force_goertzel = false;                     // test hooks: VBX_MFCC_GOERTZEL=1 / VBX_MFCC_DFT2=1 keep the
     bool mfcc_force_dft2 = false;                         //   fallback kernels covered on lengths the MFMA kernel takes

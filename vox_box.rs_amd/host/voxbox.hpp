@@ -190,6 +190,13 @@ struct Pitched {         // periodic.rs:356-358; local_peak / global_peak are un
         c.check(vbx_pitch_f64(c.get(), f.x, f.n_frames, f.frame_len, f.stride, f.window, sample_rate, threshold, min, max,
                               kmax, candidates, count, status));
     }
+    // Boersma's candidates with an unquantised lag (vbx_pitch_boersma_f64: Q5 / Q6 / Q8 undone): the lists of the pitch path.
+    // 1 <= kmax <= 63, 16 <= frame_len <= 4096; the crate's rows stay with pitch().
+    static void pitch_boersma(Context &c, const Frames &f, double sample_rate, double threshold, double min, double max,
+                              size_t kmax, Pitch *candidates /* [F, kmax] */, int32_t *count, int32_t *status) {
+        c.check(vbx_pitch_boersma_f64(c.get(), f.x, f.n_frames, f.frame_len, f.stride, f.window, sample_rate, threshold, min, max,
+                                      kmax, candidates, count, status));
+    }
 };
 
 struct Polynomial {      // polynomial.rs:10-21

@@ -326,6 +326,7 @@ def load_library():
         "vbx_improve_extremum_f64": (C.c_int, [vp, vp, sz, C.c_long, sz, vp, sz, sz, vp, vp]),
         "vbx_improve_extremum_ex_f64": (C.c_int, [vp, vp, sz, C.c_long, sz, vp, sz, i32, sz, i32, vp, vp]),
         "vbx_pitch_f64": (C.c_int, [vp, vp, sz, sz, sz, vp, dbl, dbl, dbl, dbl, sz, vp, vp, vp]),
+        "vbx_pitch_boersma_f64": (C.c_int, [vp, vp, sz, sz, sz, vp, dbl, dbl, dbl, dbl, sz, vp, vp, vp]),
         "vbx_frame_peak_f64": (C.c_int, [vp, vp, sz, sz, sz, vp]),
         "vbx_pitch_path_f64": (C.c_int, [vp, vp, vp, vp, sz, sz, vp, vp, sz, C.POINTER(PitchPathParams), vp, vp]),
         "vbx_internal_last_path_chunks_redone": (C.c_int, [vp, C.POINTER(C.c_int64)]),
@@ -1371,6 +1372,28 @@ class VoxBox:
             if d is not None:
                 d.free()
         return r
+
+    def pitch_boersma(self, x, sample_rate, threshold, fmin, fmax, kmax=15, frame_len=None, stride=None, n_frames=None,
+                      window=None, out=None):
+        """vbx_pitch_boersma_f64: Boersma's candidates with an unquantised lag (include/voxbox_hip.h has the definition).
+        Arguments and results as pitch(): (cand[F, kmax, 2], count[F], status[F]) as numpy, or writes into `out` = (cand, count,
+        status) device buffers and returns None.  1 <= kmax <= 63, 16 <= frame_len <= 4096; the lists are what pitch_path()
+        takes.  For kmax below a frame's count the rows are not prefixes of one another (selection is by first-pass strength)."""
+        ptr, F, N, S, tmp = self._frames(x, frame_len, stride, n_frames)
+        if out is None:
+            cand, cnt, st = self.empty((F, kmax, 2)), self.empty(F, np.int32), self.empty(F, np.int32)
+        else:
+            cand, cnt, st = out
+        try:
+            self._check(self.L.vbx_pitch_boersma_f64(self.ctx, ptr, F, N, S, _ptr(window), sample_rate, threshold, fmin, fmax,
+                                                     kmax, _ptr(cand), _ptr(cnt), _ptr(st)))
+            if out is not None:
+                return None
+            return cand.numpy(), cnt.numpy(), st.numpy()
+        finally:
+            for d in ((cand, cnt, st) if out is None else ()) + (tmp,):
+                if d is not None:
+                    d.free()
 
     # -- the pitch path: PitchExtractor's third pass (src/periodic.rs:320-354,394-395) -------------
     def frame_peak(self, x, frame_len=None, stride=None, n_frames=None, out=None):
